@@ -130,7 +130,11 @@ def main():
                     help="headline workload = the 24,414-stream real-text stand-in for configs[2] (strong scaling over --gpus)")
     ap.add_argument("--shard-fraction", type=int, default=1,
                     help="with --corpus-standin on one GPU: time only the first 1/F of the streams (one GPU's share at F GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -225,6 +229,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, shards[0].cap, np, prefix=f"rank{rank}_" if launched else "")
 
     in_bytes = sum(sh.in_bytes for sh in shards)      # this process, one step
     out_bytes = sum(int(r.out_len.to(torch.int64).sum().item()) for r in res)
@@ -364,6 +370,60 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 60_000_000     # bytes of array data written by --dump-outputs, all files together (64 MB less headroom)
+DUMP_PER_STREAM_MAX = 1 << 19  # streams whose per-stream values are written in full (4 x float64 each)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, res, cap, np, prefix=""):
+    """What the last timed step handed its caller, as float64/float32 .npy files in ``out_dir`` (streams of all of this
+    process's shards in shard order, i.e. global stream order):
+
+      out_len, out_off, status   float64 [n]  the BatchResult's per-stream arrays (out_off is relative to each shard's slab)
+      stream_digest              float64 [n]  first 48 bits of the SHA-256 of each compressed stream (covers every output byte)
+      sample_index               float64 [s]  a fixed, seeded sample of stream indices (sorted)
+      sample_streams             float32 [s, cap]  those streams' compressed bytes, zero past out_len (cap: the slab
+                                                   capacity per stream, so the sample depends on the inputs alone)
+
+    With more than DUMP_PER_STREAM_MAX streams the per-stream arrays are taken on a seeded sample too (``stream_index``);
+    the sample of whole streams is sized so that everything stays under DUMP_BUDGET."""
+    import hashlib
+
+    out_len = np.concatenate([r.out_len.cpu().numpy().astype(np.int64) for r in res])
+    out_off = np.concatenate([r.out_off.cpu().numpy().astype(np.int64) for r in res])
+    status = np.concatenate([r.status.cpu().numpy().astype(np.int64) for r in res])
+    slabs = [r.out.cpu().numpy() for r in res]
+    owner = np.concatenate([np.full(len(r.out_len), k) for k, r in enumerate(res)])
+    n = len(out_len)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def body(i):
+        o = int(out_off[i])
+        return slabs[owner[i]][o:o + int(out_len[i])]
+
+    arrays = {}
+    every = np.arange(n) if n <= DUMP_PER_STREAM_MAX else np.sort(rng.choice(n, DUMP_PER_STREAM_MAX, replace=False))
+    if len(every) < n:
+        arrays["stream_index"] = every.astype(np.float64)
+    arrays["out_len"] = out_len[every].astype(np.float64)
+    arrays["out_off"] = out_off[every].astype(np.float64)
+    arrays["status"] = status[every].astype(np.float64)
+    arrays["stream_digest"] = np.array([int.from_bytes(hashlib.sha256(body(i).tobytes()).digest()[:6], "little")
+                                        for i in every], dtype=np.float64)
+    room = DUMP_BUDGET - sum(a.nbytes for a in arrays.values())
+    s = min(n, max(1, room // (cap * 4 + 8)))
+    pick = np.sort(rng.choice(n, s, replace=False)) if n else np.zeros(0, np.int64)
+    sample = np.zeros((len(pick), cap), dtype=np.float32)
+    for row, i in enumerate(pick):
+        b = body(i)
+        sample[row, :len(b)] = b
+    arrays["sample_index"] = pick.astype(np.float64)
+    arrays["sample_streams"] = sample
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 def also_configs1(args, torch, np, conf_kw, steps=10, warmup=3):

@@ -78,7 +78,7 @@ def csr_for_fixed(n_streams: int, stream_len: int):
 REAL_TEXT_SOURCES = {
     "prose": ["/opt/skills/guides/*.md", "{repo}/*.md", "/usr/share/common-licenses/*", "/usr/share/doc/*/copyright"],
     "python": ["/usr/lib/python3.10/*.py", "/usr/lib/python3.10/*/*.py"],
-    "markup": ["/opt/rocm/share/html/rocgdb/*.html"],
+    "markup": ["/opt/rocm/share/html/*gdb/*.html"],  # the HTML edition of the GDB manual that ROCm ships
 }
 
 #: SHA-256 of the reference C's output for the whole enwik8 file as ONE stream, window=10 literal=8, no lazy matching

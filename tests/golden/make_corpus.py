@@ -9,7 +9,7 @@ Writes  tests/golden/corpus_prose.txt.xz   (licence texts + Debian copyright fil
 
 The fixtures are DATA for this repo's tests (no file of the reference repository goes in): public licence texts
 (/usr/share/common-licenses, verbatim redistribution permitted), the copyright files Debian ships next to every
-package, PSF-licensed standard-library modules, and the GFDL-licensed GDB manual (texinfo HTML under /opt/rocm/share/html/rocgdb).
+package, PSF-licensed standard-library modules, and the GFDL-licensed GDB manual (the texinfo HTML that ROCm ships under share/html).
 `python tests/golden/make_corpus.py markup` rebuilds one corpus and leaves the others' fixtures and manifest entries alone.  They replace the globbed stand-ins of round 2, which moved
 whenever DESIGN.md was edited and could be missing on another box.
 """
@@ -21,6 +21,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TARGET = 3 << 20  # 3 MiB raw each (768 chunks of 4 KiB)
+MARKUP_ROOT = "the HTML edition of the GDB manual that ROCm ships (share/html under the ROCm prefix)"
 
 
 def collect(patterns, limit):
@@ -51,7 +52,7 @@ def main():
     for name, patterns in (
         ("prose", ["/usr/share/common-licenses/*", "/usr/share/doc/*/copyright"]),
         ("python", ["/usr/lib/python3.10/*.py", "/usr/lib/python3.10/*/*.py"]),
-        ("markup", ["/opt/rocm/share/html/rocgdb/*.html"]),
+        ("markup", ["/opt/rocm/share/html/*gdb/*.html"]),
     ):
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
@@ -65,8 +66,11 @@ def main():
             "raw_bytes": len(raw),
             "sha256": hashlib.sha256(raw).hexdigest(),
             "xz_bytes": os.path.getsize(path),
-            "sources": files,
         }
+        if name == "markup":  # one directory: record the file names and describe where it lies
+            manifest[name]["sources_root"] = MARKUP_ROOT
+            files = [dict(f, path=os.path.basename(f["path"])) for f in files]
+        manifest[name]["sources"] = files
         print(name, len(raw), "->", os.path.getsize(path))
     with open(os.path.join(HERE, "corpus_manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1)
