@@ -745,17 +745,15 @@ int launch_decompress_long(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_le
     HIP_OK(hipStreamSynchronize(st));
     const uint8_t* const in = d_in + in_off;
     uint8_t* const out = d_out + out_off;
-    const uint32_t h0 = hdr[0], hs = 1 + (h0 & 1);
-    const uint32_t wbits = ((h0 >> 5) & 7) + 8, lbits = ((h0 >> 3) & 3) + 5;
-    const bool custom = (h0 >> 2) & 1, extended = (h0 >> 1) & 1, dreset = h0 & 1;
-    if (dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return 1;
+    const StreamHeader hd = decode_header(hdr[0]);
+    const uint32_t hs = 1 + (hdr[0] & 1), wbits = hd.wbits, lbits = hd.lbits;
+    const bool extended = hd.extended;
+    if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return 1;
     if (extended && getenv("TAMP_AMD_LONGDEC_EXT") && atoi(getenv("TAMP_AMD_LONGDEC_EXT")) == 0) return 1;  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
-    if (custom && (!d_dict || dict_len < W)) return 1;
-    // the fresh decoder's window: the custom dictionary, or the seeded table for the stream's literal size (v1: the literal >= 7
-    // table whatever the literal size, decompressor.c:318-319)
-    const uint32_t dict_sel = (!extended || lbits >= 7) ? 2u : (lbits == 6 ? 1u : 0u);
-    const uint8_t* const dict0 = custom ? d_dict : ctx->seed_dicts + ((size_t)dict_sel << 15);
+    if (hd.custom && (!d_dict || dict_len < W)) return 1;
+    // the fresh decoder's window: the custom dictionary, or the seeded table for the stream's literal size
+    const uint8_t* const dict0 = hd.custom ? d_dict : ctx->seed_dicts + ((size_t)hd.table << 15);
 
     const uint64_t total_bits = 8ull * n;
     const uint32_t chunk_bits = extended ? kLongChunkBitsExt : kLongChunkBits;
@@ -1017,6 +1015,18 @@ int launch_decompress_long(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_le
     return TAMP_OK;
 }
 
+// The wave-per-stream decoder over a batch (with a.only_flagged: over the streams the split decoder left): four streams per
+// workgroup up to 2^12-byte windows, one above; grid-stride beyond `max_groups` workgroups.
+static int launch_wave_decoder(const DecompressArgs& a, uint32_t max_wbits, size_t n_streams, size_t max_groups, hipStream_t st) {
+    const uint32_t waves = max_wbits <= 12 ? 4 : 1;
+    const uint32_t lds = decode_wave_lds(max_wbits, waves);
+    const size_t groups = std::min((n_streams + waves - 1) / waves, max_groups);
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(tamp_decompress_wave_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(tamp_decompress_wave_kernel, dim3((uint32_t)groups), dim3(waves * kWave), lds, st, a);
+    return TAMP_OK;
+}
+
 int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
                       const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                       const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed,
@@ -1193,14 +1203,9 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
         // leftovers: the wave decoder over the flagged streams only
         a.only_flagged = sa.flagged;
         a.flagged_count = sa.flagged_count;
-        const uint32_t waves = max_wbits <= 12 ? 4 : 1;
-        const uint32_t wlds = decode_wave_lds(max_wbits, waves);
-        size_t groups = (n_streams + waves - 1) / waves;
-        groups = std::min(groups, (size_t)ctx->cu_count * 64);
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(tamp_decompress_wave_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        hipLaunchKernelGGL(tamp_decompress_wave_kernel, dim3((uint32_t)groups), dim3(waves * kWave), wlds, st, a);
+        const int rc = launch_wave_decoder(a, max_wbits, n_streams, (size_t)ctx->cu_count * 64, st);
         timing_end(st);
+        if (rc != TAMP_OK) return rc;
         HIP_OK(hipGetLastError());
         return TAMP_OK;
         }  // (no scratch to be had: fall through to the lane / wave decoders)
@@ -1237,16 +1242,10 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     if (force) lds_lanes = force[0] == 'l', global_lanes = force_global;
     const bool use_wave = force ? (force[0] == 'w') : !(lds_lanes || global_lanes);
     if (valid_bits && use_wave) {
-        const uint32_t waves = max_wbits <= 12 ? 4 : 1;
-        const uint32_t lds = decode_wave_lds(max_wbits, waves);
-        size_t groups = (n_streams + waves - 1) / waves;
-        const size_t resident = (size_t)ctx->cu_count * 64;
-        if (groups > resident) groups = resident;  // grid-stride beyond that
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(tamp_decompress_wave_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         timing_begin(st);
-        hipLaunchKernelGGL(tamp_decompress_wave_kernel, dim3((uint32_t)groups), dim3(waves * kWave), lds, st, a);
+        const int rc = launch_wave_decoder(a, max_wbits, n_streams, (size_t)ctx->cu_count * 64, st);
         timing_end(st);
+        if (rc != TAMP_OK) return rc;
         HIP_OK(hipGetLastError());
         return TAMP_OK;
     }
@@ -1917,7 +1916,7 @@ int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, cons
     const HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, n_streams};
     std::vector<HostChunk> chunks;
     // a chunk fills the device three times over (256 CUs x 6 workgroups = 1,536 streams at once); measured best for
-    // 4 KiB streams (tools/host_path_bench.py), and at least 16 MiB so that short messages do not drown in call overhead
+    // 4 KiB streams (DESIGN_HISTORY.md), and at least 16 MiB so that short messages do not drown in call overhead
     plan_host_chunks(b, env_or("TAMP_AMD_HOST_CHUNK_STREAMS", (size_t)ctx->cu_count * 18),
                      (uint64_t)env_or("TAMP_AMD_HOST_CHUNK_MB", 16) << 20, 1ull << 30, chunks);
     return run_host_batch(ctx, device, b, chunks, conf->use_custom_dictionary ? dictionary : nullptr,

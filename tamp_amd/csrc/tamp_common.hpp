@@ -35,10 +35,28 @@ enum : int8_t {
 constexpr uint32_t kMaxDecodeIn = (1u << 29) - 1;
 constexpr uint32_t kMaxDecodeCall = 1u << 28;
 
-// Match-length prefix code: code without the leading 0 flag, length including it.
-__device__ __constant__ uint8_t d_code[15] = {0x00, 0x03, 0x08, 0x0b, 0x14, 0x24, 0x26, 0x2b,
-                                              0x4b, 0x54, 0x94, 0x95, 0xaa, 0x27, 0xab};
-__device__ __constant__ uint8_t d_nbits[15] = {2, 3, 5, 5, 6, 7, 7, 7, 8, 8, 9, 9, 9, 7, 9};
+// Match-length prefix code (compressor.c:33-36): code without the leading 0 flag, length including it.  Packed into
+// immediates as well (kCodeLo / kCodeHi / kNbitsPacked): no memory access on the hot paths.
+constexpr uint8_t kCodeTab[15] = {0x00, 0x03, 0x08, 0x0b, 0x14, 0x24, 0x26, 0x2b, 0x4b, 0x54, 0x94, 0x95, 0xaa, 0x27, 0xab};
+constexpr uint8_t kNbitsTab[15] = {2, 3, 5, 5, 6, 7, 7, 7, 8, 8, 9, 9, 9, 7, 9};  // incl. the flag bit
+constexpr uint64_t pack_bytes(const uint8_t* v, int first, int count) {
+    uint64_t r = 0;
+    for (int i = 0; i < count; i++) r |= (uint64_t)v[first + i] << (8 * i);
+    return r;
+}
+constexpr uint64_t pack_nibbles(const uint8_t* v, int count) {
+    uint64_t r = 0;
+    for (int i = 0; i < count; i++) r |= (uint64_t)v[i] << (4 * i);
+    return r;
+}
+constexpr uint64_t kCodeLo = pack_bytes(kCodeTab, 0, 8), kCodeHi = pack_bytes(kCodeTab, 8, 7);
+constexpr uint64_t kNbitsPacked = pack_nibbles(kNbitsTab, 15);
+static_assert(kCodeLo == 0x2b2624140b080300ull && kCodeHi == 0x00ab27aa9594544bull && kNbitsPacked == 0x979998877765532ull,
+              "packed prefix code");
+__device__ __forceinline__ uint32_t tok_code(uint32_t i) {
+    return (uint32_t)((i < 8 ? kCodeLo >> (8 * i) : kCodeHi >> (8 * (i - 8))) & 0xFF);
+}
+__device__ __forceinline__ uint32_t tok_nbits(uint32_t i) { return (uint32_t)(kNbitsPacked >> (4 * i)) & 15; }
 
 __host__ __device__ inline uint32_t align_up(uint32_t x, uint32_t a) { return (x + a - 1) & ~(a - 1); }
 

@@ -153,30 +153,11 @@ struct CompressLds {
     }
 };
 
-// Match-length prefix code (compressor.c:33-36) packed into immediates: no memory access on the hot path.
-constexpr uint64_t pack_bytes(const uint8_t* v, int first, int count) {
-    uint64_t r = 0;
-    for (int i = 0; i < count; i++) r |= (uint64_t)v[first + i] << (8 * i);
-    return r;
-}
-constexpr uint8_t kCodeTab[15] = {0x00, 0x03, 0x08, 0x0b, 0x14, 0x24, 0x26, 0x2b, 0x4b, 0x54, 0x94, 0x95, 0xaa, 0x27, 0xab};
-constexpr uint8_t kNbitsTab[15] = {2, 3, 5, 5, 6, 7, 7, 7, 8, 8, 9, 9, 9, 7, 9};  // incl. the flag bit
-constexpr uint64_t pack_nibbles(const uint8_t* v, int count) {
-    uint64_t r = 0;
-    for (int i = 0; i < count; i++) r |= (uint64_t)v[i] << (4 * i);
-    return r;
-}
-constexpr uint64_t kCodeLo = pack_bytes(kCodeTab, 0, 8), kCodeHi = pack_bytes(kCodeTab, 8, 7);
-constexpr uint64_t kNbitsPacked = pack_nibbles(kNbitsTab, 15);
 __device__ __forceinline__ uint64_t uni_u64(uint64_t x) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32));
     return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ uint32_t tok_code(uint32_t i) {
-    return (uint32_t)((i < 8 ? kCodeLo >> (8 * i) : kCodeHi >> (8 * (i - 8))) & 0xFF);
-}
-__device__ __forceinline__ uint32_t tok_nbits(uint32_t i) { return (uint32_t)(kNbitsPacked >> (4 * i)) & 15; }
 
 // 16-bit bijective mix of a bigram: top kHashBits select the bucket, the rest ride in the entry.  Any odd multiplier is a
 // bijection mod 2^16, so exactness does not depend on it -- only how many FOREIGN bigrams share a query's bucket.  Round 4
@@ -810,7 +791,7 @@ enum : uint32_t { cAct = 0, cShift = 1, cP0 = 2, cPending = 3, cWp = 4, cNtok = 
 // Instrumented builds (-DTAMP_PROF): a section whose effect does not change when it runs twice can be repeated per bit of
 // CompressArgs::dbg -- 0x100 bucket loop, 0x200 wrap-zone resolution, 0x10000 load, 0x20000 index, 0x40000 jump tables,
 // 0x80000 emit -- and the difference of two `rocprofv3 --pmc SQ_INSTS_VALU` runs is that section's exact instruction
-// count over all epochs of all streams (tools/phase_valu.sh -> profiles/r4_phase_valu.csv).
+// count over all epochs of all streams (tools/phase_valu5.sh; round 4: profiles/r4_phase_valu.csv).
 #ifdef TAMP_PROF
 #define TAMP_REPEAT(bit) for (uint32_t _rep = 0; _rep < ((a.dbg & (bit)) ? 2u : 1u); _rep++)
 #else

@@ -20,7 +20,7 @@
 //     and output moves; input through a 64-byte LDS ring; global loads / stores only at I/O points common to the wave.
 //     It ends at a token boundary whenever something needs the exact loop, which then resumes from the bit position.
 #pragma once
-#include "tamp_common.hpp"
+#include "tamp_decode_common.hpp"
 
 namespace tamp_amd {
 
@@ -81,37 +81,12 @@ __device__ __forceinline__ B16 blend16(const B16& a, const B16& b, uint32_t k) {
     return r;
 }
 
-// Prefix-code reader for the symbol that follows the 0 flag (decompressor.c:52-104).  `b` holds the
-// upcoming bits left-aligned; returns the symbol and its code length, or -1 when `avail` is too small.
-__device__ __forceinline__ int read_symbol(uint32_t b, uint32_t avail, uint32_t& used) {
-    if (avail < 1) return -1;
-    if ((b >> 31) == 0) {
-        used = 1;
-        return 0;
-    }
-    // code words (without the flag) are 2..8 bits; walk them from the packed tables
-    const uint64_t codes_lo = 0x2b2624140b080300ull, codes_hi = 0x00ab27aa9594544bull, nbits = 0x979998877765532ull;
-    int sym = -1;
-    uint32_t nb = 0;
-#pragma unroll
-    for (int s = 1; s < 15; s++) {
-        const uint32_t l = (uint32_t)((nbits >> (4 * s)) & 15) - 1u;
-        const uint32_t code = (uint32_t)((s < 8 ? codes_lo >> (8 * s) : codes_hi >> (8 * (s - 8))) & 0xFF);
-        if (sym < 0 && (b >> (32 - l)) == code) {
-            sym = s;
-            nb = l;
-        }
-    }
-    if (avail < nb) return -1;
-    used = nb;
-    return sym;
-}
-
 // LDSWIN: window rows in LDS (else per-lane slots of a global scratch slab).  BULK: the straight-line
 // bulk path with its LUT / output stage / row slack is compiled in; batches of short messages take the lean build,
-// which fits more workgroups on a CU.
+// which fits more workgroups on a CU.  Bulk builds ask for 5 waves per SIMD (<= 96 VGPRs): they need 94-96, and left to
+// itself the allocator lands on either side of that line with any change of the surrounding code.
 template <bool LDSWIN, bool BULK = false>
-__global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(DecompressArgs a) {
+__global__ void __launch_bounds__(LDSWIN ? 64 : 256, BULK ? 5 : 1) tamp_decompress_kernel(DecompressArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t nthreads = gridDim.x * blockDim.x;
@@ -121,18 +96,7 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
     uint8_t* const win = LDSWIN ? smem + (BULK ? 128 + kWave * kLaneStagePad : 0u) + threadIdx.x * a.lds_row
                                 : a.scratch + (BULK ? (size_t)gtid * a.lds_row : ((size_t)gtid << a.max_wbits));
     if constexpr (BULK) {
-        // prefix-code LUT: index = the 7 bits after the leading 1 of a code word -> (extra bits << 4) | symbol
-        // (decompressor.c:52-57 restated from the code table, compressor.c:33-36)
-        for (uint32_t v = threadIdx.x; v < 128; v += blockDim.x) {
-            const uint64_t codes_lo = 0x2b2624140b080300ull, codes_hi = 0x00ab27aa9594544bull, nbits = 0x979998877765532ull;
-            uint32_t entry = 0;
-            for (int s = 1; s < 15; s++) {
-                const uint32_t l = (uint32_t)((nbits >> (4 * s)) & 15) - 1u;  // code length without the flag: 2..8
-                const uint32_t code = (uint32_t)((s < 8 ? codes_lo >> (8 * s) : codes_hi >> (8 * (s - 8))) & 0xFF);
-                if ((code & ((1u << (l - 1)) - 1)) == (v >> (7 - (l - 1)))) entry = ((l - 1) << 4) | (uint32_t)s;
-            }
-            lut[v] = (uint8_t)entry;
-        }
+        build_prefix_lut(lut);
         __syncthreads();
     }
 
@@ -142,7 +106,8 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
         const uint32_t n = a.in_len[s];
         uint8_t* const out = a.out + a.out_off[s];
         const uint32_t cap = a.out_cap[s];
-        uint32_t ip = 0, op = 0;
+        RefReader r{in, n};  // the reference's bit reader; r.ip = the consumed count
+        uint32_t op = 0;
         int res = kInputExhausted;
 
         // output staging: bytes collect in `oacc` and leave as one aligned dword
@@ -174,18 +139,16 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
             if (n == 0) break;
             const uint32_t h0 = in[0];
             const uint32_t hs = 1 + (h0 & 1);
-            if (n < hs) { ip = 1; break; }  // first byte stashed, waiting for the second (decompressor.c:405-410)
+            if (n < hs) { r.ip = 1; break; }  // first byte stashed, waiting for the second (decompressor.c:405-410)
             if (hs == 2 && in[1]) { res = kInvalidConf; break; }
-            ip = hs;
-            const uint32_t wbits = ((h0 >> 5) & 7) + 8, lbits = ((h0 >> 3) & 3) + 5;
-            const bool custom = (h0 >> 2) & 1, extended = (h0 >> 1) & 1, dreset = h0 & 1;
+            r.ip = hs;
+            const StreamHeader hd = decode_header(h0);
+            const uint32_t wbits = hd.wbits, lbits = hd.lbits, minp = hd.minp;
             if (wbits > a.max_wbits) { res = kInvalidConf; break; }  // decompressor.c:311
             const uint32_t W = 1u << wbits, mask = W - 1;
-            const uint32_t minp = (uint32_t)min_pattern_size((int)wbits, (int)lbits);
-            const uint32_t table = (!extended || lbits >= 7) ? 2u : (lbits == 6 ? 1u : 0u);  // decompressor.c:318-319
-            const uint8_t* const seed_default = a.seed_dicts + ((size_t)table << 15);
+            const uint8_t* const seed_default = a.seed_dicts + ((size_t)hd.table << 15);
             const uint8_t* seed = seed_default;
-            if (custom) {
+            if (hd.custom) {
                 if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
                 seed = a.dict;
             }
@@ -199,30 +162,7 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                 if (filled < W) filled = wp ? (filled > wp ? filled : wp) : W;
             };
 
-            // bit reader: `bb`/`nb` behave exactly like the reference's 32-bit buffer (decompressor.c:357-365);
-            // bytes are fetched from HBM a dword at a time into `stage`
-            uint32_t bb = 0, nb = 0;
-            uint32_t stage = 0, ns = 0;  // ns prefetched bytes, next one in the low byte
             bool last_flush = false;
-            auto refill = [&]() {
-                while (ip < n && nb <= 24) {
-                    if (ns == 0) {
-                        const uint8_t* p = in + ip;
-                        if ((reinterpret_cast<uintptr_t>(p) & 3) == 0 && ip + 4 <= n) {
-                            stage = *reinterpret_cast<const uint32_t*>(p);
-                            ns = 4;
-                        } else {
-                            stage = *p;
-                            ns = 1;
-                        }
-                    }
-                    nb += 8;
-                    bb |= (stage & 0xFFu) << (32 - nb);
-                    stage >>= 8;
-                    ns--;
-                    ip++;
-                }
-            };
 
             bool first_pass = true;
             for (;;) {  // LDS variant: bulk path and exact loop alternate; otherwise a single pass of the exact loop
@@ -247,7 +187,7 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                 }
                 first_pass = false;
                 filled = W;
-                uint32_t T = 8 * ip - nb;  // bits consumed from the start of the stream
+                uint32_t T = 8 * r.ip - r.nb;  // bits consumed from the start of the stream
                 const uint32_t sp = T >> 3;  // stream offset of the byte holding the next bit
                 bool fast = sp + 32 <= n && cap - op >= 16;
                 // Input pipeline: compressed bytes pass through a 64-byte ring per lane in LDS.  A 16-byte chunk is fetched
@@ -340,7 +280,7 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                                 }
                                 if (sym == kSymFlush) {
                                     ok = false;
-                                } else if (!extended || sym < kSymRle) {  // plain match, decompressor.c:529-572
+                                } else if (!hd.extended || sym < kSymRle) {  // plain match, decompressor.c:529-572
                                     tok = sym + minp;
                                     p_off = (uint32_t)((fb << used) >> (64 - wbits));
                                     used += wbits;
@@ -421,51 +361,46 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                 if (T != T_in) {
                     // the reference's buffer at this token boundary: everything its last refill pulled in
                     last_flush = false;
-                    const uint32_t ip_ref = min(n, ((T_mark + 24) >> 3) + 1);
-                    bb = 0, nb = 0, stage = 0, ns = 0;
-                    for (uint32_t b = T >> 3; b < ip_ref; b++) {
-                        uint32_t byte = in[b], width = 8;
-                        if (b == (T >> 3)) byte &= 0xFFu >> (T & 7), width = 8 - (T & 7);
-                        bb |= byte << (32 - nb - width);
-                        nb += width;
-                    }
-                    ip = ip_ref;
+                    r.rebuild(T, T_mark);
                 }
                 // the dword staging of the exact loop assumes it starts on a dword of the output
                 out_aligned = ((reinterpret_cast<uintptr_t>(out) | op) & 3) == 0;
             }
 
-            for (;;) {  // decompressor.c:431-575
+            // The reference's token loop, decompressor.c:431-575 -- the rules of exact_token (tamp_decode_common.hpp) with the
+            // bytes written where each kind of token is decoded.  (Through exact_token's returned value, or a handler it
+            // calls per token, this loop measured 30 % / 18 % slower on batches of 256-byte messages, which run nothing else.)
+            for (;;) {
                 if (use_bulk && budget-- == 0) {  // back to the bulk path (it declines by itself near the end of the input)
                     resume = true;
                     break;
                 }
-                if (!(ip < n || nb)) break;
+                if (!(r.ip < n || r.nb)) break;
                 if (op == cap) { res = kOutputFull; break; }
-                refill();
-                if (nb == 0) break;
+                r.refill();
+                if (r.nb == 0) break;
 
-                if (bb >> 31) {  // literal, decompressor.c:466-482
+                if (r.bb >> 31) {  // literal, decompressor.c:466-482
                     last_flush = false;
-                    if (nb < 1 + lbits) break;
-                    const uint32_t c = (bb << 1) >> (32 - lbits);
-                    bb <<= 1 + lbits;
-                    nb -= 1 + lbits;
+                    if (r.nb < 1 + lbits) break;
+                    const uint32_t c = (r.bb << 1) >> (32 - lbits);
+                    r.bb <<= 1 + lbits;
+                    r.nb -= 1 + lbits;
                     emit(c);
                     wwrite(c);
                     continue;
                 }
 
-                uint32_t b2 = bb << 1, n2 = nb - 1, used = 0;
+                uint32_t b2 = r.bb << 1, n2 = r.nb - 1, used = 0;
                 const int sym = read_symbol(b2, n2, used);
                 if (sym < 0) break;
                 b2 <<= used;
                 n2 -= used;
 
                 if (sym == kSymFlush) {  // decompressor.c:501-514
-                    bb = b2 << (n2 & 7);
-                    nb = n2 & ~7u;
-                    if (dreset && last_flush) {  // double FLUSH: back to the pristine seeded dictionary
+                    r.bb = b2 << (n2 & 7);
+                    r.nb = n2 & ~7u;
+                    if (hd.dreset && last_flush) {  // double FLUSH: back to the pristine seeded dictionary
                         wp = 0;
                         filled = 0;
                         seed = seed_default;
@@ -475,9 +410,9 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                 }
                 last_flush = false;
 
-                if (extended && sym >= kSymRle) {
-                    bb = b2;  // symbol bits are committed before the payload is read (decompressor.c:521-526)
-                    nb = n2;
+                if (hd.extended && sym >= kSymRle) {
+                    r.bb = b2;  // symbol bits are committed before the payload is read (decompressor.c:521-526)
+                    r.nb = n2;
                     const uint32_t trailing = (sym == kSymRle) ? 4u : 3u;
                     uint32_t value = 0, match_len = 0, off = 0;
                     int got = 0;
@@ -485,27 +420,27 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                     for (;;) {  // decode_rle / decode_extended_match with the loop's refill-and-retry (:114-273,447-456)
                         if (got == 0) {
                             uint32_t u3 = 0;
-                            int hsym = (nb >= 1 + trailing) ? read_symbol(bb, nb, u3) : -1;
-                            if (hsym >= 0 && nb - u3 < trailing) hsym = -1;
+                            int hsym = (r.nb >= 1 + trailing) ? read_symbol(r.bb, r.nb, u3) : -1;
+                            if (hsym >= 0 && r.nb - u3 < trailing) hsym = -1;
                             if (hsym >= 0) {
-                                uint32_t b3 = bb << u3;
+                                uint32_t b3 = r.bb << u3;
                                 value = ((uint32_t)hsym << trailing) + (b3 >> (32 - trailing));
-                                bb = b3 << trailing;
-                                nb -= u3 + trailing;
+                                r.bb = b3 << trailing;
+                                r.nb -= u3 + trailing;
                                 got = (sym == kSymRle) ? 2 : 1;
                                 if (sym == kSymExt) match_len = value + minp + 12;
                             }
                         }
-                        if (got == 1 && nb >= wbits) {
-                            off = bb >> (32 - wbits);
-                            bb <<= wbits;
-                            nb -= wbits;
+                        if (got == 1 && r.nb >= wbits) {
+                            off = r.bb >> (32 - wbits);
+                            r.bb <<= wbits;
+                            r.nb -= wbits;
                             got = 2;
                         }
                         if (got == 2) break;
-                        const uint32_t before = nb;
-                        refill();
-                        if (nb == before && ip == n) { starved = true; break; }
+                        const uint32_t before = r.nb;
+                        r.refill();
+                        if (r.nb == before && r.ip == n) { starved = true; break; }
                     }
                     if (starved) break;
                     if (sym == kSymRle) {  // decompressor.c:140-173
@@ -549,8 +484,8 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
                     res = kOutputFull;
                     break;
                 }
-                bb = b2 << wbits;
-                nb = n2 - wbits;
+                r.bb = b2 << wbits;
+                r.nb = n2 - wbits;
                 for (uint32_t k = 0; k < match_len; k++) emit(wread(off + k));
                 {  // tamp_window_copy: destination wraps, memmove semantics
                     const uint32_t dist = (wp - off) & mask;
@@ -574,7 +509,7 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256) tamp_decompress_kernel(Deco
         emit_flush();
         a.out_len[s] = op;
         a.status[s] = (int8_t)res;
-        if (a.in_consumed) a.in_consumed[s] = ip;
+        if (a.in_consumed) a.in_consumed[s] = r.ip;
     }
 }
 

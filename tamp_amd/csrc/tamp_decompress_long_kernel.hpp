@@ -28,7 +28,7 @@
 // more lagging tokens in one chunk than a group lists -- is left to the exact decoders: the launcher falls back before anything
 // has been written.
 #pragma once
-#include "tamp_common.hpp"
+#include "tamp_decode_common.hpp"
 #include "tamp_decompress_split_kernel.hpp"
 
 namespace tamp_amd {
@@ -138,20 +138,6 @@ __device__ __forceinline__ uint32_t long_token(const uint8_t* in, uint32_t n, ui
     return used + wbits;
 }
 
-__device__ __forceinline__ void long_lut(uint8_t* lut) {  // (the table of tamp_decode_parse_kernel)
-    for (uint32_t v = threadIdx.x; v < 128; v += blockDim.x) {
-        const uint64_t codes_lo = 0x2b2624140b080300ull, codes_hi = 0x00ab27aa9594544bull, nbits = 0x979998877765532ull;
-        uint32_t entry = 0;
-        for (int sy = 1; sy < 15; sy++) {
-            const uint32_t l = (uint32_t)((nbits >> (4 * sy)) & 15) - 1u;
-            const uint32_t code = (uint32_t)((sy < 8 ? codes_lo >> (8 * sy) : codes_hi >> (8 * (sy - 8))) & 0xFF);
-            if ((code & ((1u << (l - 1)) - 1)) == (v >> (7 - (l - 1)))) entry = ((l - 1) << 4) | (uint32_t)sy;
-        }
-        lut[v] = (uint8_t)entry;
-    }
-    __syncthreads();
-}
-
 // Round of the start-position search: g_next[i + 1] = where the parse that starts at g[i] leaves chunk i.  The 64 chunks of a
 // workgroup settle among themselves first (their starts travel through LDS, up to 64 inner rounds -- a parse that starts at the
 // wrong phase of a PERIODIC bit stream, a run of equal tokens, never falls back into step, and the right start then moves on
@@ -160,7 +146,8 @@ __global__ void __launch_bounds__(64) tamp_long_sync_kernel(LongArgs a) {
     __shared__ uint8_t lut[128];
     __shared__ uint32_t gs[65];
     __shared__ uint32_t moved;
-    long_lut(lut);
+    build_prefix_lut(lut);
+    __syncthreads();
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < a.n_chunks;
     const uint32_t minp = (uint32_t)min_pattern_size((int)a.wbits, (int)a.lbits);
@@ -201,7 +188,8 @@ __global__ void __launch_bounds__(64) tamp_long_sync_kernel(LongArgs a) {
 // format), or written as records (write = 1).
 __global__ void __launch_bounds__(64) tamp_long_parse_kernel(LongArgs a) {
     __shared__ uint8_t lut[128];
-    long_lut(lut);
+    build_prefix_lut(lut);
+    __syncthreads();
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_chunks) return;
     const uint32_t minp = (uint32_t)min_pattern_size((int)a.wbits, (int)a.lbits);

@@ -14,7 +14,7 @@
 // a token it has pulled bytes until more than 24 bits are buffered), i.e. floor((T + 24) / 8) + 1 at the last refill
 // point.  Buffered bits at the end of the call = 8 * cursor - T; they go back into the state.
 #pragma once
-#include "tamp_common.hpp"
+#include "tamp_decode_common.hpp"
 #include "tamp_decompress_kernel.hpp"
 #include "tamp_decompress_wave_kernel.hpp"
 
@@ -40,16 +40,7 @@ __global__ void __launch_bounds__(256) tamp_decompress_resume_kernel(ResumeArgs 
     uint8_t* const win = smem + 128 + wave * ((1u << a.max_wbits) + kStage);
     uint8_t* const stage = win + (1u << a.max_wbits);
 
-    for (uint32_t v = threadIdx.x; v < 128; v += blockDim.x) {  // prefix-code LUT, as in the wave kernel
-        const uint64_t codes_lo = 0x2b2624140b080300ull, codes_hi = 0x00ab27aa9594544bull, nbits = 0x979998877765532ull;
-        uint32_t entry = 0;
-        for (int s = 1; s < 15; s++) {
-            const uint32_t l = (uint32_t)((nbits >> (4 * s)) & 15) - 1u;
-            const uint32_t code = (uint32_t)((s < 8 ? codes_lo >> (8 * s) : codes_hi >> (8 * (s - 8))) & 0xFF);
-            if ((code & ((1u << (l - 1)) - 1)) == (v >> (7 - (l - 1)))) entry = ((l - 1) << 4) | (uint32_t)s;
-        }
-        lut[v] = (uint8_t)entry;
-    }
+    build_prefix_lut(lut);
     __syncthreads();
 
     const uint32_t gw = blockIdx.x * nwaves + wave, tw = gridDim.x * nwaves;
@@ -159,7 +150,8 @@ __global__ void __launch_bounds__(256) tamp_decompress_resume_kernel(ResumeArgs 
         do {
             if (bits_max < 8 || bits_max > 15 || bits_max > a.max_wbits) { res = kInvalidConf; break; }
             // ---- header (decompressor.c:389-429), possibly split over two calls ----
-            if (!(flags & kDsConfigured)) {
+            const bool fresh = !(flags & kDsConfigured);
+            if (fresh) {
                 uint32_t h0, hs;
                 fetch();
                 if (flags & kDsHeaderStashed) {
@@ -181,22 +173,16 @@ __global__ void __launch_bounds__(256) tamp_decompress_resume_kernel(ResumeArgs 
                 take(8 * hs);
                 ip_ref = hs;
                 // tamp_decompressor_populate_from_conf, decompressor.c:304-329
-                const uint32_t wb = ((h0 >> 5) & 7) + 8;
-                if (wb > bits_max) { res = kInvalidConf; break; }
+                if (decode_header(h0).wbits > bits_max) { res = kInvalidConf; break; }
                 conf = h0, flags = (flags | kDsConfigured) & ~kDsHeaderStashed, skip = 0;
-                W = 1u << wb, mask = W - 1;
-                const uint32_t lb = ((h0 >> 3) & 3) + 5;
-                const uint32_t table = (!((h0 >> 1) & 1) || lb >= 7) ? 2u : (lb == 6 ? 1u : 0u);
-                load_window(((h0 >> 2) & 1) ? gwin : a.seed_dicts + ((size_t)table << 15));  // custom: the caller's bytes
-            } else {
-                W = 1u << (((conf >> 5) & 7) + 8), mask = W - 1;
-                load_window(gwin);
             }
+            const StreamHeader hd = decode_header(conf);
+            const uint32_t wbits = hd.wbits, lbits = hd.lbits, minp = hd.minp;
+            const bool extended = hd.extended;
+            W = 1u << wbits, mask = W - 1;
+            // a fresh decoder starts from the seeded table, or the caller's custom dictionary; a resumed one from its window
+            load_window(fresh && !hd.custom ? a.seed_dicts + ((size_t)hd.table << 15) : gwin);
             window_live = true;
-            const uint32_t wbits = ((conf >> 5) & 7) + 8, lbits = ((conf >> 3) & 3) + 5;
-            const bool extended = (conf >> 1) & 1, dreset = conf & 1;
-            const uint32_t minp = (uint32_t)min_pattern_size((int)wbits, (int)lbits);
-            const uint32_t table = (!extended || lbits >= 7) ? 2u : (lbits == 6 ? 1u : 0u);
             bool last_flush = (flags & kDsLastWasFlush) != 0;
 
             for (;;) {  // decompressor.c:431-575
@@ -231,9 +217,9 @@ __global__ void __launch_bounds__(256) tamp_decompress_resume_kernel(ResumeArgs 
                     if (sym == kSymFlush) {  // decompressor.c:501-514
                         take(used);
                         take((8 - (T & 7)) & 7);
-                        if (dreset && last_flush) {
+                        if (hd.dreset && last_flush) {
                             wp = 0;
-                            load_window(a.seed_dicts + ((size_t)table << 15));
+                            load_window(a.seed_dicts + ((size_t)hd.table << 15));
                         }
                         last_flush = true;
                         continue;

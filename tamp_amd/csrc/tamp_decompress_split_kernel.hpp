@@ -11,7 +11,7 @@
 //     final status / size / consumed count, and a short list of the tokens that wrote fewer bytes to the window than they
 //     produced (RLE runs over 8 bytes, tokens clipped at the ring end: decompressor.c:140-173,229-272).  With no window
 //     to keep per lane the kernel is bound by instruction issue, not by LDS capacity or cache-resident windows as the
-//     lane-per-stream decoders are (13-16 % VALU busy, tools/dec_pmc2.sh).
+//     lane-per-stream decoders are (13-16 % VALU busy, DESIGN_HISTORY.md).
 //   * RESOLVE (tamp_decode_resolve_kernel, one workgroup per stream): the data part, parallel over the stream's bytes.
 //     Every byte ever written to the window has a virtual position v (the dictionary sits at v = -W .. -1); ring index i
 //     holds, when V bytes have been written, the byte with v = V - 1 - ((V - 1 - i) mod W).  A copy token therefore names,
@@ -27,7 +27,6 @@
 // and status / consumed semantics are tested against it for every decoder (tests/test_gpu_parity.py, tools/fuzz_gpu.py).
 #pragma once
 #include <type_traits>
-#include "tamp_common.hpp"
 #include "tamp_decompress_kernel.hpp"
 
 namespace tamp_amd {
@@ -75,16 +74,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DecompressArgs& a = sa.d;
     uint8_t* const lut = smem;  // prefix-code LUT: index = the 7 bits after the leading 1 -> (extra bits << 4) | symbol
-    for (uint32_t v = threadIdx.x; v < 128; v += blockDim.x) {
-        const uint64_t codes_lo = 0x2b2624140b080300ull, codes_hi = 0x00ab27aa9594544bull, nbits = 0x979998877765532ull;
-        uint32_t entry = 0;
-        for (int sy = 1; sy < 15; sy++) {
-            const uint32_t l = (uint32_t)((nbits >> (4 * sy)) & 15) - 1u;  // code length without the flag: 2..8
-            const uint32_t code = (uint32_t)((sy < 8 ? codes_lo >> (8 * sy) : codes_hi >> (8 * (sy - 8))) & 0xFF);
-            if ((code & ((1u << (l - 1)) - 1)) == (v >> (7 - (l - 1)))) entry = ((l - 1) << 4) | (uint32_t)sy;
-        }
-        lut[v] = (uint8_t)entry;
-    }
+    build_prefix_lut(lut);
     __syncthreads();
     const uint32_t k = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * sa.spw + (threadIdx.x & (kWave - 1));
     const bool live = (threadIdx.x & (kWave - 1)) < sa.spw && k < sa.count;
@@ -106,7 +96,8 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
         nstage -= 16;
         st16(reinterpret_cast<uint8_t*>(rb), ld16(reinterpret_cast<const uint8_t*>(rb + 16)));  // (the up to four records behind)
     };
-    uint32_t ip = 0, op = 0, nlag = 0, cumlag = 0;  // (records so far = nflushed + nstage; bytes written = op - cumlag)
+    RefReader r{in, n};  // the reference's bit reader; r.ip = the consumed count
+    uint32_t op = 0, nlag = 0, cumlag = 0;  // (records so far = nflushed + nstage; bytes written = op - cumlag)
     uint32_t wbits = 8, dict_sel = 2;
     bool fallback = false;
     int res = kInputExhausted;
@@ -117,17 +108,17 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
         if (n == 0) break;
         const uint32_t h0 = in[0];
         const uint32_t hs = 1 + (h0 & 1);
-        if (n < hs) { ip = 1; break; }  // decompressor.c:405-410
+        if (n < hs) { r.ip = 1; break; }  // decompressor.c:405-410
         if (hs == 2 && in[1]) { res = kInvalidConf; break; }
-        ip = hs;
-        wbits = ((h0 >> 5) & 7) + 8;
-        const uint32_t lbits = ((h0 >> 3) & 3) + 5;
-        const bool custom = (h0 >> 2) & 1, extended = (h0 >> 1) & 1, dreset = h0 & 1;
+        r.ip = hs;
+        const StreamHeader hd = decode_header(h0);
+        wbits = hd.wbits;
+        const uint32_t lbits = hd.lbits, minp = hd.minp;
+        const bool extended = hd.extended;
         if (wbits > a.max_wbits) { res = kInvalidConf; break; }  // decompressor.c:311
         const uint32_t W = 1u << wbits, mask = W - 1;
-        const uint32_t minp = (uint32_t)min_pattern_size((int)wbits, (int)lbits);
-        dict_sel = (!extended || lbits >= 7) ? 2u : (lbits == 6 ? 1u : 0u);  // decompressor.c:318-319
-        if (custom) {
+        dict_sel = hd.table;
+        if (hd.custom) {
             if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
             dict_sel = 3;
         }
@@ -156,27 +147,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
             put_any(kind, olen, arg, written, std::integral_constant<bool, false>{});
         };
 
-        uint32_t bb = 0, nb = 0, stage = 0, ns = 0;
         bool last_flush = false;
-        auto refill = [&]() {  // decompressor.c:357-365; bytes reach `stage` a dword at a time
-            while (ip < n && nb <= 24) {
-                if (ns == 0) {
-                    const uint8_t* p = in + ip;
-                    if ((reinterpret_cast<uintptr_t>(p) & 3) == 0 && ip + 4 <= n) {
-                        stage = *reinterpret_cast<const uint32_t*>(p);
-                        ns = 4;
-                    } else {
-                        stage = *p;
-                        ns = 1;
-                    }
-                }
-                nb += 8;
-                bb |= (stage & 0xFFu) << (32 - nb);
-                stage >>= 8;
-                ns--;
-                ip++;
-            }
-        };
 
         // Two loops alternate.  FAST: straight-line decode from a 32-bit bit window read afresh per token (the token decode of the lane
         // decoders' bulk path, tamp_decompress_kernel.hpp, without its data movement), input through a 64-byte ring per lane
@@ -195,7 +166,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
         bool resume = false;
         uint32_t budget = 0xFFFFFFFFu;
         if (use_fast) {
-            uint32_t T = 8 * ip - nb;  // bits consumed from the start of the stream
+            uint32_t T = 8 * r.ip - r.nb;  // bits consumed from the start of the stream
             const uint32_t sp = whole ? 0u : T >> 3;
             bool fast = whole ? (T >> 3) + 4 <= n : sp + 32 <= n;
             const uint32_t sp0 = sp;  // stream byte x lives at inr[(x - sp0) & 63]
@@ -317,15 +288,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
             }
             if (T != T_in) {  // the reference's buffer at this token boundary: everything its last refill pulled in
                 last_flush = false;
-                const uint32_t ip_ref = min(n, ((T_mark + 24) >> 3) + 1);
-                bb = 0, nb = 0, stage = 0, ns = 0;
-                for (uint32_t b = T >> 3; b < ip_ref; b++) {
-                    uint32_t byte = in[b], width = 8;
-                    if (b == (T >> 3)) byte &= 0xFFu >> (T & 7), width = 8 - (T & 7);
-                    bb |= byte << (32 - nb - width);
-                    nb += width;
-                }
-                ip = ip_ref;
+                r.rebuild(T, T_mark);
             }
         }
 
@@ -334,98 +297,34 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
                 resume = true;
                 break;
             }
-            if (!(ip < n || nb)) break;
+            if (!(r.ip < n || r.nb)) break;
             if (op == cap) { res = kOutputFull; break; }
-            refill();
-            if (nb == 0) break;
+            r.refill();
+            if (r.nb == 0) break;
 
-            if (bb >> 31) {  // literal, decompressor.c:466-482
-                last_flush = false;
-                if (nb < 1 + lbits) break;
-                const uint32_t c = (bb << 1) >> (32 - lbits);
-                bb <<= 1 + lbits;
-                nb -= 1 + lbits;
-                put(kRecLit, 1, c, 1);
-                continue;
-            }
-
-            uint32_t b2 = bb << 1, n2 = nb - 1, used = 0;
-            const int sym = read_symbol(b2, n2, used);
-            if (sym < 0) break;
-            b2 <<= used;
-            n2 -= used;
-
-            if (sym == kSymFlush) {  // decompressor.c:501-514
-                bb = b2 << (n2 & 7);
-                nb = n2 & ~7u;
-                if (dreset && last_flush) fallback = true;  // dictionary reset inside the stream: lane / wave decoders
+            const ExactTok t = exact_token(r, hd);
+            if (t.kind == kExShort) break;
+            if (t.kind == kExOob) { res = kOob; break; }
+            if (t.kind == kExFlush) {
+                if (hd.dreset && last_flush) fallback = true;  // dictionary reset inside the stream: lane / wave decoders
                 last_flush = true;
                 continue;
             }
             last_flush = false;
-
-            if (extended && sym >= kSymRle) {
-                bb = b2;  // symbol bits are committed before the payload is read (decompressor.c:521-526)
-                nb = n2;
-                const uint32_t trailing = (sym == kSymRle) ? 4u : 3u;
-                uint32_t value = 0, match_len = 0, off = 0;
-                int got = 0;
-                bool starved = false;
-                for (;;) {  // decode_rle / decode_extended_match with the loop's refill-and-retry (:114-273,447-456)
-                    if (got == 0) {
-                        uint32_t u3 = 0;
-                        int hsym = (nb >= 1 + trailing) ? read_symbol(bb, nb, u3) : -1;
-                        if (hsym >= 0 && nb - u3 < trailing) hsym = -1;
-                        if (hsym >= 0) {
-                            uint32_t b3 = bb << u3;
-                            value = ((uint32_t)hsym << trailing) + (b3 >> (32 - trailing));
-                            bb = b3 << trailing;
-                            nb -= u3 + trailing;
-                            got = (sym == kSymRle) ? 2 : 1;
-                            if (sym == kSymExt) match_len = value + minp + 12;
-                        }
-                    }
-                    if (got == 1 && nb >= wbits) {
-                        off = bb >> (32 - wbits);
-                        bb <<= wbits;
-                        nb -= wbits;
-                        got = 2;
-                    }
-                    if (got == 2) break;
-                    const uint32_t before = nb;
-                    refill();
-                    if (nb == before && ip == n) { starved = true; break; }
-                }
-                if (starved) break;
-                const uint32_t wp = (op - cumlag) & mask, room = cap - op;  // (window_pos = bytes written mod W on a fresh decoder)
-                if (sym == kSymRle) {  // decompressor.c:140-173
-                    const uint32_t count = value + 2;
-                    const uint32_t w = count <= room ? count : room;
-                    put(kRecFill, w, 0, min(w, min(min(count, kRleWindowMax), W - wp)));
-                    if (w < count) { res = kOutputFull; break; }
-                } else {  // decompressor.c:229-272
-                    if (off >= W || off + match_len > W) { res = kOob; break; }
-                    const uint32_t w = match_len <= room ? match_len : room;
-                    put(kRecCopyExt, w, off, min(w, W - wp));  // up to the end of the buffer, no wrap
-                    if (w < match_len) { res = kOutputFull; break; }
-                }
+            if (t.kind == kExLit) {
+                put(kRecLit, 1, t.arg, 1);
                 continue;
             }
-
-            // plain match, decompressor.c:529-572
-            if (n2 < wbits) break;
-            const uint32_t match_len = (uint32_t)sym + minp;
-            const uint32_t off = b2 >> (32 - wbits);
-            if (off >= W || off + match_len > W) { res = kOob; break; }
-            const uint32_t room = cap - op;
-            if (match_len > room) {  // partial copy, token not consumed (decompressor.c:553-557)
-                put(kRecCopy, room, off, room);
-                res = kOutputFull;
-                break;
+            const uint32_t wp = (op - cumlag) & mask, room = cap - op;  // (window_pos = bytes written mod W on a fresh decoder)
+            const uint32_t w = t.len <= room ? t.len : room;
+            if (t.kind == kExRle) {  // decompressor.c:140-173
+                put(kRecFill, w, 0, min(w, min(min(t.len, kRleWindowMax), W - wp)));
+            } else if (t.kind == kExExt) {  // decompressor.c:229-272
+                put(kRecCopyExt, w, t.arg, min(w, W - wp));  // up to the end of the buffer, no wrap
+            } else {  // plain match, decompressor.c:529-572; partial copy when the output fills (:553-557)
+                put(kRecCopy, w, t.arg, w);
             }
-            bb = b2 << wbits;
-            nb = n2 - wbits;
-            put(kRecCopy, match_len, off, match_len);
+            if (w < t.len) { res = kOutputFull; break; }
         }
         if (!resume) break;
         }  // fast / exact alternation
@@ -438,7 +337,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
     if (ntok > 0xFFFFFu || op > 0xFFFFu) fallback = true;
     a.out_len[s] = op;
     a.status[s] = (int8_t)res;
-    if (a.in_consumed) a.in_consumed[s] = ip;
+    if (a.in_consumed) a.in_consumed[s] = r.ip;
     sa.meta[k] = (ntok & 0xFFFFFu) | ((wbits - 8) << 20) | (dict_sel << 23) | ((nlag < 63 ? nlag : 63u) << 25) | (fallback ? kMetaFallback : 0u);
     sa.flagged[s] = fallback ? 1 : 0;
     if (fallback) atomicAdd(sa.flagged_count, 1u);

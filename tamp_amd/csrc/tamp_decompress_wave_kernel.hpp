@@ -12,7 +12,7 @@
 // token it has pulled bytes until more than 24 bits are buffered, i.e. ip = min(n, floor((T + 24) / 8) + 1) for T
 // bits consumed so far.
 #pragma once
-#include "tamp_common.hpp"
+#include "tamp_decode_common.hpp"
 #include "tamp_decompress_kernel.hpp"
 
 namespace tamp_amd {
@@ -35,18 +35,7 @@ __global__ void __launch_bounds__(256) tamp_decompress_wave_kernel(DecompressArg
     uint8_t* const win = smem + 128 + wave * ((1u << a.max_wbits) + kStage);
     uint8_t* const stage = win + (1u << a.max_wbits);
 
-    // prefix-code LUT (decompressor.c:52-57 restated from the code table, compressor.c:33-36)
-    for (uint32_t v = threadIdx.x; v < 128; v += blockDim.x) {  // v = the 7 bits following the leading 1
-        const uint64_t codes_lo = 0x2b2624140b080300ull, codes_hi = 0x00ab27aa9594544bull, nbits = 0x979998877765532ull;
-        uint32_t entry = 0;
-        for (int s = 1; s < 15; s++) {
-            const uint32_t l = (uint32_t)((nbits >> (4 * s)) & 15) - 1u;  // code length without the flag: 2..8
-            const uint32_t code = (uint32_t)((s < 8 ? codes_lo >> (8 * s) : codes_hi >> (8 * (s - 8))) & 0xFF);
-            // code = 1 followed by (l-1) bits; compare those with the top (l-1) bits of v
-            if ((code & ((1u << (l - 1)) - 1)) == (v >> (7 - (l - 1)))) entry = ((l - 1) << 4) | (uint32_t)s;
-        }
-        lut[v] = (uint8_t)entry;
-    }
+    build_prefix_lut(lut);
     __syncthreads();
 
     const uint32_t gw = blockIdx.x * nwaves + wave, tw = gridDim.x * nwaves;
@@ -138,15 +127,14 @@ __global__ void __launch_bounds__(256) tamp_decompress_wave_kernel(DecompressArg
             if (hs == 2 && ((acc >> 48) & 0xFF)) { res = kInvalidConf; break; }
             take(8 * hs);
             ip_ref = hs;
-            const uint32_t wbits = ((h0 >> 5) & 7) + 8, lbits = ((h0 >> 3) & 3) + 5;
-            const bool custom = (h0 >> 2) & 1, extended = (h0 >> 1) & 1, dreset = h0 & 1;
+            const StreamHeader hd = decode_header(h0);
+            const uint32_t wbits = hd.wbits, lbits = hd.lbits, minp = hd.minp;
+            const bool extended = hd.extended;
             if (wbits > a.max_wbits) { res = kInvalidConf; break; }
             const uint32_t W = 1u << wbits, mask = W - 1;
-            const uint32_t minp = (uint32_t)min_pattern_size((int)wbits, (int)lbits);
-            const uint32_t table = (!extended || lbits >= 7) ? 2u : (lbits == 6 ? 1u : 0u);
-            const uint8_t* const seed_default = a.seed_dicts + ((size_t)table << 15);
+            const uint8_t* const seed_default = a.seed_dicts + ((size_t)hd.table << 15);
             const uint8_t* seed = seed_default;
-            if (custom) {
+            if (hd.custom) {
                 if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
                 seed = a.dict;
             }
@@ -251,7 +239,7 @@ __global__ void __launch_bounds__(256) tamp_decompress_wave_kernel(DecompressArg
                 if (sym == kSymFlush) {  // decompressor.c:501-514: drop to the byte boundary
                     take(used);
                     take((8 - (T & 7)) & 7);
-                    if (dreset && last_flush) {
+                    if (hd.dreset && last_flush) {
                         wp = 0;
                         seed = seed_default;
                         load_window(seed);
