@@ -204,6 +204,8 @@ int tamp_batch_decompress(const uint8_t *dictionary, size_t dictionary_len, uint
  * state_stride >= tamp_amd_decoder_state_size(window_bits_max), a multiple of 16.  One call advances every object by
  * one step: object i sees in[in_off[i] .. +in_len[i]) and out_cap[i] bytes of room, and status / out_len /
  * in_consumed come back as from the reference's call.  Input that was not consumed must be offered again.
+ * `mem` and `stream` as for tamp_batch_compress: with TAMP_AMD_MEM_HOST the library stages the objects, input and output
+ * itself on its own streams (`stream` is not used) and writes nothing of out[] behind out_len[i].
  */
 typedef struct TampAmdDecoderState {
     uint32_t bit_buffer;            /* bits pulled from the input and not yet decoded, left aligned */
@@ -246,6 +248,7 @@ int tamp_batch_decompress_resume(void *states, size_t state_stride, uint8_t wind
  * with the reference's results per object: status (TAMP_OK / TAMP_OUTPUT_FULL / TAMP_EXCESS_BITS), bytes written,
  * input bytes consumed -- including calls whose output buffer fills up.  Whole segments (everything between two
  * flush points, known up front) are the batch kernel's job: tamp_batch_compress / tamp_amd_compress_segment.
+ * Host memory as for tamp_batch_decompress_resume: library streams, `stream` not used, nothing behind out_len[i] written.
  */
 typedef struct TampAmdEncoderState {
     uint32_t bit_buffer;      /* pending output bits, left aligned (the header sits here after init) */
@@ -362,8 +365,9 @@ float tamp_amd_last_kernel_ms(void);
 
 /* Releases the device scratch the library keeps between calls on `device` -- decoder window slabs and the split
  * decoder's token-record slab, one set per HIP stream that ever decoded (up to a quarter of the free device memory, 8 GiB
- * at most, per stream) -- and the staging buffers of the host-memory batch calls (pinned host memory sized by the largest
- * output extent ever staged, device chunk buffers).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.
+ * at most, per stream) -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
+ * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
+ * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.
  * (The library itself falls back to decoders without scratch when an allocation fails; this call is for callers that
  * want the memory back.) */
 long long tamp_amd_trim(int device);

@@ -69,14 +69,19 @@ struct DeviceCtx {
             size_t bytes = 0;
             hipError_t need(size_t n) {
                 if (n <= bytes) return hipSuccess;
-                if (p) (void)hipFree(p);
-                p = nullptr, bytes = 0;
+                release();
                 n += n / 4 + 4096;
                 hipError_t e = hipMalloc(&p, n);
                 if (e == hipSuccess) bytes = n;
                 return e;
             }
-        } in[kDepth], out[kDepth], meta[kDepth], dict;
+            size_t release() {  // -> the bytes freed
+                const size_t n = p ? bytes : 0;
+                if (p) (void)hipFree(p);
+                p = nullptr, bytes = 0;
+                return n;
+            }
+        } in[kDepth], out[kDepth], meta[kDepth], state[kDepth], dict;  // (state: the rows of HostBatch::states)
         // pinned host staging for output slabs that do not tile their extent (gaps, padding, permuted offsets): the chunk's
         // extent comes back in ONE transfer and the produced bytes are placed by the host
         struct Pinned {
@@ -84,12 +89,17 @@ struct DeviceCtx {
             size_t bytes = 0;
             hipError_t need(size_t n) {
                 if (n <= bytes) return hipSuccess;
-                if (p) (void)hipHostFree(p);
-                p = nullptr, bytes = 0;
+                release();
                 n += n / 4 + 4096;
                 hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
                 if (e == hipSuccess) bytes = n;
                 return e;
+            }
+            size_t release() {  // -> the bytes freed
+                const size_t n = p ? bytes : 0;
+                if (p) (void)hipHostFree(p);
+                p = nullptr, bytes = 0;
+                return n;
             }
         } stage[kDepth];
     } pipe;
@@ -186,15 +196,10 @@ int get_ctx(int device, DeviceCtx** out) {
     return TAMP_OK;
 }
 
-struct DevBuf {  // RAII device allocation for host-memory calls
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
+// header byte 0 of a stream from its five fields, compressor.c:236-241 (read back by decompressor.c:276-297)
+uint8_t header_byte(unsigned window, unsigned literal, bool custom_dictionary, bool extended, bool dictionary_reset) {
+    return (uint8_t)(((window - 8) << 5) | ((literal - 5) << 3) | (custom_dictionary << 2) | (extended << 1) | dictionary_reset);
+}
 
 thread_local bool t_timing_outer = false;  // a caller's event pair spans several inner launches (up to sixteen long streams)
 void timing_begin(hipStream_t st) {
@@ -501,10 +506,8 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
     a.wbits = conf->window, a.lbits = conf->literal, a.extended = conf->extended != 0;
     a.dict_reset = conf->dictionary_reset != 0;
     a.lazy = conf->lazy_matching != 0;
-    // header byte, compressor.c:236-241 (+ a zero second byte when dictionary_reset is set)
-    const uint8_t header = (uint8_t)(((conf->window - 8) << 5) | ((conf->literal - 5) << 3) |
-                                     ((conf->use_custom_dictionary != 0) << 2) | ((conf->extended != 0) << 1) |
-                                     (conf->dictionary_reset != 0));
+    // header byte (+ a zero second byte when dictionary_reset is set)
+    const uint8_t header = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
     a.nlead = conf->dictionary_reset ? 2 : 1;
     a.lead = (uint16_t)(header << 8);
     a.seg_flags = 0;
@@ -1379,7 +1382,8 @@ bool conf_valid(const TampAmdConf* c) {
 // consecutive streams and each chunk goes copy-in -> kernel -> copy-out on one of three library streams, so the PCIe
 // transfers of neighbouring chunks (both directions) overlap the kernels.  A feeder thread issues copy-in + launch,
 // the calling thread issues copy-out: with pageable memory hipMemcpyAsync blocks its caller, and two issuers keep
-// both directions busy anyway.  Device staging is kept between calls.
+// both directions busy anyway.  Device staging is kept between calls.  The object calls (tamp_batch_*_resume) and the
+// piece / segment calls run here too: their objects' state rows travel with the chunks (HostBatch::states).
 // ---------------------------------------------------------------------------------------------
 struct HostBatch {
     const uint8_t* in;
@@ -1392,6 +1396,12 @@ struct HostBatch {
     int8_t* status;
     uint32_t* in_consumed;  // decompress only, may be null
     size_t n;
+    uint8_t* states = nullptr;  // optional per-stream state rows of state_stride bytes: in before the launch, out after it
+    size_t state_stride = 0;
+    const uint8_t* lead = nullptr;  // one-stream batches only: nlead bytes in front of the stream's input, counted in in_len[0]
+    size_t nlead = 0;
+    bool exact_out = false;    // never the whole-extent copy-back: nothing behind out_len[i] is written (HostChunk)
+    bool drop_failed = false;  // (with exact_out) a stream whose status is not TAMP_OK produces nothing: out_len = 0
 };
 
 struct HostChunk {
@@ -1431,7 +1441,7 @@ void plan_host_chunks(const HostBatch& b, size_t min_streams, uint64_t min_bytes
                                            b.out_off[i1] + b.out_cap[i1] - b.out_off[i0]);
             if ((i1 - i0 >= min_streams && have >= min_bytes) || with > max_bytes) break;
         }
-        bool packed = true;
+        bool packed = !b.exact_out;
         for (size_t i = i0 + 1; i < i1 && packed; i++) packed = b.out_off[i] == b.out_off[i - 1] + b.out_cap[i - 1];
         chunks.push_back({i0, i1, b.in_off[i0], b.in_off[i1 - 1] + b.in_len[i1 - 1], b.out_off[i0],
                           b.out_off[i1 - 1] + b.out_cap[i1 - 1], packed});
@@ -1454,6 +1464,7 @@ struct HostSlot {  // device views of one chunk: offsets stay absolute, the data
     const uint32_t *in_len, *out_cap;
     uint32_t *out_len, *in_consumed;
     int8_t* status;
+    uint8_t* states;  // row 0 = stream i0 of the chunk, or null
 };
 using HostLaunch = std::function<int(const HostSlot&, size_t count, const uint8_t* d_dict, hipStream_t)>;
 
@@ -1481,6 +1492,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         HIP_OK(P.in[j].need(max_in + 64));  // the kernels' vector loads may run past the last byte
         HIP_OK(P.out[j].need(max_out + 1));
         HIP_OK(P.meta[j].need(meta_bytes));
+        if (b.states) HIP_OK(P.state[j].need(max_cnt * b.state_stride));
     }
     auto slot_of = [&](int j, const HostChunk& ch) {
         HostSlot s;
@@ -1494,6 +1506,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         s.status = reinterpret_cast<int8_t*>(m);
         s.in = static_cast<const uint8_t*>(P.in[j].p) - ch.in_lo;
         s.out = static_cast<uint8_t*>(P.out[j].p) - ch.out_lo;
+        s.states = b.states ? static_cast<uint8_t*>(P.state[j].p) : nullptr;
         return s;
     };
     auto feed = [&](size_t k) -> int {  // copy-in + launch of chunk k
@@ -1502,8 +1515,12 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         const HostSlot s = slot_of(j, ch);
         const size_t cnt = ch.i1 - ch.i0;
         hipStream_t st = P.s[j];
-        if (ch.in_hi > ch.in_lo)
-            HIP_OK(hipMemcpyAsync(P.in[j].p, b.in + ch.in_lo, ch.in_hi - ch.in_lo, hipMemcpyHostToDevice, st));
+        uint8_t* const d_in = static_cast<uint8_t*>(P.in[j].p);
+        if (b.nlead) HIP_OK(hipMemcpyAsync(d_in, b.lead, b.nlead, hipMemcpyHostToDevice, st));
+        if (ch.in_hi > ch.in_lo + b.nlead)
+            HIP_OK(hipMemcpyAsync(d_in + b.nlead, b.in + ch.in_lo, ch.in_hi - ch.in_lo - b.nlead, hipMemcpyHostToDevice, st));
+        if (b.states)
+            HIP_OK(hipMemcpyAsync(s.states, b.states + ch.i0 * b.state_stride, cnt * b.state_stride, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.in_off), b.in_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.out_off), b.out_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.in_len), b.in_len + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
@@ -1524,7 +1541,12 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         HIP_OK(hipMemcpyAsync(b.out_len + ch.i0, s.out_len, cnt * 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(b.status + ch.i0, s.status, cnt, hipMemcpyDeviceToHost, st));
         if (b.in_consumed) HIP_OK(hipMemcpyAsync(b.in_consumed + ch.i0, s.in_consumed, cnt * 4, hipMemcpyDeviceToHost, st));
+        if (b.states)
+            HIP_OK(hipMemcpyAsync(b.states + ch.i0 * b.state_stride, s.states, cnt * b.state_stride, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
+        if (b.drop_failed)
+            for (size_t i = ch.i0; i < ch.i1; i++)
+                if (b.status[i] != TAMP_OK) b.out_len[i] = 0;
         // (staging pays when the extent is mostly produced bytes; a sparse or permuted batch can span gigabytes for a few
         // megabytes of output -- those, and extents above 512 MiB of pinned memory per slot, take the merged copies below)
         size_t produced = 0;
@@ -1640,9 +1662,7 @@ tamp_res encoder_state_fill(TampAmdEncoderState* s, unsigned char* window, const
     if (append) {  // FLUSH padded to 16 bits: with the previous stream's trailing FLUSH a dictionary reset (:227-235)
         s->bit_buffer = 0xABu << 23, s->bit_buffer_pos = 16, s->last_was_flush = 1;
     } else {  // header byte (+ a zero byte when dictionary_reset), compressor.c:236-241
-        const uint32_t header = ((conf->window - 8u) << 5) | ((conf->literal - 5u) << 3) |
-                                ((conf->use_custom_dictionary ? 1u : 0u) << 2) | ((conf->extended ? 1u : 0u) << 1) |
-                                (conf->dictionary_reset ? 1u : 0u);
+        const uint32_t header = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
         s->bit_buffer = header << 24, s->bit_buffer_pos = conf->dictionary_reset ? 16 : 8;
     }
     return TAMP_OK;
@@ -1652,6 +1672,15 @@ size_t env_or(const char* name, size_t dflt) {  // tuning knobs of the host-memo
     const char* e = getenv(name);
     const long v = e ? atol(e) : 0;
     return v > 0 ? (size_t)v : dflt;
+}
+
+// Chunks of a host-memory decode batch, and of the object calls (tamp_batch_*_resume): the lane-per-stream decoders want
+// tens of thousands of streams per launch (launch_decompress)
+std::vector<HostChunk> plan_wide_chunks(const DeviceCtx* ctx, const HostBatch& b) {
+    std::vector<HostChunk> chunks;
+    plan_host_chunks(b, env_or("TAMP_AMD_HOST_CHUNK_STREAMS", (size_t)ctx->cu_count * 128),
+                     (uint64_t)env_or("TAMP_AMD_HOST_CHUNK_MB", 32) << 20, 1ull << 30, chunks);
+    return chunks;
 }
 
 // TAMP_AMD_ALL_DEVICES with host memory: the streams are independent, so the batch is cut into one contiguous range
@@ -1823,8 +1852,7 @@ long long tamp_amd_trim(int device) {
     {   // block-mode tables and the expensive-first ordering's gathered tables (round 5)
         std::lock_guard<std::mutex> blk_lock(ctx->blk_mu);
         if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-        for (auto& kv : ctx->blk_scratch)
-            if (kv.second.p) { (void)hipFree(kv.second.p); freed += (long long)kv.second.bytes; kv.second.p = nullptr, kv.second.bytes = 0; }
+        for (auto& kv : ctx->blk_scratch) freed += (long long)kv.second.release();
         {   // expensive-first tables: a stream's enqueue lock first (a call in flight on it finishes its launches), then the map's
             std::vector<hipStream_t> streams;
             {
@@ -1835,28 +1863,24 @@ long long tamp_amd_trim(int device) {
                 std::lock_guard<std::mutex> enqueue(ctx->enqueue_lock(s2));
                 if (hipStreamSynchronize(s2) != hipSuccess) (void)hipGetLastError();
                 std::lock_guard<std::mutex> lpt_lock(ctx->lpt_mu);
-                auto& g = ctx->lpt_scratch[s2];
-                if (g.p) { (void)hipFree(g.p); freed += (long long)g.bytes; g.p = nullptr, g.bytes = 0; }
+                freed += (long long)ctx->lpt_scratch[s2].release();
             }
         }
         std::lock_guard<std::mutex> long_lock(ctx->long_mu);  // (the long-stream decoder's chunk tables and records)
-        for (auto& kv : ctx->long_scratch)
-            if (kv.second.p) { (void)hipFree(kv.second.p); freed += (long long)kv.second.bytes; kv.second.p = nullptr, kv.second.bytes = 0; }
-        for (auto& kv : ctx->long_maps)
-            if (kv.second.p) { (void)hipFree(kv.second.p); freed += (long long)kv.second.bytes; kv.second.p = nullptr, kv.second.bytes = 0; }
-        for (auto& kv : ctx->long_spec)
-            if (kv.second.p) { (void)hipFree(kv.second.p); freed += (long long)kv.second.bytes; kv.second.p = nullptr, kv.second.bytes = 0; }
+        for (auto* m : {&ctx->long_scratch, &ctx->long_maps, &ctx->long_spec})
+            for (auto& kv : *m) freed += (long long)kv.second.release();
     }
     {   // the host-memory pipeline: pinned staging of non-tiling output slabs (it grows with the largest extent ever staged,
-        // possibly gigabytes of pinned RAM) and the device-side chunk buffers; both grow again on demand
-        std::lock_guard<std::mutex> pipe_lock(ctx->pipe.mu);
+        // possibly gigabytes of pinned RAM), the device-side chunk and state-row buffers, the custom dictionary; all grow
+        // again on demand
+        DeviceCtx::HostPipe& P = ctx->pipe;
+        std::lock_guard<std::mutex> pipe_lock(P.mu);
         for (int i = 0; i < DeviceCtx::HostPipe::kDepth; i++) {
-            if (ctx->pipe.s[i] && hipStreamSynchronize(ctx->pipe.s[i]) != hipSuccess) (void)hipGetLastError();
-            auto& st = ctx->pipe.stage[i];
-            if (st.p) { (void)hipHostFree(st.p); freed += (long long)st.bytes; st.p = nullptr, st.bytes = 0; }
-            for (auto* g : {&ctx->pipe.in[i], &ctx->pipe.out[i], &ctx->pipe.meta[i]})
-                if (g->p) { (void)hipFree(g->p); freed += (long long)g->bytes; g->p = nullptr, g->bytes = 0; }
+            if (P.s[i] && hipStreamSynchronize(P.s[i]) != hipSuccess) (void)hipGetLastError();
+            freed += (long long)P.stage[i].release();
+            for (auto* g : {&P.in[i], &P.out[i], &P.meta[i], &P.state[i]}) freed += (long long)g->release();
         }
+        freed += (long long)P.dict.release();
     }
     return freed;
 }
@@ -1955,12 +1979,8 @@ int tamp_batch_decompress(const uint8_t* dictionary, size_t dictionary_len, uint
     if (n_streams == 0) return TAMP_OK;
     dictionary_len = std::min(dictionary_len, kSeedTable);
     const HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams};
-    std::vector<HostChunk> chunks;
-    // the lane-per-stream decoders want tens of thousands of streams per launch (launch_decompress)
-    plan_host_chunks(b, env_or("TAMP_AMD_HOST_CHUNK_STREAMS", (size_t)ctx->cu_count * 128),
-                     (uint64_t)env_or("TAMP_AMD_HOST_CHUNK_MB", 32) << 20, 1ull << 30, chunks);
     uint32_t* no_consumed = nullptr;
-    return run_host_batch(ctx, device, b, chunks, dictionary, dictionary_len,
+    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), dictionary, dictionary_len,
                           [&](const HostSlot& s, size_t count, const uint8_t* d_dict, hipStream_t cs) {
         return launch_decompress(ctx, d_dict, d_dict ? dictionary_len : 0, max_window_bits, s.in, s.in_off, s.in_len, s.out,
                                  s.out_off, s.out_cap, s.out_len, s.status, in_consumed ? s.in_consumed : no_consumed,
@@ -1984,8 +2004,7 @@ tamp_res tamp_amd_decoder_state_init(void* state, const TampAmdConf* conf, uint8
     if (!conf->use_custom_dictionary)
         seed_dictionary_host(reinterpret_cast<unsigned char*>(s + 1), (size_t)1 << conf->window,
                              conf->extended ? conf->literal : 8);
-    s->conf = (uint8_t)(((conf->window - 8) << 5) | ((conf->literal - 5) << 3) | ((conf->use_custom_dictionary ? 1 : 0) << 2) |
-                        ((conf->extended ? 1 : 0) << 1) | (conf->dictionary_reset ? 1 : 0));
+    s->conf = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
     s->flags = 1;
     return TAMP_OK;
 }
@@ -2009,44 +2028,13 @@ int tamp_batch_decompress_resume(void* states, size_t state_stride, uint8_t wind
         return launch_decompress_resume(ctx, static_cast<uint8_t*>(states), state_stride, window_bits_max, in, in_off,
                                         in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams, st);
     if (n_streams == 0) return TAMP_OK;
-    uint64_t in_end = 0, out_end = 0;
-    for (size_t i = 0; i < n_streams; i++) {
-        in_end = std::max(in_end, in_off[i] + in_len[i]);
-        out_end = std::max(out_end, out_off[i] + out_cap[i]);
-    }
-    DevBuf d_sta, d_in, d_out, d_io, d_il, d_oo, d_oc, d_ol, d_st, d_ic;
-    HIP_OK(d_sta.alloc(n_streams * state_stride));
-    HIP_OK(d_in.alloc(in_end + 64));
-    HIP_OK(d_out.alloc(out_end));
-    HIP_OK(d_io.alloc(n_streams * 8));
-    HIP_OK(d_il.alloc(n_streams * 4));
-    HIP_OK(d_oo.alloc(n_streams * 8));
-    HIP_OK(d_oc.alloc(n_streams * 4));
-    HIP_OK(d_ol.alloc(n_streams * 4));
-    HIP_OK(d_ic.alloc(n_streams * 4));
-    HIP_OK(d_st.alloc(n_streams));
-    HIP_OK(hipMemcpyAsync(d_sta.p, states, n_streams * state_stride, hipMemcpyHostToDevice, st));
-    if (in_end) HIP_OK(hipMemcpyAsync(d_in.p, in, in_end, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_io.p, in_off, n_streams * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_il.p, in_len, n_streams * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_oo.p, out_off, n_streams * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_oc.p, out_cap, n_streams * 4, hipMemcpyHostToDevice, st));
-    rc = launch_decompress_resume(ctx, d_sta.as<uint8_t>(), state_stride, window_bits_max, d_in.as<uint8_t>(),
-                                  d_io.as<uint64_t>(), d_il.as<uint32_t>(), d_out.as<uint8_t>(), d_oo.as<uint64_t>(),
-                                  d_oc.as<uint32_t>(), d_ol.as<uint32_t>(), d_st.as<int8_t>(), d_ic.as<uint32_t>(),
-                                  n_streams, st);
-    if (rc != TAMP_OK) return rc;
-    HIP_OK(hipMemcpyAsync(states, d_sta.p, n_streams * state_stride, hipMemcpyDeviceToHost, st));
-    // only what was written goes back: a caller's output buffer is not touched beyond out_len
-    HIP_OK(hipMemcpyAsync(out_len, d_ol.p, n_streams * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(status, d_st.p, n_streams, hipMemcpyDeviceToHost, st));
-    if (in_consumed) HIP_OK(hipMemcpyAsync(in_consumed, d_ic.p, n_streams * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < n_streams; i++)
-        if (out_len[i])
-            HIP_OK(hipMemcpyAsync(out + out_off[i], d_out.as<uint8_t>() + out_off[i], out_len[i], hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return TAMP_OK;
+    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams};
+    b.states = static_cast<uint8_t*>(states), b.state_stride = state_stride, b.exact_out = true;
+    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
+                          [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
+        return launch_decompress_resume(ctx, s.states, state_stride, window_bits_max, s.in, s.in_off, s.in_len, s.out,
+                                        s.out_off, s.out_cap, s.out_len, s.status, s.in_consumed, count, cs);
+    });
 }
 
 size_t tamp_amd_encoder_state_size(uint8_t window_bits_max) {
@@ -2080,43 +2068,13 @@ int tamp_batch_compress_resume(void* states, size_t state_stride, uint8_t window
                                       in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_objects,
                                       st);
     if (n_objects == 0) return TAMP_OK;
-    uint64_t in_end = 0, out_end = 0;
-    for (size_t i = 0; i < n_objects; i++) {
-        in_end = std::max(in_end, in_off[i] + in_len[i]);
-        out_end = std::max(out_end, out_off[i] + out_cap[i]);
-    }
-    DevBuf d_sta, d_in, d_out, d_io, d_il, d_oo, d_oc, d_ol, d_st, d_ic;
-    HIP_OK(d_sta.alloc(n_objects * state_stride));
-    HIP_OK(d_in.alloc(in_end + 64));
-    HIP_OK(d_out.alloc(out_end));
-    HIP_OK(d_io.alloc(n_objects * 8));
-    HIP_OK(d_il.alloc(n_objects * 4));
-    HIP_OK(d_oo.alloc(n_objects * 8));
-    HIP_OK(d_oc.alloc(n_objects * 4));
-    HIP_OK(d_ol.alloc(n_objects * 4));
-    HIP_OK(d_ic.alloc(n_objects * 4));
-    HIP_OK(d_st.alloc(n_objects));
-    HIP_OK(hipMemcpyAsync(d_sta.p, states, n_objects * state_stride, hipMemcpyHostToDevice, st));
-    if (in_end) HIP_OK(hipMemcpyAsync(d_in.p, in, in_end, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_io.p, in_off, n_objects * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_il.p, in_len, n_objects * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_oo.p, out_off, n_objects * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_oc.p, out_cap, n_objects * 4, hipMemcpyHostToDevice, st));
-    rc = launch_compress_resume(ctx, d_sta.as<uint8_t>(), state_stride, window_bits_max, op, write_token,
-                                d_in.as<uint8_t>(), d_io.as<uint64_t>(), d_il.as<uint32_t>(), d_out.as<uint8_t>(),
-                                d_oo.as<uint64_t>(), d_oc.as<uint32_t>(), d_ol.as<uint32_t>(), d_st.as<int8_t>(),
-                                d_ic.as<uint32_t>(), n_objects, st);
-    if (rc != TAMP_OK) return rc;
-    HIP_OK(hipMemcpyAsync(states, d_sta.p, n_objects * state_stride, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(out_len, d_ol.p, n_objects * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(status, d_st.p, n_objects, hipMemcpyDeviceToHost, st));
-    if (in_consumed) HIP_OK(hipMemcpyAsync(in_consumed, d_ic.p, n_objects * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < n_objects; i++)  // only what was written goes back
-        if (out_len[i])
-            HIP_OK(hipMemcpyAsync(out + out_off[i], d_out.as<uint8_t>() + out_off[i], out_len[i], hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return TAMP_OK;
+    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_objects};
+    b.states = static_cast<uint8_t*>(states), b.state_stride = state_stride, b.exact_out = true;
+    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
+                          [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
+        return launch_compress_resume(ctx, s.states, state_stride, window_bits_max, op, write_token, s.in, s.in_off,
+                                      s.in_len, s.out, s.out_off, s.out_cap, s.out_len, s.status, s.in_consumed, count, cs);
+    });
 }
 
 tamp_res tamp_amd_compress(const TampAmdConf* conf, const unsigned char* dictionary, unsigned char* output,
@@ -2623,8 +2581,7 @@ tamp_res tamp_decompressor_init(TampDecompressor* decompressor, const TampConf* 
     if (conf->window > window_bits) return TAMP_INVALID_CONF;
     if (!conf->use_custom_dictionary)
         seed_dictionary_host(window, (size_t)1 << conf->window, conf->extended ? conf->literal : 8);
-    s->conf = (uint8_t)(((conf->window - 8) << 5) | ((conf->literal - 5) << 3) | (conf->use_custom_dictionary << 2) |
-                        (conf->extended << 1) | conf->dictionary_reset);
+    s->conf = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
     s->flags = 1;
     return TAMP_OK;
 }
@@ -2704,15 +2661,12 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
     int rc = get_ctx(device, &ctx);
     if (rc != TAMP_OK) return (tamp_res)rc;
     const size_t W = (size_t)1 << conf->window;
-    const size_t SS = W + kSegStateExtra;
     SegmentSpec seg;
     seg.flags = kSegSave | (resume ? kSegResume : 0) | ((finish && flush_token) ? kSegFlushToken : 0) | (finish ? 0 : kSegPartial);
     if (append_marker) {  // compressor.c:227-235: FLUSH (9 bits) padded to 16 bits instead of a header
         seg.nlead = 2, seg.lead = (uint16_t)(0xABu << 7);
     } else if (emit_header) {
-        const uint8_t header = (uint8_t)(((conf->window - 8) << 5) | ((conf->literal - 5) << 3) |
-                                         ((conf->use_custom_dictionary != 0) << 2) | ((conf->extended != 0) << 1) |
-                                         (conf->dictionary_reset != 0));
+        const uint8_t header = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
         seg.nlead = conf->dictionary_reset ? 2 : 1, seg.lead = (uint16_t)(header << 8);
     } else {
         seg.nlead = 0, seg.lead = 0;
@@ -2720,9 +2674,17 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
     // what leads the input: the bytes a carried run / extended match has consumed (they are window bytes: the last byte
     // written, resp. window[pos .. pos + count)), then the carried tail of the 16-byte ring
     std::vector<unsigned char> prefix;
-    std::vector<unsigned char> stbuf(SS, 0);
+    std::vector<unsigned char> stbuf(W + kSegStateExtra, 0);  // the kernel's state slot (kSlot* fields behind the window)
     std::memcpy(stbuf.data(), window_state, W);
-    stbuf[W] = (unsigned char)(*window_pos & 0xFF), stbuf[W + 1] = (unsigned char)(*window_pos >> 8);
+    auto put = [&](uint32_t field, uint32_t v, int bytes) {
+        for (int k = 0; k < bytes; k++) stbuf[W + field + k] = (unsigned char)(v >> (8 * k));
+    };
+    auto get = [&](uint32_t field, int bytes) {
+        uint32_t v = 0;
+        for (int k = 0; k < bytes; k++) v |= (uint32_t)stbuf[W + field + k] << (8 * k);
+        return v;
+    };
+    put(kSlotWindowPos, *window_pos, 2);
     if (carry && resume) {
         if (carry->tail_len > 16 || carry->bit_count > 31 || (carry->rle_count && carry->ext_count) ||
             (size_t)carry->ext_pos + carry->ext_count > W || ((emit_header || append_marker) && carry->bit_count))
@@ -2731,11 +2693,11 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         prefix.insert(prefix.end(), carry->rle_count, last);
         prefix.insert(prefix.end(), window_state + carry->ext_pos, window_state + carry->ext_pos + carry->ext_count);
         prefix.insert(prefix.end(), carry->tail, carry->tail + carry->tail_len);
-        stbuf[W + 3] = carry->rle_count, stbuf[W + 4] = carry->ext_count, stbuf[W + 5] = carry->bit_count;
-        stbuf[W + 6] = (unsigned char)(carry->ext_pos & 0xFF), stbuf[W + 7] = (unsigned char)(carry->ext_pos >> 8);
-        for (int k = 0; k < 4; k++) stbuf[W + 16 + k] = (unsigned char)(carry->bits >> (8 * k));
+        put(kSlotRle, carry->rle_count, 1), put(kSlotExtCount, carry->ext_count, 1), put(kSlotNbits, carry->bit_count, 1);
+        put(kSlotExtPos, carry->ext_pos, 2), put(kSlotBits, carry->bits, 4);
     }
     const uint64_t zero = 0;
+    const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
     if (finish && !flush_token && !resume && emit_header && !append_marker && prefix.empty() && !conf->extended &&
         !conf->lazy_matching && conf->literal == 8 && conf->window <= 14 && input_size >= ((size_t)256 << 10) &&
         input_size <= 0xFFFFFF00ull) {
@@ -2743,11 +2705,10 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         // all workgroups (launch_compress_blocks).  The object afterwards holds what the reference's would: every consumed
         // byte was written (compressor.c:651-657), so the window is the stream's last W bytes at their ring positions.
         const uint32_t ilen1 = (uint32_t)input_size;
-        const uint32_t ocap1 = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
         uint32_t olen1 = 0;
         int8_t st1 = TAMP_ERROR;
         rc = tamp_batch_compress(conf, conf->use_custom_dictionary ? window_state : nullptr, input, &zero, &ilen1, output, &zero,
-                                 &ocap1, &olen1, &st1, 1, ilen1, TAMP_AMD_MEM_HOST, device, nullptr);
+                                 &ocap, &olen1, &st1, 1, ilen1, TAMP_AMD_MEM_HOST, device, nullptr);
         if (rc != TAMP_OK) return (tamp_res)rc;
         if (output_written_size) *output_written_size = olen1;
         if (st1 == TAMP_OK) {
@@ -2758,63 +2719,38 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         }
         return st1;
     }
-    DevBuf d_in, d_out, d_io, d_il, d_oo, d_oc, d_ol, d_st, d_state, d_dict;
     if ((uint64_t)prefix.size() + (uint64_t)input_size > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;  // (32-bit stream lengths)
+    // ONE stream on the host-memory pipeline, the prefix in front of the input, the state slot its state row.  A piece that
+    // did not complete leaves window and carry as they came in, so its bytes must not count either: a caller that consumed
+    // them and offered the piece again would emit them twice (drop_failed).  (A finishing call keeps the reference's
+    // contract -- what fitted is delivered with TAMP_OUTPUT_FULL, compressor.c:65-75.)
     const uint32_t ilen = (uint32_t)(prefix.size() + input_size);
-    const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
-    HIP_OK(d_in.alloc((size_t)ilen + 64));
-    HIP_OK(d_out.alloc(output_size));
-    HIP_OK(d_io.alloc(8));
-    HIP_OK(d_il.alloc(4));
-    HIP_OK(d_oo.alloc(8));
-    HIP_OK(d_oc.alloc(4));
-    HIP_OK(d_ol.alloc(4));
-    HIP_OK(d_st.alloc(1));
-    HIP_OK(d_state.alloc(SS));
-    hipStream_t st = nullptr;
-    if (!prefix.empty()) HIP_OK(hipMemcpyAsync(d_in.p, prefix.data(), prefix.size(), hipMemcpyHostToDevice, st));
-    if (input_size)
-        HIP_OK(hipMemcpyAsync(d_in.as<uint8_t>() + prefix.size(), input, input_size, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_io.p, &zero, 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_il.p, &ilen, 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_oo.p, &zero, 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_oc.p, &ocap, 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_state.p, stbuf.data(), SS, hipMemcpyHostToDevice, st));
-    const uint8_t* dict = nullptr;
-    if (!resume && conf->use_custom_dictionary) {  // a fresh stream with a custom dictionary: the state buffer holds it
-        HIP_OK(d_dict.alloc(W));
-        HIP_OK(hipMemcpyAsync(d_dict.p, window_state, W, hipMemcpyHostToDevice, st));
-        dict = d_dict.as<uint8_t>();
-    }
-    rc = launch_compress(ctx, conf, dict, d_in.as<uint8_t>(), d_io.as<uint64_t>(), d_il.as<uint32_t>(),
-                         d_out.as<uint8_t>(), d_oo.as<uint64_t>(), d_oc.as<uint32_t>(), d_ol.as<uint32_t>(),
-                         d_st.as<int8_t>(), 1, ilen ? ilen : 16, st, &seg, d_state.as<uint8_t>());
-    if (rc != TAMP_OK) return (tamp_res)rc;
     uint32_t olen = 0;
     int8_t status = TAMP_ERROR;
-    HIP_OK(hipMemcpyAsync(&olen, d_ol.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(&status, d_st.p, 1, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(stbuf.data(), d_state.p, SS, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    // A piece that did not complete leaves window and carry as they came in, so its bytes must not count either: a caller
-    // that consumed them and offered the piece again would emit them twice.  (A finishing call keeps the reference's
-    // contract -- what fitted is delivered with TAMP_OUTPUT_FULL, compressor.c:65-75.)
-    if (!finish && status != TAMP_OK) olen = 0;
-    if (olen) HIP_OK(hipMemcpy(output, d_out.p, olen, hipMemcpyDeviceToHost));
+    HostBatch b = {input, &zero, &ilen, output, &zero, &ocap, &olen, &status, nullptr, 1};
+    b.states = stbuf.data(), b.state_stride = stbuf.size(), b.lead = prefix.data(), b.nlead = prefix.size();
+    b.exact_out = true, b.drop_failed = !finish;
+    std::vector<HostChunk> one;
+    plan_host_chunks(b, 1, 0, ~0ull, one);
+    // (a fresh stream with a custom dictionary: window_state holds it)
+    rc = run_host_batch(ctx, device, b, one, !resume && conf->use_custom_dictionary ? window_state : nullptr, W,
+                        [&](const HostSlot& s, size_t, const uint8_t* d_dict, hipStream_t cs) {
+        return launch_compress(ctx, conf, d_dict, s.in, s.in_off, s.in_len, s.out, s.out_off, s.out_cap, s.out_len, s.status, 1,
+                               ilen ? ilen : 16, cs, &seg, s.states);
+    });
+    if (rc != TAMP_OK) return (tamp_res)rc;
     if (output_written_size) *output_written_size = olen;
     if (status == TAMP_OK) {
         std::memcpy(window_state, stbuf.data(), W);
-        *window_pos = (uint16_t)(stbuf[W] | (stbuf[W + 1] << 8));
-        if (token_written) *token_written = stbuf[W + 2];
+        *window_pos = (uint16_t)get(kSlotWindowPos, 2);
+        if (token_written) *token_written = (int)get(kSlotToken, 1);
         if (carry) {
             std::memset(carry, 0, sizeof *carry);
             if (!finish) {
-                carry->rle_count = stbuf[W + 3], carry->ext_count = stbuf[W + 4], carry->bit_count = stbuf[W + 5];
-                carry->ext_pos = (uint16_t)(stbuf[W + 6] | (stbuf[W + 7] << 8));
-                carry->bits = (uint32_t)stbuf[W + 16] | ((uint32_t)stbuf[W + 17] << 8) | ((uint32_t)stbuf[W + 18] << 16) |
-                              ((uint32_t)stbuf[W + 19] << 24);
-                const uint32_t parsed = (uint32_t)stbuf[W + 9] | ((uint32_t)stbuf[W + 10] << 8) |
-                                        ((uint32_t)stbuf[W + 11] << 16) | ((uint32_t)stbuf[W + 12] << 24);
+                carry->rle_count = (uint8_t)get(kSlotRle, 1), carry->ext_count = (uint8_t)get(kSlotExtCount, 1);
+                carry->bit_count = (uint8_t)get(kSlotNbits, 1), carry->ext_pos = (uint16_t)get(kSlotExtPos, 2);
+                carry->bits = get(kSlotBits, 4);
+                const uint32_t parsed = get(kSlotParsed, 4);
                 const uint32_t left = ilen - parsed;  // < 16: the ring never stays full (compressor.c:704-718)
                 if (parsed > ilen || left > 15) return TAMP_ERROR;
                 carry->tail_len = (uint8_t)left;

@@ -774,11 +774,18 @@ struct Walk {
 #endif
 enum : uint32_t { kActDone = 1, kActRebase = 2, kActContinue = 3 };
 enum : uint8_t { kSegResume = 1, kSegSave = 2, kSegFlushToken = 4, kSegPartial = 8 };
-// Per-stream state slot of the segment calls: the window in ring order, then
-//   [W] u16 window_pos   [W+2] u8 FLUSH token written (out)   [W+3] u8 rle_count   [W+4] u8 extended-match count
-//   [W+5] u8 pending output bits (in: 0..31, a reference object may sit on a whole token; out: 0..7)
-//   [W+6] u16 extended-match window position   [W+9] u32 input bytes parsed (out, unaligned)
-//   [W+16] u32 the pending bits, left aligned (first bit in bit 31; unaligned)
+// Per-stream state slot of the segment calls: the window in ring order, then kSegStateExtra bytes with these fields at
+// these offsets from W (multi-byte fields little endian, unaligned):
+enum : uint32_t {
+    kSlotWindowPos = 0,  // u16 window_pos
+    kSlotToken = 2,      // u8 FLUSH token written (out)
+    kSlotRle = 3,        // u8 rle_count
+    kSlotExtCount = 4,   // u8 extended-match count
+    kSlotNbits = 5,      // u8 pending output bits (in: 0..31, a reference object may sit on a whole token; out: 0..7)
+    kSlotExtPos = 6,     // u16 extended-match window position
+    kSlotParsed = 9,     // u32 input bytes parsed (out)
+    kSlotBits = 16,      // u32 the pending bits, left aligned (first bit in bit 31)
+};
 // The fields behind the token flag are what a TampCompressor carries between two calls that are NOT separated by a
 // flush (compressor.h:13-66: rle_count, extended_match_count / _position, the bit buffer); kSegPartial ends the launch
 // the way tamp_compressor_compress_cb ends a call (compressor.c:681-722): parse steps only while 16 bytes of look-ahead
@@ -1012,7 +1019,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
         } else
         if (st_io && (a.seg_flags & kSegResume)) {
             // window <- saved state (ring order) rotated so that the oldest byte comes first
-            wp0 = (uint32_t)st_io[W] | ((uint32_t)st_io[W + 1] << 8);
+            wp0 = (uint32_t)st_io[W + kSlotWindowPos] | ((uint32_t)st_io[W + kSlotWindowPos + 1] << 8);
             for (uint32_t k = tid; k < W; k += nt) ebuf[k] = st_io[(wp0 + k) & mask];
         } else if ((reinterpret_cast<uintptr_t>(a.dict) & 3) == 0) {
             // window <- dictionary (custom, or the seeded default prepared by the host shim)
@@ -1024,10 +1031,11 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
         // carried over from a call that ended without a flush (kSegStateExtra): pending run / extended match, pending bits
         uint32_t c_rle = 0, c_ext = 0, c_extpos = 0, c_nbits = 0, c_bits = 0;
         if (st_io && (a.seg_flags & kSegResume)) {
-            c_rle = Walk::uni(st_io[W + 3]), c_ext = Walk::uni(st_io[W + 4]), c_nbits = Walk::uni(st_io[W + 5]) & 31u;
-            c_extpos = Walk::uni((uint32_t)st_io[W + 6] | ((uint32_t)st_io[W + 7] << 8));
-            c_bits = Walk::uni((uint32_t)st_io[W + 16] | ((uint32_t)st_io[W + 17] << 8) | ((uint32_t)st_io[W + 18] << 16) |
-                               ((uint32_t)st_io[W + 19] << 24));
+            c_rle = Walk::uni(st_io[W + kSlotRle]), c_ext = Walk::uni(st_io[W + kSlotExtCount]);
+            c_nbits = Walk::uni(st_io[W + kSlotNbits]) & 31u;
+            c_extpos = Walk::uni((uint32_t)st_io[W + kSlotExtPos] | ((uint32_t)st_io[W + kSlotExtPos + 1] << 8));
+            c_bits = Walk::uni((uint32_t)st_io[W + kSlotBits] | ((uint32_t)st_io[W + kSlotBits + 1] << 8) |
+                               ((uint32_t)st_io[W + kSlotBits + 2] << 16) | ((uint32_t)st_io[W + kSlotBits + 3] << 24));
         }
         // bit buffer: leading bytes (header, compressor.c:236-241; FLUSH + pad when appending, :227-235) or the carried
         // bits, rest zero
@@ -2122,12 +2130,12 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
                         if (st_io && (a.seg_flags & kSegSave)) {  // hand the window back in ring order
                             for (uint32_t i = lane; i < W; i += kWave) st_io[i] = (uint8_t)wk.win_l(i);
                             if (lane == 0) {
-                                st_io[W] = (uint8_t)wk.wp();
-                                st_io[W + 1] = (uint8_t)(wk.wp() >> 8);
+                                st_io[W + kSlotWindowPos] = (uint8_t)wk.wp();
+                                st_io[W + kSlotWindowPos + 1] = (uint8_t)(wk.wp() >> 8);
                                 // what stays pending when the call ends without a flush (zero after a drain)
-                                st_io[W + 3] = (uint8_t)wk.rle_count, st_io[W + 4] = (uint8_t)wk.ext_count;
-                                st_io[W + 6] = (uint8_t)wk.ext_pos, st_io[W + 7] = (uint8_t)(wk.ext_pos >> 8);
-                                for (uint32_t k = 0; k < 4; k++) st_io[W + 9 + k] = (uint8_t)(p >> (8 * k));
+                                st_io[W + kSlotRle] = (uint8_t)wk.rle_count, st_io[W + kSlotExtCount] = (uint8_t)wk.ext_count;
+                                st_io[W + kSlotExtPos] = (uint8_t)wk.ext_pos, st_io[W + kSlotExtPos + 1] = (uint8_t)(wk.ext_pos >> 8);
+                                for (uint32_t k = 0; k < 4; k++) st_io[W + kSlotParsed + k] = (uint8_t)(p >> (8 * k));
                             }
                         }
                         act = kActDone;
@@ -2348,7 +2356,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
                     }
                 }
                 if (want) tot += 9;
-                if (st_io && tid == 0) st_io[W + 2] = want ? 1 : 0;
+                if (st_io && tid == 0) st_io[W + kSlotToken] = want ? 1 : 0;
                 __syncthreads();
             }
             // flush whole words (or, at the end, the zero-padded / truncated byte count) to HBM
@@ -2361,9 +2369,9 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
                 // the bits of the last, incomplete byte stay with the stream (partial_flush writes whole bytes only,
                 // compressor.c:65-75); after a drain the byte was padded and written: nothing is carried
                 const uint32_t nb = (partial && !excess) ? (tot & 7u) : 0u;
-                st_io[W + 5] = (uint8_t)nb;
-                st_io[W + 16] = 0, st_io[W + 17] = 0, st_io[W + 18] = 0;
-                st_io[W + 19] = nb ? reinterpret_cast<const uint8_t*>(obuf)[tot >> 3] : 0;
+                st_io[W + kSlotNbits] = (uint8_t)nb;
+                st_io[W + kSlotBits] = 0, st_io[W + kSlotBits + 1] = 0, st_io[W + kSlotBits + 2] = 0;
+                st_io[W + kSlotBits + 3] = nb ? reinterpret_cast<const uint8_t*>(obuf)[tot >> 3] : 0;
             }
             if constexpr (BLOCKM) {
                 // Block mode: the bit buffer's word 0 is word (bit position >> 5) of the stream's output; this block owns the

@@ -1028,6 +1028,170 @@ def test_reference_named_compressor_below_flush_granularity(ta):
             assert got == (wst, wout, wcons), (name, k, op[0])
 
 
+def test_host_memory_object_calls_equal_device_memory(ta, oracle, monkeypatch):
+    """tamp_batch_decompress_resume and tamp_batch_compress_resume (COMPRESS, then FLUSH) with host memory, cut into
+    several chunks, on 300 objects: states, statuses, lengths, consumed counts and produced bytes equal the same calls on
+    device memory, for tiled, gapped and permuted output slabs -- and no byte of the caller's output outside the produced
+    bytes is written (the slabs are pre-filled with 0xEE)."""
+    import ctypes as C
+
+    import torch
+
+    from tamp_amd import _lib
+    from tamp_amd import workloads as wl
+
+    lib = _lib.load()
+    monkeypatch.setenv("TAMP_AMD_HOST_CHUNK_STREAMS", "64")
+    monkeypatch.setenv("TAMP_AMD_HOST_CHUNK_MB", "1")
+    rng = random.Random(77)
+    n = 300
+    plains = [_rand_inputs(rng, wl, rng.choice([0, 1, 300, rng.randrange(2000, 20000)])) for _ in range(n)]
+    blobs = []
+    for x in plains:
+        st, blob = oracle.compress(x, window=10)
+        assert st == 0
+        blobs.append(blob)
+    dev = torch.device("cuda:0")
+
+    def layout(caps, kind):
+        if kind == "tiled":
+            off = np.cumsum(caps, dtype=np.uint64) - caps
+        elif kind == "gapped":
+            gaps = np.array([rng.randrange(1, 50) for _ in caps], dtype=np.uint64)
+            off = np.cumsum(caps + gaps, dtype=np.uint64) - caps
+        else:  # the slabs tile one extent, listed in a shuffled order
+            order = list(range(len(caps)))
+            rng.shuffle(order)
+            off = np.zeros(len(caps), dtype=np.uint64)
+            at = 0
+            for i in order:
+                off[i], at = at, at + int(caps[i])
+        return off, int((off + caps).max()) + 1
+
+    def call(fn, lead, states, chunks, caps, kind):
+        """fn(lead args..., states, in, in_off, in_len, out, out_off, out_cap, out_len, status, consumed, n, mem, dev, stream)
+        once with host and once with device memory -> the host call's results, checked against the device call's."""
+        flat, in_off, in_len = ta.pack_streams(chunks)
+        flat = flat if flat.size else np.zeros(1, np.uint8)
+        out_cap = np.asarray(caps, dtype=np.uint32)
+        out_off, total = layout(out_cap.astype(np.uint64), kind)
+        res = {}
+        for mem in (_lib.MEM_HOST, _lib.MEM_DEVICE):
+            arrs = [states.copy(), flat, in_off, in_len, np.full(total, 0xEE, np.uint8), out_off, out_cap,
+                    np.zeros(n, np.uint32), np.zeros(n, np.int8), np.zeros(n, np.uint32)]
+            if mem == _lib.MEM_DEVICE:
+                arrs = [torch.from_numpy(np.array(a)).to(dev) for a in arrs]
+            ptrs = [C.c_void_p(a.data_ptr()) if mem == _lib.MEM_DEVICE else a.ctypes.data_as(C.c_void_p) for a in arrs]
+            rc = fn(*lead(ptrs[0]), *ptrs[1:], n, mem, 0, None)
+            assert rc == 0
+            if mem == _lib.MEM_DEVICE:
+                torch.cuda.synchronize()
+                arrs = [a.cpu().numpy() for a in arrs]
+            res[mem] = arrs
+        h, d = res[_lib.MEM_HOST], res[_lib.MEM_DEVICE]
+        for k in (0, 7, 8, 9):  # states, out_len, status, consumed
+            assert np.array_equal(h[k], d[k]), (kind, k)
+        outside = np.ones(total, bool)
+        for i in range(n):
+            lo, m = int(out_off[i]), int(h[7][i])
+            assert bytes(h[4][lo : lo + m]) == bytes(d[4][lo : lo + m]), (kind, i)
+            outside[lo : lo + m] = False
+        assert (h[4][outside] == 0xEE).all(), kind
+        return h[0], h[7], h[8], h[9]
+
+    for kind in ("tiled", "gapped", "permuted"):
+        # decoder objects: header from the stream, input and room both cut short in the first step
+        stride = (lib.tamp_amd_decoder_state_size(10) + 15) & ~15
+        one = np.zeros(stride, np.uint8)
+        assert lib.tamp_amd_decoder_state_init(one.ctypes.data_as(C.c_void_p), None, 10) == 0
+        states = np.tile(one, (n, 1))
+        pos = [0] * n
+        for _ in range(3):
+            chunks = [b[pos[i] : pos[i] + rng.choice([0, 5, 700, 1 << 20])] for i, b in enumerate(blobs)]
+            caps = [rng.choice([0, 3, 100, 5000, 25000]) for _ in range(n)]
+            states, _, _, consumed = call(
+                lib.tamp_batch_decompress_resume, lambda p, stride=stride: (p, stride, 10), states, chunks, caps, kind)
+            pos = [p + int(c) for p, c in zip(pos, consumed)]
+        # encoder objects: COMPRESS (some rooms too small), then FLUSH
+        stride = (lib.tamp_amd_encoder_state_size(10) + 15) & ~15
+        one = np.zeros(stride, np.uint8)
+        conf = _lib.TampAmdConf(window=10, literal=8, extended=1)
+        assert lib.tamp_amd_encoder_state_init(one.ctypes.data_as(C.c_void_p), C.byref(conf), 0, 10) == 0
+        states = np.tile(one, (n, 1))
+        seen = set()
+        for op, chunks, tok in ((_lib.OP_COMPRESS, plains, 0), (_lib.OP_FLUSH, [b""] * n, 1)):
+            caps = [rng.choice([0, 7, 300, 30000]) for _ in range(n)]
+            states, _, status, _ = call(
+                lib.tamp_batch_compress_resume, lambda p, stride=stride, op=op, tok=tok: (p, stride, 10, op, tok),
+                states, chunks, caps, kind)
+            seen |= set(status.tolist())
+        assert {_lib.OK, _lib.OUTPUT_FULL} <= seen, (kind, seen)
+
+
+def test_threads_share_the_host_memory_object_path(ta):
+    """Two threads each drive a Compressor in forced pieces (one piece call per write) while a third steps a
+    host-memory DecoderBatch: every stream equals the same thread's run done alone."""
+    import io
+    import threading
+
+    from tamp_amd import workloads as wl
+
+    rng = random.Random(31)
+    text = wl.synth_text(1, 60000, first_index=11)[0].tobytes()
+    scripts = []
+    for _ in range(2):
+        ops, pos = [], 0
+        while pos < len(text) // 2:
+            k = rng.randrange(1, 1000)
+            ops.append(text[pos : pos + k])
+            pos += k
+            if rng.random() < 0.1:
+                ops.append(None)  # flush
+        scripts.append(ops)
+    blob = ta.compress(text, window=10)
+    feeds = [[rng.randrange(1, 400) for _ in range(40)] for _ in range(64)]
+
+    def encode(ops):
+        f = io.BytesIO()
+        c = ta.Compressor(f, window=10)
+        c.PIECE_MIN = 1
+        for op in ops:
+            if op is None:
+                c.flush()
+            else:
+                c.write(op)
+        c.flush(write_token=False)
+        return f.getvalue()
+
+    def decode():
+        batch = ta.DecoderBatch(64, window_bits=10)
+        pos, got = [0] * 64, [bytearray() for _ in range(64)]
+        for step in range(40):
+            status, outs, consumed = batch.step([blob[pos[i] : pos[i] + feeds[i][step]] for i in range(64)], 3000)
+            for i in range(64):
+                pos[i] += int(consumed[i])
+                got[i] += outs[i]
+        return [bytes(g) for g in got]
+
+    jobs = [lambda: encode(scripts[0]), lambda: encode(scripts[1]), decode]
+    alone = [job() for job in jobs]
+    together, errs = [None] * 3, []
+
+    def run(k):
+        try:
+            together[k] = jobs[k]()
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+
+    threads = [threading.Thread(target=run, args=(k,)) for k in range(3)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errs, errs
+    assert together == alone
+
+
 def test_reference_named_object_mixes_token_level_and_segment_level_calls(ta, oracle):
     """One TampCompressor object driven through both device paths: pieces below flush granularity (token-by-token
     kernel, state in the object), then whole segments of several KiB (the batch kernel's segment mode, taken when the
