@@ -204,3 +204,79 @@ def test_worst_case_size_bound(oracle):
         for ext in (False, True):
             st, comp = oracle.compress(data, literal=lit, extended=ext)
             assert st == 0 and len(comp) <= worst_case_compressed_size(4096, lit)
+
+
+def _matrix_bytes(spec):
+    """{"pieces": [[workload, row], ...], "patch": [pos, byte] (optional), "sha256": ...} of
+    tests/golden/config_matrix.json -> the bytes it names."""
+    if spec is None:
+        return None
+    data = bytearray(b"".join(workload_rows(name)(row + 1)[row].tobytes() for name, row in spec["pieces"]))
+    if spec.get("patch"):
+        data[spec["patch"][0]] = spec["patch"][1]
+    assert hashlib.sha256(data).hexdigest() == spec["sha256"], ("generator drifted", spec["pieces"])
+    return bytes(data)
+
+
+def test_config_matrix_stream_scripts(oracle):
+    """tests/golden/config_matrix.json: one reference compressor object at every literal width, windows 2^8..2^15, every
+    (window, literal) pair with a 3-byte minimum match, both formats, custom dictionaries, dictionary_reset and lazy
+    matching -- Oracle.stream_script emits the same bytes, and the decodable ones decode back to the writes."""
+    recs = load_golden("config_matrix.json")["streams"]
+    seen = {(r["conf"]["window"], r["conf"]["literal"], r["conf"]["extended"]) for r in recs}
+    for w in (8, 10, 13, 14, 15):
+        for lit in (5, 6, 7, 8):
+            assert (w, lit, True) in seen and (w, lit, False) in seen
+    assert {(w, lit) for w, lit, _ in seen if oracle.min_pattern_size(w, lit) == 3} == {
+        (w, lit) for w in range(8, 16) for lit in range(5, 9) if oracle.min_pattern_size(w, lit) == 3}
+    assert any(r["dictionary"] for r in recs) and any(r["conf"].get("dictionary_reset") for r in recs)
+    assert any(r["conf"].get("lazy_matching") for r in recs)
+    for rec in recs:
+        src, d = _matrix_bytes(rec["source"]), _matrix_bytes(rec["dictionary"])
+        ops = [("write", src[op[1] : op[2]]) if op[0] == "write" else tuple(op) for op in rec["ops"]]
+        st, got = oracle.stream_script(ops, dictionary=d, **rec["conf"])
+        assert st == rec["status"], rec["name"]
+        assert (len(got), hashlib.sha256(got).hexdigest()) == (rec["expected_len"], rec["expected_sha256"]), rec["name"]
+        if rec["decodes"]:
+            plain = b"".join(op[1] for op in ops if op[0] == "write")
+            dst, back, _ = oracle.decompress(got, dictionary=d, cap=len(src) + 64)
+            assert dst == 2 and back == plain, rec["name"]
+
+
+def test_config_matrix_encoder_scripts_are_consistent_with_the_oracle(oracle):
+    """The call scripts of tests/golden/config_matrix.json (one reference object below flush granularity, literal 5-8,
+    windows up to 2^15): the bytes each script emitted decode, with the oracle's decoder, to exactly the input its calls
+    consumed -- up to the call that failed with EXCESS_BITS, where there is one."""
+    recs = load_golden("config_matrix.json")["encoders"]
+    assert len(recs) >= 20
+    checked = 0
+    for rec in recs:
+        assert rec["init"] == 0
+        src, d = _matrix_bytes(rec["source"]), _matrix_bytes(rec["dictionary"])
+        emitted = unb64(rec["emitted"])
+        assert sum(n for _, n, _ in rec["calls"]) == len(emitted), rec["name"]
+        plain, n_out, excess = bytearray(), 0, False
+        for op, (st, n, consumed) in zip(rec["ops"], rec["calls"]):
+            if excess:
+                break
+            n_out += n
+            if op[0] in ("compress", "compress_and_flush", "sink"):
+                plain += src[op[1] : op[2]][:consumed]
+            assert st >= 0 or st == -2, rec["name"]
+            excess = st == -2
+        if excess:
+            # compressor.c:629-631: the offending byte stops the call; what was emitted before it decodes to a prefix
+            assert "excess_bits" in rec["name"], rec["name"]
+            dst, back, _ = oracle.decompress(emitted[:n_out], dictionary=d, cap=1 << 16)
+            assert dst == 2 and bytes(plain).startswith(back), rec["name"]
+            checked += 1
+            continue
+        if rec["calls"][-1][0] != 0:
+            continue
+        mid = rec["ops"][:-1]
+        if any((op[0] == "flush" and not op[1]) or (op[0] == "compress_and_flush" and not op[3]) for op in mid):
+            continue  # a flush without its token pads mid-stream
+        dst, back, _ = oracle.decompress(emitted, dictionary=d, cap=1 << 16)
+        assert dst == 2 and back == bytes(plain), rec["name"]
+        checked += 1
+    assert checked >= 10

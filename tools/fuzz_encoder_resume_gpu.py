@@ -39,8 +39,8 @@ def rand_plain(n):
 
 
 while time.time() - t0 < budget:
-    w = rng.choice([8, 8, 9, 10, 10, 11, 12, 15])
-    lit = rng.choice([5, 7, 8, 8, 8])
+    w = rng.choice([8, 8, 9, 10, 10, 11, 12, 13, 14, 15])
+    lit = rng.choice([5, 6, 7, 8, 8, 8])
     ext = rng.random() < 0.75
     lazy = rng.random() < 0.3
     dr = rng.random() < 0.3

@@ -36,16 +36,16 @@ gens.append(long_repeats)
 while time.time() - t0 < budget:
     n = rng.choice([1, 3, 64, 200, 700])
     L = rng.choice([1, 2, 17, 100, 333, 1024, 3000, 4096, 9000])
-    window = rng.choice([8, 9, 10, 10, 10, 11, 12, 15])
-    literal = rng.choice([8, 8, 8, 7])
+    window = rng.choice([8, 9, 10, 10, 10, 11, 12, 13, 14, 15])
+    literal = rng.choice([8, 8, 7, 6, 5])
     ext = rng.random() < 0.6
     lazy = rng.random() < 0.3
     rows = rng.choice(gens)(n, L, rng.randrange(1 << 20))
-    if literal == 7:
-        rows = rows & 0x7F
+    if literal < 8:
+        rows = rows & np.uint8((1 << literal) - 1)
     d = None
     if rng.random() < 0.25:
-        d = np.random.default_rng(rng.randrange(1 << 20)).integers(0, 128, 1 << window, dtype=np.uint8).tobytes()
+        d = np.random.default_rng(rng.randrange(1 << 20)).integers(0, 1 << min(literal, 7), 1 << window, dtype=np.uint8).tobytes()
     kw = dict(window=window, literal=literal, extended=ext, lazy_matching=lazy, dictionary=d)
     flat = np.ascontiguousarray(rows).reshape(-1)
     off, ln = wl.csr_for_fixed(n, L)

@@ -41,11 +41,13 @@ def source(k):
 t0 = time.time(); scripts = calls = 0
 while time.time() - t0 < budget:
     src = source(scripts)
-    window = rng.choice([8, 9, 10, 10, 10, 11, 12])
-    literal = 8
+    window = rng.choice([8, 9, 10, 10, 10, 11, 12, 13, 14, 15])
+    literal = rng.choice([8, 8, 7, 6, 5])
     ext = rng.random() < 0.75
     dreset = rng.random() < 0.2
-    if FOCUS: window, ext, dreset = 10, False, False
+    if FOCUS: window, literal, ext, dreset = 10, 8, False, False
+    if literal < 8:
+        src = bytes(b & ((1 << literal) - 1) for b in src)
     ops, pos = [], 0
     while pos < len(src):
         k = rng.choice([1, 2, 7, 15, 16, 17, 31, 100, 1000, 5000, 30000])
@@ -68,7 +70,7 @@ while time.time() - t0 < budget:
     if f.getvalue() != want:
         got = f.getvalue()
         first = next((i for i in range(min(len(got), len(want))) if got[i] != want[i]), min(len(got), len(want)))
-        print("STREAM MISMATCH", scripts, window, ext, dreset, "sizes", len(got), len(want), "first differing byte", first,
+        print("STREAM MISMATCH", scripts, window, literal, ext, dreset, "sizes", len(got), len(want), "first differing byte", first,
               "bytes out before each op", list(np.cumsum(got_counts))[:60],
               [(o[0], len(o[1]) if o[0] == 'write' else o[1:]) for o in ops][:60], flush=True)
         again = 0  # the same script three more times: a wrong answer that comes back is an algorithm bug, one that does not is a race
@@ -95,4 +97,4 @@ while time.time() - t0 < budget:
         if (op[0] == "write" and not 0 <= d <= 8) or (op[0] != "write" and d != 0):
             print("COUNT MISMATCH", scripts, i, op[0], d); sys.exit(1)
     scripts += 1
-print(f"fuzz_pieces: {scripts} scripts, {calls} calls, all equal to the reference object ({time.time()-t0:.0f} s)")
+print(f"fuzz_pieces ok: {scripts} scripts, {calls} calls, all equal to the reference object ({time.time()-t0:.0f} s)")

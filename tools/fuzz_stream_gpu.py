@@ -15,11 +15,15 @@ t0, cases = time.time(), 0
 while time.time() - t0 < budget:
     src = rng.choice(srcs)
     dr = rng.random() < 0.5
-    window = rng.choice([8, 9, 10, 12, 15])
-    conf = dict(window=window, literal=8, extended=rng.random() < 0.7, dictionary_reset=dr,
+    window = rng.choice([8, 9, 10, 11, 12, 13, 14, 15])
+    literal = rng.choice([8, 8, 7, 6, 5])
+    mask = (1 << literal) - 1
+    if literal < 8:
+        src = bytes(b & mask for b in src)
+    conf = dict(window=window, literal=literal, extended=rng.random() < 0.7, dictionary_reset=dr,
                 append=dr and rng.random() < 0.2, lazy_matching=rng.random() < 0.25)
     if not conf['append'] and rng.random() < 0.2:
-        conf['dictionary'] = bytes(rng.randrange(256) for _ in range(1 << window))
+        conf['dictionary'] = bytes(rng.randrange(256) & mask for _ in range(1 << window))
     pos, ops = rng.randrange(0, 3000), []
     for _ in range(rng.randrange(1, 8)):
         x = rng.random()
