@@ -363,9 +363,11 @@ tamp_res tamp_amd_read_header(TampAmdConf *conf, const unsigned char *input, siz
 void tamp_amd_set_timing(int enabled);
 float tamp_amd_last_kernel_ms(void);
 
-/* Releases the device scratch the library keeps between calls on `device` -- decoder window slabs and the split
- * decoder's token-record slab, one set per HIP stream that ever decoded (up to a quarter of the free device memory, 8 GiB
- * at most, per stream) -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
+/* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
+ * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
+ * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
+ * the expensive-first ordering (37 bytes per stream of the batch) and the long-stream decoder's chunk tables, tail maps and
+ * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.
  * (The library itself falls back to decoders without scratch when an allocation fails; this call is for callers that

@@ -37,6 +37,70 @@ namespace {
 constexpr int kMaxDevices = 64;
 constexpr size_t kSeedTable = (size_t)1 << 15;
 
+// A buffer the library keeps between calls and grows on demand (the contents do not survive growth).  Device memory or
+// pinned host memory: the two differ in the allocate / free pair only.
+template <hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*)>
+struct GrowBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    // `headroom`: 25 % + 4 KiB on top, so that slowly growing batches do not allocate on every call (off for the decoders'
+    // slabs, which are sized from a memory budget)
+    hipError_t need(size_t n, bool headroom = true) {
+        if (n <= bytes) return hipSuccess;
+        release();
+        if (headroom) n += n / 4 + 4096;
+        hipError_t e = Alloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        else p = nullptr;
+        return e;
+    }
+    size_t release() {  // -> the bytes freed
+        const size_t n = p ? bytes : 0;
+        if (p) (void)Free(p);
+        p = nullptr, bytes = 0;
+        return n;
+    }
+};
+hipError_t device_alloc(void** p, size_t n) { return hipMalloc(p, n); }
+hipError_t pinned_alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+using DeviceBuf = GrowBuf<device_alloc, hipFree>;
+using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
+
+// The device scratch kept between calls, one record per HIP stream of the caller: launches on one stream are ordered and
+// share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
+// concurrently and do not.
+// LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
+// launch_compress and launch_decompress and held to the call's last launch: one library call at a time enqueues on a
+// stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
+// lock -- and the record is passed down (launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
+// tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
+// with nor what a launched kernel still uses.
+struct StreamScratch {
+    std::mutex mu;
+    DeviceBuf slab;        // lane decoder with the windows in global memory: one window slot per resident lane
+    DeviceBuf split;       // split decoder: token records, per-stream meta words, lag lists, fallback flags
+    DeviceBuf scan;        // header pre-pass: largest window / longest stream / window bytes / largest out_cap (32 bytes, never trimmed)
+    DeviceBuf blk;         // block mode (one long v1 stream over all workgroups): tables of pass 1, positions of pass 2, match results
+    DeviceBuf lpt;         // expensive-first ordering of a compress batch: scores, order, gathered table rows
+    DeviceBuf long_tab;    // one long stream decoded by the whole device: chunk tables, records, group tables
+    DeviceBuf long_tails;  // ... the groups' tail maps (groups x window x 2 bytes)
+    DeviceBuf long_lags;   // ... extended format: the list of tokens that can lag, the lag lists
+    // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
+    // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
+    // hipFree waits for the device.)
+    static hipError_t drain_if_outgrown(DeviceBuf& b, size_t n, hipStream_t st) {
+        if (!b.p || n <= b.bytes) return hipSuccess;
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e == hipSuccess) b.release();
+        return e;
+    }
+    size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
+        size_t n = 0;
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags}) n += b->release();
+        return n;
+    }
+};
+
 struct DeviceCtx {
     bool ready = false;
     int cu_count = 0;
@@ -45,85 +109,23 @@ struct DeviceCtx {
     uint32_t* work_counters = nullptr;  // persistent-grid builds: one stream counter per launch, handed out round robin
     std::atomic<uint32_t> next_counter{0};
     static constexpr uint32_t kCounters = 4096;
-    // decoder window slabs, one per HIP stream that ever needed one: launches on one stream are ordered and may share
-    // a slab, launches on different streams run concurrently and may not
-    struct Slab {
-        uint8_t* p = nullptr;
-        size_t bytes = 0;
-        uint32_t* scan = nullptr;  // header pre-pass results (largest window / longest stream / window bytes / largest out_cap)
-        uint8_t* split = nullptr;  // split decoder: token records, per-stream meta words, lag lists, fallback flags
-        size_t split_bytes = 0;
-        // held from the first look at the slab to the last launch of a call: a second host thread using the same stream
-        // could otherwise grow (synchronise, free, allocate) the slab between this call's pointer read and its launch
-        std::mutex launch_mu;
-    };
-    std::map<hipStream_t, Slab> slabs;
+    std::mutex scratch_mu;  // guards the map below, never a record's fields
+    std::map<hipStream_t, StreamScratch> scratch_of;
+    StreamScratch& scratch(hipStream_t st) {
+        std::lock_guard<std::mutex> lock(scratch_mu);
+        return scratch_of[st];  // (map nodes do not move)
+    }
     // host-memory batch calls (TAMP_AMD_MEM_HOST): kept staging buffers and the library's own streams, so that a
     // call costs no hipMalloc and a large batch runs as overlapping chunks (copy in / kernel / copy out)
     struct HostPipe {
         static constexpr int kDepth = 3;
         std::mutex mu;  // one host-memory batch call per device at a time
         hipStream_t s[kDepth] = {nullptr, nullptr, nullptr};
-        struct Grow {
-            void* p = nullptr;
-            size_t bytes = 0;
-            hipError_t need(size_t n) {
-                if (n <= bytes) return hipSuccess;
-                release();
-                n += n / 4 + 4096;
-                hipError_t e = hipMalloc(&p, n);
-                if (e == hipSuccess) bytes = n;
-                return e;
-            }
-            size_t release() {  // -> the bytes freed
-                const size_t n = p ? bytes : 0;
-                if (p) (void)hipFree(p);
-                p = nullptr, bytes = 0;
-                return n;
-            }
-        } in[kDepth], out[kDepth], meta[kDepth], state[kDepth], dict;  // (state: the rows of HostBatch::states)
+        DeviceBuf in[kDepth], out[kDepth], meta[kDepth], state[kDepth], dict;  // (state: the rows of HostBatch::states)
         // pinned host staging for output slabs that do not tile their extent (gaps, padding, permuted offsets): the chunk's
         // extent comes back in ONE transfer and the produced bytes are placed by the host
-        struct Pinned {
-            void* p = nullptr;
-            size_t bytes = 0;
-            hipError_t need(size_t n) {
-                if (n <= bytes) return hipSuccess;
-                release();
-                n += n / 4 + 4096;
-                hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
-                if (e == hipSuccess) bytes = n;
-                return e;
-            }
-            size_t release() {  // -> the bytes freed
-                const size_t n = p ? bytes : 0;
-                if (p) (void)hipHostFree(p);
-                p = nullptr, bytes = 0;
-                return n;
-            }
-        } stage[kDepth];
+        PinnedBuf stage[kDepth];
     } pipe;
-    // block mode (one long v1 stream over all workgroups): per-block tables of pass 1 / positions of pass 2, and the four
-    // table words of the stream read back before the launch
-    std::mutex blk_mu;
-    std::map<hipStream_t, HostPipe::Grow> blk_scratch;  // (one per HIP stream: two calls in flight on two streams must not share tables)
-    // expensive-first ordering: gathered tables, one buffer per HIP stream (launches on a stream are ordered, so the next
-    // launch's kernels find the previous one's done with it; a stream-ordered allocation per launch cost 0.7 ms of host time)
-    std::mutex long_mu;
-    std::map<hipStream_t, HostPipe::Grow> long_scratch;  // one long stream decoded by the whole device: chunk tables, records
-    std::map<hipStream_t, HostPipe::Grow> long_maps;     // ... and the groups' tail maps (groups x window x 2 bytes)
-    std::map<hipStream_t, HostPipe::Grow> long_spec;     // ... extended format: the list of tokens that can lag, the lag lists
-    std::mutex lpt_mu;
-    std::map<hipStream_t, HostPipe::Grow> lpt_scratch;
-    // one enqueue at a time per HIP stream for the compress launches that keep per-stream scratch (the expensive-first
-    // tables): held from the scratch look-up to the last kernel of the call, so that a second host thread on the same stream
-    // can neither interleave its helper kernels with this call's nor grow (free) the buffer this call is about to launch
-    // with; tamp_amd_trim takes it before it frees.  (Looked up under lpt_mu; map nodes do not move.)
-    std::map<hipStream_t, std::mutex> enqueue_mu;
-    std::mutex& enqueue_lock(hipStream_t st) {
-        std::lock_guard<std::mutex> lock(lpt_mu);
-        return enqueue_mu[st];
-    }
 };
 
 DeviceCtx g_ctx[kMaxDevices];
@@ -414,14 +416,14 @@ __global__ void __launch_bounds__(256) tamp_block_scan_kernel(const uint32_t* ta
 
 // Block mode (tamp_compress_kernel<.., BLOCKM>): ONE long stream of the v1 format, literal 8, default parse, fresh window.
 // -> TAMP_OK when the stream was taken this way, 1 when the call does not qualify (the caller goes on with the batch kernel).
-int launch_compress_blocks(DeviceCtx* ctx, CompressArgs a0, const TampAmdConf* conf, uint32_t max_in_len, hipStream_t st, size_t n_streams) {
+// `rec`: the stream's scratch record, locked by the caller.
+int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, const TampAmdConf* conf, uint32_t max_in_len, hipStream_t st, size_t n_streams) {
     const uint32_t W = 1u << conf->window;
     uint32_t min_len = 256u << 10;
     if (const char* e = getenv("TAMP_AMD_BLOCK_MIN")) min_len = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;  // (tuning / tests; 0 = off)
     if (conf->extended || conf->lazy_matching || conf->literal != 8 || conf->window > 14 || a0.state || a0.seg_flags || max_in_len < min_len ||
         n_streams == 0 || n_streams > 64)
         return 1;
-    std::lock_guard<std::mutex> lock(ctx->blk_mu);
     // the streams' table rows: lengths, capacities (the launch geometry and the zero fill depend on them); a handful of LONG
     // streams is taken one after the other, each over all workgroups -- any shorter one among them and the batch kernel takes all
     uint64_t in_off[64], out_off[64];
@@ -456,9 +458,8 @@ int launch_compress_blocks(DeviceCtx* ctx, CompressArgs a0, const TampAmdConf* c
     // (the match results of pass 1, 3 bytes per input byte, when that stays under 1.5 GiB: pass 3 then does not match again)
     const size_t len_bytes = ((size_t)n_max + 1024 + 255) & ~(size_t)255;
     const bool keep_tables = (size_t)n_max * 3 <= ((size_t)3 << 29) && !getenv("TAMP_AMD_BLOCK_REMATCH");
-    DeviceCtx::HostPipe::Grow& scratch = ctx->blk_scratch[st];
-    HIP_OK(scratch.need(table_bytes + info_bytes + chunk_bytes + 256 + (keep_tables ? 3 * len_bytes : 0)));
-    uint8_t* const base = static_cast<uint8_t*>(scratch.p);
+    HIP_OK(rec.blk.need(table_bytes + info_bytes + chunk_bytes + 256 + (keep_tables ? 3 * len_bytes : 0)));
+    uint8_t* const base = static_cast<uint8_t*>(rec.blk.p);
     uint32_t* const chunk_table = reinterpret_cast<uint32_t*>(base + table_bytes + info_bytes);
     uint8_t* const tables = base + table_bytes + info_bytes + chunk_bytes;
     timing_begin(st);
@@ -500,6 +501,8 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
                     const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, size_t n_streams,
                     uint32_t max_in_len, hipStream_t st, const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr) {
     if (n_streams == 0) return TAMP_OK;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
     CompressArgs a;
     a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
     a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
@@ -532,7 +535,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
     a.dbg = getenv("TAMP_AMD_DBG") ? (uint32_t)atoi(getenv("TAMP_AMD_DBG")) : 0;
     a.blk_table = nullptr, a.blk_info = nullptr, a.block_pass = 0, a.n_blocks = 0, a.blk_len = nullptr, a.blk_idx = nullptr;
     if (n_streams <= 64 && !seg) {  // a handful of LONG v1 streams: each one's blocks over all workgroups (tamp_compress_kernel<.., BLOCKM>)
-        const int rc = launch_compress_blocks(ctx, a, conf, max_in_len, st, n_streams);
+        const int rc = launch_compress_blocks(ctx, rec, a, conf, max_in_len, st, n_streams);
         if (rc != 1) return rc;
     }
     const uint32_t W = 1u << conf->window;
@@ -618,7 +621,6 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
             return TAMP_AMD_BAD_ARGUMENT;
         }
         // (every argument check lies in front of the event pair: a refused call leaves no half-recorded timing)
-        std::lock_guard<std::mutex> enqueue(ctx->enqueue_lock(st));  // (per HIP stream; see DeviceCtx::enqueue_mu)
         timing_begin(st);
         // expensive streams first, for batches of more than one and at most ~18 rounds of the grid (beyond, the tail is short
         // next to the batch; TAMP_AMD_LPT=0 / =1 force it off / on)
@@ -631,11 +633,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
         if (lpt) {
             const size_t n = n_streams;
             const size_t bytes = n * (4 + 4 + 8 + 4 + 8 + 4 + 4 + 1) + 256;
-            {
-                std::lock_guard<std::mutex> lock(ctx->lpt_mu);
-                DeviceCtx::HostPipe::Grow& gbuf = ctx->lpt_scratch[st];
-                if (gbuf.need(bytes) == hipSuccess) lpt_mem = static_cast<uint8_t*>(gbuf.p);
-            }
+            if (rec.lpt.need(bytes) == hipSuccess) lpt_mem = static_cast<uint8_t*>(rec.lpt.p);
             if (!lpt_mem) {
                 (void)hipGetLastError();
                 lpt = false;
@@ -726,7 +724,7 @@ __global__ void tamp_header_scan_kernel(const uint8_t* in, const uint64_t* in_of
 // records per chunk, then the split decoder's RESOLVE over groups of at most kSplitMaxOut output bytes, in order, each with the
 // W bytes in front of it as its dictionary.  -> 1 when the call is not one (or anything is off: the exact decoders take it),
 // TAMP_OK when the stream has been decoded, an error code otherwise.  Nothing is written before the fall-back decision.
-int launch_decompress_long(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
+int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
                            const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                            const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed, hipStream_t st) {
     if (const char* e = getenv("TAMP_AMD_LONGDEC")) { if (atoi(e) == 0) return 1; }
@@ -764,17 +762,14 @@ int launch_decompress_long(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_le
     // scratch: g, g_next (N + 1 each), flags (4), ntok, outb, tokbase, rot (N each), the extended format's seven per-chunk tables,
     // then what the groups need
     const size_t b_tab = ((size_t)(14 * (size_t)N + 16) * 4 + 255) & ~(size_t)255;
-    uint8_t* tab = nullptr;
     {
-        std::lock_guard<std::mutex> lock(ctx->long_mu);
-        DeviceCtx::HostPipe::Grow& gb = ctx->long_scratch[st];
         // worst case records: the shortest token is a literal, 1 + literal bits
         const size_t max_tok = (size_t)(total_bits / (1 + lbits)) + 4096;
         const size_t b_groups = ((size_t)(max_tok / 256 + N + 64) * (16 + sizeof(LongGroup) + 4) + 255) & ~(size_t)255;
         const size_t bytes = b_tab + max_tok * 4 + b_groups + 4 * (size_t)(1u << 15) + 4096;
-        if (gb.need(bytes) != hipSuccess) return 1;
-        tab = static_cast<uint8_t*>(gb.p);
+        if (rec.long_tab.need(bytes) != hipSuccess) return 1;
     }
+    uint8_t* const tab = static_cast<uint8_t*>(rec.long_tab.p);
     uint32_t* const g0 = reinterpret_cast<uint32_t*>(tab);
     uint32_t* const g1 = g0 + (N + 1);
     uint32_t* const flags = g1 + (N + 1);
@@ -844,16 +839,11 @@ int launch_decompress_long(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_le
         uint64_t n_entries = 0;
         for (uint32_t i = 0; i < N; i++) specbase[i] = (uint32_t)n_entries, n_entries += (uint64_t)nspec[i] + 1;
         if (n_entries > 0xFFFFFFF0ull) { timing_end(st); return 1; }
-        uint32_t* d_spec = nullptr;
         const size_t n_wpblocks = (size_t)((n_entries + kLongWpBlock - 1) / kLongWpBlock);
-        {
-            std::lock_guard<std::mutex> lock(ctx->long_mu);
-            DeviceCtx::HostPipe::Grow& sb = ctx->long_spec[st];
-            // gap, token, bytes written per list entry; behind them the lag lists (at most one entry per listed token) and the
-            // window_pos tables of the list's blocks (tamp_long_wp_kernel: 8 bytes per block and start value, 20 per block)
-            if (sb.need((size_t)n_entries * (3 + 2) * 4 + n_wpblocks * ((size_t)W * 8 + 20) + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return 1; }
-            d_spec = static_cast<uint32_t*>(sb.p);
-        }
+        // gap, token, bytes written per list entry; behind them the lag lists (at most one entry per listed token) and the
+        // window_pos tables of the list's blocks (tamp_long_wp_kernel: 8 bytes per block and start value, 20 per block)
+        if (rec.long_lags.need((size_t)n_entries * (3 + 2) * 4 + n_wpblocks * ((size_t)W * 8 + 20) + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return 1; }
+        uint32_t* const d_spec = static_cast<uint32_t*>(rec.long_lags.p);
         la.specbase = d_specbase, la.spec_gap = d_spec, la.spec_kl = d_spec + n_entries, la.spec_written = d_spec + 2 * n_entries;
         d_lag = d_spec + 3 * n_entries;
         la.chunk_lag = d_chunk_lag, la.lag = d_lag;
@@ -942,16 +932,11 @@ int launch_decompress_long(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_le
         // (G x W x 2 bytes) in a buffer of their own.
         uint8_t* const ctab = d_win + 4 * (size_t)(1u << 15);
         LongGroup* const d_groups = reinterpret_cast<LongGroup*>(ctab);
-        uint16_t* d_maps = nullptr;
         const size_t n_blocks = (G + kLongScanBlock - 1) / kLongScanBlock;
-        {
-            std::lock_guard<std::mutex> lock(ctx->long_mu);
-            DeviceCtx::HostPipe::Grow& mb = ctx->long_maps[st];
-            // (behind the groups' maps: the blocks' maps and the window in front of every block)
-            // (... and, extended format, in front of every group: with lags the window is not "the last W output bytes")
-            if (mb.need((G + n_blocks) * (size_t)W * 2 + (n_blocks + (extended ? G : 0)) * (size_t)W + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return 1; }
-            d_maps = static_cast<uint16_t*>(mb.p);
-        }
+        // (behind the groups' maps: the blocks' maps and the window in front of every block)
+        // (... and, extended format, in front of every group: with lags the window is not "the last W output bytes")
+        if (rec.long_tails.need((G + n_blocks) * (size_t)W * 2 + (n_blocks + (extended ? G : 0)) * (size_t)W + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return 1; }
+        uint16_t* const d_maps = static_cast<uint16_t*>(rec.long_tails.p);
         uint16_t* const d_blockmap = d_maps + G * (size_t)W;
         uint8_t* const d_blockwin = reinterpret_cast<uint8_t*>(d_blockmap + n_blocks * (size_t)W);
         uint8_t* const d_groupwin = extended ? d_blockwin + n_blocks * (size_t)W : nullptr;
@@ -1045,12 +1030,8 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     a.only_flagged = nullptr;
     a.flagged_count = nullptr;
     a.n_streams = (uint32_t)n_streams;
-    DeviceCtx::Slab* call_slab = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        call_slab = &ctx->slabs[st];  // (map nodes do not move)
-    }
-    std::lock_guard<std::mutex> call_lock(call_slab->launch_mu);
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
     if (n_streams <= 16 && !(max_wbits & TAMP_AMD_WINDOW_BITS_EXACT)) {
         // one long v1 stream -- or a handful, one after the other: the whole device each (tamp_decompress_long_kernel.hpp).  A stream
         // that is not one (too short, extended, ...) sends the whole call to the decoders below, which write every stream again.
@@ -1060,7 +1041,7 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
         t_timing_outer = true;
         int rc = TAMP_OK;
         for (; done < n_streams; done++) {
-            rc = launch_decompress_long(ctx, d_dict, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
+            rc = launch_decompress_long(ctx, rec, d_dict, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
                                         d_out_off + done, d_out_cap + done, d_out_len + done, d_status + done,
                                         d_consumed ? d_consumed + done : nullptr, st);
             if (rc != TAMP_OK) break;
@@ -1077,13 +1058,8 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     const char* force = getenv("TAMP_AMD_DECODER");  // "wave" | "lane" | "global" | "split" (tuning / tests)
     const bool force_split = force && force[0] == 's';
     if (!exact && max_wbits >= 8 && max_wbits <= 15 && ((max_wbits > 8 && n_streams >= 256) || force_split)) {
-        uint32_t* hdr_scan = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(g_mu);
-            DeviceCtx::Slab& slab = ctx->slabs[st];
-            if (!slab.scan) HIP_OK(hipMalloc(&slab.scan, 32));
-            hdr_scan = slab.scan;
-        }
+        HIP_OK(rec.scan.need(32, false));
+        uint32_t* const hdr_scan = static_cast<uint32_t*>(rec.scan.p);
         uint32_t scan[4] = {0, 0, 0, 0};
         uint32_t& found = scan[0];
         HIP_OK(hipMemsetAsync(hdr_scan, 0, 16, st));
@@ -1134,11 +1110,7 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
             size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
             // (the slab this stream already holds is part of what the call may use: without it the budget -- and with it
             // the slice size, hence the decode time -- of the second call on a shape differed from the first's)
-            size_t held = 0;
-            {
-                std::lock_guard<std::mutex> lock(g_mu);
-                held = ctx->slabs[st].split_bytes;
-            }
+            const size_t held = rec.split.bytes;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max((free_b + held) / 4, held));
             else (void)hipGetLastError();
             if (const char* e = getenv("TAMP_AMD_SPLIT_SCRATCH_MB")) { const long v = atol(e); if (v > 0) budget = (size_t)v << 20; }
@@ -1147,32 +1119,19 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
         // The slab is kept per HIP stream between calls (tamp_amd_trim() releases it).  If the device cannot supply it the
         // slice is halved down to 4,096 streams, and below that the batch goes to the lane / wave decoders, which need
         // little or no scratch: an allocation failure here must not fail a call that another decoder can serve.
-        uint8_t* base = nullptr;
         size_t b_recs = 0, b_meta = 0, b_lag = 0;
-        {
-            std::lock_guard<std::mutex> lock(g_mu);
-            DeviceCtx::Slab& slab = ctx->slabs[st];
-            for (;;) {
-                b_recs = slice * sa.tokcap * 4, b_meta = slice * 4, b_lag = slice * kSplitMaxLag * 8;
-                const size_t need = b_recs + b_meta + b_lag + n_streams + 64;
-                if (slab.split_bytes >= need) break;
-                if (slab.split) {
-                    HIP_OK(hipStreamSynchronize(st));
-                    HIP_OK(hipFree(slab.split));
-                    slab.split = nullptr, slab.split_bytes = 0;
-                }
-                const bool deny = getenv("TAMP_AMD_SPLIT_FAIL_ABOVE") && need > (size_t)atol(getenv("TAMP_AMD_SPLIT_FAIL_ABOVE"));  // (tests)
-                if (!deny && hipMalloc(&slab.split, need) == hipSuccess) {
-                    slab.split_bytes = need;
-                    break;
-                }
-                (void)hipGetLastError();  // clear the sticky out-of-memory error
-                slab.split = nullptr;
-                if (slice <= 4096) { slice = 0; break; }
-                slice = std::max<size_t>(slice / 2, 4096);
-            }
-            base = slab.split;
+        for (;;) {
+            b_recs = slice * sa.tokcap * 4, b_meta = slice * 4, b_lag = slice * kSplitMaxLag * 8;
+            const size_t need = b_recs + b_meta + b_lag + n_streams + 64;
+            if (rec.split.bytes >= need) break;
+            HIP_OK(StreamScratch::drain_if_outgrown(rec.split, need, st));
+            const bool deny = getenv("TAMP_AMD_SPLIT_FAIL_ABOVE") && need > (size_t)atol(getenv("TAMP_AMD_SPLIT_FAIL_ABOVE"));  // (tests)
+            if (!deny && rec.split.need(need, false) == hipSuccess) break;
+            (void)hipGetLastError();  // clear the sticky out-of-memory error
+            if (slice <= 4096) { slice = 0; break; }
+            slice = std::max<size_t>(slice / 2, 4096);
         }
+        uint8_t* const base = static_cast<uint8_t*>(rec.split.p);
         if (slice) {
         sa.recs = reinterpret_cast<uint32_t*>(base);
         sa.meta = reinterpret_cast<uint32_t*>(base + b_recs);
@@ -1289,21 +1248,9 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     if (lanes > n_streams) lanes = n_streams;
     const uint32_t grid = (uint32_t)((lanes + threads - 1) / threads);
     const size_t need = (size_t)grid * threads * slot;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        DeviceCtx::Slab& slab = ctx->slabs[st];
-        if (slab.bytes < need) {
-            if (slab.p) {
-                HIP_OK(hipStreamSynchronize(st));  // earlier launches on this stream still use the old slab
-                HIP_OK(hipFree(slab.p));
-                slab.p = nullptr;
-                slab.bytes = 0;
-            }
-            HIP_OK(hipMalloc(&slab.p, need));
-            slab.bytes = need;
-        }
-        a.scratch = slab.p;
-    }
+    HIP_OK(StreamScratch::drain_if_outgrown(rec.slab, need, st));
+    HIP_OK(rec.slab.need(need, false));
+    a.scratch = static_cast<uint8_t*>(rec.slab.p);
     timing_begin(st);
     if (gbulk)
         hipLaunchKernelGGL((tamp_decompress_kernel<false, true>), dim3(grid), dim3(threads), 128 + threads * kLaneStagePad, st, a);
@@ -1825,50 +1772,25 @@ void tamp_amd_host_free(void* p) {
 void tamp_amd_set_timing(int enabled) { t_timing = enabled != 0; }
 
 
-// Release the scratch the library keeps between calls on `device` (decoder window slabs, split-decoder records, header
-// pre-pass words: one set per HIP stream that ever decoded) and, since round 4, the staging of the host-memory pipeline
-// (pinned host buffers and device chunk buffers).  Every stream that owns a slab is synchronised first.  Returns the number
-// of bytes released, or a negative TAMP_AMD_* code.
+// Release the scratch the library keeps between calls on `device`: every HIP stream's record (StreamScratch: decoder
+// window slab, split-decoder records, block-mode tables, expensive-first tables, the long-stream decoder's three buffers;
+// not the 32 bytes of the header pre-pass) and the staging of the host-memory pipeline (pinned host buffers and device chunk
+// buffers).  Every stream that owns a record is synchronised first.  Returns the number of bytes released, or a negative
+// TAMP_AMD_* code.
 long long tamp_amd_trim(int device) {
     DeviceCtx* ctx = nullptr;
     int rc = get_ctx(device, &ctx);
     if (rc != TAMP_OK) return rc;
     long long freed = 0;
-    // lock order of the decode launches: a slab's launch_mu first, g_mu inside it -- so the slabs are listed under g_mu
-    // (map nodes do not move) and released one by one in that order
-    std::vector<std::pair<hipStream_t, DeviceCtx::Slab*>> slabs;
+    std::vector<std::pair<hipStream_t, StreamScratch*>> records;
     {
-        std::lock_guard<std::mutex> lock(g_mu);
-        for (auto& kv : ctx->slabs) slabs.emplace_back(kv.first, &kv.second);
+        std::lock_guard<std::mutex> lock(ctx->scratch_mu);
+        for (auto& kv : ctx->scratch_of) records.emplace_back(kv.first, &kv.second);  // (map nodes do not move)
     }
-    for (auto& ps : slabs) {
-        DeviceCtx::Slab& slab = *ps.second;
-        std::lock_guard<std::mutex> call_lock(slab.launch_mu);
-        if (hipStreamSynchronize(ps.first) != hipSuccess) (void)hipGetLastError();
-        std::lock_guard<std::mutex> lock(g_mu);
-        if (slab.p) { (void)hipFree(slab.p); freed += (long long)slab.bytes; slab.p = nullptr, slab.bytes = 0; }
-        if (slab.split) { (void)hipFree(slab.split); freed += (long long)slab.split_bytes; slab.split = nullptr, slab.split_bytes = 0; }
-    }
-    {   // block-mode tables and the expensive-first ordering's gathered tables (round 5)
-        std::lock_guard<std::mutex> blk_lock(ctx->blk_mu);
-        if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-        for (auto& kv : ctx->blk_scratch) freed += (long long)kv.second.release();
-        {   // expensive-first tables: a stream's enqueue lock first (a call in flight on it finishes its launches), then the map's
-            std::vector<hipStream_t> streams;
-            {
-                std::lock_guard<std::mutex> lpt_lock(ctx->lpt_mu);
-                for (auto& kv : ctx->lpt_scratch) streams.push_back(kv.first);
-            }
-            for (hipStream_t s2 : streams) {
-                std::lock_guard<std::mutex> enqueue(ctx->enqueue_lock(s2));
-                if (hipStreamSynchronize(s2) != hipSuccess) (void)hipGetLastError();
-                std::lock_guard<std::mutex> lpt_lock(ctx->lpt_mu);
-                freed += (long long)ctx->lpt_scratch[s2].release();
-            }
-        }
-        std::lock_guard<std::mutex> long_lock(ctx->long_mu);  // (the long-stream decoder's chunk tables and records)
-        for (auto* m : {&ctx->long_scratch, &ctx->long_maps, &ctx->long_spec})
-            for (auto& kv : *m) freed += (long long)kv.second.release();
+    for (auto& sr : records) {
+        std::lock_guard<std::mutex> call_lock(sr.second->mu);  // a call in flight on the stream finishes its launches first
+        if (hipStreamSynchronize(sr.first) != hipSuccess) (void)hipGetLastError();  // (a stream the caller has destroyed)
+        freed += (long long)sr.second->release();
     }
     {   // the host-memory pipeline: pinned staging of non-tiling output slabs (it grows with the largest extent ever staged,
         // possibly gigabytes of pinned RAM), the device-side chunk and state-row buffers, the custom dictionary; all grow

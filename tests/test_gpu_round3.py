@@ -172,6 +172,140 @@ def test_split_decoder_scratch_failure_falls_back_and_trim_releases(ta, checker,
     decode_and_check()
 
 
+def _on_device(flat, off, ln):
+    import torch
+
+    dev = torch.device("cuda:0")
+    return (torch.from_numpy(np.array(flat, dtype=np.uint8)).to(dev), torch.from_numpy(np.asarray(off).astype(np.int64)).to(dev),
+            torch.from_numpy(np.asarray(ln).astype(np.int32)).to(dev))
+
+
+def test_trim_gives_back_every_kind_of_per_stream_scratch(ta, checker, monkeypatch):
+    """The library keeps one scratch record per HIP stream: the split decoder's records, the global-window decoder's slab, the
+    expensive-first tables of a compress batch, the block-mode tables, the long-stream decoder's tables (v1: chunk tables and
+    tail maps; extended format: the lag lists too).  Each kind in turn, on device-resident data (the host-memory pipeline's
+    staging stays empty, so what trim reports is the record's): the call's output against the reference, then trim hands
+    bytes back, and a second trim finds nothing left."""
+    import torch
+
+    from tamp_amd import workloads as wl
+
+    def trimmed():
+        torch.cuda.synchronize()
+        assert ta.trim(0) > 0
+        assert ta.trim(0) == 0
+
+    n, L = 6000, 4096
+    rows = wl.synth_text(n, L)
+    off, ln = wl.csr_for_fixed(n, L)
+    data, off_t, len_t = _on_device(rows.reshape(-1), off, ln)
+    want = checker.compress_batch(rows.reshape(-1), off, ln, window=10, literal=8, extended=True, threads=8)
+
+    # expensive-first ordering: more streams than the persistent grid has workgroups, at most 32,768
+    ta.trim(0)
+    comp = ta.compress_batch(data, off_t, len_t, window=10, literal=8, extended=True, max_in_len=L)
+    assert bool((comp.status == 0).all().item())
+    for i in range(n):
+        assert comp.stream(i) == want.stream(i), i
+    trimmed()
+
+    def decode_and_check():
+        back = ta.decompress_batch(comp.out, comp.out_off, comp.out_len, out_cap=L + 8)
+        assert bool((back.status == 2).all().item()) and bool((back.out_len == L).all().item())
+        got = back.out[: n * (L + 8)].view(n, L + 8)[:, :L].reshape(-1)
+        assert torch.equal(got, data)
+
+    decode_and_check()  # split decoder: token records
+    trimmed()
+    monkeypatch.setenv("TAMP_AMD_DECODER", "global")
+    decode_and_check()  # lane decoder with its windows in the scratch slab
+    monkeypatch.delenv("TAMP_AMD_DECODER")
+    trimmed()
+
+    # block mode: one v1 stream of 256 KiB and more, literal 8
+    text = np.frombuffer(_tiled(300001), dtype=np.uint8)
+    one_off, one_len = np.zeros(1, np.uint64), np.array([text.size], np.uint32)
+    want1 = checker.compress_batch(text, one_off, one_len, window=10, literal=8, extended=False).stream(0)
+    got1 = ta.compress_batch(*_on_device(text, one_off, one_len), window=10, literal=8, extended=False, max_in_len=text.size)
+    assert int(got1.status[0]) == 0 and got1.stream(0) == want1
+    trimmed()
+
+    # one long stream decoded by the whole device, both formats (from 64 KiB of compressed bytes on)
+    monkeypatch.setenv("TAMP_AMD_LONGDEC_MIN", "65536")
+    plain = _tiled(1_200_000)
+    for ext in (False, True):
+        blob = ta.compress(plain, extended=ext)
+        assert len(blob) >= 64 << 10 and bool(blob[0] & 2) == ext
+        ta.trim(0)  # (what the host-memory call above staged)
+        back = ta.decompress_batch(*_on_device(np.frombuffer(blob, dtype=np.uint8), [0], [len(blob)]), out_cap=len(plain) + 100)
+        st, out, used = checker.decompress(blob, cap=len(plain) + 100)
+        assert (int(back.status[0]), back.stream(0)) == (st, out) and out == plain
+        assert int(back.in_consumed[0]) == used
+        trimmed()
+
+
+def test_two_host_threads_on_one_hip_stream_compress_and_decode(ta, checker, monkeypatch):
+    """Two host threads share one HIP stream, one compressing and one decoding, 300 calls each: the library lets one call at a
+    time enqueue on a stream (both calls keep scratch in the stream's record: the expensive-first tables, the split decoder's
+    records), the device runs them in order, and every call's output is the reference's."""
+    import threading
+
+    import torch
+
+    from tamp_amd import workloads as wl
+
+    n, L, calls = 512, 4096, 300
+    rows = wl.synth_text(n, L, first_index=4242)
+    off, ln = wl.csr_for_fixed(n, L)
+    data, off_t, len_t = _on_device(rows.reshape(-1), off, ln)
+    want = checker.compress_batch(rows.reshape(-1), off, ln, window=10, literal=8, extended=True, threads=8)
+    want_streams = [want.stream(i) for i in range(n)]
+    monkeypatch.setenv("TAMP_AMD_LPT", "1")  # (expensive-first ordering whatever the grid size: per-stream tables on the compress side)
+    comp = ta.compress_batch(data, off_t, len_t, window=10, literal=8, extended=True, max_in_len=L)
+    assert comp.streams() == want_streams
+    cap = int(comp.out_off[1])  # one slab per stream; what lies behind a stream's out_len bytes is unspecified
+    assert torch.equal(comp.out_off.to(torch.int64), torch.arange(n, device=data.device) * cap)
+    produced = torch.arange(cap, device=data.device)[None, :] < comp.out_len[:, None]
+
+    def same_streams(r):
+        return (torch.equal(r.out_len, comp.out_len)
+                and torch.equal(r.out[: n * cap].view(n, cap) * produced, comp.out[: n * cap].view(n, cap) * produced))
+
+    hip_stream = torch.cuda.Stream(torch.device("cuda:0"))
+    hip_stream.wait_stream(torch.cuda.current_stream())
+    failures = []
+
+    def compressor():
+        try:
+            with torch.cuda.stream(hip_stream):
+                for k in range(calls):
+                    r = ta.compress_batch(data, off_t, len_t, window=10, literal=8, extended=True, max_in_len=L)
+                    if not bool((r.status == 0).all().item()) or not same_streams(r):
+                        failures.append(("compress", k))
+        except Exception as e:  # noqa: BLE001 -- reported by the assertion below
+            failures.append(("compress", repr(e)))
+
+    def decoder():
+        try:
+            with torch.cuda.stream(hip_stream):
+                for k in range(calls):
+                    back = ta.decompress_batch(comp.out, comp.out_off, comp.out_len, out_cap=L + 8)
+                    ok = bool((back.status == 2).all().item()) and bool((back.out_len == L).all().item())
+                    if not ok or not torch.equal(back.out[: n * (L + 8)].view(n, L + 8)[:, :L].reshape(-1), data):
+                        failures.append(("decode", k))
+        except Exception as e:  # noqa: BLE001
+            failures.append(("decode", repr(e)))
+
+    threads = [threading.Thread(target=compressor), threading.Thread(target=decoder)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=600)
+    assert not any(t.is_alive() for t in threads)
+    torch.cuda.synchronize()
+    assert not failures, failures[:5]
+
+
 def test_numpy_integer_capacities_and_workspace_reuse(ta, checker):
     """out_cap as a numpy integer scalar (`isinstance(out_cap, int)` sent it down the tensor path), and the
     `reuse=` workspace of steady-state callers: same bytes, same buffers."""
