@@ -115,6 +115,23 @@ const char *tamp_amd_last_error(void);
 int tamp_amd_compress_plan(uint8_t window_bits, uint32_t max_in_len, int lazy_matching, uint32_t *block_positions,
                            uint32_t *lds_bytes, uint32_t *threads, uint32_t *workgroups_per_cu);
 
+/* Which build of the compress kernel a device batch call would take (host only, no GPU needed).  Whole-stream calls at
+ * window 2^10, literal 8, default parse with 1,024-position blocks take a build with that geometry and the format compiled
+ * in; ANY deviation -- and TAMP_AMD_FIXED_BUILD=0 in the environment -- takes the generic build.  Same bytes either way.
+ * `call_flags`: what the call carries beyond a plain batch (TAMP_AMD_CALL_*); `dictionary_address`: the device address of
+ * the custom dictionary (ignored without one).  -> TAMP_AMD_BUILD_*, or TAMP_AMD_BAD_ARGUMENT. */
+enum {
+    TAMP_AMD_CALL_STATE = 1,        /* a per-stream window state is passed (segment / piece calls) */
+    TAMP_AMD_CALL_RESUME = 2,       /* ... and read at the start */
+    TAMP_AMD_CALL_SAVE = 4,         /* ... and written back at the end */
+    TAMP_AMD_CALL_FLUSH_TOKEN = 8,  /* the output ends with a FLUSH token */
+    TAMP_AMD_CALL_PARTIAL = 16,     /* the call ends without a drain (piece calls) */
+    TAMP_AMD_CALL_APPEND = 32,      /* FLUSH + padding lead the output instead of the plain header byte */
+    TAMP_AMD_CALL_BLOCK_MODE = 64,  /* a handful of long v1 streams: each one's blocks over all workgroups */
+};
+enum { TAMP_AMD_BUILD_GENERIC = 0, TAMP_AMD_BUILD_FIXED_EXT = 1, TAMP_AMD_BUILD_FIXED_V1 = 2 };
+int tamp_amd_compress_build(const TampAmdConf *conf, uint32_t max_in_len, uint32_t call_flags, uintptr_t dictionary_address);
+
 /* ---- batch codec ---------------------------------------------------------------------------- */
 
 /*

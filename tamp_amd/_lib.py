@@ -29,6 +29,7 @@ SYMBOLS = (
     "tamp_amd_version",
     "tamp_amd_last_error",
     "tamp_amd_compress_plan",
+    "tamp_amd_compress_build",
     "tamp_batch_compress",
     "tamp_batch_decompress",
     "tamp_amd_decoder_state_size",
@@ -135,6 +136,8 @@ def load() -> C.CDLL:
     lib.tamp_amd_device_count.restype = i32
     lib.tamp_amd_version.restype = C.c_char_p
     lib.tamp_amd_last_error.restype = C.c_char_p
+    lib.tamp_amd_compress_build.argtypes = [C.POINTER(TampAmdConf), u32, u32, sz]  # (uintptr_t: the width of size_t)
+    lib.tamp_amd_compress_build.restype = i32
     lib.tamp_batch_compress.argtypes = [C.POINTER(TampAmdConf), vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp]
     lib.tamp_batch_compress.restype = i32
     lib.tamp_batch_decompress.argtypes = [vp, sz, u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]

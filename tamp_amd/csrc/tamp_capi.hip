@@ -496,6 +496,21 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     return TAMP_OK;
 }
 
+// The fixed-geometry builds (tamp_compress_fixed::compress_kernel<FIX>): kFixExt / kFixV1 when the call is EXACTLY what they
+// were compiled for, kFixNone (the generic build) for everything else.  `a` as launch_compress has filled it in, `runlist` /
+// `threads` as it has chosen them.  TAMP_AMD_FIXED_BUILD=0 forces the generic build (A/B runs, the parity tests).
+uint32_t fixed_build_for(const TampAmdConf* conf, const CompressArgs& a, bool runlist, uint32_t threads) {
+#ifdef TAMP_SEVEN
+    return kFixNone;  // (the seven-per-CU tuning shape has another LDS layout)
+#endif
+    if (const char* e = getenv("TAMP_AMD_FIXED_BUILD")) { if (atoi(e) == 0) return kFixNone; }
+    const uint16_t plain_lead = (uint16_t)(header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, 0) << 8);
+    const bool fits = conf->window == kFixWbits && conf->literal == kFixLbits && !a.lazy && runlist && a.blk == kFixBlk &&
+                      threads == kFixThreads && a.state == nullptr && a.seg_flags == 0 && !a.dict_reset && a.nlead == 1 &&
+                      a.lead == plain_lead && (reinterpret_cast<uintptr_t>(a.dict) & 3) == 0;
+    return !fits ? kFixNone : (a.extended ? kFixExt : kFixV1);
+}
+
 int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_dict, const uint8_t* d_in,
                     const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                     const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, size_t n_streams,
@@ -565,7 +580,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
     }
     const uint32_t threads = (a.blk >= 1024 || (long_streams && a.blk >= 512 && getenv("TAMP_AMD_BLK"))) ? 256 : 64;  // (tuning: smaller blocks for long streams)
     const uint32_t grid = (uint32_t)(n_streams < (1u << 20) ? n_streams : (1u << 20));
-    // the six builds: lazy (u32 / u16 entries), run-aware (generic window / 2^10 with the scan constants as immediates),
+    // the fixed-geometry pair for the 2^10 window's whole-stream calls (fixed_build_for above), and the six generic builds: lazy (u32 / u16 entries), run-aware (generic window / 2^10 with the scan constants as immediates),
     // lean one-wavefront build for short messages (512 buckets: a quarter of the cursors to zero and scan per message),
     // lean u16 build for the 2^15 window.
     // All but the short-message build run as a PERSISTENT GRID (LOOP in the kernel): as many workgroups as the device holds
@@ -576,7 +591,10 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
     // workgroup per stream: two million fetches from one counter cost more than the balance is worth (20 instead of
     // 41 GB/s when tried), and their costs are even.
     const bool short_build = packed && !a.lazy && !runlist;
-    auto kernel = a.lazy ? (packed ? tamp_compress_kernel<true, true, false, 0, kHashBits, true> : tamp_compress_kernel<false, true, false, 0, kHashBits, true>)
+    const uint32_t fix = fixed_build_for(conf, a, runlist, threads);
+    auto kernel = fix == kFixExt ? tamp_compress_fixed::compress_kernel<kFixExt>
+                  : fix == kFixV1 ? tamp_compress_fixed::compress_kernel<kFixV1>
+                  : a.lazy ? (packed ? tamp_compress_kernel<true, true, false, 0, kHashBits, true> : tamp_compress_kernel<false, true, false, 0, kHashBits, true>)
                   : !packed ? tamp_compress_kernel<false, false, false, 0, kHashBits, true>
                   : runlist ? (conf->window == 10 ? tamp_compress_kernel<true, false, true, 1024, kHb1024, true> : tamp_compress_kernel<true, false, true, 0, kHashBits, true>)
                             : tamp_compress_kernel<true, false, false, 0, 9>;
@@ -1739,6 +1757,34 @@ int tamp_amd_compress_plan(uint8_t window_bits, uint32_t max_in_len, int lazy_ma
     if (threads) *threads = blk >= 1024 ? 256u : 64u;
     if (workgroups_per_cu) *workgroups_per_cu = by_lds < reg_cap ? by_lds : reg_cap;
     return TAMP_OK;
+}
+
+int tamp_amd_compress_build(const TampAmdConf* conf, uint32_t max_in_len, uint32_t call_flags, uintptr_t dictionary_address) {
+    if (!conf || conf->window < 8 || conf->window > 15 || conf->literal < 5 || conf->literal > 8) return TAMP_AMD_BAD_ARGUMENT;
+    if (call_flags & TAMP_AMD_CALL_BLOCK_MODE) return TAMP_AMD_BUILD_GENERIC;  // (launch_compress_blocks takes the call: its own build)
+    // (the same decisions as launch_compress, on the same argument block)
+    CompressArgs a = {};
+    a.wbits = conf->window, a.lbits = conf->literal, a.extended = conf->extended != 0;
+    a.dict_reset = conf->dictionary_reset != 0, a.lazy = conf->lazy_matching != 0;
+    a.nlead = conf->dictionary_reset ? 2 : 1;
+    a.lead = (uint16_t)(header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset) << 8);
+    if (call_flags & TAMP_AMD_CALL_APPEND) a.nlead = 2, a.lead = 0;  // (FLUSH + padding in front instead of the header: tamp_amd_compress_segment)
+    if (call_flags & TAMP_AMD_CALL_RESUME) a.seg_flags |= kSegResume, a.nlead = 0;
+    if (call_flags & TAMP_AMD_CALL_SAVE) a.seg_flags |= kSegSave;
+    if (call_flags & TAMP_AMD_CALL_FLUSH_TOKEN) a.seg_flags |= kSegFlushToken;
+    if (call_flags & TAMP_AMD_CALL_PARTIAL) a.seg_flags |= kSegPartial;
+    if (call_flags & TAMP_AMD_CALL_STATE) a.state = reinterpret_cast<uint8_t*>(uintptr_t(16));  // (any non-null address: never dereferenced)
+    a.dict = reinterpret_cast<const uint8_t*>(conf->use_custom_dictionary ? dictionary_address : uintptr_t(0));  // (the seeded tables are aligned)
+    const uint32_t W = 1u << conf->window;
+    const bool packed = conf->window <= 14;
+    const bool long_streams = max_in_len == 0 || align_up(max_in_len, 64) >= 1024;
+    bool runlist = packed && !a.lazy && (long_streams || conf->input_hint == TAMP_AMD_HINT_RUNS);
+    if (const char* e = getenv("TAMP_AMD_RUNS")) { if (!long_streams) runlist = packed && !a.lazy && atoi(e) != 0; }
+    const uint32_t hb = runlist && conf->window == 10 ? kHb1024 : kHashBits;
+    a.blk = pick_block(W, max_in_len, packed, a.lazy != 0, runlist, hb);
+    const uint32_t threads = (a.blk >= 1024 || (long_streams && a.blk >= 512 && getenv("TAMP_AMD_BLK"))) ? 256 : 64;
+    const uint32_t fix = fixed_build_for(conf, a, runlist, threads);
+    return fix == kFixExt ? TAMP_AMD_BUILD_FIXED_EXT : (fix == kFixV1 ? TAMP_AMD_BUILD_FIXED_V1 : TAMP_AMD_BUILD_GENERIC);
 }
 
 const char* tamp_amd_last_error(void) { return t_last_error; }

@@ -58,9 +58,9 @@ __device__ __forceinline__ uint32_t tok_code(uint32_t i) {
 }
 __device__ __forceinline__ uint32_t tok_nbits(uint32_t i) { return (uint32_t)(kNbitsPacked >> (4 * i)) & 15; }
 
-__host__ __device__ inline uint32_t align_up(uint32_t x, uint32_t a) { return (x + a - 1) & ~(a - 1); }
+__host__ __device__ constexpr uint32_t align_up(uint32_t x, uint32_t a) { return (x + a - 1) & ~(a - 1); }
 
-__host__ __device__ inline int min_pattern_size(int window, int literal) {
+__host__ __device__ constexpr int min_pattern_size(int window, int literal) {
     return 2 + (window > 10 + 2 * (literal - 5));
 }
 

@@ -102,9 +102,10 @@ struct CompressArgs {
 
 // LDS carve-up, shared by the host launcher and the kernel.
 struct CompressLds {
-    uint32_t ebuf, cnt, ent, blen, bidx, blen2, bidx2, obuf, ctl, runs, runsx, rxset, rbits, total;  // blen2/bidx2: lazy-matching probe results
-    uint32_t tokcap, obuf_words, jump, count, vstep;  // jump/count/vstep: byte offsets of the walk's tables inside `ent`
-    __host__ __device__ CompressLds(uint32_t W, uint32_t blk, bool packed, bool lazy = false, bool runlist = false, uint32_t hb = kHashBits) {
+    // (constexpr: the fixed-geometry builds take every offset as an immediate from the same arithmetic the launcher runs)
+    uint32_t ebuf = 0, cnt = 0, ent = 0, blen = 0, bidx = 0, blen2 = 0, bidx2 = 0, obuf = 0, ctl = 0, runs = 0, runsx = 0, rxset = 0, rbits = 0, total = 0;  // blen2/bidx2: lazy-matching probe results
+    uint32_t tokcap = 0, obuf_words = 0, jump = 0, count = 0, vstep = 0;  // jump/count/vstep: byte offsets of the walk's tables inside `ent`
+    __host__ __device__ constexpr CompressLds(uint32_t W, uint32_t blk, bool packed, bool lazy = false, bool runlist = false, uint32_t hb = kHashBits) {
         uint32_t o = 16;  // slack: the wrapped compare reads up to 15 bytes in front of ebuf (masked out)
         ebuf = o;
         o += align_up(W + blk + kRing + kPendMax + 32, 16);
@@ -855,9 +856,33 @@ __device__ __forceinline__ T* as_global(T* p) {
 //           ORed into the output at the block's bit position (first and last dword atomically: neighbours share them).
 // The work counter hands out blocks instead of streams.  Reference shape: ONE stream of 100 MB (README.md:309-312,
 // tools/c-profiler/main.c:52-54), which one workgroup takes 6 s for.
-template <bool PACKED, bool LAZY, bool RUNS = false, uint32_t WSCAN = 0, uint32_t HB = kHashBits, bool LOOP = false, bool BLOCKM = false>
-__global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG_PER_CU : TAMP_LEAN_PER_CU)) tamp_compress_kernel(CompressArgs a_k) {
+// FIX != 0 (kFixExt / kFixV1): the FIXED-GEOMETRY builds of the run-aware persistent kernel for ONE configuration, the
+// headline's -- window 2^10, 1,024-position blocks, literal 8, 256 threads, one whole stream per call (no saved state,
+// no segment flags, the plain one-byte header, a dword-aligned dictionary) -- with the format a constant too.  The body is the
+// one below: geometry, LDS offsets (kLdsFixed), minimum pattern, thread count and the format are constants instead of scalars
+// derived from the arguments per stream, and what such a call never executes (segment state, FLUSH token, excess-bits
+// pre-pass; in the v1 build everything RLE / extended) is not compiled in.  The launcher's predicate (fixed_build_for in
+// tamp_capi.hip) is the only way in; every other call keeps the generic build.
+enum : uint32_t { kFixNone = 0, kFixExt = 1, kFixV1 = 2 };
+#ifndef TAMP_FIX_STEPS
+#define TAMP_FIX_STEPS 3
+#endif
+constexpr uint32_t kFixWbits = 10, kFixBlk = 1024, kFixLbits = 8, kFixThreads = 256;
+constexpr CompressLds kLdsFixed(1u << kFixWbits, kFixBlk, true, false, true, kHb1024);
+#ifndef TAMP_SEVEN
+static_assert(kLdsFixed.total == 19616 && kLdsFixed.tokcap == 1376 && kLdsFixed.obuf_words == 516,
+              "the fixed builds' LDS layout is the generic build's for window 2^10, block 1,024, 1,024 buckets");
+#endif
+// (the body is this one function for every build; the two kernels behind it -- tamp_compress_kernel for the generic builds,
+// tamp_compress_fixed::compress_kernel for the fixed ones -- only name its instantiations)
+template <bool PACKED, bool LAZY, bool RUNS, uint32_t WSCAN, uint32_t HB, bool LOOP, bool BLOCKM, uint32_t FIX>
+__device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     static_assert(!BLOCKM || (LOOP && PACKED && !LAZY), "block mode: a persistent build of the default parse");
+    // FX: constant geometry; FXS: no segment / piece machinery; FXF: constant format (the three steps the build was made in;
+    // TAMP_FIX_STEPS = 1 / 2 rebuilds the intermediate ones for the static comparison in profiles/fixed_build_static.txt)
+    constexpr bool FX = FIX != kFixNone, FXS = FX && TAMP_FIX_STEPS >= 2, FXF = FX && TAMP_FIX_STEPS >= 3;
+    static_assert(!FX || (PACKED && !LAZY && RUNS && WSCAN == (1u << kFixWbits) && HB == kHb1024 && LOOP && !BLOCKM),
+                  "fixed geometry: the run-aware persistent build of the 2^10 window");
     // HB: bucket bits of the bigram index (2,048 buckets; 512 for the short-message build, whose blocks hold a few hundred
     // positions and pay for every cursor zeroed and scanned); the cursor region keeps its size, the walk needs it
     static_assert(HB >= 9 && HB <= 11, "entry payload: 16 - HB bigram bits + 8 bits of the third byte + the rest of the fourth");
@@ -916,10 +941,10 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
             a_l.blk_len = as_global(a_l.blk_len), a_l.blk_idx = as_global(a_l.blk_idx);
         }
         const CompressArgs& a = LOOP ? a_l : a_k;
-        const uint32_t a_wbits = a.wbits, a_blk = a.blk;
+        const uint32_t a_wbits = FX ? kFixWbits : a.wbits, a_blk = FX ? kFixBlk : a.blk;
         const uint32_t W = 1u << a_wbits, mask = W - 1;
         constexpr bool lazy = LAZY;
-        const CompressLds L(W, a_blk, PACKED, lazy, RUNS, HB == 9 ? kHashBits : HB);
+        const CompressLds L = FX ? kLdsFixed : CompressLds(W, a_blk, PACKED, lazy, RUNS, HB == 9 ? kHashBits : HB);
         uint8_t* const ebuf = smem + L.ebuf;
         uint16_t* const cnt16 = reinterpret_cast<uint16_t*>(smem + L.cnt);
         uint32_t* const cntw = reinterpret_cast<uint32_t*>(smem + L.cnt);
@@ -964,15 +989,15 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
             asm volatile("" : "+s"(wave_k));
             tid_l = (wave_k << 6) | lane_l;
         }
-        const uint32_t tid_k = tid_l, nt = blockDim.x;
+        const uint32_t tid_k = tid_l, nt = FX ? kFixThreads : blockDim.x;
         const uint32_t nt_log2 = nt == 256 ? 8u : 6u;  // (256 or 64 threads: divisions by the block size are shifts)
         uint32_t tid = tid_k;
         int lane = tid & (kWave - 1);
         uint32_t wave = tid >> 6;
-        const uint32_t minp = (uint32_t)min_pattern_size((int)a_wbits, a.lbits);
-        const bool ext = a.extended != 0;
+        const uint32_t wbits = a_wbits, lbits = FXS ? kFixLbits : a.lbits;
+        const uint32_t minp = (uint32_t)min_pattern_size((int)a_wbits, (int)lbits);
+        const bool ext = FXF ? FIX == kFixExt : a.extended != 0;
         const uint32_t maxp = ext ? minp + 11 + kExtExtraMax : minp + 13;  // compressor.c:12-19
-        const uint32_t wbits = a_wbits, lbits = a.lbits;
 #ifdef TAMP_POISON_LDS
         // test builds: every stream starts on LDS full of a pattern that changes from launch to launch and stream to stream, so
         // that a result which depends on what an earlier workgroup left behind shows in the differential runs at once
@@ -1008,8 +1033,10 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
             if (a.block_pass == 3) binfo = uni_u64(a.blk_info[s]);
         }
 
-        uint8_t* const st_io = a.state ? a.state + (size_t)s * (W + kSegStateExtra) : nullptr;
-        const bool partial = (a.seg_flags & kSegPartial) != 0;
+        // (fixed builds: whole streams only -- no state slot, no segment flags)
+        const uint32_t seg_flags = FXS ? 0u : a.seg_flags;
+        uint8_t* const st_io = (!FXS && a.state) ? a.state + (size_t)s * (W + kSegStateExtra) : nullptr;
+        const bool partial = (seg_flags & kSegPartial) != 0;
         uint32_t wp0 = 0;
         if constexpr (BLOCKM) {
             // window <- the W bytes in front of the block, oldest first: input, or -- in front of the stream -- the dictionary
@@ -1017,11 +1044,11 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
             wp0 = bpos & mask;
             for (uint32_t k = tid; k < W; k += nt) ebuf[k] = (bpos + k >= W) ? in[bpos + k - W] : a.dict[(bpos + k) & mask];
         } else
-        if (st_io && (a.seg_flags & kSegResume)) {
+        if (st_io && (seg_flags & kSegResume)) {
             // window <- saved state (ring order) rotated so that the oldest byte comes first
             wp0 = (uint32_t)st_io[W + kSlotWindowPos] | ((uint32_t)st_io[W + kSlotWindowPos + 1] << 8);
             for (uint32_t k = tid; k < W; k += nt) ebuf[k] = st_io[(wp0 + k) & mask];
-        } else if ((reinterpret_cast<uintptr_t>(a.dict) & 3) == 0) {
+        } else if (FXS || (reinterpret_cast<uintptr_t>(a.dict) & 3) == 0) {
             // window <- dictionary (custom, or the seeded default prepared by the host shim)
             for (uint32_t k = tid * 4; k < W; k += nt * 4)
                 *reinterpret_cast<uint32_t*>(ebuf + k) = *reinterpret_cast<const uint32_t*>(a.dict + k);
@@ -1030,7 +1057,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
         }
         // carried over from a call that ended without a flush (kSegStateExtra): pending run / extended match, pending bits
         uint32_t c_rle = 0, c_ext = 0, c_extpos = 0, c_nbits = 0, c_bits = 0;
-        if (st_io && (a.seg_flags & kSegResume)) {
+        if (st_io && (seg_flags & kSegResume)) {
             c_rle = Walk::uni(st_io[W + kSlotRle]), c_ext = Walk::uni(st_io[W + kSlotExtCount]);
             c_nbits = Walk::uni(st_io[W + kSlotNbits]) & 31u;
             c_extpos = Walk::uni((uint32_t)st_io[W + kSlotExtPos] | ((uint32_t)st_io[W + kSlotExtPos + 1] << 8));
@@ -1039,7 +1066,8 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
         }
         // bit buffer: leading bytes (header, compressor.c:236-241; FLUSH + pad when appending, :227-235) or the carried
         // bits, rest zero
-        const uint32_t word0 = (BLOCKM && s != 0) ? 0u : (a.nlead ? (uint32_t)a.lead << 16 : (c_nbits ? c_bits & (0xFFFFFFFFu << (32 - c_nbits)) : 0u));
+        const uint32_t nlead = FXS ? 1u : a.nlead;  // (fixed builds: the header byte)
+        const uint32_t word0 = (BLOCKM && s != 0) ? 0u : (nlead ? (uint32_t)a.lead << 16 : (c_nbits ? c_bits & (0xFFFFFFFFu << (32 - c_nbits)) : 0u));
         for (uint32_t k = tid; k < L.obuf_words; k += nt) obuf[k] = k == 0 ? __builtin_bswap32(word0) : 0;
 
         Walk wk;
@@ -1054,11 +1082,11 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
         wk.dbg = a.dbg;
 #endif
         wk.lazy = lazy, wk.lazy_valid = false, wk.lazy_idx = 0, wk.lazy_len = 0, wk.blen2 = blen2, wk.bidx2 = bidx2;
-        if (tid_k == 0) ctl[cCutThr] = a.cut_run;  // (read after the load phase's barrier)
+        if (tid_k == 0) ctl[cCutThr] = (FXF && FIX == kFixV1) ? 0u : a.cut_run;  // (read after the load phase's barrier)
         uint32_t w_p0 = bpos;  // wave 0: input position of ebuf[W]
 
         // workgroup-uniform output state
-        uint32_t carry = BLOCKM ? ((uint32_t)(binfo >> 4) & 31u) : (a.nlead ? 8u * a.nlead : c_nbits);  // bits already sitting in obuf
+        uint32_t carry = BLOCKM ? ((uint32_t)(binfo >> 4) & 31u) : (nlead ? 8u * nlead : c_nbits);  // bits already sitting in obuf
         uint32_t gpos = 0;                         // bytes already flushed to HBM
         uint32_t e_p0 = bpos, e_pending = c_rle + c_ext, e_wp = wp0;  // epoch parameters
         bool need_match = true;
@@ -1159,7 +1187,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
                 asm volatile("" : "+v"(tid));
                 lane = (int)(tid & (kWave - 1)), wave = tid >> 6, wk.lane = lane;  // (re-derived: see above)
                 const uint32_t NE0 = nvalid ? W + nvalid : 0;  // positions 0..NE0-1 (every query's own bigram included)
-                const uint32_t cut_run = Walk::uni(ctl[cCutThr]);  // (per stream: it adapts, see the walk's re-base)
+                const uint32_t cut_run = (FXF && FIX == kFixV1) ? 0u : Walk::uni(ctl[cCutThr]);  // (per stream: it adapts, see the walk's re-base; v1: no RLE token, no cut)
                 for (uint32_t c4 = tid * 4; c4 < NE0; c4 += nt * 4) {
                     const uint32_t d0 = *reinterpret_cast<const uint32_t*>(ebuf + c4);
                     const uint32_t d1 = *reinterpret_cast<const uint32_t*>(ebuf + c4 + 4);
@@ -2127,7 +2155,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
                     } else if (!partial && ext && wk.ext_count) {  // compressor.c:764-766
                         wk.emit_ext();
                     } else {
-                        if (st_io && (a.seg_flags & kSegSave)) {  // hand the window back in ring order
+                        if (st_io && (seg_flags & kSegSave)) {  // hand the window back in ring order
                             for (uint32_t i = lane; i < W; i += kWave) st_io[i] = (uint8_t)wk.win_l(i);
                             if (lane == 0) {
                                 st_io[W + kSlotWindowPos] = (uint8_t)wk.wp();
@@ -2342,7 +2370,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
             __syncthreads();
             uint32_t tot = carry + segbits;  // bits now in obuf
             if (excess) act = kActDone;
-            if (act == kActDone && !excess && (a.seg_flags & kSegFlushToken)) {
+            if (act == kActDone && !excess && (seg_flags & kSegFlushToken)) {
                 // compressor.c:784-794: FLUSH (9 bits) only if bits are pending or the stream allows dictionary resets
                 const bool want = (tot & 7) != 0 || a.dict_reset;
                 if (want && tid == 0) {
@@ -2365,7 +2393,7 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
                 nbytes = (excess || partial) ? (tot >> 3) : ((tot + 7) >> 3);  // compressor.c:629-631 / :799-807
             else
                 nbytes = (tot >> 5) << 2;
-            if (act == kActDone && st_io && (a.seg_flags & kSegSave) && tid == 0) {
+            if (act == kActDone && st_io && (seg_flags & kSegSave) && tid == 0) {
                 // the bits of the last, incomplete byte stay with the stream (partial_flush writes whole bytes only,
                 // compressor.c:65-75); after a drain the byte was padded and written: nothing is carried
                 const uint32_t nb = (partial && !excess) ? (tot & 7u) : 0u;
@@ -2495,5 +2523,21 @@ __global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG
         if constexpr (!LOOP) break;
     }
 }
+
+template <bool PACKED, bool LAZY, bool RUNS = false, uint32_t WSCAN = 0, uint32_t HB = kHashBits, bool LOOP = false, bool BLOCKM = false>
+__global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG_PER_CU : TAMP_LEAN_PER_CU)) tamp_compress_kernel(CompressArgs a_k) {
+    compress_streams<PACKED, LAZY, RUNS, WSCAN, HB, LOOP, BLOCKM, kFixNone>(a_k);
+}
+
+namespace tamp_compress_fixed {
+// FIX = kFixExt / kFixV1: window 2^10, 1,024-position blocks, literal 8, whole streams (see kFixNone above)
+// (a name of their own, with "tamp_compress" and "compress_kernel" in it: that is how bench.py and the tools pick the
+// compress launches out of a profile)
+template <uint32_t FIX>
+__global__ void __launch_bounds__(256, TAMP_WG_PER_CU) compress_kernel(CompressArgs a_k) {
+    static_assert(FIX == kFixExt || FIX == kFixV1, "the generic builds are tamp_compress_kernel's");
+    compress_streams<true, false, true, 1u << kFixWbits, kHb1024, true, false, FIX>(a_k);
+}
+}  // namespace tamp_compress_fixed
 
 }  // namespace tamp_amd

@@ -13,7 +13,9 @@ callees keep their own lines) and classed by what profiles/r5_valu_issue_probe.t
   spill  v_writelane / v_readlane whose VGPR is one of the kernel's SGPR-spill registers (listed by the caller or
          detected: a v_writelane into a register that is later only v_readlane'd)
 
-Output: one row per requested line range: instructions by class (static), and the loop heads found.
+Output: one row per requested line range: instructions by class (static), and the loop heads found.  Two more columns
+count, inside their classes: 'ds_imm' = LDS instructions with a non-zero `offset:` immediate (a region base folded into
+the instruction), 'v_sbase' = v_add_u32 / v_lshl_add_u32 / v_add_lshl_u32 with an SGPR operand (a base added per access).
 """
 import re
 import sys
@@ -85,7 +87,15 @@ def main():
         c = classify(op, operands)
         per_line[cur][c] += 1
         total[c] += 1
-    classes = ["fast", "slow", "lane", "salu", "lds", "vmem", "other"]
+        extra = None
+        if c == "lds" and re.search(r"offset[01]?:[1-9]", operands):
+            extra = "ds_imm"
+        elif op.split("_e")[0] in ("v_add_u32", "v_lshl_add_u32", "v_add_lshl_u32", "v_add3_u32") and re.search(r"(^|[ ,])s\d+", operands):
+            extra = "v_sbase"
+        if extra:
+            per_line[cur][extra] += 1
+            total[extra] += 1
+    classes = ["fast", "slow", "lane", "salu", "lds", "vmem", "other", "ds_imm", "v_sbase"]
     print("# %s" % kernel)
     print("# static instruction counts; 'fast' / 'slow' = VALU issue classes (2.2 / 4.1 cycles), 'lane' = v_readlane / v_writelane")
     print("%-28s %s" % ("range", " ".join("%7s" % c for c in classes)))
