@@ -108,7 +108,7 @@ const char *tamp_amd_version(void);
 const char *tamp_amd_last_error(void);
 
 /* How tamp_batch_compress would launch streams of up to `max_in_len` bytes (0 = unknown) at this window: positions matched
- * per epoch, LDS bytes per workgroup, threads per workgroup and the workgroups per CU its registers aim at (7 for the
+ * per epoch, LDS bytes per workgroup, threads per workgroup and the workgroups per CU its registers aim at (8 for the
  * run-aware builds, 6 lean, 5 lazy).  Pure host arithmetic -- no device needed; a diagnostics / capacity-planning call
  * (the reference has no counterpart: its state is the 16-byte ring + window of compressor.h:13-66).  Returns TAMP_OK or
  * TAMP_AMD_BAD_ARGUMENT. */
@@ -159,7 +159,10 @@ int tamp_amd_compress_build(const TampAmdConf *conf, uint32_t max_in_len, uint32
  *                                               its own pristine copy)
  *   max_in_len                                  upper bound on in_len[] (sizes the per-workgroup LDS block); 0 = unknown:
  *                                               computed from in_len for host memory, 4096-position blocks for
- *                                               device memory (any length still works, in several epochs)
+ *                                               device memory (any length still works, in several epochs).  The bound
+ *                                               ONLY sizes the block and picks the build: a stream longer than it is
+ *                                               compressed to the same bytes, in more epochs (a device-memory call
+ *                                               cannot check the bound, and a stale one costs speed, never bytes)
  *   mem                                         TAMP_AMD_MEM_HOST or TAMP_AMD_MEM_DEVICE: applies to ALL pointer
  *                                               arguments except conf
  *   device                                      HIP device ordinal

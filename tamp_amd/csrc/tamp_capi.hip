@@ -267,6 +267,13 @@ uint32_t pick_block(uint32_t W, uint32_t max_in_len, bool packed, bool lazy, boo
     return blk;
 }
 
+// Threads per workgroup for a block of `blk` positions: four wavefronts from 1,024 positions on, one below.  A block override
+// (TAMP_AMD_BLK, tuning) that gives LONG streams a block of 512..960 positions keeps the four.  One definition for the launcher,
+// tamp_amd_compress_plan and tamp_amd_compress_build.
+uint32_t compress_threads(uint32_t blk, bool long_streams) {
+    return (blk >= 1024 || (long_streams && blk >= 512 && getenv("TAMP_AMD_BLK"))) ? 256u : 64u;
+}
+
 // Expensive streams first (round 5).  One stream = one workgroup, so a batch cannot finish before its slowest stream does, and
 // a batch of only a few rounds of the persistent grid -- 3,052 streams per GPU when BASELINE configs[2] runs on eight -- waits
 // for whichever slow stream happened to start last.  What makes a stream slow are its lags and searches, and a
@@ -578,7 +585,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
         snprintf(t_last_error, sizeof t_last_error, "LDS %u B > %zu B per block", L.total, ctx->lds_per_block);
         return TAMP_AMD_BAD_ARGUMENT;
     }
-    const uint32_t threads = (a.blk >= 1024 || (long_streams && a.blk >= 512 && getenv("TAMP_AMD_BLK"))) ? 256 : 64;  // (tuning: smaller blocks for long streams)
+    const uint32_t threads = compress_threads(a.blk, long_streams);
     const uint32_t grid = (uint32_t)(n_streams < (1u << 20) ? n_streams : (1u << 20));
     // the fixed-geometry pair for the 2^10 window's whole-stream calls (fixed_build_for above), and the six generic builds: lazy (u32 / u16 entries), run-aware (generic window / 2^10 with the scan constants as immediates),
     // lean one-wavefront build for short messages (512 buckets: a quarter of the cursors to zero and scan per message),
@@ -1754,7 +1761,7 @@ int tamp_amd_compress_plan(uint8_t window_bits, uint32_t max_in_len, int lazy_ma
     const uint32_t by_lds = 160u * 1024u / align_up(L.total, 2048u);
     if (block_positions) *block_positions = blk;
     if (lds_bytes) *lds_bytes = L.total;
-    if (threads) *threads = blk >= 1024 ? 256u : 64u;
+    if (threads) *threads = compress_threads(blk, long_streams);
     if (workgroups_per_cu) *workgroups_per_cu = by_lds < reg_cap ? by_lds : reg_cap;
     return TAMP_OK;
 }
@@ -1782,7 +1789,7 @@ int tamp_amd_compress_build(const TampAmdConf* conf, uint32_t max_in_len, uint32
     if (const char* e = getenv("TAMP_AMD_RUNS")) { if (!long_streams) runlist = packed && !a.lazy && atoi(e) != 0; }
     const uint32_t hb = runlist && conf->window == 10 ? kHb1024 : kHashBits;
     a.blk = pick_block(W, max_in_len, packed, a.lazy != 0, runlist, hb);
-    const uint32_t threads = (a.blk >= 1024 || (long_streams && a.blk >= 512 && getenv("TAMP_AMD_BLK"))) ? 256 : 64;
+    const uint32_t threads = compress_threads(a.blk, long_streams);
     const uint32_t fix = fixed_build_for(conf, a, runlist, threads);
     return fix == kFixExt ? TAMP_AMD_BUILD_FIXED_EXT : (fix == kFixV1 ? TAMP_AMD_BUILD_FIXED_V1 : TAMP_AMD_BUILD_GENERIC);
 }

@@ -75,6 +75,20 @@ def test_host_helpers_need_no_device(oracle):
         assert plan(10, 4096)[0] == 1024 and plan(9, 4096)[0] == 2048
     finally:
         del os.environ["TAMP_AMD_BLK"]
+    # ... and the plan reports the workgroup the launcher starts for an overridden block: four wavefronts from 512 positions on for
+    # long streams (1 KiB and more, or unknown), one wavefront below that and for short messages up to 960 positions
+    for b in range(64, 2049, 64):
+        os.environ["TAMP_AMD_BLK"] = str(b)
+        try:
+            for w, lazy in ((9, 0), (12, 0), (15, 0), (12, 1)):
+                assert plan(w, 4625, lazy)[0] == b and plan(w, 0, lazy)[0] == b
+                assert plan(w, 4625, lazy)[2] == plan(w, 0, lazy)[2] == (256 if b >= 512 else 64), (w, lazy, b)
+                assert plan(w, 960, lazy)[2] == (256 if b >= 1024 else 64), (w, lazy, b)
+            assert plan(10, 4625)[:1] == (min(b, 1024),) and plan(10, 4625)[2] == (256 if b >= 512 else 64)
+        finally:
+            del os.environ["TAMP_AMD_BLK"]
+    for n in (64, 512, 960):
+        assert plan(10, n)[2] == 64 and plan(12, n, 1)[2] == 64   # (no override: one wavefront below 1,024 positions)
     conf = _lib.TampAmdConf()
     consumed = ctypes.c_size_t(0)
     hdr = (ctypes.c_ubyte * 2)(0x5A, 0)

@@ -5,12 +5,18 @@ reference's ring.  This checks that design, in scalar C, a
 sizes -- including blocks far smaller than the window and inputs that force a re-base after almost every token.
 """
 import ctypes as C
+import os
 import random
+import sys
 
 import numpy as np
+import pytest
 
 from oracle.checker import _OracleConf, _p, _u8
 from tamp_amd import workloads as wl
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from block_draggers import draggers  # noqa: E402
 
 
 def _model(oracle, data, *, window, literal, extended, dictionary, blk):
@@ -62,3 +68,16 @@ def test_epochs_per_stream_on_text(oracle):
     assert 2 <= np.mean(eps) < 2.6
     eps = [_model(oracle, r.tobytes(), window=10, literal=8, extended=False, dictionary=None, blk=2048)[2] for r in rows]
     assert set(eps) == {2}
+
+
+@pytest.mark.parametrize("extended", [True, False])
+def test_model_equals_oracle_on_the_block_draggers(oracle, extended):
+    """The inputs of tests/test_gpu_block_geometry.py (features at periods coprime to 64, 4,625 bytes: more than two of the largest
+    blocks) through the model at both ends of the one-wavefront and the four-wavefront block ranges and around 1,024: a
+    mismatch the GPU tier reports at these blocks is then the kernel's or the launcher's, not the design's or the inputs'."""
+    for name, data in draggers(4625).items():
+        want = oracle.compress(data, window=10, literal=8, extended=extended)
+        assert want[0] == 0
+        for blk in (64, 448, 960, 1024, 1088, 1984, 2048):
+            got = _model(oracle, data, window=10, literal=8, extended=extended, dictionary=None, blk=blk)
+            assert got[:2] == want, (name, extended, blk)
