@@ -23,6 +23,7 @@
 #include "tamp_amd.h"
 #include "tamp_compat.h"
 #include "tamp_compress_kernel.hpp"
+#include "tamp_compress_plan.hpp"
 #include "tamp_decompress_kernel.hpp"
 #include "tamp_decompress_split_kernel.hpp"
 #include "tamp_decompress_long_kernel.hpp"
@@ -198,11 +199,6 @@ int get_ctx(int device, DeviceCtx** out) {
     return TAMP_OK;
 }
 
-// header byte 0 of a stream from its five fields, compressor.c:236-241 (read back by decompressor.c:276-297)
-uint8_t header_byte(unsigned window, unsigned literal, bool custom_dictionary, bool extended, bool dictionary_reset) {
-    return (uint8_t)(((window - 8) << 5) | ((literal - 5) << 3) | (custom_dictionary << 2) | (extended << 1) | dictionary_reset);
-}
-
 thread_local bool t_timing_outer = false;  // a caller's event pair spans several inner launches (up to sixteen long streams)
 void timing_begin(hipStream_t st) {
     if (t_timing_outer) return;
@@ -223,56 +219,8 @@ void timing_end(hipStream_t st) {
 struct SegmentSpec {  // streaming Compressor over the engine: how this piece of the stream opens and closes
     uint8_t nlead;
     uint16_t lead;
-    uint8_t flags;  // kSegResume | kSegSave | kSegFlushToken
+    uint8_t flags;  // kSegResume | kSegSave | kSegFlushToken | kSegPartial
 };
-
-uint32_t pick_block(uint32_t W, uint32_t max_in_len, bool packed, bool lazy, bool runlist = false, uint32_t hb = kHashBits) {
-    // Positions matched per epoch (a multiple of 64: the walk chases 64 positions per register; of 256 when it can be:
-    // the index is scattered in tiles of 256 positions, two barriers each, and a last tile that is mostly empty costs
-    // as much as a full one).  The whole stream when it is short.  For longer ones what counts is how many workgroups a
-    // CU holds -- the kernel is bound by instruction issue and a third of a real-text stream's time is the one-wavefront
-    // walk -- so: the LARGEST block that still allows as many workgroups per CU as a 1,024-position block does (the
-    // registers allow TAMP_WG_PER_CU = 8 for the run-aware builds since round 6, 6 for the lean and 5 for the lazy ones).  At
-    // W = 1024 that is 1,024 positions at eight per CU (19.2 KB with 1,024 buckets; round 4-5: seven at 21.4 KB; rounds 1-3: 1,536
-    // positions at six, 26.3 KB): four epochs instead of three for a 4 KiB stream, and faster on every input measured
-    // (profiles/ab/r4_seven_workgroups_per_cu.log, profiles/ab/r6_experiments.log).
-    uint32_t blk = max_in_len ? align_up(max_in_len, 64) : 2048;
-    if (blk > 2048) blk = 2048;
-    if (blk > 1024) {
-        // (LDS is handed out in coarse granules: 26,960 B per workgroup measured as five per CU, 25,424 B as six)
-        const uint32_t lds_cu = 160u * 1024u, granule = 2048u;
-        const uint32_t reg_cap = lazy ? (uint32_t)TAMP_LAZY_PER_CU : (runlist ? (uint32_t)TAMP_WG_PER_CU : (uint32_t)TAMP_LEAN_PER_CU);
-        auto per_cu = [&](uint32_t b) {
-            const uint32_t v = lds_cu / align_up(CompressLds(W, b, packed, lazy, runlist, hb).total, granule);
-            return v < reg_cap ? v : reg_cap;
-        };
-        const uint32_t want = per_cu(1024);
-        uint32_t best = 1024;
-        for (uint32_t b = 1280; b <= 2048; b += 256)
-            if (b <= blk && per_cu(b) == want) best = b;
-        // (the stream's own length: one epoch instead of two for streams a little over 1 KiB, when that costs no workgroup)
-        if (blk > best && blk < 2048 && per_cu(blk) == want) best = blk;
-        blk = best;
-    }
-    if (const char* e = getenv("TAMP_AMD_BLK")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 64 && v <= 2048) blk = align_up(v, 64); }
-    if (blk < 64) blk = 64;
-    {
-        // The cursor region of LDS also serves as the sorted query list (blk x u16) and, in the run-aware builds, as the walk's
-        // explicit pieces + the step table (kSlowCap x 8 + blk bytes): a tuning override must not outgrow it.  (Checked here and
-        // not by sizing the region from the block: that arithmetic inside the kernel cost the 64-VGPR builds their last register.)
-        const uint32_t cur = (hb < kHashBits ? (1u << hb) : kHashBuckets) * 2;
-        while (blk > 64 && (blk * 2 > cur || (runlist && kSlowCap * 8 + blk > cur))) blk -= 64;
-    }
-    while (W + blk + 16 > 65536) blk >>= 1;  // 16-bit buffer positions
-    return blk;
-}
-
-// Threads per workgroup for a block of `blk` positions: four wavefronts from 1,024 positions on, one below.  A block override
-// (TAMP_AMD_BLK, tuning) that gives LONG streams a block of 512..960 positions keeps the four.  One definition for the launcher,
-// tamp_amd_compress_plan and tamp_amd_compress_build.
-uint32_t compress_threads(uint32_t blk, bool long_streams) {
-    return (blk >= 1024 || (long_streams && blk >= 512 && getenv("TAMP_AMD_BLK"))) ? 256u : 64u;
-}
 
 // Expensive streams first (round 5).  One stream = one workgroup, so a batch cannot finish before its slowest stream does, and
 // a batch of only a few rounds of the persistent grid -- 3,052 streams per GPU when BASELINE configs[2] runs on eight -- waits
@@ -421,15 +369,55 @@ __global__ void __launch_bounds__(256) tamp_block_scan_kernel(const uint32_t* ta
     for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) info[b0 + i] = res[i];
 }
 
-// Block mode (tamp_compress_kernel<.., BLOCKM>): ONE long stream of the v1 format, literal 8, default parse, fresh window.
+// The kernel's argument block as conf, the call's lead and the dictionary decide it.  The caller adds the batch's tables, the plan
+// the block and the claim.  (Value-initialised: no work counter, first stream 0, none of the block-mode tables.)
+CompressArgs fill_compress_args(const DeviceCtx* ctx, const CompressCall& call, const uint8_t* d_dict, uint8_t* d_state) {
+    const TampAmdConf* conf = call.conf;
+    CompressArgs a = {};
+    a.wbits = conf->window, a.lbits = conf->literal, a.extended = conf->extended != 0;
+    a.dict_reset = conf->dictionary_reset != 0, a.lazy = conf->lazy_matching != 0, a.prof = g_prof, a.claim = 1;
+    a.nlead = call.nlead, a.lead = call.lead, a.seg_flags = call.seg_flags, a.state = call.has_state ? d_state : nullptr;
+    // compressor.c:224-225: non-extended streams always use the literal-8 table
+    const int lit = conf->extended ? conf->literal : 8;
+    a.dict = conf->use_custom_dictionary ? d_dict : ctx->seed_dicts + (lit <= 5 ? 0 : (lit == 6 ? 1 : 2)) * kSeedTable;
+    // epoch cut at long runs (extended format only: the v1 format has no RLE token), tamp_compress_kernel.hpp
+    a.cut_run = conf->extended ? 3u : 0u;  // (doubles per stream whenever a cut turns out to be superfluous)
+    if (const char* e = getenv("TAMP_AMD_CUT_RUN")) { const int v = atoi(e); a.cut_run = (conf->extended && v >= 2 && v <= 64) ? (uint32_t)v : 0u; }
+    a.dbg = getenv("TAMP_AMD_DBG") ? (uint32_t)atoi(getenv("TAMP_AMD_DBG")) : 0;
+    return a;
+}
+
+// What the two compress launchers do with a plan.  prepare_compress_kernel: the dynamic-LDS attribute of the plan's kernel and, for
+// a persistent grid, how many of its workgroups a CU holds (the occupancy query costs ~10 us: once per shape).  launch_on_counter:
+// a work-counter slot, zeroed, and the launch over it.  (Two steps: the grid is sized, checked and used between them.)
+int prepare_compress_kernel(const CompressPlan& p, int* per_cu) {
+    const void* const kernel = reinterpret_cast<const void*>(compress_kernel_of(p.build));
+    HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds.total));
+    if (!p.persistent) return TAMP_OK;
+    static std::mutex occ_mu;
+    static std::map<std::pair<const void*, uint64_t>, int> occ;  // (0: not asked yet)
+    std::lock_guard<std::mutex> lock(occ_mu);
+    int& cached = occ[std::make_pair(kernel, (uint64_t)p.lds.total << 16 | p.threads)];
+    if (cached == 0) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kernel, (int)p.threads, p.lds.total));
+    *per_cu = cached = std::max(cached, 1);
+    return TAMP_OK;
+}
+int launch_on_counter(DeviceCtx* ctx, const CompressPlan& p, uint32_t grid, CompressArgs& a, hipStream_t st) {
+    a.work_counter = ctx->work_counters + ctx->next_counter.fetch_add(1) % DeviceCtx::kCounters;
+    HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(compress_kernel_of(p.build), dim3(grid), dim3(p.threads), p.lds.total, st, a);
+    return TAMP_OK;
+}
+
+// Block mode (the BLOCKM builds of the compress kernel): ONE long stream of the v1 format, literal 8, default parse, fresh window.
 // -> TAMP_OK when the stream was taken this way, 1 when the call does not qualify (the caller goes on with the batch kernel).
 // `rec`: the stream's scratch record, locked by the caller.
-int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, const TampAmdConf* conf, uint32_t max_in_len, hipStream_t st, size_t n_streams) {
-    const uint32_t W = 1u << conf->window;
+int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, CompressCall call, hipStream_t st, size_t n_streams) {
+    const TampAmdConf* conf = call.conf;
     uint32_t min_len = 256u << 10;
     if (const char* e = getenv("TAMP_AMD_BLOCK_MIN")) min_len = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;  // (tuning / tests; 0 = off)
-    if (conf->extended || conf->lazy_matching || conf->literal != 8 || conf->window > 14 || a0.state || a0.seg_flags || max_in_len < min_len ||
-        n_streams == 0 || n_streams > 64)
+    if (conf->extended || conf->lazy_matching || conf->literal != 8 || conf->window > 14 || call.has_state || call.seg_flags ||
+        call.max_in_len < min_len || n_streams == 0 || n_streams > 64)
         return 1;
     // the streams' table rows: lengths, capacities (the launch geometry and the zero fill depend on them); a handful of LONG
     // streams is taken one after the other, each over all workgroups -- any shorter one among them and the batch kernel takes all
@@ -445,19 +433,12 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
         if (in_len[i] < min_len) return 1;
         n_max = std::max(n_max, in_len[i]);
     }
-    const bool runs_build = !getenv("TAMP_AMD_BLOCK_LEAN");  // (the run-aware build, as for every long stream; tuning: the lean one)
-    const uint32_t hb = runs_build && conf->window == 10 ? kHb1024 : kHashBits;
-    a0.blk = pick_block(W, 0, true, false, runs_build, hb);
-    if (a0.blk > 1024) a0.blk = 1024;  // (more, smaller blocks: the unit of parallelism here)
-    const CompressLds L(W, a0.blk, true, false, runs_build, hb);
-    if (L.total > ctx->lds_per_block) return 1;
-    auto kernel = !runs_build ? tamp_compress_kernel<true, false, false, 0, kHashBits, true, true>
-                  : conf->window == 10 ? tamp_compress_kernel<true, false, true, 1024, kHb1024, true, true>
-                                       : tamp_compress_kernel<true, false, true, 0, kHashBits, true, true>;
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
+    call.block_mode = true;
+    const CompressPlan p = plan_compress(call);
+    a0.blk = p.blk, a0.claim = p.claim, a0.cut_run = 0;
+    if (p.lds.total > ctx->lds_per_block) return 1;
     int per_cu = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), 256, L.total));
-    if (per_cu < 1) per_cu = 1;
+    if (const int rc = prepare_compress_kernel(p, &per_cu)) return rc;
     // scratch for the longest of them
     const uint32_t nb_max = (n_max + a0.blk - 1) / a0.blk, nc_max = (nb_max + kScanChunk - 1) / kScanChunk;
     const size_t table_bytes = ((size_t)nb_max * 16 * 4 + 255) & ~(size_t)255, info_bytes = ((size_t)nb_max * 8 + 255) & ~(size_t)255;
@@ -480,7 +461,7 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
         a.blk_info = reinterpret_cast<unsigned long long*>(base + table_bytes);
         a.blk_len = keep_tables ? tables : nullptr;
         a.blk_idx = keep_tables ? reinterpret_cast<uint16_t*>(tables + len_bytes) : nullptr;
-        a.n_blocks = n_blocks, a.n_streams = n_blocks, a.first_stream = 0, a.claim = 1, a.cut_run = 0;
+        a.n_blocks = n_blocks, a.n_streams = n_blocks;
         const uint32_t g = (uint32_t)std::min<size_t>((size_t)per_cu * (size_t)ctx->cu_count, n_blocks);
         // every byte the emitters may OR into: header + 9 bits per input byte at most (all literals), capped by the caller's room
         const uint64_t bound = (uint64_t)a.nlead + ((uint64_t)n * 9 + 7) / 8 + 8;
@@ -491,31 +472,13 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
                 hipLaunchKernelGGL(tamp_block_scan_kernel, dim3(n_chunks), dim3(256), 0, st, a.blk_table, chunk_table, a.blk_info, n_blocks, 8u * a.nlead);
                 continue;
             }
-            const uint32_t slot = ctx->next_counter.fetch_add(1) % DeviceCtx::kCounters;
-            a.work_counter = ctx->work_counters + slot;
             a.block_pass = pass;
-            HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(kernel, dim3(g), dim3(256), L.total, st, a);
+            if (const int rc = launch_on_counter(ctx, p, g, a, st)) return rc;
         }
     }
     timing_end(st);
     HIP_OK(hipGetLastError());
     return TAMP_OK;
-}
-
-// The fixed-geometry builds (tamp_compress_fixed::compress_kernel<FIX>): kFixExt / kFixV1 when the call is EXACTLY what they
-// were compiled for, kFixNone (the generic build) for everything else.  `a` as launch_compress has filled it in, `runlist` /
-// `threads` as it has chosen them.  TAMP_AMD_FIXED_BUILD=0 forces the generic build (A/B runs, the parity tests).
-uint32_t fixed_build_for(const TampAmdConf* conf, const CompressArgs& a, bool runlist, uint32_t threads) {
-#ifdef TAMP_SEVEN
-    return kFixNone;  // (the seven-per-CU tuning shape has another LDS layout)
-#endif
-    if (const char* e = getenv("TAMP_AMD_FIXED_BUILD")) { if (atoi(e) == 0) return kFixNone; }
-    const uint16_t plain_lead = (uint16_t)(header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, 0) << 8);
-    const bool fits = conf->window == kFixWbits && conf->literal == kFixLbits && !a.lazy && runlist && a.blk == kFixBlk &&
-                      threads == kFixThreads && a.state == nullptr && a.seg_flags == 0 && !a.dict_reset && a.nlead == 1 &&
-                      a.lead == plain_lead && (reinterpret_cast<uintptr_t>(a.dict) & 3) == 0;
-    return !fits ? kFixNone : (a.extended ? kFixExt : kFixV1);
 }
 
 int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_dict, const uint8_t* d_in,
@@ -525,116 +488,32 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
     if (n_streams == 0) return TAMP_OK;
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
-    CompressArgs a;
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
+    CompressCall call = compress_call(conf, max_in_len, reinterpret_cast<uintptr_t>(d_dict));
+    if (seg) call.nlead = seg->nlead, call.lead = seg->lead, call.seg_flags = seg->flags, call.has_state = d_state != nullptr;
+    CompressArgs a = fill_compress_args(ctx, call, d_dict, d_state);
+    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len, a.n_streams = (uint32_t)n_streams;
     a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
-    a.wbits = conf->window, a.lbits = conf->literal, a.extended = conf->extended != 0;
-    a.dict_reset = conf->dictionary_reset != 0;
-    a.lazy = conf->lazy_matching != 0;
-    // header byte (+ a zero second byte when dictionary_reset is set)
-    const uint8_t header = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
-    a.nlead = conf->dictionary_reset ? 2 : 1;
-    a.lead = (uint16_t)(header << 8);
-    a.seg_flags = 0;
-    a.state = nullptr;
-    if (seg) {
-        a.nlead = seg->nlead, a.lead = seg->lead, a.seg_flags = seg->flags, a.state = d_state;
-    }
-    if (conf->use_custom_dictionary) {
-        a.dict = d_dict;
-    } else {
-        // compressor.c:224-225: non-extended streams always use the literal-8 table
-        const int lit = conf->extended ? conf->literal : 8;
-        a.dict = ctx->seed_dicts + (lit <= 5 ? 0 : (lit == 6 ? 1 : 2)) * kSeedTable;
-    }
-    a.n_streams = (uint32_t)n_streams;
-    a.prof = g_prof;
-    a.work_counter = nullptr;
-    a.claim = 1;
-    // epoch cut at long runs (extended format only: the v1 format has no RLE token), tamp_compress_kernel.hpp
-    a.cut_run = conf->extended ? 3u : 0u;  // (doubles per stream whenever a cut turns out to be superfluous)
-    if (const char* e = getenv("TAMP_AMD_CUT_RUN")) { const int v = atoi(e); a.cut_run = (conf->extended && v >= 2 && v <= 64) ? (uint32_t)v : 0u; }
-    a.dbg = getenv("TAMP_AMD_DBG") ? (uint32_t)atoi(getenv("TAMP_AMD_DBG")) : 0;
-    a.blk_table = nullptr, a.blk_info = nullptr, a.block_pass = 0, a.n_blocks = 0, a.blk_len = nullptr, a.blk_idx = nullptr;
-    if (n_streams <= 64 && !seg) {  // a handful of LONG v1 streams: each one's blocks over all workgroups (tamp_compress_kernel<.., BLOCKM>)
-        const int rc = launch_compress_blocks(ctx, rec, a, conf, max_in_len, st, n_streams);
+    if (n_streams <= 64 && !seg) {  // a handful of LONG v1 streams: each one's blocks over all workgroups (the BLOCKM builds)
+        const int rc = launch_compress_blocks(ctx, rec, a, call, st, n_streams);
         if (rc != 1) return rc;
     }
-    const uint32_t W = 1u << conf->window;
-    const bool packed = conf->window <= 14;  // u32 index entries; 2^15 windows fall back to u16 positions
-    // run-list build: long runs of one byte leave the bigram index; default parse only
-    // AUTO goes by stream length alone, for host and device batches alike (no look at the data): the run-aware build for
-    // streams of 1 KiB and more -- it settles short RLE runs and most extended matches in the match phase and is the faster
-    // one on every kind of text measured, runs or not (config 2: 6.89 against 7.29 ms) -- the lean build for short
-    // messages (256-byte telemetry: 2.2 against 2.5 ms), where its per-epoch run search does not pay
-    // Round 3: six builds instead of nine.  Streams of 1 KiB and more (256-thread workgroups) always take the run-aware
-    // build -- it was the faster one on every kind of text in both formats, so the lean 256-thread builds only served the
-    // PLAIN hint; the hint now matters for short messages alone, where the lean one-wavefront build is ahead.  The 2^15
-    // window (u16 index entries) has the lean and the lazy build only.
-    const bool long_streams = max_in_len == 0 || align_up(max_in_len, 64) >= 1024;  // (= 256-thread workgroups, pick_block)
-    bool runlist = packed && !a.lazy && (long_streams || conf->input_hint == TAMP_AMD_HINT_RUNS);
-    if (const char* e = getenv("TAMP_AMD_RUNS")) { if (!long_streams) runlist = packed && !a.lazy && atoi(e) != 0; }  // tuning / tests
-    const uint32_t hb = runlist && conf->window == 10 ? kHb1024 : kHashBits;
-    a.blk = pick_block(W, max_in_len, packed, a.lazy != 0, runlist, hb);
-    if (runlist && CompressLds(W, a.blk, packed, false, true, hb).total > ctx->lds_per_block) {
-        snprintf(t_last_error, sizeof t_last_error, "LDS %u B > %zu B per block", CompressLds(W, a.blk, packed, false, true, hb).total, ctx->lds_per_block);
-        return TAMP_AMD_BAD_ARGUMENT;  // (cannot happen for windows up to 2^14: 105 KB at most)
-    }
-    const CompressLds L(W, a.blk, packed, a.lazy != 0, runlist, hb);
-    if (L.total > ctx->lds_per_block) {
-        snprintf(t_last_error, sizeof t_last_error, "LDS %u B > %zu B per block", L.total, ctx->lds_per_block);
+    const CompressPlan p = plan_compress(call);  // (build, block, LDS layout, workgroup, grid: tamp_compress_plan.hpp)
+    a.blk = p.blk, a.claim = p.claim;
+    if (p.lds.total > ctx->lds_per_block) {
+        snprintf(t_last_error, sizeof t_last_error, "LDS %u B > %zu B per block", p.lds.total, ctx->lds_per_block);
         return TAMP_AMD_BAD_ARGUMENT;
     }
-    const uint32_t threads = compress_threads(a.blk, long_streams);
-    const uint32_t grid = (uint32_t)(n_streams < (1u << 20) ? n_streams : (1u << 20));
-    // the fixed-geometry pair for the 2^10 window's whole-stream calls (fixed_build_for above), and the six generic builds: lazy (u32 / u16 entries), run-aware (generic window / 2^10 with the scan constants as immediates),
-    // lean one-wavefront build for short messages (512 buckets: a quarter of the cursors to zero and scan per message),
-    // lean u16 build for the 2^15 window.
-    // All but the short-message build run as a PERSISTENT GRID (LOOP in the kernel): as many workgroups as the device holds
-    // at once, each taking streams from a counter until none is left.  Workgroup i of a grid runs on XCD i % 8 whatever the
-    // other XCDs are doing, so with one workgroup per stream an eighth of the batch is pinned to each XCD before anything
-    // of the streams' costs is known -- and real text is heavy-tailed (and the frozen corpora, 768 chunks long, handed every
-    // XCD the same 96 chunks over and over: 17 % lost, profiles/ab/r3_persistent_grid.log).  Short messages keep one
-    // workgroup per stream: two million fetches from one counter cost more than the balance is worth (20 instead of
-    // 41 GB/s when tried), and their costs are even.
-    const bool short_build = packed && !a.lazy && !runlist;
-    const uint32_t fix = fixed_build_for(conf, a, runlist, threads);
-    auto kernel = fix == kFixExt ? tamp_compress_fixed::compress_kernel<kFixExt>
-                  : fix == kFixV1 ? tamp_compress_fixed::compress_kernel<kFixV1>
-                  : a.lazy ? (packed ? tamp_compress_kernel<true, true, false, 0, kHashBits, true> : tamp_compress_kernel<false, true, false, 0, kHashBits, true>)
-                  : !packed ? tamp_compress_kernel<false, false, false, 0, kHashBits, true>
-                  : runlist ? (conf->window == 10 ? tamp_compress_kernel<true, false, true, 1024, kHb1024, true> : tamp_compress_kernel<true, false, true, 0, kHashBits, true>)
-                            : tamp_compress_kernel<true, false, false, 0, 9>;
-    if (short_build && threads != 64) {  // (short messages only: long streams are run-aware above)
-        snprintf(t_last_error, sizeof t_last_error, "no lean build for %u-thread workgroups", threads);
+    if (!p.persistent && p.threads != 64) {  // (short messages only: long streams are run-aware)
+        snprintf(t_last_error, sizeof t_last_error, "no lean build for %u-thread workgroups", p.threads);
         return TAMP_AMD_BAD_ARGUMENT;
     }
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)L.total));
-    if (!short_build) {
-        static std::mutex occ_mu;
-        static std::map<std::pair<const void*, uint64_t>, int> occ;  // (the occupancy query costs ~10 us: once per shape)
-        int per_cu = 0;
-        {
-            std::lock_guard<std::mutex> lock(occ_mu);
-            const auto key = std::make_pair(reinterpret_cast<const void*>(kernel), (uint64_t)L.total << 16 | threads);
-            auto it = occ.find(key);
-            if (it == occ.end()) {
-                HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), (int)threads, L.total));
-                if (per_cu < 1) per_cu = 1;
-                occ.emplace(key, per_cu);
-            } else {
-                per_cu = it->second;
-            }
-        }
+    int per_cu = 0;
+    if (const int rc = prepare_compress_kernel(p, &per_cu)) return rc;
+    if (p.persistent) {
         if (const char* e = getenv("TAMP_AMD_GRID_PER_CU")) {  // (tuning)
             if (atoi(e) > 0) per_cu = atoi(e);
-            else fprintf(stderr, "tamp_amd: %d workgroups of %u threads, %u B LDS per CU\n", per_cu, threads, L.total);
+            else fprintf(stderr, "tamp_amd: %d workgroups of %u threads, %u B LDS per CU\n", per_cu, p.threads, p.lds.total);
         }
-        a.first_stream = 0;
-        // streams per fetch from the counter: one for 256-thread workgroups (streams of 1 KiB and more), sixteen for
-        // one-wavefront ones (lazy / 2^15-window / hinted short messages)
-        a.claim = threads == 256 ? 1u : 16u;
         const size_t claims = (n_streams + a.claim - 1) / a.claim;
         size_t g = std::min<size_t>((size_t)per_cu * (size_t)ctx->cu_count, claims);
         // TAMP_AMD_STATIC_GRID=1 (tuning): one workgroup per claim instead -- each takes its claim when it starts and finds
@@ -649,8 +528,8 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
         timing_begin(st);
         // expensive streams first, for batches of more than one and at most ~18 rounds of the grid (beyond, the tail is short
         // next to the batch; TAMP_AMD_LPT=0 / =1 force it off / on)
-        bool lpt = threads == 256 && !seg && n_streams > g && n_streams <= 32768;
-        if (const char* e = getenv("TAMP_AMD_LPT")) lpt = atoi(e) != 0 && threads == 256 && !seg && n_streams > 1 && n_streams <= (1u << 20);
+        bool lpt = p.threads == 256 && !seg && n_streams > g && n_streams <= 32768;
+        if (const char* e = getenv("TAMP_AMD_LPT")) lpt = atoi(e) != 0 && p.threads == 256 && !seg && n_streams > 1 && n_streams <= (1u << 20);
         uint8_t* lpt_mem = nullptr;
         uint32_t* lpt_order = nullptr;
         uint32_t* lpt_out_len = nullptr;
@@ -679,21 +558,18 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
                 a.out_len = lpt_out_len, a.status = lpt_status;
             }
         }
-        const uint32_t slot = ctx->next_counter.fetch_add(1) % DeviceCtx::kCounters;
-        a.work_counter = ctx->work_counters + slot;
-        HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)g), dim3(threads), L.total, st, a);
+        if (const int rc = launch_on_counter(ctx, p, (uint32_t)g, a, st)) return rc;
         if (lpt) {
             hipLaunchKernelGGL(tamp_scatter_results_kernel, dim3((uint32_t)((n_streams + 255) / 256)), dim3(256), 0, st, lpt_order,
                                (uint32_t)n_streams, lpt_out_len, lpt_status, d_out_len, d_status);
         }
     } else {
         timing_begin(st);
-        const size_t launch_step = grid;
+        const size_t launch_step = 1u << 20;
         for (size_t first = 0; first < n_streams; first += launch_step) {  // one stream per workgroup
             a.first_stream = (uint32_t)first;
-            const uint32_t g = (uint32_t)std::min<size_t>(grid, n_streams - first);
-            hipLaunchKernelGGL(kernel, dim3(g), dim3(threads), L.total, st, a);
+            const uint32_t g = (uint32_t)std::min<size_t>(launch_step, n_streams - first);
+            hipLaunchKernelGGL(compress_kernel_of(p.build), dim3(g), dim3(p.threads), p.lds.total, st, a);
         }
     }
     timing_end(st);
@@ -1634,7 +1510,7 @@ tamp_res encoder_state_fill(TampAmdEncoderState* s, unsigned char* window, const
     if (append) {  // FLUSH padded to 16 bits: with the previous stream's trailing FLUSH a dictionary reset (:227-235)
         s->bit_buffer = 0xABu << 23, s->bit_buffer_pos = 16, s->last_was_flush = 1;
     } else {  // header byte (+ a zero byte when dictionary_reset), compressor.c:236-241
-        const uint32_t header = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
+        const uint32_t header = header_byte(conf, conf->dictionary_reset);
         s->bit_buffer = header << 24, s->bit_buffer_pos = conf->dictionary_reset ? 16 : 8;
     }
     return TAMP_OK;
@@ -1749,49 +1625,28 @@ const char* tamp_amd_version(void) { return "tamp_amd 0.1 (gfx950)"; }
 int tamp_amd_compress_plan(uint8_t window_bits, uint32_t max_in_len, int lazy_matching, uint32_t* block_positions,
                            uint32_t* lds_bytes, uint32_t* threads, uint32_t* workgroups_per_cu) {
     if (window_bits < 8 || window_bits > 15) return TAMP_AMD_BAD_ARGUMENT;
-    // (the same decisions as launch_compress: build, block, workgroup size)
-    const uint32_t W = 1u << window_bits;
-    const bool packed = window_bits <= 14, lazy = lazy_matching != 0;
-    const bool long_streams = max_in_len == 0 || align_up(max_in_len, 64) >= 1024;
-    const bool runlist = packed && !lazy && long_streams;
-    const uint32_t hb = runlist && window_bits == 10 ? kHb1024 : kHashBits;
-    const uint32_t blk = pick_block(W, max_in_len, packed, lazy, runlist, hb);
-    const CompressLds L(W, blk, packed, lazy, runlist, hb);
-    const uint32_t reg_cap = lazy ? (uint32_t)TAMP_LAZY_PER_CU : (runlist ? (uint32_t)TAMP_WG_PER_CU : (uint32_t)TAMP_LEAN_PER_CU);
-    const uint32_t by_lds = 160u * 1024u / align_up(L.total, 2048u);
-    if (block_positions) *block_positions = blk;
-    if (lds_bytes) *lds_bytes = L.total;
-    if (threads) *threads = compress_threads(blk, long_streams);
-    if (workgroups_per_cu) *workgroups_per_cu = by_lds < reg_cap ? by_lds : reg_cap;
+    TampAmdConf conf = {};  // (a plain batch call with TAMP_AMD_HINT_AUTO: the format and the literal width do not move what is reported)
+    conf.window = window_bits, conf.literal = 8, conf.lazy_matching = lazy_matching != 0;
+    const CompressPlan p = plan_compress(compress_call(&conf, max_in_len, 0));
+    if (block_positions) *block_positions = p.blk;
+    if (lds_bytes) *lds_bytes = p.lds.total;
+    if (threads) *threads = p.threads;
+    if (workgroups_per_cu) *workgroups_per_cu = p.per_cu;
     return TAMP_OK;
 }
 
 int tamp_amd_compress_build(const TampAmdConf* conf, uint32_t max_in_len, uint32_t call_flags, uintptr_t dictionary_address) {
     if (!conf || conf->window < 8 || conf->window > 15 || conf->literal < 5 || conf->literal > 8) return TAMP_AMD_BAD_ARGUMENT;
     if (call_flags & TAMP_AMD_CALL_BLOCK_MODE) return TAMP_AMD_BUILD_GENERIC;  // (launch_compress_blocks takes the call: its own build)
-    // (the same decisions as launch_compress, on the same argument block)
-    CompressArgs a = {};
-    a.wbits = conf->window, a.lbits = conf->literal, a.extended = conf->extended != 0;
-    a.dict_reset = conf->dictionary_reset != 0, a.lazy = conf->lazy_matching != 0;
-    a.nlead = conf->dictionary_reset ? 2 : 1;
-    a.lead = (uint16_t)(header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset) << 8);
-    if (call_flags & TAMP_AMD_CALL_APPEND) a.nlead = 2, a.lead = 0;  // (FLUSH + padding in front instead of the header: tamp_amd_compress_segment)
-    if (call_flags & TAMP_AMD_CALL_RESUME) a.seg_flags |= kSegResume, a.nlead = 0;
-    if (call_flags & TAMP_AMD_CALL_SAVE) a.seg_flags |= kSegSave;
-    if (call_flags & TAMP_AMD_CALL_FLUSH_TOKEN) a.seg_flags |= kSegFlushToken;
-    if (call_flags & TAMP_AMD_CALL_PARTIAL) a.seg_flags |= kSegPartial;
-    if (call_flags & TAMP_AMD_CALL_STATE) a.state = reinterpret_cast<uint8_t*>(uintptr_t(16));  // (any non-null address: never dereferenced)
-    a.dict = reinterpret_cast<const uint8_t*>(conf->use_custom_dictionary ? dictionary_address : uintptr_t(0));  // (the seeded tables are aligned)
-    const uint32_t W = 1u << conf->window;
-    const bool packed = conf->window <= 14;
-    const bool long_streams = max_in_len == 0 || align_up(max_in_len, 64) >= 1024;
-    bool runlist = packed && !a.lazy && (long_streams || conf->input_hint == TAMP_AMD_HINT_RUNS);
-    if (const char* e = getenv("TAMP_AMD_RUNS")) { if (!long_streams) runlist = packed && !a.lazy && atoi(e) != 0; }
-    const uint32_t hb = runlist && conf->window == 10 ? kHb1024 : kHashBits;
-    a.blk = pick_block(W, max_in_len, packed, a.lazy != 0, runlist, hb);
-    const uint32_t threads = compress_threads(a.blk, long_streams);
-    const uint32_t fix = fixed_build_for(conf, a, runlist, threads);
-    return fix == kFixExt ? TAMP_AMD_BUILD_FIXED_EXT : (fix == kFixV1 ? TAMP_AMD_BUILD_FIXED_V1 : TAMP_AMD_BUILD_GENERIC);
+    CompressCall call = compress_call(conf, max_in_len, dictionary_address);
+    if (call_flags & TAMP_AMD_CALL_APPEND) call.nlead = 2, call.lead = 0;  // (FLUSH + padding in front instead of the header: tamp_amd_compress_segment)
+    if (call_flags & TAMP_AMD_CALL_RESUME) call.seg_flags |= kSegResume, call.nlead = 0;
+    if (call_flags & TAMP_AMD_CALL_SAVE) call.seg_flags |= kSegSave;
+    if (call_flags & TAMP_AMD_CALL_FLUSH_TOKEN) call.seg_flags |= kSegFlushToken;
+    if (call_flags & TAMP_AMD_CALL_PARTIAL) call.seg_flags |= kSegPartial;
+    call.has_state = (call_flags & TAMP_AMD_CALL_STATE) != 0;
+    const CompressBuild b = plan_compress(call).build;
+    return b == CompressBuild::kFixedExt ? TAMP_AMD_BUILD_FIXED_EXT : (b == CompressBuild::kFixedV1 ? TAMP_AMD_BUILD_FIXED_V1 : TAMP_AMD_BUILD_GENERIC);
 }
 
 const char* tamp_amd_last_error(void) { return t_last_error; }
@@ -1979,7 +1834,7 @@ tamp_res tamp_amd_decoder_state_init(void* state, const TampAmdConf* conf, uint8
     if (!conf->use_custom_dictionary)
         seed_dictionary_host(reinterpret_cast<unsigned char*>(s + 1), (size_t)1 << conf->window,
                              conf->extended ? conf->literal : 8);
-    s->conf = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
+    s->conf = header_byte(conf, conf->dictionary_reset);
     s->flags = 1;
     return TAMP_OK;
 }
@@ -2556,7 +2411,7 @@ tamp_res tamp_decompressor_init(TampDecompressor* decompressor, const TampConf* 
     if (conf->window > window_bits) return TAMP_INVALID_CONF;
     if (!conf->use_custom_dictionary)
         seed_dictionary_host(window, (size_t)1 << conf->window, conf->extended ? conf->literal : 8);
-    s->conf = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
+    s->conf = header_byte(conf, conf->dictionary_reset);
     s->flags = 1;
     return TAMP_OK;
 }
@@ -2641,7 +2496,7 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
     if (append_marker) {  // compressor.c:227-235: FLUSH (9 bits) padded to 16 bits instead of a header
         seg.nlead = 2, seg.lead = (uint16_t)(0xABu << 7);
     } else if (emit_header) {
-        const uint8_t header = header_byte(conf->window, conf->literal, conf->use_custom_dictionary, conf->extended, conf->dictionary_reset);
+        const uint8_t header = header_byte(conf, conf->dictionary_reset);
         seg.nlead = conf->dictionary_reset ? 2 : 1, seg.lead = (uint16_t)(header << 8);
     } else {
         seg.nlead = 0, seg.lead = 0;
