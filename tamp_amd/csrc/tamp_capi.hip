@@ -2529,7 +2529,7 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
     const uint64_t zero = 0;
     const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
     if (finish && !flush_token && !resume && emit_header && !append_marker && prefix.empty() && !conf->extended &&
-        !conf->lazy_matching && conf->literal == 8 && conf->window <= 14 && input_size >= ((size_t)256 << 10) &&
+        !conf->lazy_matching && conf->literal == 8 && conf->window <= kPackedMaxWbits && input_size >= ((size_t)256 << 10) &&
         input_size <= 0xFFFFFF00ull) {
         // A whole fresh v1 stream in one finishing call: the batch call takes it as ONE stream and spreads its blocks over
         // all workgroups (launch_compress_blocks).  The object afterwards holds what the reference's would: every consumed

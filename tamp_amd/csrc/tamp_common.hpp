@@ -60,6 +60,37 @@ __device__ __forceinline__ uint32_t tok_nbits(uint32_t i) { return (uint32_t)(kN
 
 __host__ __device__ constexpr uint32_t align_up(uint32_t x, uint32_t a) { return (x + a - 1) & ~(a - 1); }
 
+// Widest token the compress kernel's emit phase places in ONE step (token_words below takes at most 32 bits):
+//   literal                   flag + literal bits
+//   match                     prefix code (flag included) + window bits; explicit pieces of the walk are no wider
+//   settled RLE token         symbol 12, then the count's prefix code without its flag + 4 trailing bits  (compressor.c:342-359)
+//   settled extended match    symbol 13, the size's prefix code without its flag + 3 trailing bits, window bits  (:377-415)
+// Settled tokens exist in the PACKED builds only, which take windows up to 2^kPackedMaxWbits: the one constant plan_compress
+// (tamp_compress_plan.hpp) and the block-mode test of the one-shot call (tamp_capi.hip) decide `packed` with.
+constexpr uint32_t kPackedMaxWbits = 14;
+constexpr uint32_t max_code_nbits() {
+    uint32_t m = 0;
+    for (int i = 0; i < 15; i++) m = kNbitsTab[i] > m ? kNbitsTab[i] : m;
+    return m;
+}
+constexpr uint32_t max_u32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+constexpr uint32_t kMaxTokenBits =
+    max_u32(max_u32(1 + 8, max_code_nbits() + 15),
+            max_u32(kNbitsTab[kSymRle] + max_code_nbits() - 1 + 4, kNbitsTab[kSymExt] + max_code_nbits() - 1 + 3 + kPackedMaxWbits));
+static_assert(kMaxTokenBits <= 32, "a token is placed as one 32-bit value: at most two words of the bit buffer");
+
+// Where the nb-bit token v (1 <= nb <= 32, v < 2^nb) lands when it is written MSb-first at bit `bitpos` of a byte stream
+// that is kept as 32-bit words in memory order: word *wi gets *w_hi ORed in, word *wi + 1 gets *w_lo when that is non-zero
+// (zero whenever the token ends inside word *wi).  The words must be zero where the bits land.
+__host__ __device__ __forceinline__ void token_words(uint32_t v, uint32_t nb, uint32_t bitpos, uint32_t* wi, uint32_t* w_hi,
+                                                     uint32_t* w_lo) {
+    const uint32_t ph = bitpos & 31u;
+    const uint64_t x = (uint64_t)v << (64u - ph - nb);  // shift count 1..63
+    *wi = bitpos >> 5;
+    *w_hi = __builtin_bswap32((uint32_t)(x >> 32));
+    *w_lo = __builtin_bswap32((uint32_t)x);
+}
+
 __host__ __device__ constexpr int min_pattern_size(int window, int literal) {
     return 2 + (window > 10 + 2 * (literal - 5));
 }

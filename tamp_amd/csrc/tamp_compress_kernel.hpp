@@ -106,7 +106,7 @@ struct CompressLds {
     uint32_t ebuf = 0, cnt = 0, ent = 0, blen = 0, bidx = 0, blen2 = 0, bidx2 = 0, obuf = 0, ctl = 0, runs = 0, runsx = 0, rxset = 0, rbits = 0, total = 0;  // blen2/bidx2: lazy-matching probe results
     uint32_t tokcap = 0, obuf_words = 0, jump = 0, count = 0, vstep = 0;  // jump/count/vstep: byte offsets of the walk's tables inside `ent`
     __host__ __device__ constexpr CompressLds(uint32_t W, uint32_t blk, bool packed, bool lazy = false, bool runlist = false, uint32_t hb = kHashBits) {
-        uint32_t o = 16;  // slack: the wrapped compare reads up to 15 bytes in front of ebuf (masked out)
+        uint32_t o = 16;  // slack: the wrapped compare reads up to 16 bytes in front of ebuf (masked out)
         ebuf = o;
         o += align_up(W + blk + kRing + kPendMax + 32, 16);
         cnt = o;  // 2048 x u16 bucket cursors; the walk reuses it for explicit token pieces (256 x 8 B)
@@ -228,13 +228,18 @@ __device__ __forceinline__ uint32_t prefix_len16(const uint8_t* ebuf, uint32_t c
 }
 
 // Candidate whose bytes run past the newest window byte: the ring continues with the OLDEST window byte, i.e.
-// candidate byte k is ebuf[c + k] for k < t and ebuf[c - W + k] for k >= t, with t = q + W - c in 1..15.
+// candidate byte k is ebuf[c + k] for k < t and ebuf[c - W + k] for k >= t, with t = q + W - c in 1..15 -- or 16: the
+// one-compare bucket scan sends a 16-byte hit exactly 16 bytes in front of the newest byte here too, and all sixteen bytes
+// come from the first half then (every per-dword mask is all ones).
 // Both halves are fetched as 16 unaligned bytes and blended; returns the common prefix length with P (0..16).
+// (A branch-free form like prefix_len16's -- two unaligned ds_read_b128, a byte mask from two 64-bit shifts, a bit-select per
+// dword, the first-set-bit tail -- has 100 fewer static VALU but took only 0.5 % off the headline, 2.3 x the run-to-run spread
+// where a change has to show 4 x: not kept.  profiles/emit_place_ab.txt)
 __device__ __forceinline__ uint32_t prefix_len_wrapped16(const uint8_t* ebuf, uint32_t c, uint32_t t, uint32_t W,
                                                          const uint32_t (&P)[4]) {
     const uint32_t* wa = reinterpret_cast<const uint32_t*>(ebuf + (c & ~3u));
     const uint32_t sa = c & 3u;
-    const int32_t ob = (int32_t)c - (int32_t)W;  // >= -15: the slack in front of ebuf keeps this inside LDS
+    const int32_t ob = (int32_t)c - (int32_t)W;  // >= -16: the slack in front of ebuf keeps this inside LDS
     const uint32_t* wb = reinterpret_cast<const uint32_t*>(ebuf + (ob & ~3));
     const uint32_t sb = (uint32_t)ob & 3u;
     uint32_t res = 16;
@@ -2332,6 +2337,34 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 segbits += wt;
             }
             {  // MSb-first scatter of this thread's contiguous run of tokens
+#ifndef TAMP_EMIT_ACC
+                // Every token is ORed straight to its place: at most 32 bits (kMaxTokenBits), so at most two words.  The bit
+                // buffer is all zero where bits land -- it is zeroed (1) whole at the stream's start, (2) over the scan starts
+                // the match phase kept in words 4.. of it, behind that phase, and (3) over every word the previous segment
+                // touched, behind its flush (word 0 keeps the carried bits) -- and nothing else stores into it.  Same words
+                // as the accumulator form (TAMP_EMIT_ACC, for A/B builds), which pushed the tokens through 64 bits and
+                // spilled whole words in a loop (profiles/emit_place_static.txt, profiles/emit_place_ab.txt).
+                uint32_t bp = o;
+                auto put_bits = [&](uint32_t v, uint32_t nb) {
+                    uint32_t wi, w_hi, w_lo;
+                    token_words(v, nb, bp, &wi, &w_hi, &w_lo);
+                    atomicOr(&obuf[wi], w_hi);
+                    if (w_lo) atomicOr(&obuf[wi + 1], w_lo);
+                    bp += nb;
+                };
+#ifndef TAMP_EMIT_TWICE
+                if (tok_cached) {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; j++)
+                        if (cn[j]) put_bits(cv[j], cn[j]);
+                } else
+#endif
+                for (uint32_t k = k0; k < k1 && k < limit; k++) {
+                    uint32_t v, nb;
+                    token(k, v, nb);
+                    put_bits(v, nb);
+                }
+#else
                 uint32_t wi = o >> 5, ph = o & 31, fill = 0;
                 uint64_t acc = 0;
                 auto put_bits = [&](uint32_t v, uint32_t nb) {
@@ -2366,6 +2399,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     const uint32_t w = ((uint32_t)acc & ((1u << fill) - 1)) << (32 - ph - fill);
                     atomicOr(&obuf[wi], __builtin_bswap32(w));
                 }
+#endif
             }
             __syncthreads();
             uint32_t tot = carry + segbits;  // bits now in obuf

@@ -117,7 +117,7 @@ static inline CompressPlan plan_compress(const CompressCall& c) {
     const char *const fixed_env = getenv("TAMP_AMD_FIXED_BUILD"), *const block_lean_env = getenv("TAMP_AMD_BLOCK_LEAN");
     const TampAmdConf* conf = c.conf;
     const uint32_t W = 1u << conf->window;
-    const bool w10 = conf->window == 10, packed = conf->window <= 14, lazy = conf->lazy_matching != 0, block = c.block_mode;
+    const bool w10 = conf->window == 10, packed = conf->window <= kPackedMaxWbits, lazy = conf->lazy_matching != 0, block = c.block_mode;
     // The run-aware build (u32 entries, default parse only): streams of 1 KiB and more always, so the hint and
     // TAMP_AMD_RUNS (tuning / tests) matter for short messages alone; block mode too (TAMP_AMD_BLOCK_LEAN, tuning: the lean build).
     const bool long_streams = block || c.max_in_len == 0 || align_up(c.max_in_len, 64) >= 1024;
