@@ -133,6 +133,44 @@ enum {
 enum { TAMP_AMD_BUILD_GENERIC = 0, TAMP_AMD_BUILD_FIXED_EXT = 1, TAMP_AMD_BUILD_FIXED_V1 = 2 };
 int tamp_amd_compress_build(const TampAmdConf *conf, uint32_t max_in_len, uint32_t call_flags, uintptr_t dictionary_address);
 
+/* Which decoder tamp_batch_decompress would take for a device batch and how it would size it (host only, no GPU needed: the CU
+ * count is an input).  A diagnostics / capacity-planning call; it runs the launcher's own planning code -- the one reader of the
+ * decode planning variables (TAMP_AMD_DECODER, TAMP_AMD_SPLIT_*, TAMP_AMD_SCRATCH_MB, TAMP_AMD_LONGDEC*) -- so it honours what
+ * the launcher honours.  The caller supplies what the launcher learns on the device: the four words of the header pre-pass (read
+ * only when the answer's `scan` is set), the free device memory and the bytes of split-decoder scratch the stream already holds.
+ * Returns TAMP_OK or TAMP_AMD_BAD_ARGUMENT (a null pointer, no streams). */
+typedef struct TampAmdDecodeQuery {
+    uint64_t n_streams;
+    uint8_t max_window_bits;   /* as passed to tamp_batch_decompress, TAMP_AMD_WINDOW_BITS_EXACT included */
+    uint8_t has_dictionary;    /* a custom dictionary is passed */
+    uint8_t exclude_split;     /* 1: the plan the launcher falls back to when the split decoder's scratch cannot be allocated */
+    uint8_t free_known;        /* free_bytes holds the device's free memory (0: the runtime could not tell) */
+    uint32_t cu_count;
+    uint32_t scan_found;       /* pre-pass: largest window bits in the batch's headers, 0 = no valid header */
+    uint32_t scan_longest_in;  /*           longest compressed stream */
+    uint32_t scan_window_units; /*          sum of the streams' window sizes, in 256-byte units */
+    uint32_t scan_max_out_cap; /*           largest out_cap */
+    uint64_t free_bytes, held_bytes;
+} TampAmdDecodeQuery;
+enum { TAMP_AMD_DECODER_SPLIT = 0, TAMP_AMD_DECODER_WAVE = 1, TAMP_AMD_DECODER_LANE_LDS = 2, TAMP_AMD_DECODER_LANE_GLOBAL = 3 };
+typedef struct TampAmdDecodePlan {
+    /* the long-stream path (at most 16 streams): attempted at all; shortest stream it takes; extended streams; chained groups */
+    uint32_t long_attempt, long_min_len, long_extended, long_chain;
+    uint32_t scan;             /* the header pre-pass runs */
+    uint32_t decoder;          /* TAMP_AMD_DECODER_* */
+    uint32_t max_window_bits;  /* narrowed to the largest window the pre-pass found */
+    uint32_t bulk;             /* streams of 512 compressed bytes and more (or unknown): the lane decoders' bulk builds */
+    /* geometry of the chosen decoder; zeroes for the others */
+    uint32_t split_tokcap, split_maxcap, split_wave_resolve, split_resolve_lds;
+    uint32_t split_spw;        /* streams per parse wave in the first slice */
+    uint32_t wave_waves, wave_lds, wave_groups; /* WAVE, and SPLIT (its leftovers): wavefronts per workgroup, LDS bytes, workgroups */
+    uint32_t lane_lds_row, lane_lds, lane_per_cu, lane_grid;
+    uint32_t global_slot, global_grid, global_bulk, global_lds;
+    uint64_t split_slice, split_slab_bytes; /* streams per slice before any allocation failure halves it, scratch for that */
+    uint64_t global_lanes, global_slab_bytes;
+} TampAmdDecodePlan;
+int tamp_amd_decompress_plan(const TampAmdDecodeQuery *query, TampAmdDecodePlan *plan);
+
 /* ---- batch codec ---------------------------------------------------------------------------- */
 
 /*

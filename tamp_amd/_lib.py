@@ -30,6 +30,7 @@ SYMBOLS = (
     "tamp_amd_last_error",
     "tamp_amd_compress_plan",
     "tamp_amd_compress_build",
+    "tamp_amd_decompress_plan",
     "tamp_batch_compress",
     "tamp_batch_decompress",
     "tamp_amd_decoder_state_size",
@@ -99,6 +100,27 @@ class TampAmdCarry(C.Structure):
     ]
 
 
+class TampAmdDecodeQuery(C.Structure):
+    """include/tamp_amd.h TampAmdDecodeQuery: a decompress call as far as the decode plan depends on it."""
+    _fields_ = [("n_streams", C.c_uint64), ("max_window_bits", C.c_uint8), ("has_dictionary", C.c_uint8),
+                ("exclude_split", C.c_uint8), ("free_known", C.c_uint8), ("cu_count", C.c_uint32),
+                ("scan_found", C.c_uint32), ("scan_longest_in", C.c_uint32), ("scan_window_units", C.c_uint32),
+                ("scan_max_out_cap", C.c_uint32), ("free_bytes", C.c_uint64), ("held_bytes", C.c_uint64)]
+
+
+DECODER_SPLIT, DECODER_WAVE, DECODER_LANE_LDS, DECODER_LANE_GLOBAL = 0, 1, 2, 3  # include/tamp_amd.h TAMP_AMD_DECODER_*
+
+
+class TampAmdDecodePlan(C.Structure):
+    """include/tamp_amd.h TampAmdDecodePlan: the answer of tamp_amd_decompress_plan."""
+    _fields_ = ([(f, C.c_uint32) for f in (
+        "long_attempt", "long_min_len", "long_extended", "long_chain", "scan", "decoder", "max_window_bits", "bulk",
+        "split_tokcap", "split_maxcap", "split_wave_resolve", "split_resolve_lds", "split_spw",
+        "wave_waves", "wave_lds", "wave_groups", "lane_lds_row", "lane_lds", "lane_per_cu", "lane_grid",
+        "global_slot", "global_grid", "global_bulk", "global_lds")] +
+        [(f, C.c_uint64) for f in ("split_slice", "split_slab_bytes", "global_lanes", "global_slab_bytes")])
+
+
 class NativeLibraryError(RuntimeError):
     """libtamp_amd.so is missing / unloadable, or no HIP device is available."""
 
@@ -138,6 +160,8 @@ def load() -> C.CDLL:
     lib.tamp_amd_last_error.restype = C.c_char_p
     lib.tamp_amd_compress_build.argtypes = [C.POINTER(TampAmdConf), u32, u32, sz]  # (uintptr_t: the width of size_t)
     lib.tamp_amd_compress_build.restype = i32
+    lib.tamp_amd_decompress_plan.argtypes = [C.POINTER(TampAmdDecodeQuery), C.POINTER(TampAmdDecodePlan)]
+    lib.tamp_amd_decompress_plan.restype = i32
     lib.tamp_batch_compress.argtypes = [C.POINTER(TampAmdConf), vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp]
     lib.tamp_batch_compress.restype = i32
     lib.tamp_batch_decompress.argtypes = [vp, sz, u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]

@@ -28,6 +28,7 @@
 #include "tamp_decompress_split_kernel.hpp"
 #include "tamp_decompress_long_kernel.hpp"
 #include "tamp_decompress_wave_kernel.hpp"
+#include "tamp_decompress_plan.hpp"
 #include "tamp_decompress_resume_kernel.hpp"
 #include "tamp_compress_resume_kernel.hpp"
 
@@ -625,20 +626,16 @@ __global__ void tamp_header_scan_kernel(const uint8_t* in, const uint64_t* in_of
 // records per chunk, then the split decoder's RESOLVE over groups of at most kSplitMaxOut output bytes, in order, each with the
 // W bytes in front of it as its dictionary.  -> 1 when the call is not one (or anything is off: the exact decoders take it),
 // TAMP_OK when the stream has been decoded, an error code otherwise.  Nothing is written before the fall-back decision.
-int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
-                           const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
+int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits,
+                           const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                            const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed, hipStream_t st) {
-    if (const char* e = getenv("TAMP_AMD_LONGDEC")) { if (atoi(e) == 0) return 1; }
-    if (getenv("TAMP_AMD_DECODER")) return 1;
-    uint32_t min_len = 256u << 10;
-    if (const char* e = getenv("TAMP_AMD_LONGDEC_MIN")) { const long v = atol(e); if (v >= 64) min_len = (uint32_t)v; }
     uint64_t in_off = 0, out_off = 0;
     uint32_t n = 0, cap = 0;
     HIP_OK(hipMemcpyAsync(&n, d_in_len, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     // (the chunk kernels count bits in 32-bit registers: (i + 1) * kLongChunkBits wraps for the last chunk of the top 512 bytes of
     // the accepted range -- those streams stay with the exact decoder)
-    if (n < min_len || n > kMaxDecodeIn - 512) return 1;
+    if (n < gate.min_len || n > kMaxDecodeIn - 512) return 1;
     HIP_OK(hipMemcpyAsync(&in_off, d_in_off, 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(&out_off, d_out_off, 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(&cap, d_out_cap, 4, hipMemcpyDeviceToHost, st));
@@ -651,7 +648,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const uint8_t* d_
     const uint32_t hs = 1 + (hdr[0] & 1), wbits = hd.wbits, lbits = hd.lbits;
     const bool extended = hd.extended;
     if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return 1;
-    if (extended && getenv("TAMP_AMD_LONGDEC_EXT") && atoi(getenv("TAMP_AMD_LONGDEC_EXT")) == 0) return 1;  // (tests: the exact decoder)
+    if (extended && !gate.extended) return 1;  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
     if (hd.custom && (!d_dict || dict_len < W)) return 1;
     // the fresh decoder's window: the custom dictionary, or the seeded table for the stream's literal size
@@ -770,8 +767,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const uint8_t* d_
             if (chunk_lag[2 * (size_t)i + 1] > kLongLagCap) { timing_end(st); return 1; }  // (more lagging tokens in one chunk than a group lists)
     }
     // groups of whole chunks: at most kSplitMaxOut output bytes, 2^20 - 1 records and kLongLagCap lagging tokens each
-    const char* chain_env = getenv("TAMP_AMD_LONGDEC_CHAIN");
-    const bool chain = extended || !chain_env || atoi(chain_env) != 0;
+    const bool chain = extended || gate.chain;
     const uint32_t group_out = chain ? kLongGroupOut : kSplitMaxOut;
     struct Group { uint64_t v0; uint32_t tok0, ntok, nout, lag0, nlag; uint64_t lagv0; };  // lagv0: lag of the stream in front of the group
     std::vector<Group> groups;
@@ -904,15 +900,100 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const uint8_t* d_
     return TAMP_OK;
 }
 
-// The wave-per-stream decoder over a batch (with a.only_flagged: over the streams the split decoder left): four streams per
-// workgroup up to 2^12-byte windows, one above; grid-stride beyond `max_groups` workgroups.
-static int launch_wave_decoder(const DecompressArgs& a, uint32_t max_wbits, size_t n_streams, size_t max_groups, hipStream_t st) {
-    const uint32_t waves = max_wbits <= 12 ? 4 : 1;
-    const uint32_t lds = decode_wave_lds(max_wbits, waves);
-    const size_t groups = std::min((n_streams + waves - 1) / waves, max_groups);
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(tamp_decompress_wave_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(tamp_decompress_wave_kernel, dim3((uint32_t)groups), dim3(waves * kWave), lds, st, a);
+// A wavefront-per-stream kernel (the wave decoder -- with a.only_flagged: over the streams the split decoder left -- and the two
+// resume kernels) in the geometry of wave_geometry(), with `lds` bytes of dynamic LDS.
+template <class Args>
+static int launch_waves(void (*kernel)(Args), const Args& a, const WaveGeometry& g, uint32_t lds, hipStream_t st) {
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(g.groups), dim3(g.waves * kWave), lds, st, a);
+    return TAMP_OK;
+}
+
+// Allocates what `plan` sized and launches its decoder.
+int run_decode_plan(DeviceCtx* ctx, StreamScratch& rec, DecompressArgs a, const DecodeCall& call, const DecodeScan& scan,
+                    const DecodeDevice& dev, const DecodePlan& plan, hipStream_t st) {
+    const size_t n_streams = call.n_streams;
+    a.max_wbits = plan.max_wbits;
+    switch (plan.decoder) {
+        case Decoder::kSplit: {
+            // The slab is kept per HIP stream between calls (tamp_amd_trim() releases it).  If the device cannot supply it the
+            // slice is halved down to 4,096 streams, and below that the batch goes to the lane / wave decoders, which need
+            // little or no scratch: an allocation failure here must not fail a call that another decoder can serve.
+            const SplitGeometry& g = plan.split;
+            size_t slice = g.slice;
+            for (;;) {
+                const size_t need = g.slab_bytes(slice);
+                if (rec.split.bytes >= need) break;
+                HIP_OK(StreamScratch::drain_if_outgrown(rec.split, need, st));
+                const bool deny = getenv("TAMP_AMD_SPLIT_FAIL_ABOVE") && need > (size_t)atol(getenv("TAMP_AMD_SPLIT_FAIL_ABOVE"));  // (tests)
+                if (!deny && rec.split.need(need, false) == hipSuccess) break;
+                (void)hipGetLastError();  // clear the sticky out-of-memory error
+                if (slice <= 4096) return run_decode_plan(ctx, rec, a, call, scan, dev, plan_decompress(call, scan, dev, false), st);
+                slice = std::max<size_t>(slice / 2, 4096);
+            }
+            uint8_t* const base = static_cast<uint8_t*>(rec.split.p);
+            SplitArgs sa;
+            sa.maxcap = g.maxcap, sa.tokcap = g.tokcap;
+            sa.recs = reinterpret_cast<uint32_t*>(base);
+            sa.meta = reinterpret_cast<uint32_t*>(base + g.b_recs(slice));
+            sa.lag = reinterpret_cast<uint32_t*>(base + g.b_recs(slice) + g.b_meta(slice));
+            sa.flagged = base + g.b_recs(slice) + g.b_meta(slice) + g.b_lag(slice);
+            sa.flagged_count = reinterpret_cast<uint32_t*>(sa.flagged + ((n_streams + 3) & ~(size_t)3));  // (inside the 64 bytes of slack)
+            HIP_OK(hipMemsetAsync(sa.flagged_count, 0, 4, st));
+            sa.d = a;
+            auto resolve_kernel = g.wave_resolve ? tamp_decode_resolve_kernel<64, 4> : tamp_decode_resolve_kernel<256, 4>;
+            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(resolve_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.resolve_lds));
+            timing_begin(st);
+            for (size_t first = 0; first < n_streams; first += slice) {
+                sa.first = (uint32_t)first;
+                sa.count = (uint32_t)std::min(slice, n_streams - first);
+                sa.spw = g.spw(sa.count);
+                const uint32_t pwaves = (sa.count + sa.spw - 1) / sa.spw;
+                hipLaunchKernelGGL(tamp_decode_parse_kernel, dim3((pwaves + 3) / 4), dim3(256), split_parse_lds(256), st, sa);
+                hipLaunchKernelGGL(resolve_kernel, dim3(g.wave_resolve ? (sa.count + 3) / 4 : sa.count), dim3(256), g.resolve_lds, st, sa);
+            }
+            // leftovers: the wave decoder over the flagged streams only
+            a.only_flagged = sa.flagged;
+            a.flagged_count = sa.flagged_count;
+            const int rc = launch_waves(tamp_decompress_wave_kernel, a, plan.wave, plan.wave_lds, st);
+            timing_end(st);
+            if (rc != TAMP_OK) return rc;
+            break;
+        }
+        case Decoder::kWave: {
+            timing_begin(st);
+            const int rc = launch_waves(tamp_decompress_wave_kernel, a, plan.wave, plan.wave_lds, st);
+            timing_end(st);
+            if (rc != TAMP_OK) return rc;
+            break;
+        }
+        case Decoder::kLaneLds: {
+            a.lds_row = plan.lane.lds_row;
+            auto lane_kernel = plan.bulk ? tamp_decompress_kernel<true, true> : tamp_decompress_kernel<true, false>;
+            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(lane_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)plan.lane.lds));
+            timing_begin(st);
+            hipLaunchKernelGGL(lane_kernel, dim3(plan.lane.grid), dim3(kWave), plan.lane.lds, st, a);
+            timing_end(st);
+            break;
+        }
+        case Decoder::kLaneGlobal: {
+            const LaneGlobalGeometry& g = plan.global;
+            a.lds_row = g.slot;
+            HIP_OK(StreamScratch::drain_if_outgrown(rec.slab, g.slab_bytes, st));
+            HIP_OK(rec.slab.need(g.slab_bytes, false));
+            a.scratch = static_cast<uint8_t*>(rec.slab.p);
+            timing_begin(st);
+            if (g.gbulk)
+                hipLaunchKernelGGL((tamp_decompress_kernel<false, true>), dim3(g.grid), dim3(256), g.lds, st, a);
+            else
+                hipLaunchKernelGGL((tamp_decompress_kernel<false, false>), dim3(g.grid), dim3(256), 0, st, a);
+            timing_end(st);
+            break;
+        }
+    }
+    HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
 
@@ -931,9 +1012,11 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     a.only_flagged = nullptr;
     a.flagged_count = nullptr;
     a.n_streams = (uint32_t)n_streams;
+    a.lds_row = 0;
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
-    if (n_streams <= 16 && !(max_wbits & TAMP_AMD_WINDOW_BITS_EXACT)) {
+    const DecodeCall call = {n_streams, max_wbits, d_dict != nullptr};
+    if (const DecodeLong gate = decode_wants_long(call); gate.attempt) {
         // one long v1 stream -- or a handful, one after the other: the whole device each (tamp_decompress_long_kernel.hpp).  A stream
         // that is not one (too short, extended, ...) sends the whole call to the decoders below, which write every stream again.
         // (one event pair around all of them: kernel_ms of a call with several long streams is the sum, not the last stream's)
@@ -942,7 +1025,7 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
         t_timing_outer = true;
         int rc = TAMP_OK;
         for (; done < n_streams; done++) {
-            rc = launch_decompress_long(ctx, rec, d_dict, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
+            rc = launch_decompress_long(ctx, rec, gate, d_dict, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
                                         d_out_off + done, d_out_cap + done, d_out_len + done, d_status + done,
                                         d_consumed ? d_consumed + done : nullptr, st);
             if (rc != TAMP_OK) break;
@@ -951,215 +1034,28 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
         if (rc != TAMP_OK && rc != 1) return rc;
         if (done == n_streams) return TAMP_OK;
     }
-    const bool exact = (max_wbits & TAMP_AMD_WINDOW_BITS_EXACT) != 0;
-    uint32_t longest_in = 0xFFFFFFFFu;  // longest compressed stream of the batch (unknown without the pre-pass)
-    uint64_t window_bytes = 0;          // sum of the streams' window sizes (0 = unknown)
-    uint32_t max_out_cap = 0;           // largest out_cap of the batch (0 = unknown)
-    max_wbits &= 0x7F;
-    const char* force = getenv("TAMP_AMD_DECODER");  // "wave" | "lane" | "global" | "split" (tuning / tests)
-    const bool force_split = force && force[0] == 's';
-    if (!exact && max_wbits >= 8 && max_wbits <= 15 && ((max_wbits > 8 && n_streams >= 256) || force_split)) {
+    DecodeScan scan;
+    if (decode_wants_scan(call)) {
         HIP_OK(rec.scan.need(32, false));
         uint32_t* const hdr_scan = static_cast<uint32_t*>(rec.scan.p);
-        uint32_t scan[4] = {0, 0, 0, 0};
-        uint32_t& found = scan[0];
+        uint32_t words[4] = {0, 0, 0, 0};
         HIP_OK(hipMemsetAsync(hdr_scan, 0, 16, st));
         const uint32_t sg = (uint32_t)std::min<size_t>((n_streams + 255) / 256, (size_t)ctx->cu_count * 4);
         hipLaunchKernelGGL(tamp_header_scan_kernel, dim3(sg), dim3(256), 0, st, d_in, d_in_off, d_in_len, d_out_cap,
-                           (uint32_t)n_streams, (uint32_t)max_wbits, hdr_scan);
-        HIP_OK(hipMemcpyAsync(scan, hdr_scan, 16, hipMemcpyDeviceToHost, st));
+                           (uint32_t)n_streams, (uint32_t)call.bits(), hdr_scan);
+        HIP_OK(hipMemcpyAsync(words, hdr_scan, 16, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        // streams above the limit fail with TAMP_INVALID_CONF under either value; nothing valid exceeds `found`
-        if (found >= 8 && found < max_wbits) max_wbits = (uint8_t)found;
-        if (found == 0) max_wbits = 8;
-        longest_in = scan[1];
-        window_bytes = (uint64_t)scan[2] << 8;
-        max_out_cap = scan[3];
+        scan.found = words[0], scan.longest_in = words[1], scan.window_units = words[2], scan.max_out_cap = words[3];
     }
-    a.max_wbits = max_wbits;
-    a.lds_row = 0;
-    const bool valid_bits = max_wbits >= 8 && max_wbits <= 15;
-    // Split decoder (tamp_decompress_split_kernel.hpp): parse one lane per stream without any window, resolve one
-    // workgroup (out_cap above 2 KiB) or one wavefront per stream by pointer jumping; what it flags is decoded by the wave
-    // decoder afterwards.  Needs the pre-pass (longest stream and largest out_cap size its scratch and LDS).
-    // Taken for batches of streams of 512 compressed bytes and more, and for most batches of short messages (below), whose
-    // output slabs fit RESOLVE's LDS.
-    const bool split_fits = valid_bits && max_out_cap && max_out_cap <= kSplitMaxOut && longest_in != 0xFFFFFFFFu;
-    // Short messages (round 4, with RESOLVE's wavefront-per-stream build and the parse's whole-stream ring): the split decoder
-    // has no window to set up, the lane decoders fill one per message -- from the caller's dictionary, or 2^9 bytes and more
-    // of the seeded one.  1 Mi x 256 B: custom dictionary at w = 8 1.30 against 2.18 ms, default window 2^10 2.01 against
-    // 6.13 ms, 1 Mi x 512 B at w = 9 3.2 against 20.4 ms; only w = 8 without a dictionary stays with the LDS lanes (1.65
-    // against 1.98 ms).  tools/dec_short.py.
-    const bool short_split = longest_in < 512 && (d_dict != nullptr || max_wbits >= 9);
-    const bool want_split = force ? force_split : ((longest_in >= 512 || short_split) && n_streams >= 256);
-    if (want_split && split_fits) {
-        SplitArgs sa;
-        sa.maxcap = max_out_cap;
-        sa.tokcap = std::max<uint32_t>(16, (uint32_t)std::min<uint64_t>(max_out_cap, (uint64_t)longest_in * 8 / 6 + 8));
-        sa.tokcap = (sa.tokcap + 15u) & ~15u;  // whole 64-byte groups of records per stream
-        // Streams per slice: 256 Ki = 4 parse waves per SIMD (measured on configs[3], 1 Mi streams: 2^17 29.4 ms, 2^18 25.4 ms,
-        // 2^19 26.4 ms; TAMP_AMD_SPLIT_SLICE_LOG2 overrides), less when the scratch budget says so (records dominate:
-        // tokcap x 4 B per stream; TAMP_AMD_SPLIT_SCRATCH_MB, default 8 GiB of the 288 GB).
-        size_t slice_log2 = 18;
-        if (const char* e = getenv("TAMP_AMD_SPLIT_SLICE_LOG2")) { const int v = atoi(e); if (v >= 12 && v <= 22) slice_log2 = (size_t)v; }
-        size_t slice = std::min<size_t>(n_streams, (size_t)1 << slice_log2);
-        const size_t per = (size_t)sa.tokcap * 4 + 4 + kSplitMaxLag * 8;
-        {
-            // scratch budget: a quarter of what the device has free right now, 8 GiB at most (callers that fill HBM with
-            // their own batches keep most of it; a slice of 2^18 long streams needs ~3.7 GiB, and configs[3] cut into
-            // uneven slices by a 4 GiB budget ran 6.5 instead of 5.1 ms); TAMP_AMD_SPLIT_SCRATCH_MB overrides
-            size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
-            // (the slab this stream already holds is part of what the call may use: without it the budget -- and with it
-            // the slice size, hence the decode time -- of the second call on a shape differed from the first's)
-            const size_t held = rec.split.bytes;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max((free_b + held) / 4, held));
-            else (void)hipGetLastError();
-            if (const char* e = getenv("TAMP_AMD_SPLIT_SCRATCH_MB")) { const long v = atol(e); if (v > 0) budget = (size_t)v << 20; }
-            slice = std::min(slice, std::max<size_t>(budget / per, 4096));
-        }
-        // The slab is kept per HIP stream between calls (tamp_amd_trim() releases it).  If the device cannot supply it the
-        // slice is halved down to 4,096 streams, and below that the batch goes to the lane / wave decoders, which need
-        // little or no scratch: an allocation failure here must not fail a call that another decoder can serve.
-        size_t b_recs = 0, b_meta = 0, b_lag = 0;
-        for (;;) {
-            b_recs = slice * sa.tokcap * 4, b_meta = slice * 4, b_lag = slice * kSplitMaxLag * 8;
-            const size_t need = b_recs + b_meta + b_lag + n_streams + 64;
-            if (rec.split.bytes >= need) break;
-            HIP_OK(StreamScratch::drain_if_outgrown(rec.split, need, st));
-            const bool deny = getenv("TAMP_AMD_SPLIT_FAIL_ABOVE") && need > (size_t)atol(getenv("TAMP_AMD_SPLIT_FAIL_ABOVE"));  // (tests)
-            if (!deny && rec.split.need(need, false) == hipSuccess) break;
-            (void)hipGetLastError();  // clear the sticky out-of-memory error
-            if (slice <= 4096) { slice = 0; break; }
-            slice = std::max<size_t>(slice / 2, 4096);
-        }
-        uint8_t* const base = static_cast<uint8_t*>(rec.split.p);
-        if (slice) {
-        sa.recs = reinterpret_cast<uint32_t*>(base);
-        sa.meta = reinterpret_cast<uint32_t*>(base + b_recs);
-        sa.lag = reinterpret_cast<uint32_t*>(base + b_recs + b_meta);
-        sa.flagged = base + b_recs + b_meta + b_lag;
-        sa.flagged_count = reinterpret_cast<uint32_t*>(sa.flagged + ((n_streams + 3) & ~(size_t)3));  // (inside the 64 bytes of slack)
-        HIP_OK(hipMemsetAsync(sa.flagged_count, 0, 4, st));
-        sa.d = a;
-        // resolve: a workgroup per stream, or -- short messages, out_cap up to 1 KiB -- a wavefront per stream, four per workgroup
-        bool wave_resolve = max_out_cap <= kSplitWaveMaxOut;
-        if (const char* e = getenv("TAMP_AMD_SPLIT_WAVE_MAX")) {  // (tuning; the one-wavefront RESOLVE covers 4 x 16 x 64 = 4,096 positions)
-            const int v = atoi(e);
-            wave_resolve = max_out_cap <= (uint32_t)(v < 0 ? 0 : (v > 4096 ? 4096 : v));
-        }
-        const uint32_t lds = split_resolve_lds(max_out_cap) * (wave_resolve ? 4u : 1u);
-        auto resolve_kernel = wave_resolve ? tamp_decode_resolve_kernel<64, 4> : tamp_decode_resolve_kernel<256, 4>;
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(resolve_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        timing_begin(st);
-        for (size_t first = 0; first < n_streams; first += slice) {
-            sa.first = (uint32_t)first;
-            sa.count = (uint32_t)std::min(slice, n_streams - first);
-            // streams per wave: enough waves for ~4 per SIMD (tools/dec_split_pmc.sh: the parse runs at one wave's latency)
-            const size_t want_waves = (size_t)ctx->cu_count * 16;
-            sa.spw = sa.count / 16 < want_waves ? 16 : (sa.count / 32 < want_waves ? 32 : 64);
-            if (const char* e = getenv("TAMP_AMD_SPLIT_SPW")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) sa.spw = (uint32_t)v; }
-            const uint32_t pwaves = (sa.count + sa.spw - 1) / sa.spw;
-            hipLaunchKernelGGL(tamp_decode_parse_kernel, dim3((pwaves + 3) / 4), dim3(256), split_parse_lds(256), st, sa);
-            hipLaunchKernelGGL(resolve_kernel, dim3(wave_resolve ? (sa.count + 3) / 4 : sa.count), dim3(256), lds, st, sa);
-        }
-        // leftovers: the wave decoder over the flagged streams only
-        a.only_flagged = sa.flagged;
-        a.flagged_count = sa.flagged_count;
-        const int rc = launch_wave_decoder(a, max_wbits, n_streams, (size_t)ctx->cu_count * 64, st);
-        timing_end(st);
-        if (rc != TAMP_OK) return rc;
-        HIP_OK(hipGetLastError());
-        return TAMP_OK;
-        }  // (no scratch to be had: fall through to the lane / wave decoders)
+    DecodeDevice dev = {(uint32_t)ctx->cu_count, false, 0, rec.split.bytes};
+    DecodePlan plan = plan_decompress(call, scan, dev);
+    if (plan.decoder == Decoder::kSplit) {  // its scratch budget: what the device has free right now (asked for this decoder alone)
+        size_t total_b = 0;
+        dev.free_known = hipMemGetInfo(&dev.free_bytes, &total_b) == hipSuccess;
+        if (!dev.free_known) (void)hipGetLastError();
+        plan = plan_decompress(call, scan, dev);
     }
-    // Decoder choice: one wavefront per stream (scalar token loop, window in LDS, 64-lane copies) unless the batch is
-    // a very large number of streams, where one lane per stream fills the chip and avoids per-stream set-up.
-    // Three decoders.  Wave per stream: time follows the total bytes, needs few streams.  Lane per
-    // stream with the windows in LDS: rounds of `capacity` streams (the rows limit the resident lanes), a round lasts as
-    // long as its longest stream, about twice as fast per byte -- taken when a single round is reasonably full, and for
-    // batches of short messages.  Lane per stream with the windows in a global scratch slab: no capacity limit, every
-    // wave resident at once and the memory latency hidden by the other waves of the SIMD -- taken for large batches of
-    // long streams, whatever their windows (mixed-window batches included).
-    const bool bulk = longest_in >= 512;  // short messages: the lean lane build (no bulk path, smaller rows)
-    const bool force_global = force && force[0] == 'g';
-    bool lds_lanes = false, global_lanes = false;
-    if (valid_bits) {
-        size_t capacity = 0;
-        if (max_wbits <= kLdsWinBits) {
-            const uint32_t lds = bulk ? lane_decoder_lds(max_wbits) : kWave * ((1u << max_wbits) + 4);
-            capacity = (size_t)ctx->cu_count * std::min<size_t>(160 * 1024 / lds, 16) * kWave;
-        }
-        if (!bulk) {
-            const size_t rounds = capacity ? (n_streams + capacity - 1) / capacity : 1;
-            lds_lanes = capacity && n_streams * 10 >= rounds * capacity * 2;
-        } else if (capacity && max_wbits <= 9) {
-            // small windows: four and more waves of rows fit a CU's LDS, nothing beats that
-            const size_t rounds = (n_streams + capacity - 1) / capacity;
-            lds_lanes = n_streams * 10 >= rounds * capacity * 6;
-        } else {
-            lds_lanes = capacity && n_streams * 10 >= capacity * 6 && n_streams * 4 <= capacity * 5;
-            global_lanes = !lds_lanes && n_streams >= (size_t)ctx->cu_count * 192;  // ~3/4 wave per SIMD and up
-        }
-    }
-    if (force) lds_lanes = force[0] == 'l', global_lanes = force_global;
-    const bool use_wave = force ? (force[0] == 'w') : !(lds_lanes || global_lanes);
-    if (valid_bits && use_wave) {
-        timing_begin(st);
-        const int rc = launch_wave_decoder(a, max_wbits, n_streams, (size_t)ctx->cu_count * 64, st);
-        timing_end(st);
-        if (rc != TAMP_OK) return rc;
-        HIP_OK(hipGetLastError());
-        return TAMP_OK;
-    }
-    if (valid_bits && max_wbits <= kLdsWinBits && !global_lanes) {
-        // windows in LDS: one 64-lane workgroup per 64 streams, one padded row per lane
-        a.lds_row = (1u << max_wbits) + (bulk ? kLaneRowPad : 4u);
-        const uint32_t lds = bulk ? lane_decoder_lds(max_wbits) : kWave * a.lds_row;
-        const uint32_t per_cu = (uint32_t)(160 * 1024 / lds) < 16 ? (uint32_t)(160 * 1024 / lds) : 16;
-        size_t groups = (n_streams + kWave - 1) / kWave;
-        const size_t resident = (size_t)ctx->cu_count * per_cu;
-        if (groups > resident * 4) groups = resident * 4;  // grid-stride beyond a few waves of workgroups
-        auto lane_kernel = bulk ? tamp_decompress_kernel<true, true> : tamp_decompress_kernel<true, false>;
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(lane_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        timing_begin(st);
-        hipLaunchKernelGGL(lane_kernel, dim3((uint32_t)groups), dim3(kWave), lds, st, a);
-        timing_end(st);
-        HIP_OK(hipGetLastError());
-        return TAMP_OK;
-    }
-    const uint32_t threads = 256;
-    const uint8_t slot_bits = valid_bits ? max_wbits : 8;
-    const bool gbulk = valid_bits && bulk;  // bulk path with the windows in the scratch slab (slots padded like LDS rows)
-    const size_t slot = ((size_t)1 << slot_bits) + (gbulk ? 64 : 0);
-    a.lds_row = (uint32_t)slot;
-    // Resident lanes.  Every step touches the lane's window at random: the kernel runs at the speed of the Infinity
-    // Cache (256 MB) as long as the windows in flight fit into it, and of HBM sector traffic beyond.  So: as many lanes
-    // as ~144 MB of live windows allow, but at least one wave per SIMD (and no more than eight).
-    size_t lanes = (size_t)ctx->cu_count * 2048;
-    {
-        const size_t avg_window = window_bytes ? std::max<size_t>(256, (size_t)(window_bytes / n_streams)) : ((size_t)1 << slot_bits);
-        size_t fit = ((size_t)144 << 20) / avg_window;
-        if (const char* e = getenv("TAMP_AMD_SCRATCH_MB")) fit = ((size_t)atoi(e) << 20) / avg_window;  // tuning
-        lanes = std::min(lanes, std::max(fit, (size_t)ctx->cu_count * 256));
-    }
-    const size_t budget = (size_t)4 << 30;  // hard bound of the slab
-    if (lanes * slot > budget) lanes = budget / slot;
-    if (lanes > n_streams) lanes = n_streams;
-    const uint32_t grid = (uint32_t)((lanes + threads - 1) / threads);
-    const size_t need = (size_t)grid * threads * slot;
-    HIP_OK(StreamScratch::drain_if_outgrown(rec.slab, need, st));
-    HIP_OK(rec.slab.need(need, false));
-    a.scratch = static_cast<uint8_t*>(rec.slab.p);
-    timing_begin(st);
-    if (gbulk)
-        hipLaunchKernelGGL((tamp_decompress_kernel<false, true>), dim3(grid), dim3(threads), 128 + threads * kLaneStagePad, st, a);
-    else
-        hipLaunchKernelGGL((tamp_decompress_kernel<false, false>), dim3(grid), dim3(threads), 0, st, a);
-    timing_end(st);
-    HIP_OK(hipGetLastError());
-    return TAMP_OK;
+    return run_decode_plan(ctx, rec, a, call, scan, dev, plan, st);
 }
 
 // Resumable decoding: one wavefront per decoder object (tamp_decompress_resume_kernel.hpp).
@@ -1182,15 +1078,11 @@ int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, u
     a.lds_row = 0;
     a.max_wbits = bits_max;
     ra.states = d_states, ra.state_stride = stride;
-    const uint32_t waves = bits_max <= 12 ? 4 : 1;
-    const uint32_t lds = decode_wave_lds(bits_max, waves);
-    size_t groups = (n_streams + waves - 1) / waves;
-    groups = std::min(groups, (size_t)ctx->cu_count * 64);  // grid-stride beyond that
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(tamp_decompress_resume_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const WaveGeometry g = wave_geometry(bits_max, n_streams, ctx->cu_count);
     timing_begin(st);
-    hipLaunchKernelGGL(tamp_decompress_resume_kernel, dim3((uint32_t)groups), dim3(waves * kWave), lds, st, ra);
+    const int rc = launch_waves(tamp_decompress_resume_kernel, ra, g, decode_wave_lds(bits_max, g.waves), st);
     timing_end(st);
+    if (rc != TAMP_OK) return rc;
     HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
@@ -1208,15 +1100,11 @@ int launch_compress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uin
     a.in_consumed = d_consumed;
     a.n_objects = (uint32_t)n, a.op = (uint32_t)op, a.write_token = write_token ? 1u : 0u;
     a.max_wbits = bits_max;
-    const uint32_t waves = bits_max <= 12 ? 4 : 1;
-    const uint32_t lds = encode_resume_lds(bits_max, waves);
-    size_t groups = (n + waves - 1) / waves;
-    groups = std::min(groups, (size_t)ctx->cu_count * 64);
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(tamp_compress_resume_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const WaveGeometry g = wave_geometry(bits_max, n, ctx->cu_count);
     timing_begin(st);
-    hipLaunchKernelGGL(tamp_compress_resume_kernel, dim3((uint32_t)groups), dim3(waves * kWave), lds, st, a);
+    const int rc = launch_waves(tamp_compress_resume_kernel, a, g, encode_resume_lds(bits_max, g.waves), st);
     timing_end(st);
+    if (rc != TAMP_OK) return rc;
     HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
@@ -1647,6 +1535,32 @@ int tamp_amd_compress_build(const TampAmdConf* conf, uint32_t max_in_len, uint32
     call.has_state = (call_flags & TAMP_AMD_CALL_STATE) != 0;
     const CompressBuild b = plan_compress(call).build;
     return b == CompressBuild::kFixedExt ? TAMP_AMD_BUILD_FIXED_EXT : (b == CompressBuild::kFixedV1 ? TAMP_AMD_BUILD_FIXED_V1 : TAMP_AMD_BUILD_GENERIC);
+}
+
+int tamp_amd_decompress_plan(const TampAmdDecodeQuery* q, TampAmdDecodePlan* out) {
+    if (!q || !out || q->n_streams == 0) return TAMP_AMD_BAD_ARGUMENT;
+    const DecodeCall call = {(size_t)q->n_streams, q->max_window_bits, q->has_dictionary != 0};
+    DecodeScan scan;
+    scan.found = q->scan_found, scan.longest_in = q->scan_longest_in, scan.window_units = q->scan_window_units, scan.max_out_cap = q->scan_max_out_cap;
+    const DecodeDevice dev = {q->cu_count, q->free_known != 0, (size_t)q->free_bytes, (size_t)q->held_bytes};
+    const DecodeLong gate = decode_wants_long(call);
+    const DecodePlan p = plan_decompress(call, scan, dev, !q->exclude_split);
+    *out = {};
+    out->long_attempt = gate.attempt, out->long_min_len = gate.min_len, out->long_extended = gate.extended, out->long_chain = gate.chain;
+    out->scan = decode_wants_scan(call);
+    out->decoder = p.decoder == Decoder::kSplit ? TAMP_AMD_DECODER_SPLIT : p.decoder == Decoder::kWave ? TAMP_AMD_DECODER_WAVE
+                   : p.decoder == Decoder::kLaneLds ? TAMP_AMD_DECODER_LANE_LDS : TAMP_AMD_DECODER_LANE_GLOBAL;
+    out->max_window_bits = p.max_wbits, out->bulk = p.bulk;
+    if (p.decoder == Decoder::kSplit) {
+        const SplitGeometry& g = p.split;
+        out->split_tokcap = g.tokcap, out->split_maxcap = g.maxcap, out->split_wave_resolve = g.wave_resolve, out->split_resolve_lds = g.resolve_lds;
+        out->split_spw = g.spw((uint32_t)g.slice), out->split_slice = g.slice, out->split_slab_bytes = g.slab_bytes(g.slice);
+    }
+    out->wave_waves = p.wave.waves, out->wave_lds = p.wave_lds, out->wave_groups = p.wave.groups;
+    out->lane_lds_row = p.lane.lds_row, out->lane_lds = p.lane.lds, out->lane_per_cu = p.lane.per_cu, out->lane_grid = p.lane.grid;
+    out->global_slot = p.global.slot, out->global_grid = p.global.grid, out->global_bulk = p.global.gbulk, out->global_lds = p.global.lds;
+    out->global_lanes = p.global.lanes, out->global_slab_bytes = p.global.slab_bytes;
+    return TAMP_OK;
 }
 
 const char* tamp_amd_last_error(void) { return t_last_error; }

@@ -21,7 +21,8 @@ def _declared_functions():
 def test_header_declares_the_boundary():
     names = _declared_functions()
     for must in ("tamp_batch_compress", "tamp_batch_decompress", "tamp_initialize_dictionary",
-                 "tamp_compute_min_pattern_size", "tamp_amd_compress", "tamp_amd_decompress", "tamp_amd_read_header"):
+                 "tamp_compute_min_pattern_size", "tamp_amd_compress", "tamp_amd_decompress", "tamp_amd_read_header",
+                 "tamp_amd_compress_plan", "tamp_amd_compress_build", "tamp_amd_decompress_plan"):
         assert must in names
 
 
