@@ -253,6 +253,31 @@ int tamp_batch_decompress(const uint8_t *dictionary, size_t dictionary_len, uint
                           const uint32_t *out_cap, uint32_t *out_len, int8_t *status, uint32_t *in_consumed,
                           size_t n_streams, int mem, int device, void *stream);
 
+/*
+ * How large would the output be?  A `.tamp` stream does not record the length of its plain text; this call finds it -- or refuses
+ * to look further than `limit` -- without decoding a byte.  The contract in one sentence: the call returns, per stream, exactly
+ * the out_len, status and in_consumed that tamp_batch_decompress returns for the same call with out_cap[i] = limit[i]
+ * (limit == NULL: 0xFFFFFFFF for every stream), and writes no output bytes.  So a stream that ends normally gets
+ * TAMP_INPUT_EXHAUSTED (2) and its full size, one that would outgrow its limit gets TAMP_OUTPUT_FULL (1) with
+ * decoded_size[i] == limit[i] (a decompression bomb is refused at the price of parsing up to the limit: an RLE token is 241
+ * bytes in 14 bits), malformed input TAMP_OOB / TAMP_INVALID_CONF and a stream of 2^29 bytes or more TAMP_AMD_BAD_ARGUMENT.
+ * Room that is used up exactly still reports TAMP_OUTPUT_FULL when padding bits are left, as the reference does: decode with
+ * out_cap[i] = decoded_size[i] + 1 to see the end status.
+ *
+ *   dictionary_len      length of the custom dictionary the decode call will pass (0: none).  Its bytes are not needed: a
+ *                       stream whose header has the custom bit and asks for more than dictionary_len gets TAMP_INVALID_CONF
+ *   max_window_bits     as for tamp_batch_decompress; TAMP_AMD_WINDOW_BITS_EXACT is accepted and ignored (no pre-pass exists)
+ *   limit               optional (may be NULL): per-stream bound on decoded_size
+ *   in_consumed         optional (may be NULL)
+ *   mem, device, stream as for tamp_batch_decompress.  With TAMP_AMD_MEM_DEVICE the call is one kernel on `stream` and waits
+ *                       for nothing.  With TAMP_AMD_MEM_HOST the compressed bytes are staged as for a decode call and only the
+ *                       three tables come back.
+ */
+int tamp_batch_decoded_size(size_t dictionary_len, uint8_t max_window_bits, const uint8_t *in, const uint64_t *in_off,
+                            const uint32_t *in_len, const uint32_t *limit /* may be NULL */, uint32_t *decoded_size,
+                            int8_t *status, uint32_t *in_consumed /* may be NULL */, size_t n_streams,
+                            int mem, int device, void *stream);
+
 /* ---- resumable decoding: decoder OBJECTS that survive between calls ------------------------------
  *
  * What TampDecompressor is in the reference (decompressor.h:13-57): 16 bytes of state next to a window buffer,

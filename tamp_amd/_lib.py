@@ -33,6 +33,7 @@ SYMBOLS = (
     "tamp_amd_decompress_plan",
     "tamp_batch_compress",
     "tamp_batch_decompress",
+    "tamp_batch_decoded_size",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
     "tamp_batch_decompress_resume",
@@ -166,6 +167,8 @@ def load() -> C.CDLL:
     lib.tamp_batch_compress.restype = i32
     lib.tamp_batch_decompress.argtypes = [vp, sz, u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
     lib.tamp_batch_decompress.restype = i32
+    lib.tamp_batch_decoded_size.argtypes = [sz, u8, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.tamp_batch_decoded_size.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]
     lib.tamp_amd_decoder_state_size.restype = sz
     lib.tamp_amd_decoder_state_init.argtypes = [vp, C.POINTER(TampAmdConf), u8]

@@ -206,9 +206,97 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
     return BatchResult(out, out_off, out_len, status, None, ms)
 
 
-def decompress_batch(data, in_off=None, in_len=None, *, out_cap, dictionary=None, max_window_bits: int = 15,
-                     scan_headers: bool = True, device: int = 0, stream=None, timing: bool = False) -> BatchResult:
+@dataclass
+class DecodedSizes:
+    size: object         # uint32/int32 [n] -- bytes stream i decodes to (``limit[i]`` at most)
+    status: object       # int8 [n] -- what decoding into ``limit[i]`` bytes of room would report
+    in_consumed: object  # uint32/int32 [n]
+    kernel_ms: float = -1.0
+    _keep: object = None  # device tensors the asynchronous launch still reads
+
+
+def decoded_size_batch(data, in_off=None, in_len=None, *, limit=None, dictionary=None, max_window_bits: int = 15,
+                       device: int = 0, stream=None, timing: bool = False) -> DecodedSizes:
+    """How many bytes each ``.tamp`` stream of a batch decodes to, without decoding it (``tamp_batch_decoded_size``).
+
+    Per stream exactly the size, status and consumed count that ``decompress_batch`` reports with ``out_cap = limit``
+    (``None``: no limit below 2^32 - 1): status 2 and the full size for a stream that ends normally, status 1 and
+    ``size == limit`` for one that would outgrow ``limit`` (an int or a per-stream array), -4 / -3 for malformed input.
+    ``data`` takes the three forms of ``decompress_batch``; with torch CUDA tensors the call is one asynchronous kernel on
+    torch's current stream (or ``stream``).  Of ``dictionary`` only the length is used.
+    """
+    if stream is not None and _is_torch(data):
+        import torch  # (tables on the launch stream: see compress_batch)
+
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return decoded_size_batch(data, in_off, in_len, limit=limit, dictionary=dictionary, max_window_bits=max_window_bits,
+                                      device=device, stream=None, timing=timing)
+    lib = _lib.load()
+    lib.tamp_amd_set_timing(1 if timing else 0)
+    dict_len = 0
+    if dictionary is not None:
+        dict_len = int(dictionary.numel()) if _is_torch(dictionary) else len(dictionary)
+    if _is_torch(data):
+        import torch
+
+        n = int(in_len.numel())
+        dev = data.device
+        limit_t = None
+        if limit is not None and _is_int(limit):
+            if not 0 <= int(limit) <= 0xFFFFFFFF:
+                raise ValueError("limit must fit 32 bits")
+            if int(limit) != 0xFFFFFFFF:  # (the table holds uint32 values in int32 storage)
+                limit_t = torch.full((n,), int(limit) - (1 << 32) if int(limit) >= 1 << 31 else int(limit), dtype=torch.int32, device=dev)
+        elif limit is not None:
+            limit_t = (limit if _is_torch(limit) else torch.as_tensor(np.asarray(limit, dtype=np.uint32).view(np.int32))).to(device=dev, dtype=torch.int32)
+        size_t = torch.empty(n, dtype=torch.int32, device=dev)
+        status_t = torch.empty(n, dtype=torch.int8, device=dev)
+        consumed_t = torch.empty(n, dtype=torch.int32, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        rc = lib.tamp_batch_decoded_size(dict_len, max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(limit_t),
+                                         _ptr(size_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE, dev.index or 0,
+                                         C.c_void_p(st))
+        _lib.check_launch(rc)
+        ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+        return DecodedSizes(size_t, status_t, consumed_t, ms, (data, in_off_t, in_len_t, limit_t))
+
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    n = len(in_len)
+    if limit is not None and _is_int(limit):
+        if not 0 <= int(limit) <= 0xFFFFFFFF:
+            raise ValueError("limit must fit 32 bits")
+        limit = None if int(limit) == 0xFFFFFFFF else np.full(n, int(limit), dtype=np.uint32)
+    elif limit is not None:
+        limit = np.ascontiguousarray(limit, dtype=np.uint32)
+        if len(limit) != n:
+            raise ValueError("one limit per stream expected")
+    size = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int8)
+    consumed = np.zeros(n, dtype=np.uint32)
+    rc = lib.tamp_batch_decoded_size(dict_len, max_window_bits, _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off),
+                                     _ptr(in_len), _ptr(limit), _ptr(size), _ptr(status), _ptr(consumed), n, _lib.MEM_HOST,
+                                     device, C.c_void_p(stream) if stream else None)
+    _lib.check_launch(rc)
+    ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+    return DecodedSizes(size, status, consumed, ms)
+
+
+def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: int = 0xFFFFFFFF, dictionary=None,
+                     max_window_bits: int = 15, scan_headers: bool = True, device: int = 0, stream=None,
+                     timing: bool = False) -> BatchResult:
     """Decompress many independent ``.tamp`` streams in one launch (configuration read from each header).
+
+    ``out_cap=None``: the sizes are not known.  ``decoded_size_batch(limit=max_out)`` finds them and stream ``i`` is decoded
+    into ``min(size[i] + 1, max_out)`` bytes of room -- per stream exactly the status, bytes and consumed count of
+    ``out_cap=max_out``, in slabs of ``size + 1`` bytes instead of ``max_out`` (the extra byte is what lets a stream that
+    fits report its end status 2: room used up exactly is status 1 in the reference while padding bits remain).  Host data
+    crosses the link twice this way; device data costs one device-to-host sync for the slab total.
 
     ``max_window_bits`` is the reference's limit (larger headers -> TAMP_INVALID_CONF).  With ``scan_headers`` the
     library first looks at the batch's headers to size its on-chip windows for the largest one present (one tiny
@@ -222,8 +310,23 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap, dictionary=None
         import torch  # (tables and output slab on the launch stream: see compress_batch)
 
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
-            return decompress_batch(data, in_off, in_len, out_cap=out_cap, dictionary=dictionary, max_window_bits=max_window_bits,
-                                    scan_headers=scan_headers, device=device, stream=None, timing=timing)
+            return decompress_batch(data, in_off, in_len, out_cap=out_cap, max_out=max_out, dictionary=dictionary,
+                                    max_window_bits=max_window_bits, scan_headers=scan_headers, device=device, stream=None, timing=timing)
+    if out_cap is None:
+        if not 0 <= int(max_out) <= 0xFFFFFFFF:
+            raise ValueError("max_out must fit 32 bits")
+        if not _is_torch(data) and in_off is None:
+            data, in_off, in_len = pack_streams(data)  # (packed once for both calls)
+        q = decoded_size_batch(data, in_off, in_len, limit=int(max_out), dictionary=dictionary, max_window_bits=max_window_bits,
+                               device=device, stream=stream)
+        if _is_torch(data):
+            import torch
+
+            out_cap = torch.clamp((q.size.to(torch.int64) & 0xFFFFFFFF) + 1, max=int(max_out))  # (int64: sizes are uint32 values)
+        else:
+            out_cap = np.minimum(q.size.astype(np.uint64) + 1, np.uint64(int(max_out))).astype(np.uint32)
+        return decompress_batch(data, in_off, in_len, out_cap=out_cap, dictionary=dictionary, max_window_bits=max_window_bits,
+                                scan_headers=scan_headers, device=device, stream=stream, timing=timing)
     lib = _lib.load()
     lib.tamp_amd_set_timing(1 if timing else 0)
     if not scan_headers:
@@ -239,9 +342,10 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap, dictionary=None
             out_off_t = torch.arange(n, dtype=torch.int64, device=dev) * out_cap
             total = n * out_cap
         else:
-            out_cap_t = out_cap.to(device=dev, dtype=torch.int32)
-            out_off_t = torch.cumsum(out_cap_t.to(torch.int64), 0) - out_cap_t.to(torch.int64)
-            total = int(out_cap_t.to(torch.int64).sum().item())
+            cap64 = out_cap.to(device=dev, dtype=torch.int64)
+            out_cap_t = cap64.to(torch.int32)  # (the low 32 bits: what the library reads as uint32)
+            out_off_t = torch.cumsum(cap64, 0) - cap64
+            total = int(cap64.sum().item())
         out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         out_len_t = torch.empty(n, dtype=torch.int32, device=dev)
         status_t = torch.empty(n, dtype=torch.int8, device=dev)

@@ -622,37 +622,50 @@ __global__ void tamp_header_scan_kernel(const uint8_t* in, const uint64_t* in_of
     }
 }
 
-// ONE long v1 stream (tamp_decompress_long_kernel.hpp): start positions settled by rounds of a lane per 512 compressed bytes,
-// records per chunk, then the split decoder's RESOLVE over groups of at most kSplitMaxOut output bytes, in order, each with the
-// W bytes in front of it as its dictionary.  -> 1 when the call is not one (or anything is off: the exact decoders take it),
-// TAMP_OK when the stream has been decoded, an error code otherwise.  Nothing is written before the fall-back decision.
-int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits,
-                           const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
-                           const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed, hipStream_t st) {
+// The front of the long-stream path (tamp_decompress_long_kernel.hpp), shared by the decoder and the size query: header read and
+// gates, the tables of the settle rounds and the count pass (with_records: the decoder's records and group tables behind them), the
+// tamp_long_sync_kernel rounds, and tamp_long_parse_kernel with write = 0 -- tokens and output bytes per chunk.
+struct LongFront {
+    uint32_t n, cap;       // compressed bytes; room (the size query: the stream's limit, 0xFFFFFFFF without one)
+    uint64_t out_off;      // (decoder only)
+    const uint8_t* in;
+    StreamHeader hd;
+    uint32_t hs, N, chunk_bits, lg;  // header bytes, chunks, bits per chunk, workgroups of the chunk kernels
+    const uint8_t* dict0;  // the fresh decoder's window: the custom dictionary, or the seeded table for the stream's literal size
+    size_t b_tab;          // bytes of the per-chunk tables at the start of rec.long_tab (records: behind them)
+    uint32_t *d_tokbase, *d_rot, *d_specbase, *d_chunk_lag, *d_chunk_o0, *d_chunk_lag0, *d_lagbase;
+    LongArgs la;           // as the count pass ran: g = the settled starts, write = 0
+    std::vector<uint32_t> ntok, outb;  // per chunk
+    bool dbg;              // TAMP_AMD_LONGDEC_DEBUG
+};
+// -> 1 when the stream is not one for this path (or anything is off: the exact decoders take it), TAMP_OK with `f` filled in and
+// timing begun, an error code otherwise.  `who` names the caller in the debug line.  d_out_off / d_cap may be null.
+int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, bool has_dict, size_t dict_len,
+                      uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                      const uint64_t* d_out_off, const uint32_t* d_cap, bool with_records, const char* who, hipStream_t st, LongFront& f) {
     uint64_t in_off = 0, out_off = 0;
-    uint32_t n = 0, cap = 0;
+    uint32_t n = 0, cap = 0xFFFFFFFFu;
     HIP_OK(hipMemcpyAsync(&n, d_in_len, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     // (the chunk kernels count bits in 32-bit registers: (i + 1) * kLongChunkBits wraps for the last chunk of the top 512 bytes of
     // the accepted range -- those streams stay with the exact decoder)
     if (n < gate.min_len || n > kMaxDecodeIn - 512) return 1;
     HIP_OK(hipMemcpyAsync(&in_off, d_in_off, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(&out_off, d_out_off, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(&cap, d_out_cap, 4, hipMemcpyDeviceToHost, st));
+    if (d_out_off) HIP_OK(hipMemcpyAsync(&out_off, d_out_off, 8, hipMemcpyDeviceToHost, st));
+    if (d_cap) HIP_OK(hipMemcpyAsync(&cap, d_cap, 4, hipMemcpyDeviceToHost, st));
     uint8_t hdr[2] = {0, 0};
     HIP_OK(hipMemcpyAsync(hdr, d_in + in_off, 2, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     const uint8_t* const in = d_in + in_off;
-    uint8_t* const out = d_out + out_off;
     const StreamHeader hd = decode_header(hdr[0]);
     const uint32_t hs = 1 + (hdr[0] & 1), wbits = hd.wbits, lbits = hd.lbits;
     const bool extended = hd.extended;
     if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return 1;
     if (extended && !gate.extended) return 1;  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
-    if (hd.custom && (!d_dict || dict_len < W)) return 1;
-    // the fresh decoder's window: the custom dictionary, or the seeded table for the stream's literal size
-    const uint8_t* const dict0 = hd.custom ? d_dict : ctx->seed_dicts + ((size_t)hd.table << 15);
+    if (hd.custom && (!has_dict || dict_len < W)) return 1;
+    f.n = n, f.cap = cap, f.out_off = out_off, f.in = in, f.hd = hd, f.hs = hs;
+    f.dict0 = hd.custom ? d_dict : ctx->seed_dicts + ((size_t)hd.table << 15);
 
     const uint64_t total_bits = 8ull * n;
     const uint32_t chunk_bits = extended ? kLongChunkBitsExt : kLongChunkBits;
@@ -664,7 +677,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         // worst case records: the shortest token is a literal, 1 + literal bits
         const size_t max_tok = (size_t)(total_bits / (1 + lbits)) + 4096;
         const size_t b_groups = ((size_t)(max_tok / 256 + N + 64) * (16 + sizeof(LongGroup) + 4) + 255) & ~(size_t)255;
-        const size_t bytes = b_tab + max_tok * 4 + b_groups + 4 * (size_t)(1u << 15) + 4096;
+        const size_t bytes = with_records ? b_tab + max_tok * 4 + b_groups + 4 * (size_t)(1u << 15) + 4096 : b_tab;
         if (rec.long_tab.need(bytes) != hipSuccess) return 1;
     }
     uint8_t* const tab = static_cast<uint8_t*>(rec.long_tab.p);
@@ -681,14 +694,17 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
     uint32_t* const d_chunk_o0 = d_chunk_lag + 2 * (size_t)N;
     uint32_t* const d_chunk_lag0 = d_chunk_o0 + N;
     uint32_t* const d_lagbase = d_chunk_lag0 + N;
-    uint32_t* const recs = reinterpret_cast<uint32_t*>(tab + b_tab);
+    f.N = N, f.chunk_bits = chunk_bits, f.b_tab = b_tab;
+    f.d_tokbase = d_tokbase, f.d_rot = d_rot, f.d_specbase = d_specbase, f.d_chunk_lag = d_chunk_lag, f.d_chunk_o0 = d_chunk_o0;
+    f.d_chunk_lag0 = d_chunk_lag0, f.d_lagbase = d_lagbase;
 
     timing_begin(st);
-    LongArgs la;
+    LongArgs& la = f.la;
     memset(&la, 0, sizeof la);
     la.in = in, la.n = n, la.first_bit = 8 * hs, la.n_chunks = N, la.wbits = wbits, la.lbits = lbits;
     la.chunk_bits = chunk_bits, la.extended = extended ? 1u : 0u, la.nspec = d_nspec;
-    la.flags = flags, la.ntok = d_ntok, la.outb = d_outb, la.tokbase = d_tokbase, la.rot = d_rot, la.recs = recs, la.write = 0;
+    la.flags = flags, la.ntok = d_ntok, la.outb = d_outb, la.tokbase = d_tokbase, la.rot = d_rot, la.write = 0;
+    la.recs = with_records ? reinterpret_cast<uint32_t*>(tab + b_tab) : nullptr;
     // start guesses: the chunk boundaries themselves (chunk 0: behind the header)
     {
         std::vector<uint32_t> init(N + 1);
@@ -698,6 +714,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         HIP_OK(hipStreamSynchronize(st));
     }
     const uint32_t lg = (N + 63) / 64;
+    f.lg = lg;
     uint32_t* cur = g0;
     uint32_t* nxt = g1;
     bool settled = false;
@@ -712,19 +729,42 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         std::swap(cur, nxt);
         settled = changed == 0;
     }
-    const bool dbg_long = getenv("TAMP_AMD_LONGDEC_DEBUG") != nullptr;
-    if (dbg_long) fprintf(stderr, "[tamp_amd long decode] %u bytes, %u chunks, %d sync rounds, settled %d\n", n, N, rounds, (int)settled);
+    f.dbg = getenv("TAMP_AMD_LONGDEC_DEBUG") != nullptr;
+    if (f.dbg) fprintf(stderr, "[tamp_amd long %s] %u bytes, %u chunks, %d sync rounds, settled %d\n", who, n, N, rounds, (int)settled);
     if (!settled) { timing_end(st); return 1; }
     la.g = cur, la.g_next = nullptr, la.write = 0;
     HIP_OK(hipMemsetAsync(flags, 0, 8, st));
     hipLaunchKernelGGL(tamp_long_parse_kernel, dim3(lg), dim3(64), 0, st, la);
-    std::vector<uint32_t> ntok(N), outb(N);
+    f.ntok.resize(N), f.outb.resize(N);
     uint32_t fl[2] = {0, 0};
-    HIP_OK(hipMemcpyAsync(ntok.data(), d_ntok, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(outb.data(), d_outb, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(f.ntok.data(), d_ntok, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(f.outb.data(), d_outb, (size_t)N * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(fl, flags, 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (fl[1]) { timing_end(st); return 1; }  // an out-of-bounds offset: the exact decoder reports where
+    return TAMP_OK;
+}
+
+// ONE long v1 stream (tamp_decompress_long_kernel.hpp): start positions settled by rounds of a lane per 512 compressed bytes,
+// records per chunk, then the split decoder's RESOLVE over groups of at most kSplitMaxOut output bytes, in order, each with the
+// W bytes in front of it as its dictionary.  -> 1 when the call is not one (or anything is off: the exact decoders take it),
+// TAMP_OK when the stream has been decoded, an error code otherwise.  Nothing is written before the fall-back decision.
+int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits,
+                           const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
+                           const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed, hipStream_t st) {
+    LongFront f;
+    if (const int rc = long_decode_front(ctx, rec, gate, d_dict, d_dict != nullptr, dict_len, max_wbits, d_in, d_in_off, d_in_len, d_out_off,
+                                         d_out_cap, true, "decode", st, f); rc != TAMP_OK) return rc;
+    const uint32_t n = f.n, cap = f.cap, N = f.N, wbits = f.hd.wbits, W = 1u << wbits, lg = f.lg;
+    const uint64_t out_off = f.out_off;
+    const bool extended = f.hd.extended, dbg_long = f.dbg;
+    uint8_t* const out = d_out + out_off;
+    const uint8_t* const dict0 = f.dict0;
+    LongArgs& la = f.la;
+    uint32_t* const recs = la.recs;
+    uint32_t *const d_tokbase = f.d_tokbase, *const d_rot = f.d_rot, *const d_nspec = la.nspec, *const d_specbase = f.d_specbase;
+    uint32_t *const d_chunk_lag = f.d_chunk_lag, *const d_chunk_o0 = f.d_chunk_o0, *const d_chunk_lag0 = f.d_chunk_lag0, *const d_lagbase = f.d_lagbase;
+    const std::vector<uint32_t>&ntok = f.ntok, &outb = f.outb;
     // Extended format: the tokens that can write fewer bytes to the window than they produce are listed (a second parse), one
     // workgroup walks the list for window_pos at each of them, and what comes back per chunk is the lag behind it and the number
     // of lagging tokens in it (tamp_long_wp_kernel).
@@ -950,7 +990,7 @@ int run_decode_plan(DeviceCtx* ctx, StreamScratch& rec, DecompressArgs a, const 
                 sa.count = (uint32_t)std::min(slice, n_streams - first);
                 sa.spw = g.spw(sa.count);
                 const uint32_t pwaves = (sa.count + sa.spw - 1) / sa.spw;
-                hipLaunchKernelGGL(tamp_decode_parse_kernel, dim3((pwaves + 3) / 4), dim3(256), split_parse_lds(256), st, sa);
+                hipLaunchKernelGGL(tamp_decode_parse_kernel<true>, dim3((pwaves + 3) / 4), dim3(256), split_parse_lds(256), st, sa);
                 hipLaunchKernelGGL(resolve_kernel, dim3(g.wave_resolve ? (sa.count + 3) / 4 : sa.count), dim3(256), g.resolve_lds, st, sa);
             }
             // leftovers: the wave decoder over the flagged streams only
@@ -1058,6 +1098,69 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     return run_decode_plan(ctx, rec, a, call, scan, dev, plan, st);
 }
 
+// The size of ONE long stream: the long decoder's front counts output bytes per chunk, their sum is the answer (status 2, all of
+// the input consumed) as long as it stays below the stream's limit.  -> 1 when the lane kernel has to answer: the stream fails the
+// gate, the chunk starts do not settle, an offset is out of bounds, or the sum reaches the limit (TAMP_OUTPUT_FULL, and how much
+// of the input that takes, is the exact loop's to say).
+int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
+                             const uint64_t* d_in_off, const uint32_t* d_in_len, const uint32_t* d_limit, uint32_t* d_size, int8_t* d_status,
+                             uint32_t* d_consumed, hipStream_t st) {
+    LongFront f;
+    if (const int rc = long_decode_front(ctx, rec, gate, nullptr, true, dict_len, max_wbits, d_in, d_in_off, d_in_len, nullptr, d_limit, false,
+                                         "size query", st, f); rc != TAMP_OK) return rc;
+    uint64_t v = 0;
+    for (const uint32_t b : f.outb) v += b;
+    if (f.dbg) fprintf(stderr, "[tamp_amd long size query] %llu bytes out, limit %u\n", (unsigned long long)v, f.cap);
+    if (v >= f.cap) { timing_end(st); return 1; }
+    hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, d_size, d_status, d_consumed, (uint32_t)v, f.n);
+    timing_end(st);
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
+// tamp_batch_decoded_size on device memory: the parse's size-only build (tamp_decompress_split_kernel.hpp), one launch, no scratch,
+// no pre-pass, nothing that waits for `st` -- except for a handful of long streams, which the long decoder's front counts with the
+// whole device (and waits as the long decoder does).  `d_limit` may be null; of the dictionary only the length matters.
+int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off,
+                        const uint32_t* d_in_len, const uint32_t* d_limit, uint32_t* d_size, int8_t* d_status, uint32_t* d_consumed,
+                        size_t n_streams, hipStream_t st) {
+    if (n_streams == 0) return TAMP_OK;
+    SplitArgs sa;
+    memset(&sa, 0, sizeof sa);
+    DecompressArgs& a = sa.d;
+    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
+    a.out_cap = d_limit, a.out_len = d_size, a.status = d_status, a.in_consumed = d_consumed;
+    a.dict_len = (uint32_t)(dict_len > 0xFFFFFFFFu ? 0xFFFFFFFFu : dict_len);
+    a.n_streams = (uint32_t)n_streams;
+    a.max_wbits = max_wbits & 0x7F;  // (TAMP_AMD_WINDOW_BITS_EXACT: there is no pre-pass to skip)
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (one library call at a time enqueues on a stream: the lock rule above StreamScratch)
+    if (const DecodeLong gate = decode_wants_long({n_streams, max_wbits, dict_len != 0}); gate.attempt) {
+        // (as launch_decompress: one after the other, one event pair around all of them; a stream that is not one for this path sends
+        // the whole call to the kernel below, which answers for every stream again)
+        size_t done = 0;
+        timing_begin(st);
+        t_timing_outer = true;
+        int rc = TAMP_OK;
+        for (; done < n_streams; done++) {
+            rc = launch_decoded_size_long(ctx, rec, gate, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done,
+                                          d_limit ? d_limit + done : nullptr, d_size + done, d_status + done,
+                                          d_consumed ? d_consumed + done : nullptr, st);
+            if (rc != TAMP_OK) break;
+        }
+        t_timing_outer = false;
+        if (rc != TAMP_OK && rc != 1) return rc;
+        if (done == n_streams) return TAMP_OK;
+    }
+    const SizeGeometry g = size_geometry(n_streams, (uint32_t)ctx->cu_count);
+    sa.first = 0, sa.count = (uint32_t)n_streams, sa.spw = g.spw;
+    timing_begin(st);
+    hipLaunchKernelGGL(tamp_decode_parse_kernel<false>, dim3(g.grid), dim3(256), g.lds, st, sa);
+    timing_end(st);
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
 // Resumable decoding: one wavefront per decoder object (tamp_decompress_resume_kernel.hpp).
 int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uint8_t bits_max, const uint8_t* d_in,
                              const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out,
@@ -1138,6 +1241,10 @@ struct HostBatch {
     size_t nlead = 0;
     bool exact_out = false;    // never the whole-extent copy-back: nothing behind out_len[i] is written (HostChunk)
     bool drop_failed = false;  // (with exact_out) a stream whose status is not TAMP_OK produces nothing: out_len = 0
+    // out == nullptr (tamp_batch_decoded_size): no output bytes at all -- out_off is null, out_cap (the limits, may be null) rides
+    // along as a table only and takes no part in the chunks' extents; out_len / status / in_consumed come back as always
+    uint64_t slab_off(size_t i) const { return out ? out_off[i] : 0; }
+    uint64_t slab_cap(size_t i) const { return out ? out_cap[i] : 0; }
 };
 
 struct HostChunk {
@@ -1158,10 +1265,10 @@ void plan_host_chunks(const HostBatch& b, size_t min_streams, uint64_t min_bytes
     bool ordered = true;
     uint64_t in_end = 0, out_end = 0, in_max = 0, out_max = 0, in_min = ~0ull, out_min = ~0ull;
     for (size_t i = 0; i < b.n; i++) {
-        ordered = ordered && b.in_off[i] >= in_end && b.out_off[i] >= out_end;
-        in_end = b.in_off[i] + b.in_len[i], out_end = b.out_off[i] + b.out_cap[i];
+        ordered = ordered && b.in_off[i] >= in_end && b.slab_off(i) >= out_end;
+        in_end = b.in_off[i] + b.in_len[i], out_end = b.slab_off(i) + b.slab_cap(i);
         in_max = std::max(in_max, in_end), out_max = std::max(out_max, out_end);
-        in_min = std::min(in_min, b.in_off[i]), out_min = std::min(out_min, b.out_off[i]);
+        in_min = std::min(in_min, b.in_off[i]), out_min = std::min(out_min, b.slab_off(i));
     }
     if (!ordered) {
         chunks.push_back({0, b.n, in_min, in_max, out_min, out_max, false});
@@ -1172,15 +1279,15 @@ void plan_host_chunks(const HostBatch& b, size_t min_streams, uint64_t min_bytes
         size_t i1 = i0 + 1;
         for (; i1 < b.n; i1++) {
             const uint64_t have = std::max(b.in_off[i1 - 1] + b.in_len[i1 - 1] - b.in_off[i0],
-                                           b.out_off[i1 - 1] + b.out_cap[i1 - 1] - b.out_off[i0]);
+                                           b.slab_off(i1 - 1) + b.slab_cap(i1 - 1) - b.slab_off(i0));
             const uint64_t with = std::max(b.in_off[i1] + b.in_len[i1] - b.in_off[i0],
-                                           b.out_off[i1] + b.out_cap[i1] - b.out_off[i0]);
+                                           b.slab_off(i1) + b.slab_cap(i1) - b.slab_off(i0));
             if ((i1 - i0 >= min_streams && have >= min_bytes) || with > max_bytes) break;
         }
         bool packed = !b.exact_out;
-        for (size_t i = i0 + 1; i < i1 && packed; i++) packed = b.out_off[i] == b.out_off[i - 1] + b.out_cap[i - 1];
-        chunks.push_back({i0, i1, b.in_off[i0], b.in_off[i1 - 1] + b.in_len[i1 - 1], b.out_off[i0],
-                          b.out_off[i1 - 1] + b.out_cap[i1 - 1], packed});
+        for (size_t i = i0 + 1; i < i1 && packed; i++) packed = b.slab_off(i) == b.slab_off(i - 1) + b.slab_cap(i - 1);
+        chunks.push_back({i0, i1, b.in_off[i0], b.in_off[i1 - 1] + b.in_len[i1 - 1], b.slab_off(i0),
+                          b.slab_off(i1 - 1) + b.slab_cap(i1 - 1), packed});
         i0 = i1;
     }
     // a short last chunk is a badly filled launch: give it to its neighbour
@@ -1188,7 +1295,7 @@ void plan_host_chunks(const HostBatch& b, size_t min_streams, uint64_t min_bytes
         const HostChunk last = chunks.back();
         chunks.pop_back();
         HostChunk& prev = chunks.back();
-        prev.out_packed = prev.out_packed && last.out_packed && b.out_off[last.i0] == prev.out_hi;
+        prev.out_packed = prev.out_packed && last.out_packed && b.slab_off(last.i0) == prev.out_hi;
         prev.i1 = last.i1, prev.in_hi = last.in_hi, prev.out_hi = last.out_hi;
     }
 }
@@ -1236,7 +1343,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         s.in_off = reinterpret_cast<uint64_t*>(m), m += max_cnt * 8;
         s.out_off = reinterpret_cast<uint64_t*>(m), m += max_cnt * 8;
         s.in_len = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
-        s.out_cap = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
+        s.out_cap = b.out_cap ? reinterpret_cast<uint32_t*>(m) : nullptr, m += max_cnt * 4;
         s.out_len = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
         s.in_consumed = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
         s.status = reinterpret_cast<int8_t*>(m);
@@ -1258,9 +1365,9 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         if (b.states)
             HIP_OK(hipMemcpyAsync(s.states, b.states + ch.i0 * b.state_stride, cnt * b.state_stride, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.in_off), b.in_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.out_off), b.out_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
+        if (b.out_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.out_off), b.out_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.in_len), b.in_len + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.out_cap), b.out_cap + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
+        if (b.out_cap) HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.out_cap), b.out_cap + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
         return launch(s, cnt, d_dict, st);
     };
     auto drain = [&](size_t k) -> int {  // copy-out of chunk k, complete on return
@@ -1283,6 +1390,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         if (b.drop_failed)
             for (size_t i = ch.i0; i < ch.i1; i++)
                 if (b.status[i] != TAMP_OK) b.out_len[i] = 0;
+        if (!b.out) return TAMP_OK;  // (tables only)
         // (staging pays when the extent is mostly produced bytes; a sparse or permuted batch can span gigabytes for a few
         // megabytes of output -- those, and extents above 512 MiB of pinned memory per slot, take the merged copies below)
         size_t produced = 0;
@@ -1729,6 +1837,38 @@ int tamp_batch_decompress(const uint8_t* dictionary, size_t dictionary_len, uint
         return launch_decompress(ctx, d_dict, d_dict ? dictionary_len : 0, max_window_bits, s.in, s.in_off, s.in_len, s.out,
                                  s.out_off, s.out_cap, s.out_len, s.status, in_consumed ? s.in_consumed : no_consumed,
                                  count, cs);
+    });
+}
+
+int tamp_batch_decoded_size(size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,
+                            const uint32_t* in_len, const uint32_t* limit, uint32_t* decoded_size, int8_t* status,
+                            uint32_t* in_consumed, size_t n_streams, int mem, int device, void* stream) {
+    if (n_streams && (!in_off || !in_len || !decoded_size || !status)) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
+    if (device == TAMP_AMD_ALL_DEVICES) {
+        if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
+        return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
+            return tamp_batch_decoded_size(dictionary_len, max_window_bits, in, in_off + i0, in_len + i0, limit ? limit + i0 : nullptr,
+                                           decoded_size + i0, status + i0, in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev,
+                                           nullptr);
+        });
+    }
+    DeviceCtx* ctx = nullptr;
+    int rc = get_ctx(device, &ctx);
+    if (rc != TAMP_OK) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE)
+        return launch_decoded_size(ctx, dictionary_len, max_window_bits, in, in_off, in_len, limit, decoded_size, status, in_consumed,
+                                   n_streams, static_cast<hipStream_t>(stream));
+
+    if (n_streams == 0) return TAMP_OK;
+    // (no slab: out = out_off = null, the limits travel as the out_cap table; no dictionary bytes either, only their count)
+    const HostBatch b = {in, in_off, in_len, nullptr, nullptr, limit, decoded_size, status, in_consumed, n_streams};
+    uint32_t* no_consumed = nullptr;
+    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
+                          [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
+        return launch_decoded_size(ctx, dictionary_len, max_window_bits, s.in, s.in_off, s.in_len, s.out_cap, s.out_len, s.status,
+                                   in_consumed ? s.in_consumed : no_consumed, count, cs);
     });
 }
 

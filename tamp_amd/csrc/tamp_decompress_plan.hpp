@@ -69,6 +69,20 @@ static inline WaveGeometry wave_geometry(uint32_t bits_max, size_t n, uint32_t c
     return {waves, (uint32_t)std::min((n + waves - 1) / waves, (size_t)cu_count * 64)};
 }
 
+// TAMP_AMD_SPLIT_SPW = 16 | 32 | 64 (tuning / tests): streams per parse wavefront; 0 = the geometry's own choice.
+static inline uint32_t forced_split_spw() {
+    const char* e = getenv("TAMP_AMD_SPLIT_SPW");
+    const int v = e ? atoi(e) : 0;
+    return (v == 16 || v == 32 || v == 64) ? (uint32_t)v : 0u;
+}
+
+// Streams per parse wavefront for `count` streams (PARSE and its size-only build): enough waves for ~4 per SIMD before lanes are
+// filled (tools/dec_split_pmc.sh: the parse runs at one wave's latency)
+static inline size_t parse_want_waves(uint32_t cu_count) { return (size_t)cu_count * 16; }
+static inline uint32_t parse_spw(size_t count, size_t want_waves, uint32_t forced) {
+    return forced ? forced : (count / 16 < want_waves ? 16u : (count / 32 < want_waves ? 32u : 64u));
+}
+
 // Split decoder (tamp_decompress_split_kernel.hpp): records, meta word and lag list per stream of a SLICE, a flag byte per stream
 // of the batch.  The launcher halves `slice` when the device cannot supply slab_bytes(slice), and asks again.
 struct SplitGeometry {
@@ -82,10 +96,7 @@ struct SplitGeometry {
     size_t b_meta(size_t s) const { return s * 4; }
     size_t b_lag(size_t s) const { return s * kSplitMaxLag * 8; }
     size_t slab_bytes(size_t s) const { return b_recs(s) + b_meta(s) + b_lag(s) + n_streams + 64; }
-    // streams per parse wave for a slice of `count`: enough waves for ~4 per SIMD (tools/dec_split_pmc.sh: the parse runs at one wave's latency)
-    uint32_t spw(uint32_t count) const {
-        return spw_forced ? spw_forced : (count / 16 < want_waves ? 16u : (count / 32 < want_waves ? 32u : 64u));
-    }
+    uint32_t spw(uint32_t count) const { return parse_spw(count, want_waves, spw_forced); }  // for a slice of `count` streams
 };
 static inline SplitGeometry split_geometry(const DecodeCall& c, const DecodeScan& s, const DecodeDevice& d) {
     SplitGeometry g = {};
@@ -112,9 +123,19 @@ static inline SplitGeometry split_geometry(const DecodeCall& c, const DecodeScan
         g.wave_resolve = s.max_out_cap <= (uint32_t)(v < 0 ? 0 : (v > 4096 ? 4096 : v));
     }
     g.resolve_lds = split_resolve_lds(s.max_out_cap) * (g.wave_resolve ? 4u : 1u);
-    g.want_waves = (size_t)d.cu_count * 16;
-    if (const char* e = getenv("TAMP_AMD_SPLIT_SPW")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) g.spw_forced = (uint32_t)v; }
+    g.want_waves = parse_want_waves(d.cu_count);
+    g.spw_forced = forced_split_spw();
     return g;
+}
+
+// The size query (tamp_batch_decoded_size: the parse's size-only build): streams per wavefront by SplitGeometry::spw's rule --
+// enough waves for ~4 per SIMD before lanes are filled, TAMP_AMD_SPLIT_SPW forces 16 / 32 / 64 -- and ONE grid of 256-thread
+// workgroups, in strides beyond eight per CU -- about what is resident at 57 VGPRs (seven waves per SIMD) and 68 bytes of LDS per lane.
+struct SizeGeometry { uint32_t spw, grid, lds; };
+static inline SizeGeometry size_geometry(size_t n_streams, uint32_t cu_count) {
+    const uint32_t spw = parse_spw(n_streams, parse_want_waves(cu_count), forced_split_spw());
+    const size_t waves = (n_streams + spw - 1) / spw;
+    return {spw, (uint32_t)std::max<size_t>(1, std::min((waves + 3) / 4, (size_t)cu_count * 8)), split_size_lds(256)};
 }
 
 // Lane per stream, windows in LDS: one 64-lane workgroup per 64 streams, one padded row per lane; the bulk build (streams of 512

@@ -69,25 +69,28 @@ struct SplitArgs {
 // (+ 4 bytes behind the ring that mirror its first dword: a bit window is two aligned dwords from anywhere in the ring)
 constexpr uint32_t kParseRing = 64, kParseStage = 20, kParseLane = 64 + 4 + 4 * kParseStage + 8;  // 156 B: odd dword stride
 __host__ __device__ constexpr uint32_t split_parse_lds(uint32_t threads) { return 128u + threads * kParseLane; }
+// SIZE ONLY (kRecords = false, tamp_batch_decoded_size): the same token loop answering out_len / status / in_consumed and nothing
+// else.  What a token produces follows from its own bits and the out-of-bounds rule from offset + length <= W, so the answer needs
+// no window and none of what PARSE prepares for RESOLVE: no records and no stage, no lag list (cumlag, window_pos), no meta word,
+// no fallback flag -- a dictionary reset, any number of tokens and any output size are all the same to a counter.  Its lane keeps
+// the input ring and the mirror dword: 68 bytes, an odd dword stride as well.  sa.d.out_cap is the per-stream LIMIT and may be
+// null (no limit below 2^32 - 1), sa.d.dict_len alone stands for the dictionary, and one grid covers the batch in strides.
+constexpr uint32_t kSizeLane = kParseRing + 4;
+__host__ __device__ constexpr uint32_t split_size_lds(uint32_t threads) { return 128u + threads * kSizeLane; }
 
-__global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+// One stream by one lane (`live`: the lane has one; the others walk along with n = 0).  lut: the prefix-code LUT, inr: the lane's LDS.
+template <bool kRecords>
+__device__ __forceinline__ void parse_stream(const SplitArgs& sa, const uint8_t* const lut, uint8_t* const inr, const uint32_t k, const bool live) {
     const DecompressArgs& a = sa.d;
-    uint8_t* const lut = smem;  // prefix-code LUT: index = the 7 bits after the leading 1 -> (extra bits << 4) | symbol
-    build_prefix_lut(lut);
-    __syncthreads();
-    const uint32_t k = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * sa.spw + (threadIdx.x & (kWave - 1));
-    const bool live = (threadIdx.x & (kWave - 1)) < sa.spw && k < sa.count;
     const uint32_t s = sa.first + (live ? k : 0u);
     const uint8_t* const in = a.in + a.in_off[s];
     const uint32_t n = live ? a.in_len[s] : 0u;
-    const uint32_t cap = a.out_cap[s];
-    uint32_t* const rec = sa.recs + (size_t)(live ? k : 0u) * sa.tokcap;
-    uint32_t* const lag = sa.lag + (size_t)(live ? k : 0u) * kSplitMaxLag * 2;
-    uint8_t* const inr = smem + 128 + threadIdx.x * kParseLane;
-    uint32_t* const rb = reinterpret_cast<uint32_t*>(inr + kParseRing + 4);  // staged records
-    uint32_t nflushed = 0, nstage = 0;                                    // records in HBM / in the stage
-    auto flush16 = [&]() {  // the stage's first 16 records -> HBM as four 16-byte stores; the rest moves to the front
+    const uint32_t cap = (kRecords || a.out_cap) ? a.out_cap[s] : 0xFFFFFFFFu;
+    [[maybe_unused]] uint32_t* const rec = kRecords ? sa.recs + (size_t)(live ? k : 0u) * sa.tokcap : nullptr;
+    [[maybe_unused]] uint32_t* const lag = kRecords ? sa.lag + (size_t)(live ? k : 0u) * kSplitMaxLag * 2 : nullptr;
+    [[maybe_unused]] uint32_t* const rb = reinterpret_cast<uint32_t*>(inr + kParseRing + 4);  // staged records (kRecords)
+    [[maybe_unused]] uint32_t nflushed = 0, nstage = 0;                   // records in HBM / in the stage
+    [[maybe_unused]] auto flush16 = [&]() {  // the stage's first 16 records -> HBM as four 16-byte stores; the rest moves to the front
         if (nflushed + 16 <= sa.tokcap) {
 #pragma unroll
             for (uint32_t q = 0; q < 4; q++) st16(reinterpret_cast<uint8_t*>(rec + nflushed + 4 * q), ld16(reinterpret_cast<const uint8_t*>(rb + 4 * q)));
@@ -97,9 +100,11 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
         st16(reinterpret_cast<uint8_t*>(rb), ld16(reinterpret_cast<const uint8_t*>(rb + 16)));  // (the up to four records behind)
     };
     RefReader r{in, n};  // the reference's bit reader; r.ip = the consumed count
-    uint32_t op = 0, nlag = 0, cumlag = 0;  // (records so far = nflushed + nstage; bytes written = op - cumlag)
-    uint32_t wbits = 8, dict_sel = 2;
-    bool fallback = false;
+    uint32_t op = 0;
+    [[maybe_unused]] uint32_t nlag = 0, cumlag = 0;  // (records so far = nflushed + nstage; bytes written = op - cumlag)
+    uint32_t wbits = 8;
+    [[maybe_unused]] uint32_t dict_sel = 2;
+    [[maybe_unused]] bool fallback = false;
     int res = kInputExhausted;
 
     do {
@@ -119,14 +124,19 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
         const uint32_t W = 1u << wbits, mask = W - 1;
         dict_sel = hd.table;
         if (hd.custom) {
-            if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
+            if ((kRecords && !a.dict) || a.dict_len < W) { res = kInvalidConf; break; }
             dict_sel = 3;
         }
-        if (cap > sa.maxcap) fallback = true;  // (cannot happen: maxcap is the batch maximum)
+        if constexpr (kRecords) {
+            if (cap > sa.maxcap) fallback = true;  // (cannot happen: maxcap is the batch maximum)
+        }
 
         // one record; `written` = bytes of it that enter the window
         // (FAST: from the fast loop, where the stage is emptied every four tokens and cannot fill up, and every token has bytes)
         auto put_any = [&](uint32_t kind, uint32_t olen, uint32_t arg, uint32_t written, auto fast_loop) {
+            if constexpr (!kRecords) {
+                op += olen;  // (all a size needs of a token)
+            } else {
             if (!fast_loop.value && olen == 0) return;
             fallback = fallback | (nflushed + nstage >= sa.tokcap);
             rb[nstage++] = kind | (olen << 2) | (arg << 10);
@@ -142,12 +152,13 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
                 }
                 nlag++;
             }
+            }
         };
         auto put = [&](uint32_t kind, uint32_t olen, uint32_t arg, uint32_t written) {
             put_any(kind, olen, arg, written, std::integral_constant<bool, false>{});
         };
 
-        bool last_flush = false;
+        [[maybe_unused]] bool last_flush = false;
 
         // Two loops alternate.  FAST: straight-line decode from a 32-bit bit window read afresh per token (the token decode of the lane
         // decoders' bulk path, tamp_decompress_kernel.hpp, without its data movement), input through a 64-byte ring per lane
@@ -206,7 +217,9 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
             uint32_t T_mark = T;  // bit position at the reference's most recent refill
             while (__ballot(fast)) {
                 if (fast) {  // ---- I/O point: every fourth step, the same step for the whole wave ----
-                    if (nstage >= 16) flush16();
+                    if constexpr (kRecords) {
+                        if (nstage >= 16) flush16();
+                    }
                     if (cb_valid && fill + 16 - (T >> 3) <= kParseRing) {  // (nothing at or behind the read position is overwritten)
                         const uint32_t ro = (fill - sp0) & (kParseRing - 1);
                         st16(inr + ro, cb);
@@ -227,7 +240,8 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
                 uint32_t Tl = T0;  // bit position inside the token
                 bool ok = (T0 >> 3) + 4 <= fill;  // a dry ring (the end of the input, mostly): the exact loop takes over
                 uint32_t mark = T0;  // the reference refills at the top of every token (decompressor.c:357-365,431-445)
-                const uint32_t wp = (op - cumlag) & mask, room = cap - op;  // (window_pos = bytes written mod W on a fresh decoder)
+                [[maybe_unused]] const uint32_t wp = (op - cumlag) & mask;  // (window_pos = bytes written mod W on a fresh decoder)
+                const uint32_t room = cap - op;
                 // literal and plain match decoded side by side and selected (one branch instead of a tree of them: the
                 // values a branch tree assigns on different paths meet in register copies); a stale window of a dry ring
                 // decodes to garbage that `ok` discards
@@ -271,7 +285,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
                     const uint32_t nb_top = 8 * (((T0 + 24) >> 3) + 1) - T0;
                     mark = (!is_rle & (nb_top - (Tl - T0) - u < wbits)) ? Tl + u : mark;
                     tok = is_rle ? value + 2 : value + minp + 12;
-                    wl = is_rle ? min(min(tok, kRleWindowMax), W - wp) : min(tok, W - wp);
+                    if constexpr (kRecords) wl = is_rle ? min(min(tok, kRleWindowMax), W - wp) : min(tok, W - wp);
                     kind = is_rle ? (uint32_t)kRecFill : (uint32_t)kRecCopyExt;
                     arg = is_rle ? 0u : arg_x;
                     used = is_rle ? u : u + wbits;
@@ -306,7 +320,7 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
             if (t.kind == kExShort) break;
             if (t.kind == kExOob) { res = kOob; break; }
             if (t.kind == kExFlush) {
-                if (hd.dreset && last_flush) fallback = true;  // dictionary reset inside the stream: lane / wave decoders
+                if (kRecords && hd.dreset && last_flush) fallback = true;  // dictionary reset inside the stream: lane / wave decoders
                 last_flush = true;
                 continue;
             }
@@ -315,7 +329,8 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
                 put(kRecLit, 1, t.arg, 1);
                 continue;
             }
-            const uint32_t wp = (op - cumlag) & mask, room = cap - op;  // (window_pos = bytes written mod W on a fresh decoder)
+            [[maybe_unused]] const uint32_t wp = (op - cumlag) & mask;  // (window_pos = bytes written mod W on a fresh decoder)
+            const uint32_t room = cap - op;
             const uint32_t w = t.len <= room ? t.len : room;
             if (t.kind == kExRle) {  // decompressor.c:140-173
                 put(kRecFill, w, 0, min(w, min(min(t.len, kRleWindowMax), W - wp)));
@@ -331,16 +346,44 @@ __global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
     } while (false);
 
     if (!live) return;
-    for (uint32_t i = 0; i < nstage; i++)
-        if (nflushed + i < sa.tokcap) rec[nflushed + i] = rb[i];
-    const uint32_t ntok = nflushed + nstage;
-    if (ntok > 0xFFFFFu || op > 0xFFFFu) fallback = true;
+    [[maybe_unused]] const uint32_t ntok = nflushed + nstage;
+    if constexpr (kRecords) {
+        for (uint32_t i = 0; i < nstage; i++)
+            if (nflushed + i < sa.tokcap) rec[nflushed + i] = rb[i];
+        if (ntok > 0xFFFFFu || op > 0xFFFFu) fallback = true;
+    }
     a.out_len[s] = op;
     a.status[s] = (int8_t)res;
     if (a.in_consumed) a.in_consumed[s] = r.ip;
-    sa.meta[k] = (ntok & 0xFFFFFu) | ((wbits - 8) << 20) | (dict_sel << 23) | ((nlag < 63 ? nlag : 63u) << 25) | (fallback ? kMetaFallback : 0u);
-    sa.flagged[s] = fallback ? 1 : 0;
-    if (fallback) atomicAdd(sa.flagged_count, 1u);
+    if constexpr (kRecords) {
+        sa.meta[k] = (ntok & 0xFFFFFu) | ((wbits - 8) << 20) | (dict_sel << 23) | ((nlag < 63 ? nlag : 63u) << 25) | (fallback ? kMetaFallback : 0u);
+        sa.flagged[s] = fallback ? 1 : 0;
+        if (fallback) atomicAdd(sa.flagged_count, 1u);
+    }
+}
+
+// kRecords: PARSE of the split decoder, one launch per slice (sa.first, sa.count), a stream per lane and no more.
+// !kRecords: the size query over the whole batch; wavefront w takes streams [w * spw, (w + 1) * spw), then those of w + (waves of
+// the grid), ... -- the bound is the same for every lane of a wavefront, as the fast loop's wave-wide I/O points need it.
+template <bool kRecords>
+__global__ void __launch_bounds__(256) tamp_decode_parse_kernel(SplitArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t* const lut = smem;  // prefix-code LUT: index = the 7 bits after the leading 1 -> (extra bits << 4) | symbol
+    build_prefix_lut(lut);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    uint8_t* const inr = smem + 128 + threadIdx.x * (kRecords ? kParseLane : kSizeLane);
+    uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if constexpr (kRecords) {
+        const uint32_t k = wave * sa.spw + lane;
+        parse_stream<true>(sa, lut, inr, k, lane < sa.spw && k < sa.count);
+    } else {
+        const uint32_t stride = gridDim.x * (blockDim.x >> 6);
+        for (; (uint64_t)wave * sa.spw < sa.count; wave += stride) {
+            const uint64_t k = (uint64_t)wave * sa.spw + lane;
+            parse_stream<false>(sa, lut, inr, (uint32_t)k, lane < sa.spw && k < sa.count);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""Decoder timing, both variants (TAMP_AMD_DECODER=wave|lane), default max_window_bits.  Dev tool."""
+"""Decoder timing, both variants (TAMP_AMD_DECODER=wave|lane), default max_window_bits.  Dev tool.
+--decoded-size: only the size query and decompress_batch(out_cap=None) against an explicit capacity, on the bench's decode batch."""
 import sys, os
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
 import numpy as np, torch
@@ -23,6 +24,35 @@ def run(name, rows, **kw):
             ms.append(d.kernel_ms)
         ok = bool((d.out[:n*L].cpu().numpy() == rows.reshape(-1)).all())
         print(f"{name:26s} {mode}: {min(ms):7.3f} ms  {n*L/min(ms)/1e6:7.1f} GB/s out  ok={ok}", flush=True)
+def run_decoded_size(n=65536, L=4096, reps=12):
+    """--decoded-size: the bench's decode batch (n x 4 KiB synthetic text, window 10, extended, compressed on the device), device
+    memory, hipEvents around each call: decompress_batch(out_cap=L) against decompress_batch(out_cap=None) = size query, one
+    device-to-host sync for the slab total, decode into slabs of size + 1; and the size query alone."""
+    rows = wl.synth_text(n, L)
+    off, ln = wl.csr_for_fixed(n, L)
+    data = torch.from_numpy(rows.reshape(-1)).to(dev); off_t = torch.from_numpy(off.astype(np.int64)).to(dev); len_t = torch.from_numpy(ln.astype(np.int32)).to(dev)
+    r = tamp_amd.compress_batch(data, off_t, len_t, max_in_len=L)
+    def timed(fn):
+        ms = []
+        for it in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); d = fn(); e1.record(); e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        ms = sorted(ms[2:])  # (the first two: allocations)
+        return d, ms
+    d, ms = timed(lambda: tamp_amd.decompress_batch(r.out, r.out_off, r.out_len, out_cap=L))
+    ok = bool((d.out[:n*L].cpu().numpy() == rows.reshape(-1)).all())
+    print(f"decompress_batch(out_cap={L}):   min {ms[0]:7.3f}  median {ms[len(ms)//2]:7.3f}  max {ms[-1]:7.3f} ms  ok={ok}", flush=True)
+    d, ms = timed(lambda: tamp_amd.decompress_batch(r.out, r.out_off, r.out_len))
+    ok = bool((d.status == 2).all()) and bool((d.out_len == L).all()) and d.out.numel() == n * (L + 1)
+    ok = ok and bool((d.out.view(n, L + 1)[:, :L].reshape(-1).cpu().numpy() == rows.reshape(-1)).all())
+    print(f"decompress_batch(out_cap=None):   min {ms[0]:7.3f}  median {ms[len(ms)//2]:7.3f}  max {ms[-1]:7.3f} ms  ok={ok}", flush=True)
+    q, ms = timed(lambda: tamp_amd.decoded_size_batch(r.out, r.out_off, r.out_len, timing=True))
+    ok = bool((q.size == L).all()) and bool((q.status == 2).all())
+    print(f"decoded_size_batch:               min {ms[0]:7.3f}  median {ms[len(ms)//2]:7.3f}  max {ms[-1]:7.3f} ms  kernel {q.kernel_ms:.3f} ms  ok={ok}", flush=True)
+if '--decoded-size' in sys.argv:
+    run_decoded_size()
+    sys.exit(0)
 for nn in (16384,):
     run(f"text {nn}x4K w10 ext", wl.synth_text(nn, 4096))
 run("text 65536x4K w10 ext", wl.synth_text(65536, 4096))
