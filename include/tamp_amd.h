@@ -414,7 +414,7 @@ tamp_res tamp_amd_compress_segment(const TampAmdConf *conf, int emit_header, int
  * byte is taken, parse steps run only while the 16-byte ring is full, whole output bytes leave, nothing is drained) and
  * *carry receives what the reference's object still holds: a run or extended match that is still growing
  * (compressor.h rle_count, extended_match_count / _position), up to 7 pending output bits, up to 15 unparsed input
- * bytes.  The next piece continues from it (resume = 1).  finish = 1 ends the segment like tamp_amd_compress_segment
+ * bytes (16 when the last poll took none).  The next piece continues from it (resume = 1).  finish = 1 ends the segment like tamp_amd_compress_segment
  * (tamp_compressor_flush with write_token = flush_token) and clears the carry.  This is what bounded-memory writers are
  * built from: tamp_amd.Compressor.write() sends a piece whenever it has gathered enough and returns the bytes written,
  * as tamp/_c_compressor.pyx:74-118 does.  Not offered with conf->lazy_matching (the cached match of compressor.c:576-619
@@ -427,7 +427,8 @@ typedef struct TampAmdCarry {
     uint16_t ext_pos;    /* ... and its window position */
     uint8_t bit_count;   /* output bits not written yet: 0..7 on return; up to 31 accepted on entry (a reference object
                             sits on its last token's bits until the next poll, compressor.c:549-551) */
-    uint8_t tail_len;    /* 0..16 input bytes taken but not parsed yet (0..15 on return) */
+    uint8_t tail_len;    /* 0..16 input bytes taken but not parsed yet; 16 on return only when the call's last poll emitted
+                            a run / extended match that could not grow and so took no byte (compressor.c:449-466,505-509) */
     uint16_t reserved;
     uint32_t bits;       /* the pending bits, left aligned: first one in bit 31 */
     uint8_t tail[16];

@@ -51,7 +51,7 @@ class Compressor:
     ``write()`` gathers bytes and, whenever ``PIECE_MIN`` of them are waiting, hands them to the GPU as one PIECE
     (``tamp_amd_compress_piece``, finish = 0): the piece ends as a ``tamp_compressor_compress`` call ends -- no FLUSH token,
     no drain -- and the object keeps what the reference's object keeps (window, window position, a run / extended match
-    that is still growing, < 8 output bits, < 16 unparsed input bytes).  ``write()`` returns the bytes that reached ``f``
+    that is still growing, < 8 output bits, the unparsed bytes of the 16-byte ring).  ``write()`` returns the bytes that reached ``f``
     during the call, like the reference (tamp/_c_compressor.pyx:74-118), and memory stays bounded by ``PIECE_MAX``.
     ``flush()`` / ``reset_dictionary()`` / ``close()`` end the segment on the GPU (FLUSH tokens, ``dictionary_reset``,
     ``append`` are produced by the kernel, not emulated on the host).  With ``lazy_matching`` the cached match of

@@ -2580,6 +2580,17 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         put(kSlotRle, carry->rle_count, 1), put(kSlotExtCount, carry->ext_count, 1), put(kSlotNbits, carry->bit_count, 1);
         put(kSlotExtPos, carry->ext_pos, 2), put(kSlotBits, carry->bits, 4);
     }
+    if (!finish && resume && input_size == 0 && !seg.nlead) {
+        // tamp_compressor_compress without input: nothing is sunk and nothing polled, even on a full ring
+        // (compressor.c:700); the whole bytes among the pending bits leave, as at the end of every piece
+        const size_t whole = carry->bit_count >> 3;
+        if (output_size < whole) return TAMP_OUTPUT_FULL;
+        for (size_t k = 0; k < whole; k++) output[k] = (unsigned char)(carry->bits >> (24 - 8 * k));
+        carry->bits = whole ? carry->bits << (8 * whole) : carry->bits;
+        carry->bit_count &= 7;
+        if (output_written_size) *output_written_size = whole;
+        return TAMP_OK;
+    }
     const uint64_t zero = 0;
     const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
     if (finish && !flush_token && !resume && emit_header && !append_marker && prefix.empty() && !conf->extended &&
@@ -2635,8 +2646,11 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
                 carry->bit_count = (uint8_t)get(kSlotNbits, 1), carry->ext_pos = (uint16_t)get(kSlotExtPos, 2);
                 carry->bits = get(kSlotBits, 4);
                 const uint32_t parsed = get(kSlotParsed, 4);
-                const uint32_t left = ilen - parsed;  // < 16: the ring never stays full (compressor.c:704-718)
-                if (parsed > ilen || left > 15) return TAMP_ERROR;
+                // <= 16.  The ring is full when the call's last poll consumed nothing (a run or an extended match that
+                // could not grow emits its token without taking a byte, compressor.c:449-466,505-509): the reference's
+                // call ends there all the same (:700-720)
+                const uint32_t left = ilen - parsed;
+                if (parsed > ilen || left > 16) return TAMP_ERROR;
                 carry->tail_len = (uint8_t)left;
                 for (uint32_t j = 0; j < left; j++) {
                     const size_t at = (size_t)parsed + j;

@@ -1095,6 +1095,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         uint32_t gpos = 0;                         // bytes already flushed to HBM
         uint32_t e_p0 = bpos, e_pending = c_rle + c_ext, e_wp = wp0;  // epoch parameters
         bool need_match = true;
+        // kSegPartial: the poll on the ring that took the call's last byte has run.  The reference's call ends there
+        // (compressor.c:700-720) even when that poll consumed nothing -- a run or an extended match that could not grow
+        // emits its token and leaves the 16 bytes where they are -- so the ring may still be full.
+        bool piece_done = false;
         // Positions matched per epoch.  A token that breaks the speculation throws the rest of the block away, so
         // after such a break the next block is small (data with long runs / window-end truncations tends to break
         // again soon); a block that ends cleanly doubles it back up to the LDS capacity.
@@ -1854,8 +1858,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             const uint32_t cnt = min(m, lim);
                             if (cnt >= t0 || cnt < len || wpq + cnt > W) continue;
                             // (kSegPartial: the reference takes this match a 16-byte ring at a time; the poll that emits
-                            // the token must still have had a full ring)
-                            if (partial && leftq < cnt + kRing) continue;
+                            // the token must still have had a full ring, and not the call's last one: that poll may emit
+                            // without consuming a byte, and the call ends behind it -- the state machine's to decide)
+                            if (partial && leftq <= cnt + kRing) continue;
                             if (!dry) blen[q] = (uint8_t)(0x20u | len), xcnt[q] = (uint8_t)cnt;
                         }
                     }
@@ -2062,7 +2067,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         act = kActContinue;
                         break;
                     }
-                    const bool clean = wk.wr == wk.rd && wk.rle_count == 0 && wk.ext_count == 0;
+                    const bool clean = wk.wr == wk.rd && wk.rle_count == 0 && wk.ext_count == 0 && !piece_done;
                     // (lazy: a match cached before this epoch began has no table entry -- the state machine takes that step)
                     if (clean && wk.rd < nvalid && !(LAZY && wk.lazy_valid && wk.rd == e_pending)) {
                         // Plain steps: hop from block to block through the jump tables (one dependent LDS read per 64
@@ -2108,7 +2113,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         if (nhop) continue;
                     }
                     const uint32_t p = w_p0 + wk.rd;
-                    if (partial ? n - p >= kRing : p < n) {
+                    if (partial ? (!piece_done && n - p >= kRing) : p < n) {
                         const uint32_t pending = wk.rle_count + wk.ext_count;
                         int r = Walk::kStepRebase;
                         if (wk.rd <= cur_blk + pending) {
@@ -2148,6 +2153,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             act = kActDone;
                             break;
                         }
+                        if (partial && n - p == kRing) piece_done = true;  // (that was the call's last poll)
                     } else if (!partial && ext && wk.rle_count >= 1) {  // compressor.c:748-763
                         if (wk.rle_count == 1) {
                             const uint32_t c = wk.win((wk.wp() - 1) & mask);  // uniform (readfirstlane inside)
