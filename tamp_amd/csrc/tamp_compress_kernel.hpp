@@ -34,12 +34,6 @@ constexpr uint32_t kHashBits = 11;
 constexpr uint32_t kHashBuckets = 1u << kHashBits;
 constexpr uint32_t kRemBits = 16 - kHashBits;  // bigram bits not implied by the bucket number
 constexpr uint32_t kRunCap = 128;   // long runs listed per epoch (RUNS builds); further runs stay fully indexed
-#ifndef TAMP_LONG_RUN
-#define TAMP_LONG_RUN 8
-#endif
-#ifndef TAMP_DEFER_MIN
-#define TAMP_DEFER_MIN 24
-#endif
 // Extended format, default parse: a position INSIDE a short run of one byte (previous byte, this one and the next equal,
 // 2..6 of them ahead) whose bucket lists this many entries or more is not matched in the match phase: blen = kDeferred | slow.
 // The walk gets there only when a token happens to end inside the run -- rarely -- and asks Walk::best_on_demand then.
@@ -50,20 +44,15 @@ constexpr uint32_t kRunCap = 128;   // long runs listed per epoch (RUNS builds);
 // Same instructions, less waiting: synthetic text 6.66 -> 6.43 ms, prose 13.7 -> 13.2, Python sources 33.4 -> 32.7
 // (profiles/ab/r3_persistent_grid.log).
 constexpr int kPrioScan = 0, kPrioShort = 2, kPrioWalk = 3;
-constexpr uint32_t kDeferMin = TAMP_DEFER_MIN;
+constexpr uint32_t kDeferMin = 24;
 constexpr uint32_t kDeferred = 0x1Fu;  // length field of blen: no real first match is longer than the 16-byte ring
-constexpr uint32_t kLongRun = TAMP_LONG_RUN;    // a run of one byte this long is listed; its interior leaves the bigram index
+constexpr uint32_t kLongRun = 8;    // a run of one byte this long is listed; its interior leaves the bigram index
 // Round 6, late: EIGHT workgroups per CU for the W = 2^10 run-aware build.  The round's loop fits 64 VGPRs without a spill, and
 // 1,024 buckets (2 KB of cursors instead of 4; a foreign entry costs six instructions since the one-compare layout) with 128
 // explicit pieces per walk segment bring the workgroup to 19,616 B of LDS: synthetic 5.31 -> 4.97 ms, prose / markup / Python
-// sources -6 % each (profiles/ab/r6_experiments.log).  TAMP_SEVEN restores the round's earlier shape for A/B runs.
-#ifdef TAMP_SEVEN
-#define TAMP_WG_PER_CU 7
-constexpr uint32_t kSlowCap = 256, kHb1024 = kHashBits;
-#else
+// sources -6 % each (profiles/ab/r6_experiments.log).
 constexpr uint32_t kSlowCap = 128;             // explicit (non-derivable) token pieces per walk segment
 constexpr uint32_t kHb1024 = 10;               // bucket bits of the W = 2^10 run-aware build
-#endif
 
 struct CompressArgs {
     const uint8_t* in;
@@ -89,7 +78,7 @@ struct CompressArgs {
     uint32_t claim;            // LOOP builds: streams a workgroup takes per fetch from the counter
     unsigned long long* prof;  // optional: per-phase cycle sums (debug builds with -DTAMP_PROF)
     uint32_t cut_run;          // epoch cut: a run of this many aligned dwords of one byte ends the block (0 = off)
-    uint32_t dbg;              // debug builds only: bit mask of phases to skip (instruction-count experiments)
+    uint32_t dbg;              // -DTAMP_PROF builds only: sections to run twice, marks to stop at (see TAMP_DBG)
     // BLOCK builds (round 5: ONE long v1 stream spread over all workgroups, see the template parameter BLOCKM): the "streams"
     // the work counter hands out are the stream's blocks of `blk` positions
     uint32_t* blk_table;            // n_blocks x 16 words, pass 1 writes: entry offset e -> exit offset | bits of the chain << 4
@@ -185,8 +174,7 @@ __device__ __forceinline__ uint32_t entry_payload(uint32_t bytes4, uint32_t mix)
 }
 
 // Length (0..16) of the common prefix of ebuf[c..c+16) and the pattern dwords P[0..3].  Branch-free: 64 lanes in
-// lockstep would walk every branch of a staged compare anyway, so all 16 bytes are fetched (five aligned dwords,
-// funnel-shifted by the byte phase) and the first differing byte is found with two 64-bit count-trailing-zeros.
+// lockstep would walk every branch of a staged compare anyway, so all 16 bytes are fetched and compared at once.
 // v_ffbl_b32 as the hardware defines it: 0xFFFFFFFF for a zero operand (__builtin_ctz leaves that case undefined)
 __device__ __forceinline__ uint32_t ffbl_or_ones(uint32_t x) {
     uint32_t r;
@@ -194,22 +182,11 @@ __device__ __forceinline__ uint32_t ffbl_or_ones(uint32_t x) {
     return r;
 }
 __device__ __forceinline__ uint32_t prefix_len16(const uint8_t* ebuf, uint32_t c, const uint32_t (&P)[4]) {
-#ifndef TAMP_CMP_ALIGNED
     // Round 6: ONE hardware-unaligned ds_read_b128 (gfx950's LDS serves it) instead of five aligned dwords + four funnel shifts:
     // with the rest of the loop slimmed down the LDS pipe has the room (synthetic 5.64 -> 5.51 ms; in rounds 1-2 it was the bound:
     // +7 %).  profiles/ab/r6_experiments.log
     const LdsU128 v = *reinterpret_cast<const LdsU128*>(ebuf + c);
     const uint32_t x0 = v.x ^ P[0], x1 = v.y ^ P[1], x2 = v.z ^ P[2], x3 = v.w ^ P[3];
-#else
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(ebuf + (c & ~3u));
-    const uint32_t sh = c & 3u;
-    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-    const uint32_t x0 = __builtin_amdgcn_alignbyte(w1, w0, sh) ^ P[0];
-    const uint32_t x1 = __builtin_amdgcn_alignbyte(w2, w1, sh) ^ P[1];
-    const uint32_t x2 = __builtin_amdgcn_alignbyte(w3, w2, sh) ^ P[2];
-    const uint32_t x3 = __builtin_amdgcn_alignbyte(w4, w3, sh) ^ P[3];
-#endif
-#ifndef TAMP_CMP_STAGED
     // Round 6: no branch at all.  First set bit of each difference dword (all ones when it has none), the dword's bit offset
     // added with unsigned saturation (v_add_u32 ... clamp keeps "none" at all ones), the smallest of the four: 4 ffbl + 3 add +
     // min3 + min + shift = 10 instructions behind the xors where the staged form ran 6 + 13 in nearly every lock-step
@@ -220,11 +197,6 @@ __device__ __forceinline__ uint32_t prefix_len16(const uint8_t* ebuf, uint32_t c
     const uint32_t t2 = __builtin_elementwise_add_sat(ffbl_or_ones(x2), 64u);
     const uint32_t t3 = __builtin_elementwise_add_sat(ffbl_or_ones(x3), 96u);
     return min(min(min(t0, t1), min(t2, t3)) >> 3, 16u);
-#endif
-    const uint64_t lo = (uint64_t)x0 | ((uint64_t)x1 << 32), hi = (uint64_t)x2 | ((uint64_t)x3 << 32);
-    const uint32_t nlo = (uint32_t)__builtin_ctzll(lo | (1ull << 63)) >> 3;          // 0..7 (7 also when lo == 0)
-    const uint32_t nhi = 8u + ((uint32_t)__builtin_ctzll(hi | (1ull << 63)) >> 3);   // 8..15
-    return lo ? nlo : (hi ? nhi : 16u);
 }
 
 // Candidate whose bytes run past the newest window byte: the ring continues with the OLDEST window byte, i.e.
@@ -272,10 +244,8 @@ struct Walk {
     uint32_t rle_count, ext_count, ext_pos;
     bool ext_resolved;
     bool last_ext_direct = false;  // (instrumented builds)
-    uint32_t dbg_lag_rle = 0, dbg_lag_ext = 0, dbg_lag_rle_short = 0;  // (instrumented builds)
     uint32_t ntok, ns;
     bool partial = false;  // kSegPartial: every slow step is ONE poll with a full 16-byte ring (no whole-run / whole-match shortcuts)
-    uint32_t dbg = 0;      // (instrumented builds: 0x400000 / 0x800000 skip the two searches -- wrong bytes, the time they cost)
     // Cooperative searches (256-thread workgroups): the walk is ONE wavefront and the other three wait for it at a barrier;
     // a search is posted in the control words, every wavefront takes a quarter of the candidate rounds, and the four keys
     // are combined by the walking one (kCoop* below; two s_barrier per search).
@@ -365,9 +335,6 @@ struct Walk {
         put_exthuff(count - 2, 4);
         uint32_t w = min(min(count, kRleWindowMax), W - wp());
         const bool clean = (wr + count == rd) && (w == count);
-#ifdef TAMP_PROF
-        if (w < count) { dbg_lag_rle++; if (count < 24) dbg_lag_rle_short++; }
-#endif
         append(w, clean, [&](uint32_t) { return sym; });
     }
 
@@ -379,9 +346,6 @@ struct Walk {
         put(pos, wbits);
         uint32_t w = min(count, W - wp());
         const bool clean = (wr + count == rd) && (w == count);
-#ifdef TAMP_PROF
-        if (w < count) dbg_lag_ext++;
-#endif
         const uint32_t wr0 = wr, wp0 = wp();
         // Sources are read in the pre-token window; appended bytes land beyond it (the memmove
         // semantics of tamp_window_copy, common.c:58-86, for free).
@@ -469,9 +433,6 @@ struct Walk {
     // and min+131; ties -> lowest index" among the candidates >= the first match -- which one search with the whole
     // look-ahead finds directly.
     __device__ void ext_search(uint32_t avail, uint32_t& npos, uint32_t& ncnt) {
-#ifdef TAMP_PROF
-        if (dbg & 0x400000u) { npos = ext_pos, ncnt = ext_count; return; }
-#endif
         uint32_t key;
         if (coop) {
             if (lane == 0) {
@@ -558,13 +519,6 @@ struct Walk {
 
     __device__ void best_on_demand(uint32_t R) {
         uint32_t idx, len;
-#ifdef TAMP_PROF
-        if (dbg & 0x800000u) {
-            if (lane == 0) const_cast<uint8_t*>(blen)[rd] = 0x80u, const_cast<uint16_t*>(bidx)[rd] = 0;
-            __builtin_amdgcn_wave_barrier();
-            return;
-        }
-#endif
         uint32_t key;
         if (coop) {
             if (lane == 0) {
@@ -758,26 +712,15 @@ struct Walk {
 // (26.3 KB): a 4 KiB stream takes four epochs instead of three and the kernel is still 0.7 % faster on the synthetic text;
 // real text, whose workgroups spend a third of their time in the one-wavefront walk, gains 8-10 % from the seventh
 // (profiles/ab/r4_seven_workgroups_per_cu.log).  Eight (64 VGPRs) spills 92 registers.
-#ifndef TAMP_WG_PER_CU
-#define TAMP_WG_PER_CU 8
-#endif
-#ifndef TAMP_LEAN_PER_CU  // (workgroups of 256 threads per CU the lean / lazy builds' registers are budgeted for: 6 -> 80 VGPRs, 5 -> 96)
-#define TAMP_LEAN_PER_CU 6
-#endif
-#ifndef TAMP_LAZY_PER_CU
-#define TAMP_LAZY_PER_CU 5
-#endif
+// Round 6: eight without a spill (see kSlowCap).  The lean / lazy builds' registers are budgeted for six (80 VGPRs) / five (96).
+// (one constant each for __launch_bounds__ below and the launcher's register_cap)
+constexpr uint32_t kWgPerCu = 8, kLeanPerCu = 6, kLazyPerCu = 5;
 // Block size after a break (a token that wrote fewer bytes than it consumed threw the rest of the block away): with the
 // 1,536-position blocks of rounds 1-3 halving it (512 at least) was worth 15 % on real text; with 1,024-position blocks
 // at seven workgroups per CU the full block is the better guess again (prose 11.55 -> 10.9 ms, Python sources 28.3 -> 26.8,
-// profiles/ab/r4_seven_workgroups_per_cu.log).  Tuning builds override.
-#ifndef TAMP_ALIGN_MIN  // shortest block the ring-end alignment may produce (tuning builds override; 65536 = off)
-#define TAMP_ALIGN_MIN 256
-#endif
-#ifndef TAMP_BRK_SHIFT
-#define TAMP_BRK_SHIFT 0
-#define TAMP_BRK_MIN 512
-#endif
+// profiles/ab/r4_seven_workgroups_per_cu.log).
+constexpr uint32_t kBrkShift = 0, kBrkMin = 512;
+constexpr uint32_t kAlignMin = 256;  // shortest block the ring-end alignment may produce (profiles/ab/r4_ring_end_alignment_and_knobs.log)
 enum : uint32_t { kActDone = 1, kActRebase = 2, kActContinue = 3 };
 enum : uint8_t { kSegResume = 1, kSegSave = 2, kSegFlushToken = 4, kSegPartial = 8 };
 // Per-stream state slot of the segment calls: the window in ring order, then kSegStateExtra bytes with these fields at
@@ -801,28 +744,43 @@ constexpr uint32_t kSegStateExtra = 24;
 // ctl words
 enum : uint32_t { cAct = 0, cShift = 1, cP0 = 2, cPending = 3, cWp = 4, cNtok = 5, cExcess = 6, cBlk = 7, cWave = 8, cNruns = 12, cQuad = 13, cNext = 14, cCut = 15, cCutThr = 16 };
 
-// Instrumented builds (-DTAMP_PROF): a section whose effect does not change when it runs twice can be repeated per bit of
-// CompressArgs::dbg -- 0x100 bucket loop, 0x200 wrap-zone resolution, 0x10000 load, 0x20000 index, 0x40000 jump tables,
-// 0x80000 emit -- and the difference of two `rocprofv3 --pmc SQ_INSTS_VALU` runs is that section's exact instruction
-// count over all epochs of all streams (tools/phase_valu5.sh; round 4: profiles/r4_phase_valu.csv).
+// Instrumented builds (-DTAMP_PROF; tools/prof_phases.py, tools/solo_phases.py, tools/phase_valu5.sh).  Everything they add to
+// the kernel goes through these macros, and in a product build every one of them expands to nothing (TAMP_DBG: to `false`):
+//   TAMP_PROF_ONLY(...)  statements and declarations of the instrumented build alone: the cycle sums pt[0..15] that
+//                        tamp_amd_prof_read hands out, the fine timers of the match phase;
+//   TAMP_PROF_MARK(i)    a barrier, the cycles since the previous mark into pt[i], and with bit 8 << i of CompressArgs::dbg
+//                        the end of the kernel (truncation experiments: instruction counts up to this mark);
+//   TAMP_FINE(v)         the cycles since the previous TAMP_FINE into v;
+//   TAMP_DBG(bit)        that bit of CompressArgs::dbg;
+//   TAMP_REPEAT(bit)     in front of a statement: with the bit set it runs twice, and TAMP_SECOND tells the second time.
+// A section whose effect does not change when it runs twice is repeated per bit of CompressArgs::dbg -- 0x100 bucket loop,
+// 0x1000000 its 16-byte compares, 0x200 wrap-zone resolution, 0x10000 load, 0x20000 index, 0x40000 jump tables, 0x80000 emit,
+// 0x2000000 second pass, 0x4000000 settled tokens (a dry run in front), 0x8000000 the walk, 0x18000000 the walk without its
+// listing -- and the difference of two `rocprofv3 --pmc SQ_INSTS_VALU` runs is that section's exact instruction count over all
+// epochs of all streams (tools/phase_valu5.sh; round 4: profiles/r4_phase_valu.csv).  None of these bits changes the output;
+// tools/prof_phases.py checks that.  (The index, the walk and emit declare what later phases read and repeat with a goto
+// under a plain #ifdef.)
 #ifdef TAMP_PROF
-#define TAMP_REPEAT(bit) for (uint32_t _rep = 0; _rep < ((a.dbg & (bit)) ? 2u : 1u); _rep++)
-#else
-#define TAMP_REPEAT(bit)
-#endif
-#ifdef TAMP_PROF
+#define TAMP_PROF_ONLY(...) __VA_ARGS__
+#define TAMP_DBG(bit) ((a.dbg & (bit)) != 0)
+#define TAMP_REPEAT(bit) for (uint32_t _rep = 0; _rep < (TAMP_DBG(bit) ? 2u : 1u); _rep++)
+#define TAMP_SECOND (_rep != 0)
+#define TAMP_FINE(v) do { unsigned long long _n = __builtin_readcyclecounter(); v += _n - fc; fc = _n; } while (0)
 #define TAMP_PROF_MARK(i)                                     \
     do {                                                      \
         __syncthreads();                                      \
         unsigned long long _n = __builtin_readcyclecounter(); \
         pt[i] += _n - pc;                                     \
         pc = _n;                                              \
-        if (a.dbg & (8u << (i))) return; /* truncation experiments: instruction counts up to this mark */ \
+        if (TAMP_DBG(8u << (i))) return;                      \
     } while (0)
 #else
-#define TAMP_PROF_MARK(i) \
-    do {                  \
-    } while (0)
+#define TAMP_PROF_ONLY(...)
+#define TAMP_DBG(bit) false
+#define TAMP_REPEAT(bit)
+#define TAMP_SECOND false
+#define TAMP_FINE(v) do { } while (0)
+#define TAMP_PROF_MARK(i) do { } while (0)
 #endif
 
 // ---------------------------------------------------------------------------------------------
@@ -869,23 +827,17 @@ __device__ __forceinline__ T* as_global(T* p) {
 // pre-pass; in the v1 build everything RLE / extended) is not compiled in.  The launcher's predicate (fixed_build_for in
 // tamp_capi.hip) is the only way in; every other call keeps the generic build.
 enum : uint32_t { kFixNone = 0, kFixExt = 1, kFixV1 = 2 };
-#ifndef TAMP_FIX_STEPS
-#define TAMP_FIX_STEPS 3
-#endif
 constexpr uint32_t kFixWbits = 10, kFixBlk = 1024, kFixLbits = 8, kFixThreads = 256;
 constexpr CompressLds kLdsFixed(1u << kFixWbits, kFixBlk, true, false, true, kHb1024);
-#ifndef TAMP_SEVEN
 static_assert(kLdsFixed.total == 19616 && kLdsFixed.tokcap == 1376 && kLdsFixed.obuf_words == 516,
               "the fixed builds' LDS layout is the generic build's for window 2^10, block 1,024, 1,024 buckets");
-#endif
 // (the body is this one function for every build; the two kernels behind it -- tamp_compress_kernel for the generic builds,
 // tamp_compress_fixed::compress_kernel for the fixed ones -- only name its instantiations)
 template <bool PACKED, bool LAZY, bool RUNS, uint32_t WSCAN, uint32_t HB, bool LOOP, bool BLOCKM, uint32_t FIX>
 __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     static_assert(!BLOCKM || (LOOP && PACKED && !LAZY), "block mode: a persistent build of the default parse");
-    // FX: constant geometry; FXS: no segment / piece machinery; FXF: constant format (the three steps the build was made in;
-    // TAMP_FIX_STEPS = 1 / 2 rebuilds the intermediate ones for the static comparison in profiles/fixed_build_static.txt)
-    constexpr bool FX = FIX != kFixNone, FXS = FX && TAMP_FIX_STEPS >= 2, FXF = FX && TAMP_FIX_STEPS >= 3;
+    // FX: constant geometry, no segment / piece machinery, constant format (made in these three steps: profiles/fixed_build_static.txt)
+    constexpr bool FX = FIX != kFixNone;
     static_assert(!FX || (PACKED && !LAZY && RUNS && WSCAN == (1u << kFixWbits) && HB == kHb1024 && LOOP && !BLOCKM),
                   "fixed geometry: the run-aware persistent build of the 2^10 window");
     // HB: bucket bits of the bigram index (2,048 buckets; 512 for the short-message build, whose blocks hold a few hundred
@@ -999,9 +951,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         uint32_t tid = tid_k;
         int lane = tid & (kWave - 1);
         uint32_t wave = tid >> 6;
-        const uint32_t wbits = a_wbits, lbits = FXS ? kFixLbits : a.lbits;
+        const uint32_t wbits = a_wbits, lbits = FX ? kFixLbits : a.lbits;
         const uint32_t minp = (uint32_t)min_pattern_size((int)a_wbits, (int)lbits);
-        const bool ext = FXF ? FIX == kFixExt : a.extended != 0;
+        const bool ext = FX ? FIX == kFixExt : a.extended != 0;
         const uint32_t maxp = ext ? minp + 11 + kExtExtraMax : minp + 13;  // compressor.c:12-19
 #ifdef TAMP_POISON_LDS
         // test builds: every stream starts on LDS full of a pattern that changes from launch to launch and stream to stream, so
@@ -1039,8 +991,8 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         }
 
         // (fixed builds: whole streams only -- no state slot, no segment flags)
-        const uint32_t seg_flags = FXS ? 0u : a.seg_flags;
-        uint8_t* const st_io = (!FXS && a.state) ? a.state + (size_t)s * (W + kSegStateExtra) : nullptr;
+        const uint32_t seg_flags = FX ? 0u : a.seg_flags;
+        uint8_t* const st_io = (!FX && a.state) ? a.state + (size_t)s * (W + kSegStateExtra) : nullptr;
         const bool partial = (seg_flags & kSegPartial) != 0;
         uint32_t wp0 = 0;
         if constexpr (BLOCKM) {
@@ -1053,7 +1005,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             // window <- saved state (ring order) rotated so that the oldest byte comes first
             wp0 = (uint32_t)st_io[W + kSlotWindowPos] | ((uint32_t)st_io[W + kSlotWindowPos + 1] << 8);
             for (uint32_t k = tid; k < W; k += nt) ebuf[k] = st_io[(wp0 + k) & mask];
-        } else if (FXS || (reinterpret_cast<uintptr_t>(a.dict) & 3) == 0) {
+        } else if (FX || (reinterpret_cast<uintptr_t>(a.dict) & 3) == 0) {
             // window <- dictionary (custom, or the seeded default prepared by the host shim)
             for (uint32_t k = tid * 4; k < W; k += nt * 4)
                 *reinterpret_cast<uint32_t*>(ebuf + k) = *reinterpret_cast<const uint32_t*>(a.dict + k);
@@ -1071,7 +1023,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         }
         // bit buffer: leading bytes (header, compressor.c:236-241; FLUSH + pad when appending, :227-235) or the carried
         // bits, rest zero
-        const uint32_t nlead = FXS ? 1u : a.nlead;  // (fixed builds: the header byte)
+        const uint32_t nlead = FX ? 1u : a.nlead;  // (fixed builds: the header byte)
         const uint32_t word0 = (BLOCKM && s != 0) ? 0u : (nlead ? (uint32_t)a.lead << 16 : (c_nbits ? c_bits & (0xFFFFFFFFu << (32 - c_nbits)) : 0u));
         for (uint32_t k = tid; k < L.obuf_words; k += nt) obuf[k] = k == 0 ? __builtin_bswap32(word0) : 0;
 
@@ -1083,11 +1035,8 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         wk.rle_count = c_rle, wk.ext_count = c_ext, wk.ext_pos = c_extpos, wk.rd = c_rle + c_ext, wk.partial = partial;
         wk.ext_resolved = false, wk.ntok = 0, wk.ns = 0, wk.lane = lane;
         wk.ctlw = (Walk::CtlWord*)ctl, wk.coop = nt == 256;
-#ifdef TAMP_PROF
-        wk.dbg = a.dbg;
-#endif
         wk.lazy = lazy, wk.lazy_valid = false, wk.lazy_idx = 0, wk.lazy_len = 0, wk.blen2 = blen2, wk.bidx2 = bidx2;
-        if (tid_k == 0) ctl[cCutThr] = (FXF && FIX == kFixV1) ? 0u : a.cut_run;  // (read after the load phase's barrier)
+        if (tid_k == 0) ctl[cCutThr] = (FIX == kFixV1) ? 0u : a.cut_run;  // (read after the load phase's barrier)
         uint32_t w_p0 = bpos;  // wave 0: input position of ebuf[W]
 
         // workgroup-uniform output state
@@ -1103,10 +1052,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         // after such a break the next block is small (data with long runs / window-end truncations tends to break
         // again soon); a block that ends cleanly doubles it back up to the LDS capacity.
         uint32_t cur_blk = a_blk;
-#ifdef TAMP_PROF
-        unsigned long long pt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        unsigned long long pc = __builtin_readcyclecounter();
-#endif
+        TAMP_PROF_ONLY(unsigned long long pt[16] = {}, pc = __builtin_readcyclecounter();)
         for (;;) {
             // (opaque re-definition: thread-indexed LDS addresses are recomputed per epoch instead of being hoisted out of
             // the stream loop, where they would sit in -- and spill from -- registers across every phase)
@@ -1126,7 +1072,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             // cost only, like the cut below.
             if (ext && !LAZY) {
                 const uint32_t k0 = W - e_wp;
-                if (k0 >= TAMP_ALIGN_MIN && k0 < nvalid) nvalid = k0;
+                if (k0 >= kAlignMin && k0 < nvalid) nvalid = k0;
             }
             const uint32_t nplan = nvalid;  // (what the block would be without a cut)
             if (!need_match) nvalid = Walk::uni(ctl[cCut]);
@@ -1140,37 +1086,22 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 TAMP_REPEAT(0x10000u) {
                     const uint8_t* src = in + e_p0;
                     const uint32_t nfill = align_up(nload + 20, 4);  // zero tail: stray look-ahead reads are defined
-#ifndef TAMP_LOAD_BYTES
-                    {
-                        // whole dwords wherever the block starts in the stream (global loads need no alignment on gfx950): behind a
-                        // lag the block starts at an odd position three times out of four, and a byte at a time this was six
-                        // dependent round trips to HBM per epoch -- 156 us of the 1.1 ms the slowest chunk of the stand-in takes alone
-                        const uint32_t nw = nload >> 2;
-                        for (uint32_t k = tid; k < nw; k += nt) {
-                            uint32_t v;
-                            __builtin_memcpy(&v, src + 4 * k, 4);
-                            reinterpret_cast<uint32_t*>(ebuf + W)[k] = v;
-                        }
-                        for (uint32_t k = (nw << 2) + tid; k < nfill; k += nt) ebuf[W + k] = k < nload ? src[k] : 0;
+                    // whole dwords wherever the block starts in the stream (global loads need no alignment on gfx950): behind a
+                    // lag the block starts at an odd position three times out of four, and a byte at a time this was six
+                    // dependent round trips to HBM per epoch -- 156 us of the 1.1 ms the slowest chunk of the stand-in takes alone
+                    const uint32_t nw = nload >> 2;
+                    for (uint32_t k = tid; k < nw; k += nt) {
+                        uint32_t v;
+                        __builtin_memcpy(&v, src + 4 * k, 4);
+                        reinterpret_cast<uint32_t*>(ebuf + W)[k] = v;
                     }
-#else
-                    if ((reinterpret_cast<uintptr_t>(src) & 3) == 0) {
-                        const uint32_t nw = nload >> 2;
-                        for (uint32_t k = tid; k < nw; k += nt)
-                            reinterpret_cast<uint32_t*>(ebuf + W)[k] = reinterpret_cast<const uint32_t*>(src)[k];
-                        for (uint32_t k = (nw << 2) + tid; k < nfill; k += nt) ebuf[W + k] = k < nload ? src[k] : 0;
-                    } else {
-                        for (uint32_t k = tid; k < nfill; k += nt) ebuf[W + k] = k < nload ? src[k] : 0;
-                    }
-#endif
+                    for (uint32_t k = (nw << 2) + tid; k < nfill; k += nt) ebuf[W + k] = k < nload ? src[k] : 0;
                 }
                 for (uint32_t k = tid; k < kBuckets / 2; k += nt) cntw[k] = 0;
                 if (tid == 0) ctl[cCut] = 0xFFFFFFFFu;
                 __syncthreads();
                 TAMP_PROF_MARK(0);
-#ifdef TAMP_PROF
-                pt[12] += 1, pt[13] += nvalid;  // epochs, positions matched
-#endif
+                TAMP_PROF_ONLY(pt[12] += 1, pt[13] += nvalid;)  // epochs, positions matched
 
                 bool have_tables = false;
                 if constexpr (BLOCKM) {
@@ -1190,13 +1121,13 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 if (!have_tables) {
                 // ---------------- index: counting sort of buffer positions by bigram ----------------
 #ifdef TAMP_PROF
-                uint32_t index_reps = (a.dbg & 0x20000u) ? 2u : 1u;
+                uint32_t index_reps = TAMP_DBG(0x20000u) ? 2u : 1u;
             index_again:
 #endif
                 asm volatile("" : "+v"(tid));
                 lane = (int)(tid & (kWave - 1)), wave = tid >> 6, wk.lane = lane;  // (re-derived: see above)
                 const uint32_t NE0 = nvalid ? W + nvalid : 0;  // positions 0..NE0-1 (every query's own bigram included)
-                const uint32_t cut_run = (FXF && FIX == kFixV1) ? 0u : Walk::uni(ctl[cCutThr]);  // (per stream: it adapts, see the walk's re-base; v1: no RLE token, no cut)
+                const uint32_t cut_run = (FIX == kFixV1) ? 0u : Walk::uni(ctl[cCutThr]);  // (per stream: it adapts, see the walk's re-base; v1: no RLE token, no cut)
                 for (uint32_t c4 = tid * 4; c4 < NE0; c4 += nt * 4) {
                     const uint32_t d0 = *reinterpret_cast<const uint32_t*>(ebuf + c4);
                     const uint32_t d1 = *reinterpret_cast<const uint32_t*>(ebuf + c4 + 4);
@@ -1367,16 +1298,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 asm volatile("" : "+v"(tid));
                 lane = (int)(tid & (kWave - 1)), wave = tid >> 6, wk.lane = lane;  // (re-derived: see above)
                 const uint32_t nq = nvalid - e_pending;
-#ifdef TAMP_PROF
-                unsigned long long f0 = 0, f1 = 0, f2 = 0, f3 = 0, niter = 0;
-#define TAMP_FINE(v) do { unsigned long long _n = __builtin_readcyclecounter(); v += _n - fc; fc = _n; } while (0)
-                unsigned long long fc = __builtin_readcyclecounter();
-#else
-#define TAMP_FINE(v) do { } while (0)
-#endif
-#ifdef TAMP_PROF
-                if (!(a.dbg & 1))
-#endif
+                TAMP_PROF_ONLY(unsigned long long f0 = 0, f1 = 0, f2 = 0, f3 = 0, niter = 0, fc = __builtin_readcyclecounter();)
                 for (uint32_t j = tid; j < nq; j += nt) {
                     const uint32_t q = sorted[j];
                     const uint32_t leftq = n - (e_p0 + q);
@@ -1401,17 +1323,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     // Skipping the scan there removes the worst buckets.
                     const uint32_t rep = (P[0] & 0xFFu) * 0x01010101u;
                     bool in_run = false;
-#ifndef TAMP_SETUP_R5
                     // (round 6: the byte in front of the pattern is read ONCE -- it is also the newest window byte of the wrap-zone
                     // test and the byte the slow flag looks at -- and the run arithmetic runs only where the pattern starts with
                     // TWO of it: with one, r <= 1 < the shortest pattern and nothing below applies, and some lane of nearly every
                     // wavefront had one)
                     const uint32_t prevb = ebuf[W + q - 1];
                     if (ext && !lazy && (P[0] & 0xFFFFu) == prevb * 0x0101u) {
-#else
-                    const uint32_t prevb = ebuf[W + q - 1];
-                    if (ext && !lazy && prevb == (P[0] & 0xFFu)) {
-#endif
                         // r = leading ring bytes equal to the previous byte, looked at up to 7
                         const uint32_t x0 = P[0] ^ rep, x1 = (P[1] ^ rep) & 0x00FFFFFFu;
                         const uint32_t r = x0 ? (uint32_t)__builtin_ctz(x0) >> 3 : (x1 ? 4 + ((uint32_t)__builtin_ctz(x1) >> 3) : 7u);
@@ -1420,11 +1337,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         // (the marker travels in `key`: length field kDeferred, slow by the bytes' own rule below)
                         if (!in_run && r >= 2 && (uint32_t)bidx[q] - (uint32_t)qstart[q] >= kDeferMin) in_run = true, key = kDeferred << 16;
                     }
-#ifdef TAMP_PROF
-                    if (R >= minp && !in_run && !(a.dbg & 2)) {
-#else
                     if (R >= minp && !in_run) {
-#endif
                         const uint32_t cap_len = R < maxp ? R : maxp;
                         const uint32_t pk = entry_payload<kRem>(P[0], mix16<HB>(P[0] & 0xFFFFu));
                         const uint32_t chi = q + W - 2;  // newest candidate served by the index
@@ -1439,16 +1352,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             const uint32_t nb = ~(q + e_wp);  // W - window index of the candidate at distance d = ((nb - d) & (W - 1)) + 1
                             const uint32_t* pe = ent + sl;
                             const uint32_t* const pe_end = ent + s_hi;
-#ifdef TAMP_PROF
-                            // instruction-count experiments: run the (idempotent) loop twice, count the difference
-                            uint32_t n16_first = 0;
-                            for (uint32_t rep = 0; rep < ((a.dbg & 0x100u) ? 2u : 1u); rep++) {
-                            if (rep) { n16_first = n16; pe = ent + sl; e_next = *pe; }
-#endif
+                            TAMP_REPEAT(0x100u) {  // (the loop is idempotent but for the count of its 16-byte hits)
+                            TAMP_PROF_ONLY(if (TAMP_SECOND) n16 = 0, pe = ent + sl, e_next = *pe;)
                             while (pe < pe_end) {
-#ifdef TAMP_PROF
-                                niter++;
-#endif
+                                TAMP_PROF_ONLY(niter++;)
                                 const uint32_t e = e_next;
                                 pe++;
                                 e_next = *pe;  // one past the range at the end: harmless
@@ -1457,17 +1364,13 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                     const uint32_t d = y >> kLB;  // Ws - d bytes before the candidate reaches the newest byte
                                     const uint32_t low = y & ((1u << kLB) - 1);
                                     uint32_t len = (low & 0xFFu) ? 2u : 3u;
-#ifdef TAMP_PROF
-                                    if (low == 0 && !(a.dbg & 0x8000u)) {
+                                    if (low == 0) {  // the next two bytes agree too (the entry's bits of the second)
                                         len = prefix_len16(ebuf, q + d, P);
-                                        if (a.dbg & 0x1000000u) {  // (the compare once more -- same result -- for its exact count)
+                                        if (TAMP_DBG(0x1000000u)) {  // (the compare once more -- same result -- for its exact count)
                                             asm volatile("" ::: "memory");
                                             len = max(len, prefix_len16(ebuf, q + d, P));
                                         }
-                                    } else if (low == 0) len = 4u;
-#else
-                                    if (low == 0) len = prefix_len16(ebuf, q + d, P);  // the next two bytes agree too (the entry's bits of the second)
-#endif
+                                    }
                                     // (the wrap zone and the key: as in the generic loop below.  One test: the compare reaches the
                                     // newest byte iff d + len >= Ws; a 16-byte hit exactly 16 bytes in front of it -- exact as it
                                     // stands -- goes the same way and comes out of the wrapped compare with the same 16)
@@ -1480,23 +1383,14 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                     }
                                 }
                             }
-#ifdef TAMP_PROF
-                            if (rep) n16 = n16_first;
-                            }
-#endif
+                            }  // TAMP_REPEAT
                         } else if constexpr (!LAZY) {
                             const uint32_t Ws = WSCAN ? WSCAN : W;  // (see the template parameter)
-#ifdef TAMP_PROF
-                            // instruction-count experiments: run the (idempotent) loop twice, count the difference
-                            const uint32_t sl0 = sl;
-                            uint32_t n16_first = 0;
-                            for (uint32_t rep = 0; rep < ((a.dbg & 0x100u) ? 2u : 1u); rep++) {
-                            if (rep) { n16_first = n16; sl = sl0; e_next = PACKED ? ent[sl] : (uint32_t)ent16[sl]; }
-#endif
+                            TAMP_PROF_ONLY(const uint32_t sl0 = sl;)
+                            TAMP_REPEAT(0x100u) {  // (as above)
+                            TAMP_PROF_ONLY(if (TAMP_SECOND) n16 = 0, sl = sl0, e_next = PACKED ? ent[sl] : (uint32_t)ent16[sl];)
                             while (sl < s_hi) {
-#ifdef TAMP_PROF
-                                niter++;
-#endif
+                                TAMP_PROF_ONLY(niter++;)
                                 const uint32_t e = e_next;
                                 sl++;
                                 e_next = PACKED ? ent[sl] : (uint32_t)ent16[sl];  // one past the range at the end: harmless
@@ -1510,19 +1404,13 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                 if (d <= Ws - 2 && (x & ((1u << kRem) - 1)) == 0) {
                                     const uint32_t t = Ws - d;  // bytes before the candidate reaches the newest byte
                                     uint32_t len = (x & (0xFFu << kRem)) ? 2u : 3u;
-#ifdef TAMP_PROF
-                                    // (0x8000: instruction-count experiment -- the loop without its 16-byte compares, i.e.
-                                    // what any scheme that takes the deep compares elsewhere leaves behind; results are wrong)
-                                    if ((x >> kRem) == 0 && !(a.dbg & 0x8000u)) {
+                                    if ((x >> kRem) == 0) {  // next two bytes agree too
                                         len = prefix_len16(ebuf, c, P);
-                                        if (a.dbg & 0x1000000u) {  // (round 5: the compare once more -- same result -- for its exact count)
+                                        if (TAMP_DBG(0x1000000u)) {  // (as above)
                                             asm volatile("" ::: "memory");
                                             len = max(len, prefix_len16(ebuf, c, P));
                                         }
-                                    } else if ((x >> kRem) == 0) len = 4u;
-#else
-                                    if ((x >> kRem) == 0) len = prefix_len16(ebuf, c, P);  // next two bytes agree too
-#endif
+                                    }
                                     // The candidate's first t bytes lie in front of the newest window byte, where the
                                     // buffer IS the ring: a common prefix shorter than t is exact whatever follows.  Only
                                     // a candidate that agrees all the way to the newest byte (periodic input: rare) goes
@@ -1541,15 +1429,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                     }
                                 }
                             }
-#ifdef TAMP_PROF
-                            if (rep) n16 = n16_first;
-                            }
-#endif
+                            }  // TAMP_REPEAT
                         } else
                         while (sl < s_hi) {
-#ifdef TAMP_PROF
-                            niter++;
-#endif
+                            TAMP_PROF_ONLY(niter++;)
                             const uint32_t e = e_next;
                             sl++;
                             e_next = PACKED ? ent[sl] : (uint32_t)ent16[sl];  // one past the range at the end: harmless
@@ -1590,11 +1473,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         // not in the index at all: test its first byte here.
                         // (a match there needs the oldest byte to equal the pattern's second byte as well)
                         if (prevb == (P[0] & 0xFFu) && ebuf[q] == ((P[0] >> 8) & 0xFFu)) wrapmask |= 2u;
-#ifdef TAMP_PROF
-                        const uint32_t wrapmask0 = wrapmask;
-                        for (uint32_t rep = 0; rep < ((a.dbg & 0x200u) ? 2u : 1u); rep++) {
-                        wrapmask = wrapmask0;
-#endif
+                        TAMP_PROF_ONLY(const uint32_t wrapmask0 = wrapmask;)
+                        TAMP_REPEAT(0x200u) {
+                        TAMP_PROF_ONLY(wrapmask = wrapmask0;)
                         while (wrapmask) {
                             const uint32_t t = (uint32_t)__builtin_ctz(wrapmask);
                             wrapmask &= wrapmask - 1;
@@ -1607,9 +1488,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             const uint32_t k = (len << 16) | (W - i);
                             if (len >= 2 && k > key) key = k;
                         }
-#ifdef TAMP_PROF
-                        }
-#endif
+                        }  // TAMP_REPEAT
                         if constexpr (RUNS) {
                             // Extended matches (compressor.c:437-468, 636-644): a first match longer than min+11 starts
                             // a continuation that ends at "the candidate at or above the first match's index with the
@@ -1676,12 +1555,8 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     // are compared like any index entry and merged into the result of the first pass (each thread
                     // revisits its own queries).  Interior positions within 15 bytes of the newest window byte run into
                     // the oldest ones like their indexed neighbours (prefix_len_wrapped16).
-#ifdef TAMP_PROF
-                    if (nruns && !(a.dbg & 0x4000u))  // (0x4000: instruction-count experiments without the second pass)
-                    TAMP_REPEAT(0x2000000u) {         // (0x2000000: twice -- the second time it finds its own results -- for its count)
-#else
-                    if (nruns) {
-#endif
+                    if (nruns)
+                    TAMP_REPEAT(0x2000000u) {  // (the second time it finds its own results)
                         for (uint32_t j = tid; j < nq; j += nt) {
                             const uint32_t q = sorted[j];
                             const uint32_t b01 = lds_u32_unaligned(ebuf, W + q);
@@ -1792,9 +1667,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 __syncthreads();
                 __builtin_amdgcn_s_setprio(kPrioShort);
                 TAMP_FINE(f3);
-#ifdef TAMP_PROF
-                pt[6] += f0, pt[7] += f1, pt[8] += f2, pt[10] += niter;
-#endif
+                TAMP_PROF_ONLY(pt[6] += f0, pt[7] += f1, pt[8] += f2, pt[10] += niter;)
                 if constexpr (RUNS && PACKED) {
                     // Tokens of the extended format that need no state machine.  A position is flagged slow when
                     // poll_extended_handling does more than fall through there (compressor.c:437-525).  Two of those
@@ -1812,13 +1685,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     // input and matches with rivals stay with the state machine.
                     if (ext && (kSlowCap * 8 + a_blk) <= (HB == 9 ? kHashBuckets : kBuckets) * 2) {
                         const uint32_t max_ext = minp + 11 + kExtExtraMax;
-#ifdef TAMP_PROF
-                        // (0x4000000: a dry run in front -- everything but the stores -- for the pass's instruction count)
-                        for (uint32_t dry = (a.dbg & 0x4000000u) ? 1u : 0u; dry != 0xFFFFFFFFu; dry--)
-#else
-                        constexpr uint32_t dry = 0;
-#endif
+                        TAMP_REPEAT(0x4000000u)  // (the pass changes what it reads: the first of the two is a dry run, everything but the stores)
                         for (uint32_t q = e_pending + tid; q < nvalid; q += nt) {
+                            const bool dry = TAMP_DBG(0x4000000u) && !TAMP_SECOND;
                             const uint32_t sv = blen[q];
                             if (!(sv & 0x80u)) continue;
                             const uint32_t len = sv & 0x1Fu;
@@ -2004,7 +1873,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 // to LDS is the same both times, positions matched on demand are marked "deferred" again in between;
                 // with 0x10000000 the second run skips the token listing: the difference is the listing's count)
                 const Walk wk_save = wk;
-                uint32_t walk_reps = (a.dbg & 0x8000000u) ? 2u : 1u, ndef = 0;
+                uint32_t walk_reps = TAMP_DBG(0x8000000u) ? 2u : 1u, ndef = 0;
                 bool walk_second = false;
             walk_again:
 #endif
@@ -2013,24 +1882,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 uint32_t act = 0, excess_tok = 0xFFFFFFFFu;
                 uint32_t nqueued = 0;  // blocks whose tokens are still to be listed
                 uint32_t segv = 0;     // lane k: first position | first token slot << 16 of queued block k
-#ifdef TAMP_PROF
-                unsigned long long dbg_list = 0, dbg_hop = 0, dbg_calls = 0;
-#endif
                 auto list_queued = [&]() {
-#ifdef TAMP_PROF
-                    const unsigned long long lt0 = __builtin_readcyclecounter();
-                    dbg_calls++;
-#endif
                     __builtin_amdgcn_wave_barrier();
-#ifdef TAMP_PROF
-                    if ((a.dbg & 0x10000000u) && walk_second) { nqueued = 0; return; }
-                    // (0x200000: the listing without its chain of dependent reads -- valid positions, wrong tokens: the
-                    // time the chain costs)
-                    if ((a.dbg & 0x200000u) && (uint32_t)lane < nqueued) {
-                        uint32_t pp = segv & 0xFFFFu, slot = segv >> 16;
-                        for (uint32_t cleft = LAZY ? (uint32_t)count8[pp] : jc32[pp] >> 16; cleft; cleft--) toklist[slot++] = (uint16_t)pp++;
-                    } else
-#endif
+                    TAMP_PROF_ONLY(if (TAMP_DBG(0x10000000u) && walk_second) { nqueued = 0; return; })
                     if ((uint32_t)lane < nqueued) {
                         uint32_t pp = segv & 0xFFFFu;
                         uint32_t slot = segv >> 16;
@@ -2049,9 +1903,6 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     }
                     __builtin_amdgcn_wave_barrier();
                     nqueued = 0;
-#ifdef TAMP_PROF
-                    dbg_list += __builtin_readcyclecounter() - lt0;
-#endif
                 };
                 for (;;) {
                     // (round 5: the walk's scalars are changed inside `if (wave == 0)` -- a divergent branch to the compiler --
@@ -2077,9 +1928,6 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         // later, many blocks at a time (list_queued): a listing pass costs as many dependent LDS
                         // round trips as the fullest block has tokens, however few blocks it serves.
                         uint32_t total = 0, nhop = 0;
-#ifdef TAMP_PROF
-                        const unsigned long long ht0 = __builtin_readcyclecounter();
-#endif
                         while (pos < nv && nqueued < 64 && wk.ntok + total + 64 <= L.tokcap) {
                             uint32_t j, cpos;
                             if constexpr (LAZY) {
@@ -2095,9 +1943,6 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             total += cpos;
                             pos = j;
                         }
-#ifdef TAMP_PROF
-                        dbg_hop += __builtin_readcyclecounter() - ht0;
-#endif
                         if (nqueued > 64 - 34) list_queued();  // room for the next chain of hops (at most blk / 64 = 32 blocks)
                         wk.ntok += total;
                         if constexpr (LAZY) {
@@ -2119,30 +1964,20 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         if (wk.rd <= cur_blk + pending) {
                             // (kSegPartial: exactly one poll -- the ring holds 16 bytes and nothing is known beyond it)
                             const uint32_t leftp = partial ? kRing : n - p;
-#ifdef TAMP_PROF
-                            const unsigned long long t0 = __builtin_readcyclecounter();
-                            const uint32_t ec0 = wk.ext_count;
-#endif
+                            TAMP_PROF_ONLY(const unsigned long long t0 = __builtin_readcyclecounter(); const uint32_t ec0 = wk.ext_count;)
                             if constexpr (!LAZY) {
                                 if (ext && wk.wr == wk.rd && wk.rd < nvalid && (Walk::uni(blen[wk.rd]) & 0x1Fu) == kDeferred) {
-#ifdef TAMP_PROF
-                                    if constexpr (RUNS) {
-                                        if (lane == 0 && ndef < kRunCap) runs[ndef] = wk.rd;  // (the run list is dead during the walk)
-                                        ndef++;
-                                    }
-#endif
+                                    // (noted for the walk's repeat, which marks it deferred again; the run list is dead during the walk)
+                                    TAMP_PROF_ONLY(if constexpr (RUNS) { if (lane == 0 && ndef < kRunCap) runs[ndef] = wk.rd; ndef++; })
                                     wk.best_on_demand(leftp < kRing ? leftp : kRing);  // (a position the match phase left out)
                                 }
                             }
                             r = wk.template step<RUNS>(leftp < kRing ? leftp : kRing, leftp);
-#ifdef TAMP_PROF
-                            pt[11] += 1;
-                            if (ec0) pt[5] += __builtin_readcyclecounter() - t0;  // time in extended-match continuation steps
-                            else pt[9] += __builtin_readcyclecounter() - t0;      // other slow steps
-                            if (ec0) pt[14] += 1;                         // extended matches that went through the search
-                            if (!ec0 && wk.ntok >= 3 && wk.ns >= 3 && wk.last_ext_direct) pt[15] += 1;  // ... settled without one
-                            wk.last_ext_direct = false;
-#endif
+                            // slow steps; time in, and number of, extended-match continuation steps (the match went through the search);
+                            // time in other slow steps; extended matches settled without a search
+                            TAMP_PROF_ONLY(const unsigned long long dt = __builtin_readcyclecounter() - t0; pt[11] += 1;)
+                            TAMP_PROF_ONLY(if (ec0) pt[5] += dt, pt[14] += 1; else pt[9] += dt;)
+                            TAMP_PROF_ONLY(if (!ec0 && wk.ntok >= 3 && wk.ns >= 3 && wk.last_ext_direct) pt[15] += 1; wk.last_ext_direct = false;)
                         }
                         if (r == Walk::kStepRebase) {
                             act = kActRebase;
@@ -2195,7 +2030,6 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     walk_second = true;
                     goto walk_again;
                 }
-                if (a.dbg & 0x2000u) wk.dbg_lag_rle += (uint32_t)dbg_hop, wk.dbg_lag_ext += (uint32_t)dbg_list, wk.dbg_lag_rle_short += (uint32_t)dbg_calls;
 #endif
                 if (act == kActRebase) {
                     // drop the lag, keep the bytes a pending RLE run / extended match has consumed but not
@@ -2206,7 +2040,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     // (measured on 16,384 x 4 KiB: quarter / 256 prose 12.75, Python 5.72 GB/s; halve / 512: 13.64, 5.76; halve / 1024: 13.15,
                     // 5.42; never shrink: 11.62, 4.81)
                     const bool broke = wk.wr + pending != wk.rd;  // bytes were consumed that will never be written
-                    uint32_t nb2 = broke ? max(cur_blk >> TAMP_BRK_SHIFT, (uint32_t)TAMP_BRK_MIN) : min(cur_blk << 1, a_blk);
+                    uint32_t nb2 = broke ? max(cur_blk >> kBrkShift, kBrkMin) : min(cur_blk << 1, a_blk);
                     nb2 = min(nb2, a_blk);
                     if (lane == 0) ctl[cBlk] = nb2;
                     // The cut was a guess: when the walk arrives at the end of a shortened block without a lag, a match
@@ -2249,7 +2083,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
 
             // ---------------- emit: token list -> bits (all threads) ----------------
 #ifdef TAMP_PROF
-            uint32_t emit_reps = (a.dbg & 0x80000u) ? 2u : 1u;
+            uint32_t emit_reps = TAMP_DBG(0x80000u) ? 2u : 1u;
         emit_again:
 #endif
             asm volatile("" : "+v"(tid));
@@ -2314,7 +2148,6 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             const uint32_t limit = min((uint32_t)ctl[cExcess], ntok);
             const bool excess = ctl[cExcess] != 0xFFFFFFFFu;
             uint32_t mybits = 0;
-#ifndef TAMP_EMIT_TWICE
             // (round 6: a thread's tokens -- three for a 1,024-position block of text -- are put together once and kept in registers for the
             // scatter below instead of being put together a second time there: synthetic 4.92 -> 4.86 ms, real text -0.3 .. -1 %)
             const bool tok_cached = K <= 4;
@@ -2327,7 +2160,6 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     mybits += cn[j];
                 }
             } else
-#endif
             for (uint32_t k = k0; k < k1 && k < limit; k++) {
                 uint32_t v, nb;
                 token(k, v, nb);
@@ -2343,13 +2175,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 segbits += wt;
             }
             {  // MSb-first scatter of this thread's contiguous run of tokens
-#ifndef TAMP_EMIT_ACC
                 // Every token is ORed straight to its place: at most 32 bits (kMaxTokenBits), so at most two words.  The bit
                 // buffer is all zero where bits land -- it is zeroed (1) whole at the stream's start, (2) over the scan starts
                 // the match phase kept in words 4.. of it, behind that phase, and (3) over every word the previous segment
                 // touched, behind its flush (word 0 keeps the carried bits) -- and nothing else stores into it.  Same words
-                // as the accumulator form (TAMP_EMIT_ACC, for A/B builds), which pushed the tokens through 64 bits and
-                // spilled whole words in a loop (profiles/emit_place_static.txt, profiles/emit_place_ab.txt).
+                // as the earlier accumulator form, which pushed the tokens through 64 bits and spilled whole words in a
+                // loop (profiles/emit_place_static.txt, profiles/emit_place_ab.txt).
                 uint32_t bp = o;
                 auto put_bits = [&](uint32_t v, uint32_t nb) {
                     uint32_t wi, w_hi, w_lo;
@@ -2358,54 +2189,16 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     if (w_lo) atomicOr(&obuf[wi + 1], w_lo);
                     bp += nb;
                 };
-#ifndef TAMP_EMIT_TWICE
                 if (tok_cached) {
 #pragma unroll
                     for (uint32_t j = 0; j < 4; j++)
                         if (cn[j]) put_bits(cv[j], cn[j]);
                 } else
-#endif
                 for (uint32_t k = k0; k < k1 && k < limit; k++) {
                     uint32_t v, nb;
                     token(k, v, nb);
                     put_bits(v, nb);
                 }
-#else
-                uint32_t wi = o >> 5, ph = o & 31, fill = 0;
-                uint64_t acc = 0;
-                auto put_bits = [&](uint32_t v, uint32_t nb) {
-                    acc = (acc << nb) | v;
-                    fill += nb;
-                    while (ph + fill >= 32) {
-                        const uint32_t take = 32 - ph;
-                        uint32_t w = (uint32_t)(acc >> (fill - take));
-                        if (take < 32) w &= (1u << take) - 1;
-                        if (ph == 0)
-                            obuf[wi] = __builtin_bswap32(w);
-                        else
-                            atomicOr(&obuf[wi], __builtin_bswap32(w));
-                        fill -= take;
-                        ph = 0;
-                        wi++;
-                    }
-                };
-#ifndef TAMP_EMIT_TWICE
-                if (tok_cached) {
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; j++)
-                        if (cn[j]) put_bits(cv[j], cn[j]);
-                } else
-#endif
-                for (uint32_t k = k0; k < k1 && k < limit; k++) {
-                    uint32_t v, nb;
-                    token(k, v, nb);
-                    put_bits(v, nb);
-                }
-                if (fill) {
-                    const uint32_t w = ((uint32_t)acc & ((1u << fill) - 1)) << (32 - ph - fill);
-                    atomicOr(&obuf[wi], __builtin_bswap32(w));
-                }
-#endif
             }
             __syncthreads();
             uint32_t tot = carry + segbits;  // bits now in obuf
@@ -2536,12 +2329,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             }
             __syncthreads();
         }
-#ifdef TAMP_PROF
-        if (tid == 0 && a.prof) {
-            if (a.dbg & 0x3000u) pt[6] = wk.dbg_lag_rle, pt[7] = wk.dbg_lag_ext, pt[8] = wk.dbg_lag_rle_short;  // lag causes instead of the fine timers
-            for (int i = 0; i < 16; i++) atomicAdd(&a.prof[i], pt[i]);
-        }
-#endif
+        TAMP_PROF_ONLY(if (tid == 0 && a.prof) for (int i = 0; i < 16; i++) atomicAdd(&a.prof[i], pt[i]);)
         if constexpr (LOOP) {
             // the next stream of this workgroup's current claim, or the first of the next claim of a.claim consecutive
             // streams (1 for long streams; short ones are claimed sixteen at a time: fewer fetches from the one counter).
@@ -2565,7 +2353,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
 }
 
 template <bool PACKED, bool LAZY, bool RUNS = false, uint32_t WSCAN = 0, uint32_t HB = kHashBits, bool LOOP = false, bool BLOCKM = false>
-__global__ void __launch_bounds__(256, LAZY ? TAMP_LAZY_PER_CU : (RUNS ? TAMP_WG_PER_CU : TAMP_LEAN_PER_CU)) tamp_compress_kernel(CompressArgs a_k) {
+__global__ void __launch_bounds__(256, LAZY ? kLazyPerCu : (RUNS ? kWgPerCu : kLeanPerCu)) tamp_compress_kernel(CompressArgs a_k) {
     compress_streams<PACKED, LAZY, RUNS, WSCAN, HB, LOOP, BLOCKM, kFixNone>(a_k);
 }
 
@@ -2574,7 +2362,7 @@ namespace tamp_compress_fixed {
 // (a name of their own, with "tamp_compress" and "compress_kernel" in it: that is how bench.py and the tools pick the
 // compress launches out of a profile)
 template <uint32_t FIX>
-__global__ void __launch_bounds__(256, TAMP_WG_PER_CU) compress_kernel(CompressArgs a_k) {
+__global__ void __launch_bounds__(256, kWgPerCu) compress_kernel(CompressArgs a_k) {
     static_assert(FIX == kFixExt || FIX == kFixV1, "the generic builds are tamp_compress_kernel's");
     compress_streams<true, false, true, 1u << kFixWbits, kHb1024, true, false, FIX>(a_k);
 }

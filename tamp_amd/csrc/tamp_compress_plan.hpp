@@ -63,7 +63,7 @@ struct CompressPlan {  // (in the order plan_compress decides them)
 
 // Workgroups per CU: what the registers allow (8 for the run-aware builds, 6 lean, 5 lazy), and the estimate for a layout of `lds`
 // bytes: 160 KiB per CU, handed out in coarse granules (26,960 B per workgroup measured as five per CU, 25,424 B as six).
-static inline uint32_t register_cap(bool lazy, bool runlist) { return lazy ? TAMP_LAZY_PER_CU : (runlist ? TAMP_WG_PER_CU : TAMP_LEAN_PER_CU); }
+static inline uint32_t register_cap(bool lazy, bool runlist) { return lazy ? kLazyPerCu : (runlist ? kWgPerCu : kLeanPerCu); }
 static inline uint32_t workgroups_per_cu(uint32_t lds, uint32_t reg_cap) { return std::min(160u * 1024u / align_up(lds, 2048u), reg_cap); }
 
 // Positions matched per epoch (a multiple of 64: the walk chases 64 positions per register; of 256 when it can be: the index is
@@ -100,9 +100,6 @@ static inline uint32_t compress_threads(uint32_t blk, bool long_streams, bool bl
 // The fixed-geometry builds: kFixedExt / kFixedV1 when the call is EXACTLY what they were compiled for; for all
 // else, and with TAMP_AMD_FIXED_BUILD=0 (`fixed_env`: A/B runs, parity tests), the generic build plan_compress has put into `p`.
 static inline CompressBuild fixed_build_for(const CompressCall& c, const CompressPlan& p, const char* fixed_env) {
-#ifdef TAMP_SEVEN
-    return p.build;  // (the seven-per-CU tuning shape has another LDS layout)
-#endif
     const TampAmdConf* conf = c.conf;
     const bool fits = !c.block_mode && !(fixed_env && atoi(fixed_env) == 0) && conf->window == kFixWbits && conf->literal == kFixLbits &&
                       !p.lazy && p.runlist && p.blk == kFixBlk && p.threads == kFixThreads && !c.has_state && c.seg_flags == 0 &&
@@ -110,7 +107,7 @@ static inline CompressBuild fixed_build_for(const CompressCall& c, const Compres
     return !fits ? p.build : (conf->extended ? CompressBuild::kFixedExt : CompressBuild::kFixedV1);
 }
 
-// The launch decisions for `c`.  The planning overrides are read here and nowhere else (TAMP_SEVEN: at compile time, further down).
+// The launch decisions for `c`.  The planning overrides are read here and nowhere else.
 static inline CompressPlan plan_compress(const CompressCall& c) {
     using B = CompressBuild;
     const char *const blk_env = getenv("TAMP_AMD_BLK"), *const runs_env = getenv("TAMP_AMD_RUNS");

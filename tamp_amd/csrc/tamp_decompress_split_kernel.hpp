@@ -514,9 +514,6 @@ __global__ void __launch_bounds__(256) tamp_decode_resolve_kernel(SplitArgs sa) 
         }
     }
     sync();
-#if defined(TAMP_SPLIT_STOP) && TAMP_SPLIT_STOP == 1
-    return;
-#endif
     for (uint32_t r0 = 0, carry = 0; r0 < n_out; r0 += BPT * nt) {  // 4,096 bytes per round (NT = 256, BPT = 16)
         const uint32_t p0 = r0 + BPT * tid;
         uint32_t h[BPT >= 2 ? BPT / 2 : 1];  // this thread's marks
@@ -599,9 +596,6 @@ __global__ void __launch_bounds__(256) tamp_decode_resolve_kernel(SplitArgs sa) 
         sync();
     }
 
-#if defined(TAMP_SPLIT_STOP) && TAMP_SPLIT_STOP == 2
-    return;
-#endif
     // ---- pointer jumping: every round halves the chains; a byte is final when it points at itself.  Each thread keeps
     // working on its own unresolved bytes (one mask per 4,096 bytes), so a round costs what is still unresolved.  The bytes
     // of a thread are spread out (byte t, t + 256, t + 512, ... of each 4,096): sixteen neighbours are all literals or all
@@ -657,9 +651,6 @@ __global__ void __launch_bounds__(256) tamp_decode_resolve_kernel(SplitArgs sa) 
         if (!sync_or((int)(um0 | um1 | um2 | um3))) break;
     }
 
-#if defined(TAMP_SPLIT_STOP) && TAMP_SPLIT_STOP == 3
-    return;
-#endif
     // ---- out: aligned dwords, byte head / tail ----
     uint8_t* const out = a.out + a.out_off[s];
     const uint32_t head = min((uint32_t)((4 - (reinterpret_cast<uintptr_t>(out) & 3)) & 3), n_out);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static histogram of one kernel's ISA by source-line range and VALU issue class.
 
-Input: the `.s` of a `hipcc --save-temps -gline-tables-only` build (tools/isa_dump.sh) and the kernel's mangled name.
+Input: the `.s` of a `hipcc --save-temps -gline-tables-only` build of tamp_capi.hip (the Makefile's HIPFLAGS) and the kernel's mangled name.
 Every instruction is attributed to the last `.loc` in front of it (file 'tamp_compress_kernel.hpp' only; inlined
 callees keep their own lines) and classed by what profiles/r5_valu_issue_probe.txt measured on gfx950:
 
