@@ -638,8 +638,13 @@ struct LongFront {
     std::vector<uint32_t> ntok, outb;  // per chunk
     bool dbg;              // TAMP_AMD_LONGDEC_DEBUG
 };
+// A stream behind the length gate that goes to the exact decoders after all: -> 1, and under TAMP_AMD_LONGDEC_DEBUG one line that says why.
+static int long_declined(bool dbg, const char* who, const char* why) {
+    if (dbg) fprintf(stderr, "[tamp_amd long %s] declined: %s\n", who, why);
+    return 1;
+}
 // -> 1 when the stream is not one for this path (or anything is off: the exact decoders take it), TAMP_OK with `f` filled in and
-// timing begun, an error code otherwise.  `who` names the caller in the debug line.  d_out_off / d_cap may be null.
+// timing begun, an error code otherwise.  `who` names the caller in the debug lines.  d_out_off / d_cap may be null.
 int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, bool has_dict, size_t dict_len,
                       uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                       const uint64_t* d_out_off, const uint32_t* d_cap, bool with_records, const char* who, hipStream_t st, LongFront& f) {
@@ -650,6 +655,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     // (the chunk kernels count bits in 32-bit registers: (i + 1) * kLongChunkBits wraps for the last chunk of the top 512 bytes of
     // the accepted range -- those streams stay with the exact decoder)
     if (n < gate.min_len || n > kMaxDecodeIn - 512) return 1;
+    const bool dbg = f.dbg = getenv("TAMP_AMD_LONGDEC_DEBUG") != nullptr;
     HIP_OK(hipMemcpyAsync(&in_off, d_in_off, 8, hipMemcpyDeviceToHost, st));
     if (d_out_off) HIP_OK(hipMemcpyAsync(&out_off, d_out_off, 8, hipMemcpyDeviceToHost, st));
     if (d_cap) HIP_OK(hipMemcpyAsync(&cap, d_cap, 4, hipMemcpyDeviceToHost, st));
@@ -660,10 +666,10 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     const StreamHeader hd = decode_header(hdr[0]);
     const uint32_t hs = 1 + (hdr[0] & 1), wbits = hd.wbits, lbits = hd.lbits;
     const bool extended = hd.extended;
-    if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return 1;
-    if (extended && !gate.extended) return 1;  // (tests: the exact decoder)
+    if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return long_declined(dbg, who, "header");
+    if (extended && !gate.extended) return long_declined(dbg, who, "extended off");  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
-    if (hd.custom && (!has_dict || dict_len < W)) return 1;
+    if (hd.custom && (!has_dict || dict_len < W)) return long_declined(dbg, who, "dictionary");
     f.n = n, f.cap = cap, f.out_off = out_off, f.in = in, f.hd = hd, f.hs = hs;
     f.dict0 = hd.custom ? d_dict : ctx->seed_dicts + ((size_t)hd.table << 15);
 
@@ -678,7 +684,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
         const size_t max_tok = (size_t)(total_bits / (1 + lbits)) + 4096;
         const size_t b_groups = ((size_t)(max_tok / 256 + N + 64) * (16 + sizeof(LongGroup) + 4) + 255) & ~(size_t)255;
         const size_t bytes = with_records ? b_tab + max_tok * 4 + b_groups + 4 * (size_t)(1u << 15) + 4096 : b_tab;
-        if (rec.long_tab.need(bytes) != hipSuccess) return 1;
+        if (rec.long_tab.need(bytes) != hipSuccess) return long_declined(dbg, who, "scratch");
     }
     uint8_t* const tab = static_cast<uint8_t*>(rec.long_tab.p);
     uint32_t* const g0 = reinterpret_cast<uint32_t*>(tab);
@@ -729,9 +735,8 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
         std::swap(cur, nxt);
         settled = changed == 0;
     }
-    f.dbg = getenv("TAMP_AMD_LONGDEC_DEBUG") != nullptr;
-    if (f.dbg) fprintf(stderr, "[tamp_amd long %s] %u bytes, %u chunks, %d sync rounds, settled %d\n", who, n, N, rounds, (int)settled);
-    if (!settled) { timing_end(st); return 1; }
+    if (dbg) fprintf(stderr, "[tamp_amd long %s] %u bytes, %u chunks, %d sync rounds, settled %d\n", who, n, N, rounds, (int)settled);
+    if (!settled) { timing_end(st); return long_declined(dbg, who, "not settled"); }
     la.g = cur, la.g_next = nullptr, la.write = 0;
     HIP_OK(hipMemsetAsync(flags, 0, 8, st));
     hipLaunchKernelGGL(tamp_long_parse_kernel, dim3(lg), dim3(64), 0, st, la);
@@ -741,7 +746,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     HIP_OK(hipMemcpyAsync(f.outb.data(), d_outb, (size_t)N * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(fl, flags, 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if (fl[1]) { timing_end(st); return 1; }  // an out-of-bounds offset: the exact decoder reports where
+    if (fl[1]) { timing_end(st); return long_declined(dbg, who, "offset out of window"); }  // an out-of-bounds offset: the exact decoder reports where
     return TAMP_OK;
 }
 
@@ -770,17 +775,20 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
     // of lagging tokens in it (tamp_long_wp_kernel).
     std::vector<uint32_t> chunk_lag;  // per chunk: cumulative lag behind it, lagging tokens in it
     uint32_t* d_lag = nullptr;        // the lag lists
+    uint64_t dbg_entries = 0;         // (debug line: list entries, window_pos blocks, most lagging tokens in one chunk)
+    size_t dbg_wpblocks = 0;
+    uint32_t dbg_maxlag = 0;
     if (extended) {
         std::vector<uint32_t> nspec(N), specbase(N);
         HIP_OK(hipMemcpyAsync(nspec.data(), d_nspec, (size_t)N * 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         uint64_t n_entries = 0;
         for (uint32_t i = 0; i < N; i++) specbase[i] = (uint32_t)n_entries, n_entries += (uint64_t)nspec[i] + 1;
-        if (n_entries > 0xFFFFFFF0ull) { timing_end(st); return 1; }
+        if (n_entries > 0xFFFFFFF0ull) { timing_end(st); return long_declined(dbg_long, "decode", "list too long"); }
         const size_t n_wpblocks = (size_t)((n_entries + kLongWpBlock - 1) / kLongWpBlock);
         // gap, token, bytes written per list entry; behind them the lag lists (at most one entry per listed token) and the
         // window_pos tables of the list's blocks (tamp_long_wp_kernel: 8 bytes per block and start value, 20 per block)
-        if (rec.long_lags.need((size_t)n_entries * (3 + 2) * 4 + n_wpblocks * ((size_t)W * 8 + 20) + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return 1; }
+        if (rec.long_lags.need((size_t)n_entries * (3 + 2) * 4 + n_wpblocks * ((size_t)W * 8 + 20) + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return long_declined(dbg_long, "decode", "scratch"); }
         uint32_t* const d_spec = static_cast<uint32_t*>(rec.long_lags.p);
         la.specbase = d_specbase, la.spec_gap = d_spec, la.spec_kl = d_spec + n_entries, la.spec_written = d_spec + 2 * n_entries;
         d_lag = d_spec + 3 * n_entries;
@@ -803,8 +811,10 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         chunk_lag.resize(2 * (size_t)N);
         HIP_OK(hipMemcpyAsync(chunk_lag.data(), d_chunk_lag, 2 * (size_t)N * 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));  // (also: specbase goes out of scope)
+        dbg_entries = n_entries, dbg_wpblocks = n_wpblocks;
+        for (uint32_t i = 0; i < N; i++) dbg_maxlag = std::max(dbg_maxlag, chunk_lag[2 * (size_t)i + 1]);
         for (uint32_t i = 0; i < N; i++)
-            if (chunk_lag[2 * (size_t)i + 1] > kLongLagCap) { timing_end(st); return 1; }  // (more lagging tokens in one chunk than a group lists)
+            if (chunk_lag[2 * (size_t)i + 1] > kLongLagCap) { timing_end(st); return long_declined(dbg_long, "decode", "lags per chunk"); }  // (more lagging tokens in one chunk than a group lists)
     }
     // groups of whole chunks: at most kSplitMaxOut output bytes, 2^20 - 1 records and kLongLagCap lagging tokens each
     const bool chain = extended || gate.chain;
@@ -832,7 +842,8 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
     }
     // (room that is used up -- even exactly -- is TAMP_OUTPUT_FULL in the reference when padding bits are left, decompressor.c:431-436,
     // and a partial last token when it is not enough: the exact decoder's)
-    if (v >= cap || tk > 0xFFFFFFFFull - 4096) { timing_end(st); return 1; }
+    if (v >= cap) { timing_end(st); return long_declined(dbg_long, "decode", "output room"); }
+    if (tk > 0xFFFFFFFFull - 4096) { timing_end(st); return long_declined(dbg_long, "decode", "records"); }
     HIP_OK(hipMemcpyAsync(d_tokbase, tokbase.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_rot, rot.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
     if (extended) {
@@ -862,7 +873,13 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         HIP_OK(hipMemcpyAsync(d_gmeta, gmeta.data(), G * 4, hipMemcpyHostToDevice, st));
         HIP_OK(hipStreamSynchronize(st));  // (the vectors go out of scope)
     }
-    if (dbg_long) fprintf(stderr, "[tamp_amd long decode] %zu groups, %llu tokens, %llu bytes out\n", G, (unsigned long long)tk, (unsigned long long)v);
+    if (dbg_long) {
+        size_t early = 0;  // groups that start inside the first W bytes (TAMP_AMD_LONGDEC_CHAIN=0: they get a window of their own below)
+        for (const Group& gr : groups) early += gr.nout != 0 && gr.v0 < W;
+        fprintf(stderr, "[tamp_amd long decode] %zu groups, %llu tokens, %llu bytes out, %llu entries, %zu wp blocks, max lags %u, %zu early groups, %zu scan blocks\n",
+                G, (unsigned long long)tk, (unsigned long long)v, (unsigned long long)dbg_entries, dbg_wpblocks, dbg_maxlag, early,
+                chain ? (G + kLongScanBlock - 1) / kLongScanBlock : (size_t)0);
+    }
     if (chain) {
         // every group by a workgroup of its own, no workgroup waiting for another (tamp_decompress_long_kernel.hpp, step 3):
         // tail maps, their composition by one workgroup, finish.  The group table sits behind the tables above, the maps
@@ -872,7 +889,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         const size_t n_blocks = (G + kLongScanBlock - 1) / kLongScanBlock;
         // (behind the groups' maps: the blocks' maps and the window in front of every block)
         // (... and, extended format, in front of every group: with lags the window is not "the last W output bytes")
-        if (rec.long_tails.need((G + n_blocks) * (size_t)W * 2 + (n_blocks + (extended ? G : 0)) * (size_t)W + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return 1; }
+        if (rec.long_tails.need((G + n_blocks) * (size_t)W * 2 + (n_blocks + (extended ? G : 0)) * (size_t)W + 256) != hipSuccess) { (void)hipGetLastError(); timing_end(st); return long_declined(dbg_long, "decode", "scratch"); }
         uint16_t* const d_maps = static_cast<uint16_t*>(rec.long_tails.p);
         uint16_t* const d_blockmap = d_maps + G * (size_t)W;
         uint8_t* const d_blockwin = reinterpret_cast<uint8_t*>(d_blockmap + n_blocks * (size_t)W);
@@ -1111,7 +1128,7 @@ int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLon
     uint64_t v = 0;
     for (const uint32_t b : f.outb) v += b;
     if (f.dbg) fprintf(stderr, "[tamp_amd long size query] %llu bytes out, limit %u\n", (unsigned long long)v, f.cap);
-    if (v >= f.cap) { timing_end(st); return 1; }
+    if (v >= f.cap) { timing_end(st); return long_declined(f.dbg, "size query", "output room"); }
     hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, d_size, d_status, d_consumed, (uint32_t)v, f.n);
     timing_end(st);
     HIP_OK(hipGetLastError());

@@ -34,6 +34,15 @@ def _corpus(kind, n):
     return (blob * (n // len(blob) + 1))[:n]
 
 
+def _long_path_lines(capfd):
+    """The long-stream decoder's debug lines since the last look (TAMP_AMD_LONGDEC_DEBUG): -> (decoded, reasons it declined for).
+    Without them a long path that hands every stream to the exact decoders returns the same bytes and nobody notices."""
+    import re
+
+    err = capfd.readouterr().err
+    return bool(re.search(r"\[tamp_amd long decode\] \d+ groups, ", err)), re.findall(r"\[tamp_amd long decode\] declined: (.+)", err)
+
+
 def _same_as_checker(ta, checker, blob, cap, dictionary=None):
     r = ta.decompress_batch([blob], out_cap=cap, dictionary=dictionary)
     st, out, used = checker.decompress(blob, cap=cap, dictionary=dictionary)
@@ -70,13 +79,16 @@ def _data(kind, n):
 
 
 @pytest.mark.parametrize("name,conf,kind,n", CASES, ids=[c[0] for c in CASES])
-def test_one_long_v1_stream_decodes_like_the_reference(ta, checker, name, conf, kind, n, monkeypatch):
+def test_one_long_v1_stream_decodes_like_the_reference(ta, checker, name, conf, kind, n, monkeypatch, capfd):
     data = _data(kind, n)
     blob = ta.compress(data, extended=False, **conf)
     assert len(blob) >= 256 << 10 or kind in ("zeros",)  # (long enough for the long-stream decoder; zeros compress to 280 KB)
     assert bytes(ta.decompress(blob)) == data
+    monkeypatch.setenv("TAMP_AMD_LONGDEC_DEBUG", "1")
+    capfd.readouterr()
     st, out = _same_as_checker(ta, checker, blob, n + 100)
     assert st == 2 and out == data
+    assert _long_path_lines(capfd) == (True, [])  # decoded by the long path, not handed on
     # groups through RESOLVE one launch after the other: the same bytes
     monkeypatch.setenv("TAMP_AMD_LONGDEC_CHAIN", "0")
     r = ta.decompress_batch([blob], out_cap=n + 100)
@@ -95,7 +107,10 @@ EXT_CASES = [
     ("markup_w15", dict(window=15), "markup", 1_500_000),
     ("prose_literal7", dict(literal=7), "prose7", 1_200_000),
     ("prose_literal6", dict(literal=6), "prose6", 1_200_000),  # the seeded dictionary of 6-bit literals (decompressor.c:318-319)
-    ("zeros", dict(), "zeros", 40_000_000),         # nothing but 241-byte RLE tokens: more lags per chunk than a group lists
+    # nothing but 241-byte RLE tokens, every one lagging: 9 + 8 + 4 = 21 bits each, so 48 or 49 start in a 1,024-bit chunk -- below
+    # the 63 a group lists, every group is ONE chunk (two would pass 63), and the long path takes the stream: what the case
+    # measures is the long path with 320,000 one-chunk groups, not the fall-back ("lags per chunk" would be 64 and more)
+    ("zeros", dict(), "zeros", 40_000_000),
     ("random", dict(), "random", 600_000),
     ("period_1000", dict(), "period", 3_500_000),    # extended matches of 130+ bytes, clipped at the ring's end
     ("runs_mixed", dict(), "runs", 2_000_000),       # runs of 2..300 bytes between words
@@ -103,7 +118,7 @@ EXT_CASES = [
 
 
 @pytest.mark.parametrize("name,conf,kind,n", EXT_CASES, ids=[c[0] for c in EXT_CASES])
-def test_one_long_extended_stream_decodes_like_the_reference(ta, checker, name, conf, kind, n, monkeypatch):
+def test_one_long_extended_stream_decodes_like_the_reference(ta, checker, name, conf, kind, n, monkeypatch, capfd):
     """Round 6: the library's default format.  RLE / extended-match tokens write fewer bytes to the window than they produce
     (decompressor.c:162-170,266-268); window_pos at those tokens comes from one pass over them (tamp_long_wp_kernel), the
     groups' lag lists from there."""
@@ -125,8 +140,11 @@ def test_one_long_extended_stream_decodes_like_the_reference(ta, checker, name, 
     assert blob[0] & 2
     monkeypatch.setenv("TAMP_AMD_LONGDEC_MIN", "65536")  # (the long-stream decoder from 64 KiB of compressed bytes on)
     assert len(blob) >= 64 << 10
+    monkeypatch.setenv("TAMP_AMD_LONGDEC_DEBUG", "1")
+    capfd.readouterr()
     st, out = _same_as_checker(ta, checker, blob, len(data) + 100)
     assert st == 2 and out == data
+    assert _long_path_lines(capfd) == (True, [])  # decoded by the long path, not handed on
     assert bytes(ta.decompress(blob)) == data
     # the exact decoders give the same answer (the path the launcher falls back to)
     monkeypatch.setenv("TAMP_AMD_LONGDEC_EXT", "0")

@@ -246,10 +246,12 @@ def test_fuzz_regression_fixtures(ta):
 
 
 @pytest.mark.parametrize("tool,seconds", [("fuzz_gpu.py", 25), ("fuzz_stream_gpu.py", 15), ("fuzz_resume_gpu.py", 15),
-                                          ("fuzz_encoder_resume_gpu.py", 15), ("fuzz_pieces_gpu.py", 15)])
+                                          ("fuzz_encoder_resume_gpu.py", 15), ("fuzz_pieces_gpu.py", 15),
+                                          ("fuzz_long_decode_gpu.py", 8)])
 def test_bounded_randomised_differential(ta, tool, seconds):
     """tools/fuzz_*.py for a bounded budget each: compress (all modes, both builds) and decompress (all three decoders),
-    streaming scripts, decoder objects, encoder objects -- against the oracle / live reference objects."""
+    streaming scripts, decoder objects, encoder objects, the long-stream decoder (which also has to TAKE every intact stream it
+    has no reason to decline) -- against the oracle / live reference objects."""
     if tool in ("fuzz_encoder_resume_gpu.py", "fuzz_pieces_gpu.py"):
         from oracle.checker import Ref
 
