@@ -129,6 +129,7 @@ enum {
     TAMP_AMD_CALL_PARTIAL = 16,     /* the call ends without a drain (piece calls) */
     TAMP_AMD_CALL_APPEND = 32,      /* FLUSH + padding lead the output instead of the plain header byte */
     TAMP_AMD_CALL_BLOCK_MODE = 64,  /* a handful of long v1 streams: each one's blocks over all workgroups */
+    TAMP_AMD_CALL_DICT_TABLE = 128, /* a tamp_batch_compress_dicts call with dict_off: always a generic build (its table twin) */
 };
 enum { TAMP_AMD_BUILD_GENERIC = 0, TAMP_AMD_BUILD_FIXED_EXT = 1, TAMP_AMD_BUILD_FIXED_V1 = 2 };
 int tamp_amd_compress_build(const TampAmdConf *conf, uint32_t max_in_len, uint32_t call_flags, uintptr_t dictionary_address);
@@ -277,6 +278,49 @@ int tamp_batch_decoded_size(size_t dictionary_len, uint8_t max_window_bits, cons
                             const uint32_t *in_len, const uint32_t *limit /* may be NULL */, uint32_t *decoded_size,
                             int8_t *status, uint32_t *in_consumed /* may be NULL */, size_t n_streams,
                             int mem, int device, void *stream);
+
+/* ---- dictionary tables: one launch, one custom dictionary PER STREAM ---------------------------------
+ *
+ * A feed with several message types carries one trained dictionary per type.  The three calls below take a BUFFER of
+ * dictionaries and a per-stream selector instead of one dictionary:
+ *
+ *   dictionaries / dictionaries_len   the buffer: any number of dictionaries, laid out as the caller likes
+ *   dict_off[i]                       byte offset of stream i's dictionary in the buffer, a multiple of 16.  A table of K
+ *                                     equal dictionaries of D bytes is dict_off[i] = k_i * D (D a multiple of 16).  Lives
+ *                                     where the other tables live (`mem`); ALL_DEVICES and the launches of very large batches
+ *                                     slice it together with in_off
+ *
+ * Stream i behaves exactly as the plain call would with dictionary = dictionaries + dict_off[i].  With dict_off == NULL each call
+ * IS its plain twin (which is how the plain calls are implemented).  Everything else -- tables, status codes, mem / device /
+ * stream, block mode, the long-stream decoder -- is as documented above.
+ *
+ * The compress kernel's table builds are twins of the generic builds, compiled apart from them: the plain calls run the code they
+ * ran before the table existed.  A table call never takes a fixed-geometry build (tamp_amd_compress_build: TAMP_AMD_CALL_DICT_TABLE).
+ *
+ * tamp_batch_compress_dicts: conf->use_custom_dictionary must be set when dict_off is given (the custom bit sits in the one header
+ *   byte the launch shares), else the call returns TAMP_AMD_BAD_ARGUMENT.  A stream whose row is not a multiple of 16, or with
+ *   dict_off[i] + (1 << window) > dictionaries_len, gets status TAMP_AMD_BAD_ARGUMENT and out_len = 0; nothing of it is read and
+ *   nothing written, and the rest of the batch is unaffected.
+ * tamp_batch_decompress_dicts: a stream whose header lacks the custom bit ignores its row.  One that has it starts from
+ *   dictionaries + dict_off[i]; if dict_off[i] + (1 << its own window) > dictionaries_len it gets TAMP_INVALID_CONF (what too
+ *   short a shared dictionary gets), and a row that is not a multiple of 16 gets TAMP_AMD_BAD_ARGUMENT.  Nothing outside the
+ *   buffer is ever read.
+ * tamp_batch_decoded_size_dicts: only the lengths matter; per stream exactly the out_len, status and in_consumed of
+ *   tamp_batch_decompress_dicts with out_cap = limit.
+ */
+int tamp_batch_compress_dicts(const TampAmdConf *conf, const uint8_t *dictionaries, size_t dictionaries_len,
+                              const uint64_t *dict_off, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                              uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
+                              int8_t *status, size_t n_streams, uint32_t max_in_len, int mem, int device, void *stream);
+int tamp_batch_decompress_dicts(const uint8_t *dictionaries, size_t dictionaries_len, const uint64_t *dict_off,
+                                uint8_t max_window_bits, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                                uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
+                                int8_t *status, uint32_t *in_consumed, size_t n_streams, int mem, int device, void *stream);
+int tamp_batch_decoded_size_dicts(size_t dictionaries_len, const uint64_t *dict_off, uint8_t max_window_bits,
+                                  const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                                  const uint32_t *limit /* may be NULL */, uint32_t *decoded_size, int8_t *status,
+                                  uint32_t *in_consumed /* may be NULL */, size_t n_streams, int mem, int device,
+                                  void *stream);
 
 /* ---- resumable decoding: decoder OBJECTS that survive between calls ------------------------------
  *

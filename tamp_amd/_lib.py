@@ -34,6 +34,9 @@ SYMBOLS = (
     "tamp_batch_compress",
     "tamp_batch_decompress",
     "tamp_batch_decoded_size",
+    "tamp_batch_compress_dicts",
+    "tamp_batch_decompress_dicts",
+    "tamp_batch_decoded_size_dicts",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
     "tamp_batch_decompress_resume",
@@ -169,6 +172,12 @@ def load() -> C.CDLL:
     lib.tamp_batch_decompress.restype = i32
     lib.tamp_batch_decoded_size.argtypes = [sz, u8, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
     lib.tamp_batch_decoded_size.restype = i32
+    lib.tamp_batch_compress_dicts.argtypes = [C.POINTER(TampAmdConf), vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp]
+    lib.tamp_batch_compress_dicts.restype = i32
+    lib.tamp_batch_decompress_dicts.argtypes = [vp, sz, vp, u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.tamp_batch_decompress_dicts.restype = i32
+    lib.tamp_batch_decoded_size_dicts.argtypes = [sz, vp, u8, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.tamp_batch_decoded_size_dicts.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]
     lib.tamp_amd_decoder_state_size.restype = sz
     lib.tamp_amd_decoder_state_init.argtypes = [vp, C.POINTER(TampAmdConf), u8]

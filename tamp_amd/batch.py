@@ -73,6 +73,104 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+class DictionaryTable:
+    """K custom dictionaries of D bytes each and a per-stream selector: what ``dictionaries=`` + ``dictionary_index=`` of
+    ``compress_batch`` / ``decompress_batch`` stand for, and what ``dictionary=`` of the three batch calls takes as well
+    (``decoded_size_batch`` in this form only).
+
+    ``dictionaries``: K bytes objects of equal length, or a uint8 array / CUDA tensor of shape ``(K, D)``; D a multiple of 16.
+    ``index``: an integer array or CUDA tensor, one entry per stream, each in ``[0, K)`` -- checked here for host arrays; a CUDA
+    tensor is not looked at (that would take a sync): an entry outside the table makes its stream fail, alone, with status -21
+    (compress) / -3 (decode).  Every check raises ``ValueError`` before anything is loaded or launched.
+
+    Device calls: dictionaries given as bytes or a host array are uploaded on the first call to a device (a synchronous copy
+    of K x D bytes) and the tensor is kept on this object -- build the table once and pass it as ``dictionary=`` to every
+    call, or pass a CUDA tensor; ``dictionaries=`` makes a new object, and a new upload, per call.
+    """
+
+    def __init__(self, dictionaries, index):
+        if index is None:
+            raise ValueError("dictionaries needs a dictionary_index.")
+        if _is_torch(dictionaries) or isinstance(dictionaries, np.ndarray):
+            if dictionaries.ndim != 2 or "uint8" not in str(dictionaries.dtype):
+                raise ValueError("dictionaries: a uint8 array of shape (K, D) expected.")
+            k, d = int(dictionaries.shape[0]), int(dictionaries.shape[1])
+            if _is_torch(dictionaries) and not dictionaries.is_cuda:
+                dictionaries = dictionaries.numpy()
+            buf = dictionaries.contiguous().reshape(-1) if _is_torch(dictionaries) else np.ascontiguousarray(dictionaries).reshape(-1)
+        else:
+            rows = [bytes(x) for x in dictionaries]
+            k, d = len(rows), (len(rows[0]) if rows else 0)
+            if any(len(r) != d for r in rows):
+                raise ValueError("dictionaries: K dictionaries of equal length expected.")
+            buf = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        if k == 0 or d == 0 or d % 16:
+            raise ValueError("Dictionary size must be a non-zero multiple of 16.")
+        if not (_is_torch(index) and index.is_cuda):
+            index = np.asarray(index)
+            if index.ndim != 1 or index.dtype.kind not in "iu":
+                raise ValueError("dictionary_index: a 1-D integer array expected.")
+            if index.size and (int(index.min()) < 0 or int(index.max()) >= k):
+                raise ValueError("dictionary_index out of range.")
+        elif index.ndim != 1 or index.is_floating_point():
+            raise ValueError("dictionary_index: a 1-D integer array expected.")
+        self.buffer, self.count, self.size, self.index = buf, k, d, index  # (flat uint8 buffer, K, D, selector)
+        self._uploaded = {}  # device -> the buffer there
+
+    def __len__(self):
+        return self.count * self.size
+
+    def on_device(self, n, dev, with_bytes=True):
+        """-> (buffer tensor or None, dict_off int64 tensor) on ``dev``; the offsets are formed there, without a sync."""
+        import torch
+
+        if int(self.index.shape[0]) != n:
+            raise ValueError("one dictionary_index per stream expected")
+        buf = self.buffer
+        buf_t = None
+        if with_bytes:
+            buf_t = self._uploaded.get(str(dev))
+            if buf_t is None:
+                buf_t = self._uploaded[str(dev)] = buf.to(dev) if _is_torch(buf) else torch.from_numpy(np.array(buf)).to(dev)
+        idx = self.index
+        idx_t = idx.to(device=dev, dtype=torch.int64) if _is_torch(idx) else torch.from_numpy(idx.astype(np.int64)).to(dev)
+        return buf_t, idx_t * self.size
+
+    def on_host(self, n, with_bytes=True):
+        """-> (buffer array or None, dict_off uint64 array) in host memory."""
+        buf, index = self.buffer, self.index
+        if _is_torch(index):
+            index = index.cpu().numpy()
+            if index.size and (int(index.min()) < 0 or int(index.max()) >= self.count):
+                raise ValueError("dictionary_index out of range.")
+        if len(index) != n:
+            raise ValueError("one dictionary_index per stream expected")
+        if with_bytes and _is_torch(buf):
+            buf = buf.cpu().numpy()
+        return (buf if with_bytes else None), np.ascontiguousarray(index.astype(np.uint64) * np.uint64(self.size))
+
+
+def _dict_table(dictionary, dictionaries, dictionary_index, window=None):
+    """The dictionary arguments of a batch call -> ``(dictionary, table)``, one of them None at least: ``dictionaries=`` +
+    ``dictionary_index=`` or ``dictionary=DictionaryTable(...)`` give the table.  ``window``: compress calls, where D must be
+    the window itself.  Raises ``ValueError`` before anything is loaded or launched."""
+    table = None
+    if isinstance(dictionary, DictionaryTable):
+        dictionary, table = None, dictionary
+        if dictionaries is not None or dictionary_index is not None:
+            raise ValueError("dictionary and dictionaries exclude each other.")
+    elif dictionaries is None:
+        if dictionary_index is not None:
+            raise ValueError("dictionary_index needs dictionaries.")
+    else:
+        if dictionary is not None:
+            raise ValueError("dictionary and dictionaries exclude each other.")
+        table = DictionaryTable(dictionaries, dictionary_index)
+    if table is not None and window is not None and table.size != (1 << window):
+        raise ValueError("Dictionary-window size mismatch.")  # (as for one dictionary)
+    return dictionary, table
+
+
 def pack_streams(streams: Sequence[bytes]):
     """list of bytes -> (flat uint8 array, in_off uint64[n], in_len uint32[n])."""
     lens = np.fromiter((len(s) for s in streams), dtype=np.uint32, count=len(streams))
@@ -102,7 +200,7 @@ def trim(device: int = 0) -> int:
 def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal: int = 8, extended: bool = True,
                    dictionary=None, dictionary_reset: bool = False, lazy_matching: bool = False, out_cap=None,
                    max_in_len: int = 0, device: int = 0, stream=None, timing: bool = False,
-                   run_aware=None, reuse=None) -> BatchResult:
+                   run_aware=None, reuse=None, dictionaries=None, dictionary_index=None) -> BatchResult:
     """Compress many independent streams in one launch.
 
     ``data`` is a list of bytes-likes (host), a flat numpy uint8 array + ``in_off``/``in_len`` (host), or a flat
@@ -116,7 +214,12 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
     (like ``$TAMP_AMD_RUNS``) is ignored for them.
     ``reuse`` (device batches with an integer ``out_cap``): the result of an earlier call with the same stream count and
     capacity on the same device; its output slab and tables are overwritten instead of allocating new ones.
+    ``dictionaries`` + ``dictionary_index``: one custom dictionary PER STREAM in one launch (``tamp_batch_compress_dicts``).
+    ``dictionaries`` is K bytes objects of ``1 << window`` bytes each, or a uint8 array / CUDA tensor of shape
+    ``(K, 1 << window)``; stream ``i`` is compressed as ``dictionary=dictionaries[dictionary_index[i]]`` would compress it
+    (``dictionary=DictionaryTable(dictionaries, dictionary_index)`` says the same).
     """
+    dictionary, table = _dict_table(dictionary, dictionaries, dictionary_index, window)
     if stream is not None and _is_torch(data):
         # The call makes its tables (capacities, offsets) and its output slab with torch: they have to come into being on the
         # stream the kernels are enqueued on, or the launch races the fill kernels of torch's current stream (and the caching
@@ -124,11 +227,12 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
         import torch
 
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
-            return compress_batch(data, in_off, in_len, window=window, literal=literal, extended=extended, dictionary=dictionary,
+            return compress_batch(data, in_off, in_len, window=window, literal=literal, extended=extended,
+                                  dictionary=dictionary if table is None else table,
                                   dictionary_reset=dictionary_reset, lazy_matching=lazy_matching, out_cap=out_cap,
                                   max_in_len=max_in_len, device=device, stream=None, timing=timing, run_aware=run_aware, reuse=reuse)
     lib = _lib.load()
-    conf = _conf(window, literal, extended, dictionary, dictionary_reset, lazy_matching, run_aware)
+    conf = _conf(window, literal, extended, dictionary if table is None else table, dictionary_reset, lazy_matching, run_aware)
     if dictionary is not None and not _is_torch(dictionary) and len(dictionary) != (1 << window):
         raise ValueError("Dictionary-window size mismatch.")  # tamp/_c_compressor.pyx:43-46
     lib.tamp_amd_set_timing(1 if timing else 0)
@@ -170,13 +274,21 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         # the launch is asynchronous: converted copies of the tables must outlive it (they ride on the result)
         in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)
-        rc = lib.tamp_batch_compress(C.byref(conf), _ptr(dict_t), _ptr(data), _ptr(in_off_t),
-                                     _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
-                                     _ptr(out_len_t), _ptr(status_t), n, int(max_in_len), _lib.MEM_DEVICE,
-                                     dev.index or 0, C.c_void_p(st))
+        dict_off_t = None
+        if table is not None:
+            dict_t, dict_off_t = table.on_device(n, dev)
+            rc = lib.tamp_batch_compress_dicts(C.byref(conf), _ptr(dict_t), int(dict_t.numel()), _ptr(dict_off_t), _ptr(data),
+                                               _ptr(in_off_t), _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
+                                               _ptr(out_len_t), _ptr(status_t), n, int(max_in_len), _lib.MEM_DEVICE,
+                                               dev.index or 0, C.c_void_p(st))
+        else:
+            rc = lib.tamp_batch_compress(C.byref(conf), _ptr(dict_t), _ptr(data), _ptr(in_off_t),
+                                         _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
+                                         _ptr(out_len_t), _ptr(status_t), n, int(max_in_len), _lib.MEM_DEVICE,
+                                         dev.index or 0, C.c_void_p(st))
         _lib.check_launch(rc)
         ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
-        res = BatchResult(out, out_off_t, out_len_t, status_t, None, ms, (data, in_off_t, in_len_t, out_cap_t, dict_t))
+        res = BatchResult(out, out_off_t, out_len_t, status_t, None, ms, (data, in_off_t, in_len_t, out_cap_t, dict_t, dict_off_t))
         res._ws_key = (n, int(out_cap), str(dev)) if (out_cap is not None and _is_int(out_cap)) else None
         return res
 
@@ -197,10 +309,17 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
     out_len = np.zeros(n, dtype=np.uint32)
     status = np.zeros(n, dtype=np.int8)
     d = _np_u8(dictionary) if dictionary is not None else None
-    rc = lib.tamp_batch_compress(C.byref(conf), _ptr(d), _ptr(flat if flat.size else np.zeros(1, np.uint8)),
-                                 _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),
-                                 _ptr(status), n, int(max_in_len), _lib.MEM_HOST, device,
-                                 C.c_void_p(stream) if stream else None)
+    if table is not None:
+        d, dict_off = table.on_host(n)
+        rc = lib.tamp_batch_compress_dicts(C.byref(conf), _ptr(d), d.size, _ptr(dict_off),
+                                           _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len), _ptr(out),
+                                           _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), n, int(max_in_len),
+                                           _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
+    else:
+        rc = lib.tamp_batch_compress(C.byref(conf), _ptr(d), _ptr(flat if flat.size else np.zeros(1, np.uint8)),
+                                     _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),
+                                     _ptr(status), n, int(max_in_len), _lib.MEM_HOST, device,
+                                     C.c_void_p(stream) if stream else None)
     _lib.check_launch(rc)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
     return BatchResult(out, out_off, out_len, status, None, ms)
@@ -223,14 +342,16 @@ def decoded_size_batch(data, in_off=None, in_len=None, *, limit=None, dictionary
     (``None``: no limit below 2^32 - 1): status 2 and the full size for a stream that ends normally, status 1 and
     ``size == limit`` for one that would outgrow ``limit`` (an int or a per-stream array), -4 / -3 for malformed input.
     ``data`` takes the three forms of ``decompress_batch``; with torch CUDA tensors the call is one asynchronous kernel on
-    torch's current stream (or ``stream``).  Of ``dictionary`` only the length is used.
+    torch's current stream (or ``stream``).  Of ``dictionary`` only the length is used; a ``DictionaryTable`` (one dictionary
+    per stream, see ``decompress_batch``) is passed as ``dictionary=`` too, and only its shape and selector are used.
     """
+    dictionary, table = _dict_table(dictionary, None, None)
     if stream is not None and _is_torch(data):
         import torch  # (tables on the launch stream: see compress_batch)
 
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
-            return decoded_size_batch(data, in_off, in_len, limit=limit, dictionary=dictionary, max_window_bits=max_window_bits,
-                                      device=device, stream=None, timing=timing)
+            return decoded_size_batch(data, in_off, in_len, limit=limit, dictionary=dictionary if table is None else table,
+                                      max_window_bits=max_window_bits, device=device, stream=None, timing=timing)
     lib = _lib.load()
     lib.tamp_amd_set_timing(1 if timing else 0)
     dict_len = 0
@@ -254,12 +375,19 @@ def decoded_size_batch(data, in_off=None, in_len=None, *, limit=None, dictionary
         consumed_t = torch.empty(n, dtype=torch.int32, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
-        rc = lib.tamp_batch_decoded_size(dict_len, max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(limit_t),
-                                         _ptr(size_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE, dev.index or 0,
-                                         C.c_void_p(st))
+        dict_off_t = None
+        if table is not None:
+            _, dict_off_t = table.on_device(n, dev, with_bytes=False)
+            rc = lib.tamp_batch_decoded_size_dicts(len(table), _ptr(dict_off_t), max_window_bits, _ptr(data), _ptr(in_off_t),
+                                                   _ptr(in_len_t), _ptr(limit_t), _ptr(size_t), _ptr(status_t), _ptr(consumed_t), n,
+                                                   _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st))
+        else:
+            rc = lib.tamp_batch_decoded_size(dict_len, max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(limit_t),
+                                             _ptr(size_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE, dev.index or 0,
+                                             C.c_void_p(st))
         _lib.check_launch(rc)
         ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
-        return DecodedSizes(size_t, status_t, consumed_t, ms, (data, in_off_t, in_len_t, limit_t))
+        return DecodedSizes(size_t, status_t, consumed_t, ms, (data, in_off_t, in_len_t, limit_t, dict_off_t))
 
     if in_off is None:
         flat, in_off, in_len = pack_streams(data)
@@ -279,9 +407,16 @@ def decoded_size_batch(data, in_off=None, in_len=None, *, limit=None, dictionary
     size = np.zeros(n, dtype=np.uint32)
     status = np.zeros(n, dtype=np.int8)
     consumed = np.zeros(n, dtype=np.uint32)
-    rc = lib.tamp_batch_decoded_size(dict_len, max_window_bits, _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off),
-                                     _ptr(in_len), _ptr(limit), _ptr(size), _ptr(status), _ptr(consumed), n, _lib.MEM_HOST,
-                                     device, C.c_void_p(stream) if stream else None)
+    if table is not None:
+        _, dict_off = table.on_host(n, with_bytes=False)
+        rc = lib.tamp_batch_decoded_size_dicts(len(table), _ptr(dict_off), max_window_bits,
+                                               _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len),
+                                               _ptr(limit), _ptr(size), _ptr(status), _ptr(consumed), n, _lib.MEM_HOST, device,
+                                               C.c_void_p(stream) if stream else None)
+    else:
+        rc = lib.tamp_batch_decoded_size(dict_len, max_window_bits, _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off),
+                                         _ptr(in_len), _ptr(limit), _ptr(size), _ptr(status), _ptr(consumed), n, _lib.MEM_HOST,
+                                         device, C.c_void_p(stream) if stream else None)
     _lib.check_launch(rc)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
     return DecodedSizes(size, status, consumed, ms)
@@ -289,7 +424,7 @@ def decoded_size_batch(data, in_off=None, in_len=None, *, limit=None, dictionary
 
 def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: int = 0xFFFFFFFF, dictionary=None,
                      max_window_bits: int = 15, scan_headers: bool = True, device: int = 0, stream=None,
-                     timing: bool = False) -> BatchResult:
+                     timing: bool = False, dictionaries=None, dictionary_index=None) -> BatchResult:
     """Decompress many independent ``.tamp`` streams in one launch (configuration read from each header).
 
     ``out_cap=None``: the sizes are not known.  ``decoded_size_batch(limit=max_out)`` finds them and stream ``i`` is decoded
@@ -305,19 +440,26 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
     ``out_cap`` (int or per-stream array) bounds each stream's output.  ``status[i]`` is the reference's code:
     2 (INPUT_EXHAUSTED) on normal completion, 1 (OUTPUT_FULL) if ``out_cap[i]`` was reached with work left,
     -4 / -3 for malformed input.
+
+    ``dictionaries`` + ``dictionary_index``: one custom dictionary PER STREAM in one launch (``tamp_batch_decompress_dicts``).
+    ``dictionaries`` is K bytes objects of equal length D, or a uint8 array / CUDA tensor of shape ``(K, D)``, D a multiple of
+    16; a stream whose header has the custom bit is decoded as ``dictionary=dictionaries[dictionary_index[i]]`` would decode
+    it, one without the bit ignores its selector (``dictionary=DictionaryTable(dictionaries, dictionary_index)`` says the same).
     """
+    dictionary, table = _dict_table(dictionary, dictionaries, dictionary_index)
+    dict_arg = dictionary if table is None else table  # (what the calls below pass on)
     if stream is not None and _is_torch(data):
         import torch  # (tables and output slab on the launch stream: see compress_batch)
 
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
-            return decompress_batch(data, in_off, in_len, out_cap=out_cap, max_out=max_out, dictionary=dictionary,
+            return decompress_batch(data, in_off, in_len, out_cap=out_cap, max_out=max_out, dictionary=dict_arg,
                                     max_window_bits=max_window_bits, scan_headers=scan_headers, device=device, stream=None, timing=timing)
     if out_cap is None:
         if not 0 <= int(max_out) <= 0xFFFFFFFF:
             raise ValueError("max_out must fit 32 bits")
         if not _is_torch(data) and in_off is None:
             data, in_off, in_len = pack_streams(data)  # (packed once for both calls)
-        q = decoded_size_batch(data, in_off, in_len, limit=int(max_out), dictionary=dictionary, max_window_bits=max_window_bits,
+        q = decoded_size_batch(data, in_off, in_len, limit=int(max_out), dictionary=dict_arg, max_window_bits=max_window_bits,
                                device=device, stream=stream)
         if _is_torch(data):
             import torch
@@ -325,7 +467,7 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
             out_cap = torch.clamp((q.size.to(torch.int64) & 0xFFFFFFFF) + 1, max=int(max_out))  # (int64: sizes are uint32 values)
         else:
             out_cap = np.minimum(q.size.astype(np.uint64) + 1, np.uint64(int(max_out))).astype(np.uint32)
-        return decompress_batch(data, in_off, in_len, out_cap=out_cap, dictionary=dictionary, max_window_bits=max_window_bits,
+        return decompress_batch(data, in_off, in_len, out_cap=out_cap, dictionary=dict_arg, max_window_bits=max_window_bits,
                                 scan_headers=scan_headers, device=device, stream=stream, timing=timing)
     lib = _lib.load()
     lib.tamp_amd_set_timing(1 if timing else 0)
@@ -356,13 +498,22 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
             dict_len = int(dict_t.numel())
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
-        rc = lib.tamp_batch_decompress(_ptr(dict_t), dict_len, max_window_bits, _ptr(data), _ptr(in_off_t),
-                                       _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
-                                       _ptr(out_len_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE,
-                                       dev.index or 0, C.c_void_p(st))
+        dict_off_t = None
+        if table is not None:
+            dict_t, dict_off_t = table.on_device(n, dev)
+            rc = lib.tamp_batch_decompress_dicts(_ptr(dict_t), int(dict_t.numel()), _ptr(dict_off_t), max_window_bits, _ptr(data),
+                                                 _ptr(in_off_t), _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
+                                                 _ptr(out_len_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE,
+                                                 dev.index or 0, C.c_void_p(st))
+        else:
+            rc = lib.tamp_batch_decompress(_ptr(dict_t), dict_len, max_window_bits, _ptr(data), _ptr(in_off_t),
+                                           _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
+                                           _ptr(out_len_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE,
+                                           dev.index or 0, C.c_void_p(st))
         _lib.check_launch(rc)
         ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
-        return BatchResult(out, out_off_t, out_len_t, status_t, consumed_t, ms, (data, in_off_t, in_len_t, out_cap_t, dict_t))
+        return BatchResult(out, out_off_t, out_len_t, status_t, consumed_t, ms,
+                           (data, in_off_t, in_len_t, out_cap_t, dict_t, dict_off_t))
 
     if in_off is None:
         flat, in_off, in_len = pack_streams(data)
@@ -380,10 +531,17 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
     status = np.zeros(n, dtype=np.int8)
     consumed = np.zeros(n, dtype=np.uint32)
     d = _np_u8(dictionary) if dictionary is not None else None
-    rc = lib.tamp_batch_decompress(_ptr(d), len(d) if d is not None else 0, max_window_bits,
-                                   _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len),
-                                   _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
-                                   _ptr(consumed), n, _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
+    if table is not None:
+        d, dict_off = table.on_host(n)
+        rc = lib.tamp_batch_decompress_dicts(_ptr(d), d.size, _ptr(dict_off), max_window_bits,
+                                             _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len),
+                                             _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
+                                             _ptr(consumed), n, _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
+    else:
+        rc = lib.tamp_batch_decompress(_ptr(d), len(d) if d is not None else 0, max_window_bits,
+                                       _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len),
+                                       _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
+                                       _ptr(consumed), n, _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
     _lib.check_launch(rc)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
     return BatchResult(out, out_off, out_len, status, consumed, ms)

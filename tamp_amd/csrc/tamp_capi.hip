@@ -300,6 +300,11 @@ __global__ void __launch_bounds__(1024) tamp_stream_order_kernel(const uint32_t*
         if (live) order[slot] = s;
     }
 }
+// (the dictionary-table column of a *_dicts call, in the same order)
+__global__ void tamp_gather_u64_kernel(const uint32_t* order, uint32_t n, const uint64_t* src, uint64_t* dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[order[i]];
+}
 __global__ void tamp_gather_rows_kernel(const uint32_t* order, uint32_t n, const uint64_t* in_off, const uint32_t* in_len,
                                         const uint64_t* out_off, const uint32_t* out_cap, uint64_t* g_in_off, uint32_t* g_in_len,
                                         uint64_t* g_out_off, uint32_t* g_out_cap) {
@@ -392,7 +397,7 @@ CompressArgs fill_compress_args(const DeviceCtx* ctx, const CompressCall& call, 
 // a persistent grid, how many of its workgroups a CU holds (the occupancy query costs ~10 us: once per shape).  launch_on_counter:
 // a work-counter slot, zeroed, and the launch over it.  (Two steps: the grid is sized, checked and used between them.)
 int prepare_compress_kernel(const CompressPlan& p, int* per_cu) {
-    const void* const kernel = reinterpret_cast<const void*>(compress_kernel_of(p.build));
+    const void* const kernel = reinterpret_cast<const void*>(compress_kernel_of(p.build, p.dicts));
     HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds.total));
     if (!p.persistent) return TAMP_OK;
     static std::mutex occ_mu;
@@ -406,7 +411,7 @@ int prepare_compress_kernel(const CompressPlan& p, int* per_cu) {
 int launch_on_counter(DeviceCtx* ctx, const CompressPlan& p, uint32_t grid, CompressArgs& a, hipStream_t st) {
     a.work_counter = ctx->work_counters + ctx->next_counter.fetch_add(1) % DeviceCtx::kCounters;
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(compress_kernel_of(p.build), dim3(grid), dim3(p.threads), p.lds.total, st, a);
+    hipLaunchKernelGGL(compress_kernel_of(p.build, p.dicts), dim3(grid), dim3(p.threads), p.lds.total, st, a);
     return TAMP_OK;
 }
 
@@ -422,8 +427,9 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
         return 1;
     // the streams' table rows: lengths, capacities (the launch geometry and the zero fill depend on them); a handful of LONG
     // streams is taken one after the other, each over all workgroups -- any shorter one among them and the batch kernel takes all
-    uint64_t in_off[64], out_off[64];
+    uint64_t in_off[64], out_off[64], dict_off[64];
     uint32_t in_len[64], out_cap[64];
+    if (a0.dict_off) HIP_OK(hipMemcpyAsync(dict_off, a0.dict_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(in_off, a0.in_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(out_off, a0.out_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(in_len, a0.in_len, 4 * n_streams, hipMemcpyDeviceToHost, st));
@@ -432,6 +438,8 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     uint32_t n_max = 0;
     for (size_t i = 0; i < n_streams; i++) {
         if (in_len[i] < min_len) return 1;
+        // (a dictionary-table row the batch kernel would refuse: the batch kernel refuses it)
+        if (a0.dict_off && !(dict_off_aligned(dict_off[i]) && dict_off_in_bounds(dict_off[i], 1u << conf->window, a0.dict_len))) return 1;
         n_max = std::max(n_max, in_len[i]);
     }
     call.block_mode = true;
@@ -455,6 +463,7 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     for (size_t i = 0; i < n_streams; i++) {
         CompressArgs a = a0;
         a.in_off += i, a.in_len += i, a.out_off += i, a.out_cap += i, a.out_len += i, a.status += i;  // (the kernel reads row 0)
+        if (a.dict_off) a.dict_off += i;
         const uint32_t n = in_len[i];
         const uint32_t n_blocks = (n + a.blk - 1) / a.blk;
         const uint32_t n_chunks = (n_blocks + kScanChunk - 1) / kScanChunk;
@@ -482,18 +491,22 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     return TAMP_OK;
 }
 
+// `d_dict_off` (the *_dicts calls, else null): stream i's dictionary is d_dict + d_dict_off[i], inside dict_len bytes.
 int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_dict, const uint8_t* d_in,
                     const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                     const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, size_t n_streams,
-                    uint32_t max_in_len, hipStream_t st, const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr) {
+                    uint32_t max_in_len, hipStream_t st, const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr,
+                    const uint64_t* d_dict_off = nullptr, size_t dict_len = 0) {
     if (n_streams == 0) return TAMP_OK;
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
     CompressCall call = compress_call(conf, max_in_len, reinterpret_cast<uintptr_t>(d_dict));
     if (seg) call.nlead = seg->nlead, call.lead = seg->lead, call.seg_flags = seg->flags, call.has_state = d_state != nullptr;
+    call.dict_table = d_dict_off != nullptr;
     CompressArgs a = fill_compress_args(ctx, call, d_dict, d_state);
     a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len, a.n_streams = (uint32_t)n_streams;
     a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
+    a.dict_off = d_dict_off, a.dict_len = dict_len;
     if (n_streams <= 64 && !seg) {  // a handful of LONG v1 streams: each one's blocks over all workgroups (the BLOCKM builds)
         const int rc = launch_compress_blocks(ctx, rec, a, call, st, n_streams);
         if (rc != 1) return rc;
@@ -537,7 +550,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
         int8_t* lpt_status = nullptr;
         if (lpt) {
             const size_t n = n_streams;
-            const size_t bytes = n * (4 + 4 + 8 + 4 + 8 + 4 + 4 + 1) + 256;
+            const size_t bytes = n * (4 + 4 + 8 + 4 + 8 + 4 + 4 + 1) + 256 + (a.dict_off ? n * 8 + 8 : 0);
             if (rec.lpt.need(bytes) == hipSuccess) lpt_mem = static_cast<uint8_t*>(rec.lpt.p);
             if (!lpt_mem) {
                 (void)hipGetLastError();
@@ -557,6 +570,11 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
                                    a.in_len, a.out_off, a.out_cap, g_in_off, g_in_len, g_out_off, g_out_cap);
                 a.in_off = g_in_off, a.in_len = g_in_len, a.out_off = g_out_off, a.out_cap = g_out_cap;
                 a.out_len = lpt_out_len, a.status = lpt_status;
+                if (a.dict_off) {  // (behind the status bytes, at the next multiple of 8)
+                    uint64_t* const g_dict_off = reinterpret_cast<uint64_t*>(lpt_mem + ((n * (4 + 4 + 8 + 4 + 8 + 4 + 4 + 1) + 7) & ~(size_t)7));
+                    hipLaunchKernelGGL(tamp_gather_u64_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, lpt_order, (uint32_t)n, a.dict_off, g_dict_off);
+                    a.dict_off = g_dict_off;
+                }
             }
         }
         if (const int rc = launch_on_counter(ctx, p, (uint32_t)g, a, st)) return rc;
@@ -570,7 +588,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
         for (size_t first = 0; first < n_streams; first += launch_step) {  // one stream per workgroup
             a.first_stream = (uint32_t)first;
             const uint32_t g = (uint32_t)std::min<size_t>(launch_step, n_streams - first);
-            hipLaunchKernelGGL(compress_kernel_of(p.build), dim3(g), dim3(p.threads), p.lds.total, st, a);
+            hipLaunchKernelGGL(compress_kernel_of(p.build, p.dicts), dim3(g), dim3(p.threads), p.lds.total, st, a);
         }
     }
     timing_end(st);
@@ -646,9 +664,9 @@ static int long_declined(bool dbg, const char* who, const char* why) {
 // -> 1 when the stream is not one for this path (or anything is off: the exact decoders take it), TAMP_OK with `f` filled in and
 // timing begun, an error code otherwise.  `who` names the caller in the debug lines.  d_out_off / d_cap may be null.
 int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, bool has_dict, size_t dict_len,
-                      uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                      const uint64_t* d_dict_off, uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                       const uint64_t* d_out_off, const uint32_t* d_cap, bool with_records, const char* who, hipStream_t st, LongFront& f) {
-    uint64_t in_off = 0, out_off = 0;
+    uint64_t in_off = 0, out_off = 0, dict_off = 0;  // (dict_off: the stream's row of a dictionary table, 0 without one)
     uint32_t n = 0, cap = 0xFFFFFFFFu;
     HIP_OK(hipMemcpyAsync(&n, d_in_len, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -659,6 +677,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     HIP_OK(hipMemcpyAsync(&in_off, d_in_off, 8, hipMemcpyDeviceToHost, st));
     if (d_out_off) HIP_OK(hipMemcpyAsync(&out_off, d_out_off, 8, hipMemcpyDeviceToHost, st));
     if (d_cap) HIP_OK(hipMemcpyAsync(&cap, d_cap, 4, hipMemcpyDeviceToHost, st));
+    if (d_dict_off) HIP_OK(hipMemcpyAsync(&dict_off, d_dict_off, 8, hipMemcpyDeviceToHost, st));
     uint8_t hdr[2] = {0, 0};
     HIP_OK(hipMemcpyAsync(hdr, d_in + in_off, 2, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -669,9 +688,10 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return long_declined(dbg, who, "header");
     if (extended && !gate.extended) return long_declined(dbg, who, "extended off");  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
-    if (hd.custom && (!has_dict || dict_len < W)) return long_declined(dbg, who, "dictionary");
+    // (its own row's length; a misaligned row is the exact decoders' to report as well)
+    if (hd.custom && (!has_dict || !dict_off_aligned(dict_off) || !dict_off_in_bounds(dict_off, W, dict_len))) return long_declined(dbg, who, "dictionary");
     f.n = n, f.cap = cap, f.out_off = out_off, f.in = in, f.hd = hd, f.hs = hs;
-    f.dict0 = hd.custom ? d_dict : ctx->seed_dicts + ((size_t)hd.table << 15);
+    f.dict0 = hd.custom ? d_dict + dict_off : ctx->seed_dicts + ((size_t)hd.table << 15);
 
     const uint64_t total_bits = 8ull * n;
     const uint32_t chunk_bits = extended ? kLongChunkBitsExt : kLongChunkBits;
@@ -754,11 +774,12 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
 // records per chunk, then the split decoder's RESOLVE over groups of at most kSplitMaxOut output bytes, in order, each with the
 // W bytes in front of it as its dictionary.  -> 1 when the call is not one (or anything is off: the exact decoders take it),
 // TAMP_OK when the stream has been decoded, an error code otherwise.  Nothing is written before the fall-back decision.
-int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits,
+int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, size_t dict_len,
+                           const uint64_t* d_dict_off, uint8_t max_wbits,
                            const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                            const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed, hipStream_t st) {
     LongFront f;
-    if (const int rc = long_decode_front(ctx, rec, gate, d_dict, d_dict != nullptr, dict_len, max_wbits, d_in, d_in_off, d_in_len, d_out_off,
+    if (const int rc = long_decode_front(ctx, rec, gate, d_dict, d_dict != nullptr, dict_len, d_dict_off, max_wbits, d_in, d_in_off, d_in_len, d_out_off,
                                          d_out_cap, true, "decode", st, f); rc != TAMP_OK) return rc;
     const uint32_t n = f.n, cap = f.cap, N = f.N, wbits = f.hd.wbits, W = 1u << wbits, lg = f.lg;
     const uint64_t out_off = f.out_off;
@@ -927,7 +948,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
     SplitArgs sa;
     DecompressArgs& a = sa.d;
     a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len, a.out = d_out, a.out_cap = d_out_cap, a.status = d_status;
-    a.in_consumed = nullptr, a.dict_len = W, a.seed_dicts = ctx->seed_dicts, a.scratch = nullptr, a.only_flagged = nullptr;
+    a.in_consumed = nullptr, a.dict_len = W, a.dict_off = nullptr, a.seed_dicts = ctx->seed_dicts, a.scratch = nullptr, a.only_flagged = nullptr;
     a.flagged_count = nullptr, a.n_streams = 1, a.lds_row = 0, a.max_wbits = (uint8_t)wbits;
     sa.lag = nullptr, sa.flagged = nullptr, sa.flagged_count = nullptr, sa.maxcap = kSplitMaxOut, sa.first = 0, sa.count = 1, sa.spw = 64;
     const uint32_t lds = split_resolve_lds(kSplitMaxOut);
@@ -1054,7 +1075,8 @@ int run_decode_plan(DeviceCtx* ctx, StreamScratch& rec, DecompressArgs a, const 
     return TAMP_OK;
 }
 
-int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
+// `d_dict_off` (the *_dicts calls, else null): a stream with the custom bit starts from d_dict + d_dict_off[i], inside dict_len bytes.
+int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, const uint64_t* d_dict_off, uint8_t max_wbits, const uint8_t* d_in,
                       const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
                       const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed,
                       size_t n_streams, hipStream_t st) {
@@ -1063,7 +1085,7 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
     a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
     a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
     a.in_consumed = d_consumed;
-    a.dict = d_dict, a.dict_len = (uint32_t)(dict_len > 0xFFFFFFFFu ? 0xFFFFFFFFu : dict_len);
+    a.dict = d_dict, a.dict_len = dict_len, a.dict_off = d_dict_off;
     a.seed_dicts = ctx->seed_dicts;
     a.scratch = nullptr;
     a.only_flagged = nullptr;
@@ -1082,7 +1104,7 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
         t_timing_outer = true;
         int rc = TAMP_OK;
         for (; done < n_streams; done++) {
-            rc = launch_decompress_long(ctx, rec, gate, d_dict, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
+            rc = launch_decompress_long(ctx, rec, gate, d_dict, dict_len, d_dict_off ? d_dict_off + done : nullptr, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
                                         d_out_off + done, d_out_cap + done, d_out_len + done, d_status + done,
                                         d_consumed ? d_consumed + done : nullptr, st);
             if (rc != TAMP_OK) break;
@@ -1119,11 +1141,12 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, ui
 // the input consumed) as long as it stays below the stream's limit.  -> 1 when the lane kernel has to answer: the stream fails the
 // gate, the chunk starts do not settle, an offset is out of bounds, or the sum reaches the limit (TAMP_OUTPUT_FULL, and how much
 // of the input that takes, is the exact loop's to say).
-int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in,
+int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, size_t dict_len, const uint64_t* d_dict_off,
+                             uint8_t max_wbits, const uint8_t* d_in,
                              const uint64_t* d_in_off, const uint32_t* d_in_len, const uint32_t* d_limit, uint32_t* d_size, int8_t* d_status,
                              uint32_t* d_consumed, hipStream_t st) {
     LongFront f;
-    if (const int rc = long_decode_front(ctx, rec, gate, nullptr, true, dict_len, max_wbits, d_in, d_in_off, d_in_len, nullptr, d_limit, false,
+    if (const int rc = long_decode_front(ctx, rec, gate, nullptr, true, dict_len, d_dict_off, max_wbits, d_in, d_in_off, d_in_len, nullptr, d_limit, false,
                                          "size query", st, f); rc != TAMP_OK) return rc;
     uint64_t v = 0;
     for (const uint32_t b : f.outb) v += b;
@@ -1138,7 +1161,7 @@ int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLon
 // tamp_batch_decoded_size on device memory: the parse's size-only build (tamp_decompress_split_kernel.hpp), one launch, no scratch,
 // no pre-pass, nothing that waits for `st` -- except for a handful of long streams, which the long decoder's front counts with the
 // whole device (and waits as the long decoder does).  `d_limit` may be null; of the dictionary only the length matters.
-int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off,
+int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, const uint64_t* d_dict_off, uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off,
                         const uint32_t* d_in_len, const uint32_t* d_limit, uint32_t* d_size, int8_t* d_status, uint32_t* d_consumed,
                         size_t n_streams, hipStream_t st) {
     if (n_streams == 0) return TAMP_OK;
@@ -1147,7 +1170,7 @@ int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, uint8_t max_wbits, cons
     DecompressArgs& a = sa.d;
     a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
     a.out_cap = d_limit, a.out_len = d_size, a.status = d_status, a.in_consumed = d_consumed;
-    a.dict_len = (uint32_t)(dict_len > 0xFFFFFFFFu ? 0xFFFFFFFFu : dict_len);
+    a.dict_len = dict_len, a.dict_off = d_dict_off;
     a.n_streams = (uint32_t)n_streams;
     a.max_wbits = max_wbits & 0x7F;  // (TAMP_AMD_WINDOW_BITS_EXACT: there is no pre-pass to skip)
     StreamScratch& rec = ctx->scratch(st);
@@ -1160,7 +1183,7 @@ int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, uint8_t max_wbits, cons
         t_timing_outer = true;
         int rc = TAMP_OK;
         for (; done < n_streams; done++) {
-            rc = launch_decoded_size_long(ctx, rec, gate, dict_len, max_wbits, d_in, d_in_off + done, d_in_len + done,
+            rc = launch_decoded_size_long(ctx, rec, gate, dict_len, d_dict_off ? d_dict_off + done : nullptr, max_wbits, d_in, d_in_off + done, d_in_len + done,
                                           d_limit ? d_limit + done : nullptr, d_size + done, d_status + done,
                                           d_consumed ? d_consumed + done : nullptr, st);
             if (rc != TAMP_OK) break;
@@ -1189,7 +1212,7 @@ int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, u
     a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
     a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
     a.in_consumed = d_consumed;
-    a.dict = nullptr, a.dict_len = 0;  // a custom dictionary is the initial content of the object's window
+    a.dict = nullptr, a.dict_len = 0, a.dict_off = nullptr;  // a custom dictionary is the initial content of the object's window
     a.seed_dicts = ctx->seed_dicts;
     a.scratch = nullptr;
     a.only_flagged = nullptr;
@@ -1258,6 +1281,7 @@ struct HostBatch {
     size_t nlead = 0;
     bool exact_out = false;    // never the whole-extent copy-back: nothing behind out_len[i] is written (HostChunk)
     bool drop_failed = false;  // (with exact_out) a stream whose status is not TAMP_OK produces nothing: out_len = 0
+    const uint64_t* dict_off = nullptr;  // the *_dicts calls: per stream, travels with the chunks; the whole dictionary buffer is staged
     // out == nullptr (tamp_batch_decoded_size): no output bytes at all -- out_off is null, out_cap (the limits, may be null) rides
     // along as a table only and takes no part in the chunks' extents; out_len / status / in_consumed come back as always
     uint64_t slab_off(size_t i) const { return out ? out_off[i] : 0; }
@@ -1320,7 +1344,7 @@ void plan_host_chunks(const HostBatch& b, size_t min_streams, uint64_t min_bytes
 struct HostSlot {  // device views of one chunk: offsets stay absolute, the data pointers are shifted instead
     const uint8_t* in;
     uint8_t* out;
-    const uint64_t *in_off, *out_off;
+    const uint64_t *in_off, *out_off, *dict_off;  // (dict_off: null without a dictionary table)
     const uint32_t *in_len, *out_cap;
     uint32_t *out_len, *in_consumed;
     int8_t* status;
@@ -1335,8 +1359,10 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
     std::lock_guard<std::mutex> call_lock(P.mu);
     const uint8_t* d_dict = nullptr;
     if (dictionary && dictionary_len) {
-        HIP_OK(P.dict.need(kSeedTable));
-        HIP_OK(hipMemcpy(P.dict.p, dictionary, std::min(dictionary_len, kSeedTable), hipMemcpyHostToDevice));
+        // one dictionary: at most a window of it; a table of them (b.dict_off): all of it, once per call (the buffer is kept and grows)
+        const size_t stage = b.dict_off ? dictionary_len : std::min(dictionary_len, kSeedTable);
+        HIP_OK(P.dict.need(std::max(stage, kSeedTable)));
+        HIP_OK(hipMemcpy(P.dict.p, dictionary, stage, hipMemcpyHostToDevice));
         d_dict = static_cast<const uint8_t*>(P.dict.p);
     }
     size_t max_in = 0, max_out = 0, max_cnt = 0;
@@ -1346,7 +1372,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         max_cnt = std::max(max_cnt, ch.i1 - ch.i0);
     }
     const int depth = (int)std::min<size_t>(Pipe::kDepth, chunks.size());
-    const size_t meta_bytes = max_cnt * (8 + 8 + 4 + 4 + 4 + 4 + 1) + 64;
+    const size_t meta_bytes = max_cnt * (8 + 8 + 8 + 4 + 4 + 4 + 4 + 1) + 64;
     for (int j = 0; j < depth; j++) {
         if (!P.s[j]) HIP_OK(hipStreamCreateWithFlags(&P.s[j], hipStreamNonBlocking));
         HIP_OK(P.in[j].need(max_in + 64));  // the kernels' vector loads may run past the last byte
@@ -1359,6 +1385,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         uint8_t* m = static_cast<uint8_t*>(P.meta[j].p);
         s.in_off = reinterpret_cast<uint64_t*>(m), m += max_cnt * 8;
         s.out_off = reinterpret_cast<uint64_t*>(m), m += max_cnt * 8;
+        s.dict_off = b.dict_off ? reinterpret_cast<uint64_t*>(m) : nullptr, m += max_cnt * 8;
         s.in_len = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
         s.out_cap = b.out_cap ? reinterpret_cast<uint32_t*>(m) : nullptr, m += max_cnt * 4;
         s.out_len = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
@@ -1383,6 +1410,7 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
             HIP_OK(hipMemcpyAsync(s.states, b.states + ch.i0 * b.state_stride, cnt * b.state_stride, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.in_off), b.in_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
         if (b.out_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.out_off), b.out_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
+        if (b.dict_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.dict_off), b.dict_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.in_len), b.in_len + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
         if (b.out_cap) HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.out_cap), b.out_cap + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
         return launch(s, cnt, d_dict, st);
@@ -1658,6 +1686,7 @@ int tamp_amd_compress_build(const TampAmdConf* conf, uint32_t max_in_len, uint32
     if (call_flags & TAMP_AMD_CALL_FLUSH_TOKEN) call.seg_flags |= kSegFlushToken;
     if (call_flags & TAMP_AMD_CALL_PARTIAL) call.seg_flags |= kSegPartial;
     call.has_state = (call_flags & TAMP_AMD_CALL_STATE) != 0;
+    call.dict_table = (call_flags & TAMP_AMD_CALL_DICT_TABLE) != 0;
     const CompressBuild b = plan_compress(call).build;
     return b == CompressBuild::kFixedExt ? TAMP_AMD_BUILD_FIXED_EXT : (b == CompressBuild::kFixedV1 ? TAMP_AMD_BUILD_FIXED_V1 : TAMP_AMD_BUILD_GENERIC);
 }
@@ -1762,21 +1791,27 @@ float tamp_amd_last_kernel_ms(void) {
     return ms;
 }
 
-int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, const uint8_t* in, const uint64_t* in_off,
-                        const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                        uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem, int device,
-                        void* stream) {
+// The batch calls.  Each *_dicts call is the whole of its plain twin plus a per-stream dictionary offset table; the plain call
+// passes none (dict_off = null) and behaves as it always has.
+int tamp_batch_compress_dicts(const TampAmdConf* conf, const uint8_t* dictionaries, size_t dictionaries_len, const uint64_t* dict_off,
+                              const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                              const uint32_t* out_cap, uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem,
+                              int device, void* stream) {
     if (!conf || (n_streams && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)))
         return TAMP_AMD_BAD_ARGUMENT;
+    // (a table selects among CUSTOM dictionaries: the custom bit sits in the one header byte the launch shares)
+    if (dict_off && (!conf->use_custom_dictionary || !dictionaries)) return TAMP_AMD_BAD_ARGUMENT;
     if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
     if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
+    const uint8_t* const dictionary = dictionaries;
     if (device == TAMP_AMD_ALL_DEVICES) {
         if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;  // device pointers belong to one device
         if (!max_in_len)
             for (size_t i = 0; i < n_streams; i++) max_in_len = std::max(max_in_len, in_len[i]);
         return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
-            return tamp_batch_compress(conf, dictionary, in, in_off + i0, in_len + i0, out, out_off + i0, out_cap + i0,
-                                       out_len + i0, status + i0, cnt, max_in_len, mem, dev, nullptr);
+            return tamp_batch_compress_dicts(conf, dictionaries, dictionaries_len, dict_off ? dict_off + i0 : nullptr, in, in_off + i0,
+                                             in_len + i0, out, out_off + i0, out_cap + i0, out_len + i0, status + i0, cnt, max_in_len,
+                                             mem, dev, nullptr);
         });
     }
     DeviceCtx* ctx = nullptr;
@@ -1792,7 +1827,7 @@ int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, cons
             return TAMP_OK;
         }
         return launch_compress(ctx, conf, dictionary, in, in_off, in_len, out, out_off, out_cap, out_len, status,
-                               n_streams, max_in_len, st);
+                               n_streams, max_in_len, st, nullptr, nullptr, dict_off, dictionaries_len);
     }
 
     // ---- host memory: stage, run, copy back ----
@@ -1806,17 +1841,66 @@ int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, cons
         for (size_t i = 0; i < n_streams; i++) maxlen = std::max(maxlen, in_len[i]);
         max_in_len = maxlen ? maxlen : 16;
     }
-    const HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, n_streams};
+    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, n_streams};
+    b.dict_off = dict_off;
     std::vector<HostChunk> chunks;
     // a chunk fills the device three times over (256 CUs x 6 workgroups = 1,536 streams at once); measured best for
     // 4 KiB streams (DESIGN_HISTORY.md), and at least 16 MiB so that short messages do not drown in call overhead
     plan_host_chunks(b, env_or("TAMP_AMD_HOST_CHUNK_STREAMS", (size_t)ctx->cu_count * 18),
                      (uint64_t)env_or("TAMP_AMD_HOST_CHUNK_MB", 16) << 20, 1ull << 30, chunks);
     return run_host_batch(ctx, device, b, chunks, conf->use_custom_dictionary ? dictionary : nullptr,
-                          (size_t)1 << conf->window,
+                          dict_off ? dictionaries_len : (size_t)1 << conf->window,
                           [&](const HostSlot& s, size_t count, const uint8_t* d_dict, hipStream_t cs) {
         return launch_compress(ctx, conf, d_dict, s.in, s.in_off, s.in_len, s.out, s.out_off, s.out_cap, s.out_len,
-                               s.status, count, max_in_len, cs);
+                               s.status, count, max_in_len, cs, nullptr, nullptr, s.dict_off, dictionaries_len);
+    });
+}
+
+int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, const uint8_t* in, const uint64_t* in_off,
+                        const uint32_t* in_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                        uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem, int device,
+                        void* stream) {
+    return tamp_batch_compress_dicts(conf, dictionary, 0, nullptr, in, in_off, in_len, out, out_off, out_cap, out_len, status, n_streams,
+                                     max_in_len, mem, device, stream);
+}
+
+int tamp_batch_decompress_dicts(const uint8_t* dictionaries, size_t dictionaries_len, const uint64_t* dict_off, uint8_t max_window_bits,
+                                const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                const uint32_t* out_cap, uint32_t* out_len, int8_t* status, uint32_t* in_consumed, size_t n_streams,
+                                int mem, int device, void* stream) {
+    if (n_streams && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
+    if (device == TAMP_AMD_ALL_DEVICES) {
+        if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
+        return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
+            return tamp_batch_decompress_dicts(dictionaries, dictionaries_len, dict_off ? dict_off + i0 : nullptr, max_window_bits, in,
+                                               in_off + i0, in_len + i0, out, out_off + i0, out_cap + i0, out_len + i0, status + i0,
+                                               in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev, nullptr);
+        });
+    }
+    DeviceCtx* ctx = nullptr;
+    int rc = get_ctx(device, &ctx);
+    if (rc != TAMP_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t* const dictionary = dictionaries;
+    size_t dictionary_len = dictionaries_len;
+    if (!dictionary) dictionary_len = 0, dict_off = nullptr;  // (no buffer: every stream with the custom bit is TAMP_INVALID_CONF, as ever)
+
+    if (mem == TAMP_AMD_MEM_DEVICE)
+        return launch_decompress(ctx, dictionary, dictionary_len, dict_off, max_window_bits, in, in_off, in_len, out, out_off,
+                                 out_cap, out_len, status, in_consumed, n_streams, st);
+
+    if (n_streams == 0) return TAMP_OK;
+    if (!dict_off) dictionary_len = std::min(dictionary_len, kSeedTable);  // (one dictionary: no window reads beyond 32 KiB of it)
+    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams};
+    b.dict_off = dict_off;
+    uint32_t* no_consumed = nullptr;
+    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), dictionary, dictionary_len,
+                          [&](const HostSlot& s, size_t count, const uint8_t* d_dict, hipStream_t cs) {
+        return launch_decompress(ctx, d_dict, d_dict ? dictionary_len : 0, d_dict ? s.dict_off : nullptr, max_window_bits, s.in, s.in_off,
+                                 s.in_len, s.out, s.out_off, s.out_cap, s.out_len, s.status, in_consumed ? s.in_consumed : no_consumed,
+                                 count, cs);
     });
 }
 
@@ -1824,69 +1908,49 @@ int tamp_batch_decompress(const uint8_t* dictionary, size_t dictionary_len, uint
                           const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                           const uint32_t* out_cap, uint32_t* out_len, int8_t* status, uint32_t* in_consumed,
                           size_t n_streams, int mem, int device, void* stream) {
-    if (n_streams && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return TAMP_AMD_BAD_ARGUMENT;
-    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
-    if (device == TAMP_AMD_ALL_DEVICES) {
-        if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
-        return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
-            return tamp_batch_decompress(dictionary, dictionary_len, max_window_bits, in, in_off + i0, in_len + i0, out,
-                                         out_off + i0, out_cap + i0, out_len + i0, status + i0,
-                                         in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev, nullptr);
-        });
-    }
-    DeviceCtx* ctx = nullptr;
-    int rc = get_ctx(device, &ctx);
-    if (rc != TAMP_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!dictionary) dictionary_len = 0;
-
-    if (mem == TAMP_AMD_MEM_DEVICE)
-        return launch_decompress(ctx, dictionary, dictionary_len, max_window_bits, in, in_off, in_len, out, out_off,
-                                 out_cap, out_len, status, in_consumed, n_streams, st);
-
-    if (n_streams == 0) return TAMP_OK;
-    dictionary_len = std::min(dictionary_len, kSeedTable);
-    const HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams};
-    uint32_t* no_consumed = nullptr;
-    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), dictionary, dictionary_len,
-                          [&](const HostSlot& s, size_t count, const uint8_t* d_dict, hipStream_t cs) {
-        return launch_decompress(ctx, d_dict, d_dict ? dictionary_len : 0, max_window_bits, s.in, s.in_off, s.in_len, s.out,
-                                 s.out_off, s.out_cap, s.out_len, s.status, in_consumed ? s.in_consumed : no_consumed,
-                                 count, cs);
-    });
+    return tamp_batch_decompress_dicts(dictionary, dictionary_len, nullptr, max_window_bits, in, in_off, in_len, out, out_off, out_cap,
+                                       out_len, status, in_consumed, n_streams, mem, device, stream);
 }
 
-int tamp_batch_decoded_size(size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,
-                            const uint32_t* in_len, const uint32_t* limit, uint32_t* decoded_size, int8_t* status,
-                            uint32_t* in_consumed, size_t n_streams, int mem, int device, void* stream) {
+int tamp_batch_decoded_size_dicts(size_t dictionaries_len, const uint64_t* dict_off, uint8_t max_window_bits, const uint8_t* in,
+                                  const uint64_t* in_off, const uint32_t* in_len, const uint32_t* limit, uint32_t* decoded_size,
+                                  int8_t* status, uint32_t* in_consumed, size_t n_streams, int mem, int device, void* stream) {
     if (n_streams && (!in_off || !in_len || !decoded_size || !status)) return TAMP_AMD_BAD_ARGUMENT;
     if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
     if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
     if (device == TAMP_AMD_ALL_DEVICES) {
         if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
         return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
-            return tamp_batch_decoded_size(dictionary_len, max_window_bits, in, in_off + i0, in_len + i0, limit ? limit + i0 : nullptr,
-                                           decoded_size + i0, status + i0, in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev,
-                                           nullptr);
+            return tamp_batch_decoded_size_dicts(dictionaries_len, dict_off ? dict_off + i0 : nullptr, max_window_bits, in, in_off + i0,
+                                                 in_len + i0, limit ? limit + i0 : nullptr, decoded_size + i0, status + i0,
+                                                 in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev, nullptr);
         });
     }
     DeviceCtx* ctx = nullptr;
     int rc = get_ctx(device, &ctx);
     if (rc != TAMP_OK) return rc;
+    if (!dictionaries_len) dict_off = nullptr;  // (as the decode call without a buffer)
     if (mem == TAMP_AMD_MEM_DEVICE)
-        return launch_decoded_size(ctx, dictionary_len, max_window_bits, in, in_off, in_len, limit, decoded_size, status, in_consumed,
-                                   n_streams, static_cast<hipStream_t>(stream));
+        return launch_decoded_size(ctx, dictionaries_len, dict_off, max_window_bits, in, in_off, in_len, limit, decoded_size, status,
+                                   in_consumed, n_streams, static_cast<hipStream_t>(stream));
 
     if (n_streams == 0) return TAMP_OK;
     // (no slab: out = out_off = null, the limits travel as the out_cap table; no dictionary bytes either, only their count)
-    const HostBatch b = {in, in_off, in_len, nullptr, nullptr, limit, decoded_size, status, in_consumed, n_streams};
+    HostBatch b = {in, in_off, in_len, nullptr, nullptr, limit, decoded_size, status, in_consumed, n_streams};
+    b.dict_off = dict_off;
     uint32_t* no_consumed = nullptr;
     return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
                           [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
-        return launch_decoded_size(ctx, dictionary_len, max_window_bits, s.in, s.in_off, s.in_len, s.out_cap, s.out_len, s.status,
-                                   in_consumed ? s.in_consumed : no_consumed, count, cs);
+        return launch_decoded_size(ctx, dictionaries_len, s.dict_off, max_window_bits, s.in, s.in_off, s.in_len, s.out_cap, s.out_len,
+                                   s.status, in_consumed ? s.in_consumed : no_consumed, count, cs);
     });
+}
+
+int tamp_batch_decoded_size(size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,
+                            const uint32_t* in_len, const uint32_t* limit, uint32_t* decoded_size, int8_t* status,
+                            uint32_t* in_consumed, size_t n_streams, int mem, int device, void* stream) {
+    return tamp_batch_decoded_size_dicts(dictionary_len, nullptr, max_window_bits, in, in_off, in_len, limit, decoded_size, status,
+                                         in_consumed, n_streams, mem, device, stream);
 }
 
 size_t tamp_amd_decoder_state_size(uint8_t window_bits_max) {

@@ -91,6 +91,12 @@ __host__ __device__ __forceinline__ void token_words(uint32_t v, uint32_t nb, ui
     *w_lo = __builtin_bswap32((uint32_t)x);
 }
 
+// Dictionary tables (the *_dicts calls): stream i's dictionary is the W bytes at `off` = dict_off[i] of a buffer of `len`
+// bytes.  Offsets are multiples of 16: the decoders seed their windows with 16-byte loads, the compress kernel with dwords.
+constexpr uint32_t kDictOffAlign = 16;
+__host__ __device__ constexpr bool dict_off_aligned(uint64_t off) { return (off & (kDictOffAlign - 1)) == 0; }
+__host__ __device__ constexpr bool dict_off_in_bounds(uint64_t off, uint32_t W, uint64_t len) { return off <= len && W <= len - off; }
+
 __host__ __device__ constexpr int min_pattern_size(int window, int literal) {
     return 2 + (window > 10 + 2 * (literal - 5));
 }

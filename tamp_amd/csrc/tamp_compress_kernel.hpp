@@ -63,7 +63,7 @@ struct CompressArgs {
     const uint32_t* out_cap;
     uint32_t* out_len;
     int8_t* status;
-    const uint8_t* dict;  // 1<<wbits bytes: the custom dictionary or the seeded default
+    const uint8_t* dict;  // 1<<wbits bytes: the custom dictionary or the seeded default; with `dict_off`, the buffer of dictionaries
     uint32_t n_streams;
     uint32_t first_stream;  // stream index of workgroup 0 (batches above 2^20 streams take several launches)
     uint32_t blk;  // epoch block: positions matched per epoch (multiple of 64)
@@ -87,7 +87,12 @@ struct CompressArgs {
     uint32_t n_blocks;
     uint8_t* blk_len;               // optional, n bytes: pass 1 leaves every position's match length here ...
     uint16_t* blk_idx;              // ... and its window index here, and pass 3 reads them instead of matching again
+    // DICTS builds (the *_dicts calls) -- last, and read by those builds alone: the others load the words in front and are what they
+    // were before the table existed
+    const uint64_t* dict_off;  // per stream (indexed like in_off): its dictionary starts at dict + dict_off[i], a multiple of 16
+    uint64_t dict_len;         // ... and ends within these bytes, or the stream is refused (kBadArgument, nothing read or written)
 };
+constexpr uint32_t kPlainArgWords = offsetof(CompressArgs, dict_off) / 4;
 
 // LDS carve-up, shared by the host launcher and the kernel.
 struct CompressLds {
@@ -833,8 +838,11 @@ static_assert(kLdsFixed.total == 19616 && kLdsFixed.tokcap == 1376 && kLdsFixed.
               "the fixed builds' LDS layout is the generic build's for window 2^10, block 1,024, 1,024 buckets");
 // (the body is this one function for every build; the two kernels behind it -- tamp_compress_kernel for the generic builds,
 // tamp_compress_fixed::compress_kernel for the fixed ones -- only name its instantiations)
-template <bool PACKED, bool LAZY, bool RUNS, uint32_t WSCAN, uint32_t HB, bool LOOP, bool BLOCKM, uint32_t FIX>
+// DICTS: a dictionary table (CompressArgs::dict_off) selects each stream's dictionary; the generic builds have a twin each
+// (tamp_compress_dict_kernel), the fixed-geometry builds none -- a table call at their geometry takes the generic twin.
+template <bool PACKED, bool LAZY, bool RUNS, uint32_t WSCAN, uint32_t HB, bool LOOP, bool BLOCKM, uint32_t FIX, bool DICTS = false>
 __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
+    static_assert(!DICTS || FIX == kFixNone, "table calls take the generic builds");
     static_assert(!BLOCKM || (LOOP && PACKED && !LAZY), "block mode: a persistent build of the default parse");
     // FX: constant geometry, no segment / piece machinery, constant format (made in these three steps: profiles/fixed_build_static.txt)
     constexpr bool FX = FIX != kFixNone;
@@ -884,7 +892,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         if constexpr (LOOP) {
             asm volatile("" : "+s"(ap));
 #pragma unroll
-            for (uint32_t i = 0; i < sizeof(CompressArgs) / 4; i++) aw.w[i] = ap[i];
+            for (uint32_t i = 0; i < (DICTS ? (uint32_t)(sizeof(CompressArgs) / 4) : kPlainArgWords); i++) aw.w[i] = ap[i];
         }
         CompressArgs a_l = __builtin_bit_cast(CompressArgs, aw);
         if constexpr (LOOP) {
@@ -896,6 +904,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             a_l.state = as_global(a_l.state), a_l.work_counter = as_global(a_l.work_counter), a_l.prof = as_global(a_l.prof);
             a_l.blk_table = as_global(a_l.blk_table), a_l.blk_info = as_global(a_l.blk_info);
             a_l.blk_len = as_global(a_l.blk_len), a_l.blk_idx = as_global(a_l.blk_idx);
+            if constexpr (DICTS) a_l.dict_off = as_global(a_l.dict_off);
         }
         const CompressArgs& a = LOOP ? a_l : a_k;
         const uint32_t a_wbits = FX ? kFixWbits : a.wbits, a_blk = FX ? kFixBlk : a.blk;
@@ -931,6 +940,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         uint32_t* const bins = reinterpret_cast<uint32_t*>(smem + L.ctl + 80);
         // prefix codes by symbol for per-lane look-ups (the packed 64-bit constants would sit in four VGPRs all kernel long)
         uint8_t* const codetab = smem + L.ctl + 80 + 256;
+        constexpr uint32_t kDictBadByte = 15;  // the table's spare 16th byte: this stream's dictionary-table row was refused
         uint32_t* const runs = reinterpret_cast<uint32_t*>(smem + L.runs);    // RUNS builds only
         uint32_t* const runsx = reinterpret_cast<uint32_t*>(smem + L.runsx);  // RUNS builds only
         uint32_t* const rxset = reinterpret_cast<uint32_t*>(smem + L.rxset);  // RUNS builds only
@@ -981,9 +991,19 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         // tables invariant): pin them to scalar registers, or the two base pointers sit in VGPR pairs -- and spill
         const uint32_t si = BLOCKM ? 0u : s;  // (block mode: `s` is the block, the tables have one row)
         const uint8_t* const in = a.in + uni_u64(a.in_off[si]);
-        const uint32_t n = Walk::uni(a.in_len[si]);
+        // the stream's dictionary: the call's, or its own row of the table.  A row that is misaligned or ends beyond the buffer
+        // makes the stream an empty one without room (no window load, no input read, no byte stored); its status follows at the
+        // end of the stream body, from a flag byte in LDS -- nothing of the test stays in registers across the body.
+        const uint8_t* sdict = a.dict;
+        bool dict_ok = true;
+        if constexpr (DICTS) {
+            const uint64_t off = uni_u64(a.dict_off[si]);
+            dict_ok = dict_off_aligned(off) && dict_off_in_bounds(off, W, a.dict_len);
+            sdict += dict_ok ? off : 0;
+        }
+        const uint32_t n = dict_ok ? Walk::uni(a.in_len[si]) : 0u;
         uint8_t* const gout = a.out + uni_u64(a.out_off[si]);
-        const uint32_t cap = Walk::uni(a.out_cap[si]);
+        const uint32_t cap = dict_ok ? Walk::uni(a.out_cap[si]) : 0u;
         const uint32_t bpos = BLOCKM ? s * a_blk : 0u;  // block mode: input position of this block
         unsigned long long binfo = 0;                   // ... and (pass 3) bit position << 4 | entry offset
         if constexpr (BLOCKM) {
@@ -999,18 +1019,20 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             // window <- the W bytes in front of the block, oldest first: input, or -- in front of the stream -- the dictionary
             // byte that still sits at that ring index (window_pos of a fresh stream = bytes written mod W)
             wp0 = bpos & mask;
-            for (uint32_t k = tid; k < W; k += nt) ebuf[k] = (bpos + k >= W) ? in[bpos + k - W] : a.dict[(bpos + k) & mask];
+            for (uint32_t k = tid; k < W; k += nt) ebuf[k] = (bpos + k >= W) ? in[bpos + k - W] : sdict[(bpos + k) & mask];
         } else
         if (st_io && (seg_flags & kSegResume)) {
             // window <- saved state (ring order) rotated so that the oldest byte comes first
             wp0 = (uint32_t)st_io[W + kSlotWindowPos] | ((uint32_t)st_io[W + kSlotWindowPos + 1] << 8);
             for (uint32_t k = tid; k < W; k += nt) ebuf[k] = st_io[(wp0 + k) & mask];
-        } else if (FX || (reinterpret_cast<uintptr_t>(a.dict) & 3) == 0) {
+        } else if (DICTS && !dict_ok) {
+            // (a refused table row: no dictionary to load, and no position to match against it)
+        } else if (FX || (reinterpret_cast<uintptr_t>(sdict) & 3) == 0) {
             // window <- dictionary (custom, or the seeded default prepared by the host shim)
             for (uint32_t k = tid * 4; k < W; k += nt * 4)
-                *reinterpret_cast<uint32_t*>(ebuf + k) = *reinterpret_cast<const uint32_t*>(a.dict + k);
+                *reinterpret_cast<uint32_t*>(ebuf + k) = *reinterpret_cast<const uint32_t*>(sdict + k);
         } else {
-            for (uint32_t k = tid; k < W; k += nt) ebuf[k] = a.dict[k];
+            for (uint32_t k = tid; k < W; k += nt) ebuf[k] = sdict[k];
         }
         // carried over from a call that ended without a flush (kSegStateExtra): pending run / extended match, pending bits
         uint32_t c_rle = 0, c_ext = 0, c_extpos = 0, c_nbits = 0, c_bits = 0;
@@ -1037,6 +1059,8 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         wk.ctlw = (Walk::CtlWord*)ctl, wk.coop = nt == 256;
         wk.lazy = lazy, wk.lazy_valid = false, wk.lazy_idx = 0, wk.lazy_len = 0, wk.blen2 = blen2, wk.bidx2 = bidx2;
         if (tid_k == 0) ctl[cCutThr] = (FIX == kFixV1) ? 0u : a.cut_run;  // (read after the load phase's barrier)
+        // (the byte behind the 15 prefix codes: every control word has a second use during the walk; read by the same thread, behind the stream)
+        if (DICTS && !BLOCKM && tid_k == 0) codetab[kDictBadByte] = dict_ok ? 0 : 1;
         uint32_t w_p0 = bpos;  // wave 0: input position of ebuf[W]
 
         // workgroup-uniform output state
@@ -2330,6 +2354,11 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
             __syncthreads();
         }
         TAMP_PROF_ONLY(if (tid == 0 && a.prof) for (int i = 0; i < 16; i++) atomicAdd(&a.prof[i], pt[i]);)
+        if constexpr (DICTS && !BLOCKM) {
+            // a refused dictionary-table row (see the stream's prologue): the empty stream's status gives way to the refusal
+            // (block mode: the launcher checks the row before it spreads the stream)
+            if (tid_k == 0 && codetab[kDictBadByte]) a.out_len[s] = 0, a.status[s] = kBadArgument;
+        }
         if constexpr (LOOP) {
             // the next stream of this workgroup's current claim, or the first of the next claim of a.claim consecutive
             // streams (1 for long streams; short ones are claimed sixteen at a time: fewer fetches from the one counter).
@@ -2355,6 +2384,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
 template <bool PACKED, bool LAZY, bool RUNS = false, uint32_t WSCAN = 0, uint32_t HB = kHashBits, bool LOOP = false, bool BLOCKM = false>
 __global__ void __launch_bounds__(256, LAZY ? kLazyPerCu : (RUNS ? kWgPerCu : kLeanPerCu)) tamp_compress_kernel(CompressArgs a_k) {
     compress_streams<PACKED, LAZY, RUNS, WSCAN, HB, LOOP, BLOCKM, kFixNone>(a_k);
+}
+
+// the DICTS twins of the generic builds (a name of their own: the plain builds keep theirs, and their code)
+template <bool PACKED, bool LAZY, bool RUNS = false, uint32_t WSCAN = 0, uint32_t HB = kHashBits, bool LOOP = false, bool BLOCKM = false>
+__global__ void __launch_bounds__(256, LAZY ? kLazyPerCu : (RUNS ? kWgPerCu : kLeanPerCu)) tamp_compress_dict_kernel(CompressArgs a_k) {
+    compress_streams<PACKED, LAZY, RUNS, WSCAN, HB, LOOP, BLOCKM, kFixNone, true>(a_k);
 }
 
 namespace tamp_compress_fixed {

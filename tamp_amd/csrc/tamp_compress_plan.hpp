@@ -22,6 +22,7 @@ struct CompressCall {
     uint8_t seg_flags;    // kSegResume | kSegSave | kSegFlushToken | kSegPartial
     uintptr_t dict;       // device address of the custom dictionary, 0 without one (the seeded tables are aligned)
     bool has_state, block_mode;  // a per-stream window state is passed; launch_compress_blocks: a long stream over all workgroups
+    bool dict_table = false;     // a *_dicts call: `dict` is the buffer of dictionaries, every stream has a row in dict_off
 };
 static inline CompressCall compress_call(const TampAmdConf* conf, uint32_t max_in_len, uintptr_t dictionary_address) {
     const bool reset = conf->dictionary_reset != 0;
@@ -32,7 +33,20 @@ static inline CompressCall compress_call(const TampAmdConf* conf, uint32_t max_i
 // Every build of the compress kernel the library launches (the table of DESIGN.md 3.2), and the one place that names them.
 enum class CompressBuild : uint8_t { kShortLean, kLeanU16, kLazyPacked, kLazyU16, kRuns, kRuns1024, kFixedExt, kFixedV1,
                                      kBlockLean, kBlockRuns, kBlockRuns1024 };
-static inline auto compress_kernel_of(CompressBuild b) -> void (*)(CompressArgs) {
+// `dicts`: the build's twin for a dictionary-table call (the fixed-geometry builds have none: fixed_build_for keeps such calls generic)
+static inline auto compress_kernel_of(CompressBuild b, bool dicts = false) -> void (*)(CompressArgs) {
+    if (dicts) switch (b) {
+        case CompressBuild::kShortLean: return tamp_compress_dict_kernel<true, false, false, 0, 9>;
+        case CompressBuild::kLeanU16: return tamp_compress_dict_kernel<false, false, false, 0, kHashBits, true>;
+        case CompressBuild::kLazyPacked: return tamp_compress_dict_kernel<true, true, false, 0, kHashBits, true>;
+        case CompressBuild::kLazyU16: return tamp_compress_dict_kernel<false, true, false, 0, kHashBits, true>;
+        case CompressBuild::kRuns: return tamp_compress_dict_kernel<true, false, true, 0, kHashBits, true>;
+        case CompressBuild::kRuns1024: return tamp_compress_dict_kernel<true, false, true, 1024, kHb1024, true>;
+        case CompressBuild::kBlockLean: return tamp_compress_dict_kernel<true, false, false, 0, kHashBits, true, true>;
+        case CompressBuild::kBlockRuns: return tamp_compress_dict_kernel<true, false, true, 0, kHashBits, true, true>;
+        case CompressBuild::kBlockRuns1024: return tamp_compress_dict_kernel<true, false, true, 1024, kHb1024, true, true>;
+        case CompressBuild::kFixedExt: case CompressBuild::kFixedV1: return nullptr;
+    }
     switch (b) {
         case CompressBuild::kShortLean: return tamp_compress_kernel<true, false, false, 0, 9>;  // (512 buckets, one wavefront)
         case CompressBuild::kLeanU16: return tamp_compress_kernel<false, false, false, 0, kHashBits, true>;
@@ -59,6 +73,7 @@ struct CompressPlan {  // (in the order plan_compress decides them)
     CompressBuild build;       // (tamp_amd_compress_build derives its TAMP_AMD_BUILD_* from it)
     bool persistent;           // as many workgroups as the device holds, claiming streams from a work counter
     uint32_t claim;            // ... this many per fetch
+    bool dicts;                // a dictionary-table call: the build's DICTS twin (compress_kernel_of(build, dicts))
 };
 
 // Workgroups per CU: what the registers allow (8 for the run-aware builds, 6 lean, 5 lazy), and the estimate for a layout of `lds`
@@ -101,7 +116,7 @@ static inline uint32_t compress_threads(uint32_t blk, bool long_streams, bool bl
 // else, and with TAMP_AMD_FIXED_BUILD=0 (`fixed_env`: A/B runs, parity tests), the generic build plan_compress has put into `p`.
 static inline CompressBuild fixed_build_for(const CompressCall& c, const CompressPlan& p, const char* fixed_env) {
     const TampAmdConf* conf = c.conf;
-    const bool fits = !c.block_mode && !(fixed_env && atoi(fixed_env) == 0) && conf->window == kFixWbits && conf->literal == kFixLbits &&
+    const bool fits = !c.block_mode && !c.dict_table && !(fixed_env && atoi(fixed_env) == 0) && conf->window == kFixWbits && conf->literal == kFixLbits &&
                       !p.lazy && p.runlist && p.blk == kFixBlk && p.threads == kFixThreads && !c.has_state && c.seg_flags == 0 &&
                       !conf->dictionary_reset && c.nlead == 1 && c.lead == header_byte(conf, false) << 8 && (c.dict & 3) == 0;
     return !fits ? p.build : (conf->extended ? CompressBuild::kFixedExt : CompressBuild::kFixedV1);
@@ -135,6 +150,7 @@ static inline CompressPlan plan_compress(const CompressCall& c) {
     // All but the short-message build run as a PERSISTENT GRID (LOOP in the kernel).  Streams per fetch: one for
     // 256-thread workgroups (1 KiB and more; block mode's blocks), sixteen for one-wavefront ones (lazy / 2^15 / hinted short).
     p.persistent = p.build != B::kShortLean, p.claim = (!p.persistent || p.threads == 256) ? 1u : 16u;
+    p.dicts = c.dict_table;
     return p;
 }
 

@@ -28,6 +28,17 @@ __host__ __device__ inline StreamHeader decode_header(uint32_t h0) {
     return h;
 }
 
+// The custom dictionary of stream `s`, whose header asks for one: the call's buffer, or -- with a table (the *_dicts calls) -- the
+// W bytes at dict_off[s] of it.  -> kOk and *off, or the stream's status: kBadArgument for a misaligned row, kInvalidConf where
+// W bytes are not there (what too short a shared dictionary gets, decompressor.c:304-329).  `have`: a buffer was passed (the
+// size query has its length alone).  Nothing is read through a refused row.
+__device__ __forceinline__ int custom_dict_offset(bool have, uint64_t dict_len, const uint64_t* dict_off, uint32_t s, uint32_t W, uint64_t* off) {
+    const uint64_t o = dict_off ? dict_off[s] : 0;
+    *off = o;
+    if (!dict_off_aligned(o)) return kBadArgument;  // (a call without a table: o = 0)
+    return (have && dict_off_in_bounds(o, W, dict_len)) ? kOk : kInvalidConf;
+}
+
 // Prefix-code LUT, 128 bytes: index = the 7 bits after the leading 1 of a code word -> (extra bits << 4) | symbol
 // (decompressor.c:52-57 restated from the code table).  Filled by the whole workgroup; the caller synchronises.
 __device__ __forceinline__ void build_prefix_lut(uint8_t* lut) {

@@ -34,8 +34,9 @@ struct DecompressArgs {
     uint32_t* out_len;
     int8_t* status;
     uint32_t* in_consumed;      // may be null
-    const uint8_t* dict;        // custom dictionary (>= 1<<window bytes) or null
-    uint32_t dict_len;
+    const uint8_t* dict;        // custom dictionary (>= 1<<window bytes) or null; with `dict_off`, the buffer of dictionaries
+    uint64_t dict_len;
+    const uint64_t* dict_off;   // null, or per stream: a stream with the custom bit starts from dict + dict_off[s] (a multiple of 16)
     const uint8_t* seed_dicts;  // 3 tables of 1<<15 bytes: literal<=5, literal==6, literal>=7 (common.c:18-25)
     uint8_t* scratch;           // global variant: one window slot of (1 << max_wbits) bytes per resident lane
     const uint8_t* only_flagged;  // null, or one byte per stream: decode only the streams whose byte is set (what the
@@ -149,8 +150,9 @@ __global__ void __launch_bounds__(LDSWIN ? 64 : 256, BULK ? 5 : 1) tamp_decompre
             const uint8_t* const seed_default = a.seed_dicts + ((size_t)hd.table << 15);
             const uint8_t* seed = seed_default;
             if (hd.custom) {
-                if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
-                seed = a.dict;
+                uint64_t doff;
+                if (const int rc = custom_dict_offset(a.dict != nullptr, a.dict_len, a.dict_off, s, W, &doff)) { res = rc; break; }
+                seed = a.dict + doff;
             }
             // window[i] is the private copy once it has been written, the shared dictionary before that
             uint32_t filled = 0;  // slots [0, filled) are private (saturates at W)

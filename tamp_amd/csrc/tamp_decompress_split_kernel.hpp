@@ -124,7 +124,8 @@ __device__ __forceinline__ void parse_stream(const SplitArgs& sa, const uint8_t*
         const uint32_t W = 1u << wbits, mask = W - 1;
         dict_sel = hd.table;
         if (hd.custom) {
-            if ((kRecords && !a.dict) || a.dict_len < W) { res = kInvalidConf; break; }
+            uint64_t doff;  // (the resolve reads the row again)
+            if (const int rc = custom_dict_offset(!kRecords || a.dict, a.dict_len, a.dict_off, s, W, &doff)) { res = rc; break; }
             dict_sel = 3;
         }
         if constexpr (kRecords) {
@@ -428,7 +429,7 @@ __global__ void __launch_bounds__(256) tamp_decode_resolve_kernel(SplitArgs sa) 
     if (n_out == 0) return;
     const uint32_t ntok = meta & 0xFFFFFu, wbits = 8 + ((meta >> 20) & 7), dict_sel = (meta >> 23) & 3, nlag = (meta >> 25) & 63;
     const uint32_t W = 1u << wbits, mask = W - 1;
-    const uint8_t* const dict = dict_sel == 3 ? a.dict : a.seed_dicts + ((size_t)dict_sel << 15);
+    const uint8_t* const dict = dict_sel == 3 ? a.dict + (a.dict_off ? a.dict_off[s] : 0) : a.seed_dicts + ((size_t)dict_sel << 15);
     const uint32_t* const rec = sa.recs + (size_t)k * sa.tokcap;
 
     constexpr uint32_t nt = NT;  // (a constant keeps divisions by it shifts)

@@ -135,8 +135,9 @@ __global__ void __launch_bounds__(256) tamp_decompress_wave_kernel(DecompressArg
             const uint8_t* const seed_default = a.seed_dicts + ((size_t)hd.table << 15);
             const uint8_t* seed = seed_default;
             if (hd.custom) {
-                if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
-                seed = a.dict;
+                uint64_t doff;
+                if (const int rc = custom_dict_offset(a.dict != nullptr, a.dict_len, a.dict_off, s, W, &doff)) { res = rc; break; }
+                seed = a.dict + doff;
             }
             auto load_window = [&](const uint8_t* src) {
                 if ((reinterpret_cast<uintptr_t>(src) & 3) == 0) {
