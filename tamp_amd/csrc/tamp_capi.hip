@@ -223,6 +223,35 @@ struct SegmentSpec {  // streaming Compressor over the engine: how this piece of
     uint8_t flags;  // kSegResume | kSegSave | kSegFlushToken | kSegPartial
 };
 
+// The per-stream tables of a batch call, from the C entry points down to the kernels' argument blocks: one row per stream, the
+// data buffers the offsets point into, the dictionary bytes.  The pointers are the caller's (host or device memory, as the call
+// says) or, inside the host pipeline, one chunk's staging buffers.  A column is added here, in rows() and in the *_args functions.
+struct BatchTables {
+    const uint8_t* in = nullptr;
+    const uint64_t* in_off = nullptr;
+    const uint32_t* in_len = nullptr;
+    uint8_t* out = nullptr;              // null, with out_off: the size query (out_cap holds the limits, may be null)
+    const uint64_t* out_off = nullptr;
+    const uint32_t* out_cap = nullptr;
+    uint32_t* out_len = nullptr;
+    int8_t* status = nullptr;
+    uint32_t* in_consumed = nullptr;     // may be null
+    const uint64_t* dict_off = nullptr;  // the *_dicts calls, else null: stream i's dictionary is dict + dict_off[i], inside dict_len bytes
+    const uint8_t* dict = nullptr;
+    size_t dict_len = 0;
+    size_t n = 0;
+    // Rows [i0, i0 + count): every table shifted, null tables stay null, the data pointers stay (offsets are absolute).  The only
+    // place where a table pointer is advanced by a stream index.
+    BatchTables rows(size_t i0, size_t count) const {
+        BatchTables t = *this;
+        auto shift = [i0](auto*& p) { if (p) p += i0; };
+        shift(t.in_off), shift(t.in_len), shift(t.out_off), shift(t.out_cap), shift(t.out_len), shift(t.status);
+        shift(t.in_consumed), shift(t.dict_off);
+        t.n = count;
+        return t;
+    }
+};
+
 // Expensive streams first (round 5).  One stream = one workgroup, so a batch cannot finish before its slowest stream does, and
 // a batch of only a few rounds of the persistent grid -- 3,052 streams per GPU when BASELINE configs[2] runs on eight -- waits
 // for whichever slow stream happened to start last.  What makes a stream slow are its lags and searches, and a
@@ -375,11 +404,18 @@ __global__ void __launch_bounds__(256) tamp_block_scan_kernel(const uint32_t* ta
     for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) info[b0 + i] = res[i];
 }
 
-// The kernel's argument block as conf, the call's lead and the dictionary decide it.  The caller adds the batch's tables, the plan
-// the block and the claim.  (Value-initialised: no work counter, first stream 0, none of the block-mode tables.)
-CompressArgs fill_compress_args(const DeviceCtx* ctx, const CompressCall& call, const uint8_t* d_dict, uint8_t* d_state) {
+// The kernel's argument block as conf, the call's lead, the dictionary and the batch's tables decide it.  The plan adds the block
+// and the claim.  (Value-initialised: no work counter, first stream 0, none of the block-mode tables.)
+void set_tables(CompressArgs& a, const BatchTables& t) {
+    a.in = t.in, a.in_off = t.in_off, a.in_len = t.in_len, a.n_streams = (uint32_t)t.n;
+    a.out = t.out, a.out_off = t.out_off, a.out_cap = t.out_cap, a.out_len = t.out_len, a.status = t.status;
+    a.dict_off = t.dict_off, a.dict_len = t.dict_len;
+}
+CompressArgs fill_compress_args(const DeviceCtx* ctx, const CompressCall& call, const BatchTables& t, uint8_t* d_state) {
     const TampAmdConf* conf = call.conf;
+    const uint8_t* const d_dict = t.dict;
     CompressArgs a = {};
+    set_tables(a, t);
     a.wbits = conf->window, a.lbits = conf->literal, a.extended = conf->extended != 0;
     a.dict_reset = conf->dictionary_reset != 0, a.lazy = conf->lazy_matching != 0, a.prof = g_prof, a.claim = 1;
     a.nlead = call.nlead, a.lead = call.lead, a.seg_flags = call.seg_flags, a.state = call.has_state ? d_state : nullptr;
@@ -417,9 +453,10 @@ int launch_on_counter(DeviceCtx* ctx, const CompressPlan& p, uint32_t grid, Comp
 
 // Block mode (the BLOCKM builds of the compress kernel): ONE long stream of the v1 format, literal 8, default parse, fresh window.
 // -> TAMP_OK when the stream was taken this way, 1 when the call does not qualify (the caller goes on with the batch kernel).
-// `rec`: the stream's scratch record, locked by the caller.
-int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, CompressCall call, hipStream_t st, size_t n_streams) {
+// `rec`: the stream's scratch record, locked by the caller.  `a0`: the batch's argument block (its tables are those of `t`).
+int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, const BatchTables& t, CompressCall call, hipStream_t st) {
     const TampAmdConf* conf = call.conf;
+    const size_t n_streams = t.n;
     uint32_t min_len = 256u << 10;
     if (const char* e = getenv("TAMP_AMD_BLOCK_MIN")) min_len = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;  // (tuning / tests; 0 = off)
     if (conf->extended || conf->lazy_matching || conf->literal != 8 || conf->window > 14 || call.has_state || call.seg_flags ||
@@ -429,17 +466,17 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     // streams is taken one after the other, each over all workgroups -- any shorter one among them and the batch kernel takes all
     uint64_t in_off[64], out_off[64], dict_off[64];
     uint32_t in_len[64], out_cap[64];
-    if (a0.dict_off) HIP_OK(hipMemcpyAsync(dict_off, a0.dict_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(in_off, a0.in_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(out_off, a0.out_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(in_len, a0.in_len, 4 * n_streams, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(out_cap, a0.out_cap, 4 * n_streams, hipMemcpyDeviceToHost, st));
+    if (t.dict_off) HIP_OK(hipMemcpyAsync(dict_off, t.dict_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(in_off, t.in_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out_off, t.out_off, 8 * n_streams, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(in_len, t.in_len, 4 * n_streams, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out_cap, t.out_cap, 4 * n_streams, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     uint32_t n_max = 0;
     for (size_t i = 0; i < n_streams; i++) {
         if (in_len[i] < min_len) return 1;
         // (a dictionary-table row the batch kernel would refuse: the batch kernel refuses it)
-        if (a0.dict_off && !(dict_off_aligned(dict_off[i]) && dict_off_in_bounds(dict_off[i], 1u << conf->window, a0.dict_len))) return 1;
+        if (t.dict_off && !(dict_off_aligned(dict_off[i]) && dict_off_in_bounds(dict_off[i], 1u << conf->window, t.dict_len))) return 1;
         n_max = std::max(n_max, in_len[i]);
     }
     call.block_mode = true;
@@ -462,8 +499,7 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     timing_begin(st);
     for (size_t i = 0; i < n_streams; i++) {
         CompressArgs a = a0;
-        a.in_off += i, a.in_len += i, a.out_off += i, a.out_cap += i, a.out_len += i, a.status += i;  // (the kernel reads row 0)
-        if (a.dict_off) a.dict_off += i;
+        set_tables(a, t.rows(i, 1));  // (the kernel reads row 0; n_streams: the blocks, below)
         const uint32_t n = in_len[i];
         const uint32_t n_blocks = (n + a.blk - 1) / a.blk;
         const uint32_t n_chunks = (n_blocks + kScanChunk - 1) / kScanChunk;
@@ -491,24 +527,19 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
     return TAMP_OK;
 }
 
-// `d_dict_off` (the *_dicts calls, else null): stream i's dictionary is d_dict + d_dict_off[i], inside dict_len bytes.
-int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_dict, const uint8_t* d_in,
-                    const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
-                    const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, size_t n_streams,
-                    uint32_t max_in_len, hipStream_t st, const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr,
-                    const uint64_t* d_dict_off = nullptr, size_t dict_len = 0) {
+// `t`: device memory.  `seg` / `d_state`: a piece of one stream (segment_core), its state row.
+int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len, hipStream_t st,
+                    const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr) {
+    const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
-    CompressCall call = compress_call(conf, max_in_len, reinterpret_cast<uintptr_t>(d_dict));
+    CompressCall call = compress_call(conf, max_in_len, reinterpret_cast<uintptr_t>(t.dict));
     if (seg) call.nlead = seg->nlead, call.lead = seg->lead, call.seg_flags = seg->flags, call.has_state = d_state != nullptr;
-    call.dict_table = d_dict_off != nullptr;
-    CompressArgs a = fill_compress_args(ctx, call, d_dict, d_state);
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len, a.n_streams = (uint32_t)n_streams;
-    a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
-    a.dict_off = d_dict_off, a.dict_len = dict_len;
+    call.dict_table = t.dict_off != nullptr;
+    CompressArgs a = fill_compress_args(ctx, call, t, d_state);
     if (n_streams <= 64 && !seg) {  // a handful of LONG v1 streams: each one's blocks over all workgroups (the BLOCKM builds)
-        const int rc = launch_compress_blocks(ctx, rec, a, call, st, n_streams);
+        const int rc = launch_compress_blocks(ctx, rec, a, t, call, st);
         if (rc != 1) return rc;
     }
     const CompressPlan p = plan_compress(call);  // (build, block, LDS layout, workgroup, grid: tamp_compress_plan.hpp)
@@ -580,7 +611,7 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_di
         if (const int rc = launch_on_counter(ctx, p, (uint32_t)g, a, st)) return rc;
         if (lpt) {
             hipLaunchKernelGGL(tamp_scatter_results_kernel, dim3((uint32_t)((n_streams + 255) / 256)), dim3(256), 0, st, lpt_order,
-                               (uint32_t)n_streams, lpt_out_len, lpt_status, d_out_len, d_status);
+                               (uint32_t)n_streams, lpt_out_len, lpt_status, t.out_len, t.status);
         }
     } else {
         timing_begin(st);
@@ -640,6 +671,24 @@ __global__ void tamp_header_scan_kernel(const uint8_t* in, const uint64_t* in_of
     }
 }
 
+// The decoders' argument block from the batch's tables: no scratch, no flagged list, the plan's fields unset.  What a caller passes
+// differently (no dictionary for the object calls, a window limit) it says at the call.
+DecompressArgs decompress_args(const DeviceCtx* ctx, const BatchTables& t) {
+    DecompressArgs a;
+    a.in = t.in, a.in_off = t.in_off, a.in_len = t.in_len;
+    a.out = t.out, a.out_off = t.out_off, a.out_cap = t.out_cap, a.out_len = t.out_len, a.status = t.status;
+    a.in_consumed = t.in_consumed;
+    a.dict = t.dict, a.dict_len = t.dict_len, a.dict_off = t.dict_off;
+    a.seed_dicts = ctx->seed_dicts;
+    a.scratch = nullptr;
+    a.only_flagged = nullptr;
+    a.flagged_count = nullptr;
+    a.n_streams = (uint32_t)t.n;
+    a.lds_row = 0;
+    a.max_wbits = 0;
+    return a;
+}
+
 // The front of the long-stream path (tamp_decompress_long_kernel.hpp), shared by the decoder and the size query: header read and
 // gates, the tables of the settle rounds and the count pass (with_records: the decoder's records and group tables behind them), the
 // tamp_long_sync_kernel rounds, and tamp_long_parse_kernel with write = 0 -- tokens and output bytes per chunk.
@@ -662,26 +711,26 @@ static int long_declined(bool dbg, const char* who, const char* why) {
     return 1;
 }
 // -> 1 when the stream is not one for this path (or anything is off: the exact decoders take it), TAMP_OK with `f` filled in and
-// timing begun, an error code otherwise.  `who` names the caller in the debug lines.  d_out_off / d_cap may be null.
-int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, bool has_dict, size_t dict_len,
-                      const uint64_t* d_dict_off, uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                      const uint64_t* d_out_off, const uint32_t* d_cap, bool with_records, const char* who, hipStream_t st, LongFront& f) {
+// timing begun, an error code otherwise.  `who` names the caller in the debug lines.  `t`: the stream's single row; out_off and
+// out_cap may be null.  `has_dict`: a stream with the custom bit has a dictionary (the size query: its length alone, t.dict is null).
+int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const BatchTables& t, bool has_dict, uint8_t max_wbits,
+                      bool with_records, const char* who, hipStream_t st, LongFront& f) {
     uint64_t in_off = 0, out_off = 0, dict_off = 0;  // (dict_off: the stream's row of a dictionary table, 0 without one)
     uint32_t n = 0, cap = 0xFFFFFFFFu;
-    HIP_OK(hipMemcpyAsync(&n, d_in_len, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&n, t.in_len, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     // (the chunk kernels count bits in 32-bit registers: (i + 1) * kLongChunkBits wraps for the last chunk of the top 512 bytes of
     // the accepted range -- those streams stay with the exact decoder)
     if (n < gate.min_len || n > kMaxDecodeIn - 512) return 1;
     const bool dbg = f.dbg = getenv("TAMP_AMD_LONGDEC_DEBUG") != nullptr;
-    HIP_OK(hipMemcpyAsync(&in_off, d_in_off, 8, hipMemcpyDeviceToHost, st));
-    if (d_out_off) HIP_OK(hipMemcpyAsync(&out_off, d_out_off, 8, hipMemcpyDeviceToHost, st));
-    if (d_cap) HIP_OK(hipMemcpyAsync(&cap, d_cap, 4, hipMemcpyDeviceToHost, st));
-    if (d_dict_off) HIP_OK(hipMemcpyAsync(&dict_off, d_dict_off, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&in_off, t.in_off, 8, hipMemcpyDeviceToHost, st));
+    if (t.out_off) HIP_OK(hipMemcpyAsync(&out_off, t.out_off, 8, hipMemcpyDeviceToHost, st));
+    if (t.out_cap) HIP_OK(hipMemcpyAsync(&cap, t.out_cap, 4, hipMemcpyDeviceToHost, st));
+    if (t.dict_off) HIP_OK(hipMemcpyAsync(&dict_off, t.dict_off, 8, hipMemcpyDeviceToHost, st));
     uint8_t hdr[2] = {0, 0};
-    HIP_OK(hipMemcpyAsync(hdr, d_in + in_off, 2, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(hdr, t.in + in_off, 2, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    const uint8_t* const in = d_in + in_off;
+    const uint8_t* const in = t.in + in_off;
     const StreamHeader hd = decode_header(hdr[0]);
     const uint32_t hs = 1 + (hdr[0] & 1), wbits = hd.wbits, lbits = hd.lbits;
     const bool extended = hd.extended;
@@ -689,9 +738,9 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     if (extended && !gate.extended) return long_declined(dbg, who, "extended off");  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
     // (its own row's length; a misaligned row is the exact decoders' to report as well)
-    if (hd.custom && (!has_dict || !dict_off_aligned(dict_off) || !dict_off_in_bounds(dict_off, W, dict_len))) return long_declined(dbg, who, "dictionary");
+    if (hd.custom && (!has_dict || !dict_off_aligned(dict_off) || !dict_off_in_bounds(dict_off, W, t.dict_len))) return long_declined(dbg, who, "dictionary");
     f.n = n, f.cap = cap, f.out_off = out_off, f.in = in, f.hd = hd, f.hs = hs;
-    f.dict0 = hd.custom ? d_dict + dict_off : ctx->seed_dicts + ((size_t)hd.table << 15);
+    f.dict0 = hd.custom ? t.dict + dict_off : ctx->seed_dicts + ((size_t)hd.table << 15);
 
     const uint64_t total_bits = 8ull * n;
     const uint32_t chunk_bits = extended ? kLongChunkBitsExt : kLongChunkBits;
@@ -774,17 +823,14 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
 // records per chunk, then the split decoder's RESOLVE over groups of at most kSplitMaxOut output bytes, in order, each with the
 // W bytes in front of it as its dictionary.  -> 1 when the call is not one (or anything is off: the exact decoders take it),
 // TAMP_OK when the stream has been decoded, an error code otherwise.  Nothing is written before the fall-back decision.
-int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const uint8_t* d_dict, size_t dict_len,
-                           const uint64_t* d_dict_off, uint8_t max_wbits,
-                           const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
-                           const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed, hipStream_t st) {
+// `t`: the stream's single row.
+int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
     LongFront f;
-    if (const int rc = long_decode_front(ctx, rec, gate, d_dict, d_dict != nullptr, dict_len, d_dict_off, max_wbits, d_in, d_in_off, d_in_len, d_out_off,
-                                         d_out_cap, true, "decode", st, f); rc != TAMP_OK) return rc;
+    if (const int rc = long_decode_front(ctx, rec, gate, t, t.dict != nullptr, max_wbits, true, "decode", st, f); rc != TAMP_OK) return rc;
     const uint32_t n = f.n, cap = f.cap, N = f.N, wbits = f.hd.wbits, W = 1u << wbits, lg = f.lg;
     const uint64_t out_off = f.out_off;
     const bool extended = f.hd.extended, dbg_long = f.dbg;
-    uint8_t* const out = d_out + out_off;
+    uint8_t* const out = t.out + out_off;
     const uint8_t* const dict0 = f.dict0;
     LongArgs& la = f.la;
     uint32_t* const recs = la.recs;
@@ -940,16 +986,15 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         hipLaunchKernelGGL(tamp_long_tail_scan_kernel<1>, dim3(1), dim3(kLongScanThreads), 2 * W, st, sc);
         hipLaunchKernelGGL(tamp_long_tail_scan_kernel<2>, dim3((uint32_t)n_blocks), dim3(kLongScanThreads), 2 * W, st, sc);
         hipLaunchKernelGGL(k_finish, dim3((uint32_t)G), dim3(256), long_resolve_lds(), st, ra);
-        hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, d_out_len, d_status, d_consumed, (uint32_t)v, n);
+        hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, t.out_len, t.status, t.in_consumed, (uint32_t)v, n);
         timing_end(st);
         HIP_OK(hipGetLastError());
         return TAMP_OK;
     }
     SplitArgs sa;
     DecompressArgs& a = sa.d;
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len, a.out = d_out, a.out_cap = d_out_cap, a.status = d_status;
-    a.in_consumed = nullptr, a.dict_len = W, a.dict_off = nullptr, a.seed_dicts = ctx->seed_dicts, a.scratch = nullptr, a.only_flagged = nullptr;
-    a.flagged_count = nullptr, a.n_streams = 1, a.lds_row = 0, a.max_wbits = (uint8_t)wbits;
+    a = decompress_args(ctx, t);  // (per group below: its window as the dictionary, its own output offset and length)
+    a.in_consumed = nullptr, a.dict_len = W, a.dict_off = nullptr, a.max_wbits = (uint8_t)wbits;
     sa.lag = nullptr, sa.flagged = nullptr, sa.flagged_count = nullptr, sa.maxcap = kSplitMaxOut, sa.first = 0, sa.count = 1, sa.spw = 64;
     const uint32_t lds = split_resolve_lds(kSplitMaxOut);
     auto resolve_kernel = tamp_decode_resolve_kernel<256, 4>;
@@ -972,7 +1017,7 @@ int launch_decompress_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong&
         sa.tokcap = gr.ntok > 2048 ? gr.ntok : 2048;
         hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(256), lds, st, sa);
     }
-    hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, d_out_len, d_status, d_consumed, (uint32_t)v, n);
+    hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, t.out_len, t.status, t.in_consumed, (uint32_t)v, n);
     timing_end(st);
     HIP_OK(hipGetLastError());
     return TAMP_OK;
@@ -1075,43 +1120,31 @@ int run_decode_plan(DeviceCtx* ctx, StreamScratch& rec, DecompressArgs a, const 
     return TAMP_OK;
 }
 
-// `d_dict_off` (the *_dicts calls, else null): a stream with the custom bit starts from d_dict + d_dict_off[i], inside dict_len bytes.
-int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, const uint64_t* d_dict_off, uint8_t max_wbits, const uint8_t* d_in,
-                      const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out, const uint64_t* d_out_off,
-                      const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status, uint32_t* d_consumed,
-                      size_t n_streams, hipStream_t st) {
+// A handful of long streams, one after the other, each as a single-row record with the whole device (`one`: the long decoder or
+// its size query).  One event pair around all of them: kernel_ms of a call with several long streams is the sum, not the last
+// stream's.  -> TAMP_OK: all taken; 1: a stream is not one for this path (too short, ...), and the caller's exact path takes the WHOLE
+// call, answering for every stream again; an error code otherwise.
+template <class One>  // One(const BatchTables& row) -> TAMP_OK, 1 or an error code
+int each_long_stream(const BatchTables& t, hipStream_t st, const One& one) {
+    timing_begin(st);
+    t_timing_outer = true;
+    int rc = TAMP_OK;
+    for (size_t i = 0; i < t.n && rc == TAMP_OK; i++) rc = one(t.rows(i, 1));
+    t_timing_outer = false;
+    return rc;
+}
+
+// `t`: device memory.  A stream with the custom bit starts from its row of the dictionary table, or from t.dict without one.
+int launch_decompress(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
+    const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
-    DecompressArgs a;
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
-    a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
-    a.in_consumed = d_consumed;
-    a.dict = d_dict, a.dict_len = dict_len, a.dict_off = d_dict_off;
-    a.seed_dicts = ctx->seed_dicts;
-    a.scratch = nullptr;
-    a.only_flagged = nullptr;
-    a.flagged_count = nullptr;
-    a.n_streams = (uint32_t)n_streams;
-    a.lds_row = 0;
+    const DecompressArgs a = decompress_args(ctx, t);
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
-    const DecodeCall call = {n_streams, max_wbits, d_dict != nullptr};
-    if (const DecodeLong gate = decode_wants_long(call); gate.attempt) {
-        // one long v1 stream -- or a handful, one after the other: the whole device each (tamp_decompress_long_kernel.hpp).  A stream
-        // that is not one (too short, extended, ...) sends the whole call to the decoders below, which write every stream again.
-        // (one event pair around all of them: kernel_ms of a call with several long streams is the sum, not the last stream's)
-        size_t done = 0;
-        timing_begin(st);
-        t_timing_outer = true;
-        int rc = TAMP_OK;
-        for (; done < n_streams; done++) {
-            rc = launch_decompress_long(ctx, rec, gate, d_dict, dict_len, d_dict_off ? d_dict_off + done : nullptr, max_wbits, d_in, d_in_off + done, d_in_len + done, d_out,
-                                        d_out_off + done, d_out_cap + done, d_out_len + done, d_status + done,
-                                        d_consumed ? d_consumed + done : nullptr, st);
-            if (rc != TAMP_OK) break;
-        }
-        t_timing_outer = false;
-        if (rc != TAMP_OK && rc != 1) return rc;
-        if (done == n_streams) return TAMP_OK;
+    const DecodeCall call = {n_streams, max_wbits, t.dict != nullptr};
+    if (const DecodeLong gate = decode_wants_long(call); gate.attempt) {  // (tamp_decompress_long_kernel.hpp)
+        const int rc = each_long_stream(t, st, [&](const BatchTables& row) { return launch_decompress_long(ctx, rec, gate, row, max_wbits, st); });
+        if (rc != 1) return rc;
     }
     DecodeScan scan;
     if (decode_wants_scan(call)) {
@@ -1120,7 +1153,7 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, co
         uint32_t words[4] = {0, 0, 0, 0};
         HIP_OK(hipMemsetAsync(hdr_scan, 0, 16, st));
         const uint32_t sg = (uint32_t)std::min<size_t>((n_streams + 255) / 256, (size_t)ctx->cu_count * 4);
-        hipLaunchKernelGGL(tamp_header_scan_kernel, dim3(sg), dim3(256), 0, st, d_in, d_in_off, d_in_len, d_out_cap,
+        hipLaunchKernelGGL(tamp_header_scan_kernel, dim3(sg), dim3(256), 0, st, t.in, t.in_off, t.in_len, t.out_cap,
                            (uint32_t)n_streams, (uint32_t)call.bits(), hdr_scan);
         HIP_OK(hipMemcpyAsync(words, hdr_scan, 16, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -1141,18 +1174,15 @@ int launch_decompress(DeviceCtx* ctx, const uint8_t* d_dict, size_t dict_len, co
 // the input consumed) as long as it stays below the stream's limit.  -> 1 when the lane kernel has to answer: the stream fails the
 // gate, the chunk starts do not settle, an offset is out of bounds, or the sum reaches the limit (TAMP_OUTPUT_FULL, and how much
 // of the input that takes, is the exact loop's to say).
-int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, size_t dict_len, const uint64_t* d_dict_off,
-                             uint8_t max_wbits, const uint8_t* d_in,
-                             const uint64_t* d_in_off, const uint32_t* d_in_len, const uint32_t* d_limit, uint32_t* d_size, int8_t* d_status,
-                             uint32_t* d_consumed, hipStream_t st) {
+// `t`: the stream's single row (out_cap: its limit or null, out_len: the size).
+int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
     LongFront f;
-    if (const int rc = long_decode_front(ctx, rec, gate, nullptr, true, dict_len, d_dict_off, max_wbits, d_in, d_in_off, d_in_len, nullptr, d_limit, false,
-                                         "size query", st, f); rc != TAMP_OK) return rc;
+    if (const int rc = long_decode_front(ctx, rec, gate, t, true, max_wbits, false, "size query", st, f); rc != TAMP_OK) return rc;
     uint64_t v = 0;
     for (const uint32_t b : f.outb) v += b;
     if (f.dbg) fprintf(stderr, "[tamp_amd long size query] %llu bytes out, limit %u\n", (unsigned long long)v, f.cap);
     if (v >= f.cap) { timing_end(st); return long_declined(f.dbg, "size query", "output room"); }
-    hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, d_size, d_status, d_consumed, (uint32_t)v, f.n);
+    hipLaunchKernelGGL(tamp_long_finish_kernel, dim3(1), dim3(1), 0, st, t.out_len, t.status, t.in_consumed, (uint32_t)v, f.n);
     timing_end(st);
     HIP_OK(hipGetLastError());
     return TAMP_OK;
@@ -1160,37 +1190,20 @@ int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLon
 
 // tamp_batch_decoded_size on device memory: the parse's size-only build (tamp_decompress_split_kernel.hpp), one launch, no scratch,
 // no pre-pass, nothing that waits for `st` -- except for a handful of long streams, which the long decoder's front counts with the
-// whole device (and waits as the long decoder does).  `d_limit` may be null; of the dictionary only the length matters.
-int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, const uint64_t* d_dict_off, uint8_t max_wbits, const uint8_t* d_in, const uint64_t* d_in_off,
-                        const uint32_t* d_in_len, const uint32_t* d_limit, uint32_t* d_size, int8_t* d_status, uint32_t* d_consumed,
-                        size_t n_streams, hipStream_t st) {
+// whole device (and waits as the long decoder does).  `t`: device memory, no slab -- out and out_off are null, out_cap holds the
+// limits (may be null), out_len takes the sizes; of the dictionary only the length matters (dict is null).
+int launch_decoded_size(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
+    const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
     SplitArgs sa;
     memset(&sa, 0, sizeof sa);
-    DecompressArgs& a = sa.d;
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
-    a.out_cap = d_limit, a.out_len = d_size, a.status = d_status, a.in_consumed = d_consumed;
-    a.dict_len = dict_len, a.dict_off = d_dict_off;
-    a.n_streams = (uint32_t)n_streams;
-    a.max_wbits = max_wbits & 0x7F;  // (TAMP_AMD_WINDOW_BITS_EXACT: there is no pre-pass to skip)
+    sa.d = decompress_args(ctx, t);
+    sa.d.max_wbits = max_wbits & 0x7F;  // (TAMP_AMD_WINDOW_BITS_EXACT: there is no pre-pass to skip)
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (one library call at a time enqueues on a stream: the lock rule above StreamScratch)
-    if (const DecodeLong gate = decode_wants_long({n_streams, max_wbits, dict_len != 0}); gate.attempt) {
-        // (as launch_decompress: one after the other, one event pair around all of them; a stream that is not one for this path sends
-        // the whole call to the kernel below, which answers for every stream again)
-        size_t done = 0;
-        timing_begin(st);
-        t_timing_outer = true;
-        int rc = TAMP_OK;
-        for (; done < n_streams; done++) {
-            rc = launch_decoded_size_long(ctx, rec, gate, dict_len, d_dict_off ? d_dict_off + done : nullptr, max_wbits, d_in, d_in_off + done, d_in_len + done,
-                                          d_limit ? d_limit + done : nullptr, d_size + done, d_status + done,
-                                          d_consumed ? d_consumed + done : nullptr, st);
-            if (rc != TAMP_OK) break;
-        }
-        t_timing_outer = false;
-        if (rc != TAMP_OK && rc != 1) return rc;
-        if (done == n_streams) return TAMP_OK;
+    if (const DecodeLong gate = decode_wants_long({n_streams, max_wbits, t.dict_len != 0}); gate.attempt) {
+        const int rc = each_long_stream(t, st, [&](const BatchTables& row) { return launch_decoded_size_long(ctx, rec, gate, row, max_wbits, st); });
+        if (rc != 1) return rc;
     }
     const SizeGeometry g = size_geometry(n_streams, (uint32_t)ctx->cu_count);
     sa.first = 0, sa.count = (uint32_t)n_streams, sa.spw = g.spw;
@@ -1202,23 +1215,13 @@ int launch_decoded_size(DeviceCtx* ctx, size_t dict_len, const uint64_t* d_dict_
 }
 
 // Resumable decoding: one wavefront per decoder object (tamp_decompress_resume_kernel.hpp).
-int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uint8_t bits_max, const uint8_t* d_in,
-                             const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out,
-                             const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status,
-                             uint32_t* d_consumed, size_t n_streams, hipStream_t st) {
+int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uint8_t bits_max, const BatchTables& t, hipStream_t st) {
+    const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
     ResumeArgs ra;
     DecompressArgs& a = ra.d;
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
-    a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
-    a.in_consumed = d_consumed;
+    a = decompress_args(ctx, t);
     a.dict = nullptr, a.dict_len = 0, a.dict_off = nullptr;  // a custom dictionary is the initial content of the object's window
-    a.seed_dicts = ctx->seed_dicts;
-    a.scratch = nullptr;
-    a.only_flagged = nullptr;
-    a.flagged_count = nullptr;
-    a.n_streams = (uint32_t)n_streams;
-    a.lds_row = 0;
     a.max_wbits = bits_max;
     ra.states = d_states, ra.state_stride = stride;
     const WaveGeometry g = wave_geometry(bits_max, n_streams, ctx->cu_count);
@@ -1232,15 +1235,14 @@ int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, u
 
 // Compressor objects below flush granularity: one wavefront per object (tamp_compress_resume_kernel.hpp).
 int launch_compress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uint8_t bits_max, int op, int write_token,
-                           const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint8_t* d_out,
-                           const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len, int8_t* d_status,
-                           uint32_t* d_consumed, size_t n, hipStream_t st) {
+                           const BatchTables& t, hipStream_t st) {
+    const size_t n = t.n;
     if (n == 0) return TAMP_OK;
     EncodeResumeArgs a;
     a.states = d_states, a.state_stride = stride;
-    a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
-    a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap, a.out_len = d_out_len, a.status = d_status;
-    a.in_consumed = d_consumed;
+    a.in = t.in, a.in_off = t.in_off, a.in_len = t.in_len;
+    a.out = t.out, a.out_off = t.out_off, a.out_cap = t.out_cap, a.out_len = t.out_len, a.status = t.status;
+    a.in_consumed = t.in_consumed;
     a.n_objects = (uint32_t)n, a.op = (uint32_t)op, a.write_token = write_token ? 1u : 0u;
     a.max_wbits = bits_max;
     const WaveGeometry g = wave_geometry(bits_max, n, ctx->cu_count);
@@ -1264,24 +1266,13 @@ bool conf_valid(const TampAmdConf* c) {
 // both directions busy anyway.  Device staging is kept between calls.  The object calls (tamp_batch_*_resume) and the
 // piece / segment calls run here too: their objects' state rows travel with the chunks (HostBatch::states).
 // ---------------------------------------------------------------------------------------------
-struct HostBatch {
-    const uint8_t* in;
-    const uint64_t* in_off;
-    const uint32_t* in_len;
-    uint8_t* out;
-    const uint64_t* out_off;
-    const uint32_t* out_cap;
-    uint32_t* out_len;
-    int8_t* status;
-    uint32_t* in_consumed;  // decompress only, may be null
-    size_t n;
+struct HostBatch : BatchTables {  // the caller's arrays, in host memory, and what the host path alone needs to know
     uint8_t* states = nullptr;  // optional per-stream state rows of state_stride bytes: in before the launch, out after it
     size_t state_stride = 0;
     const uint8_t* lead = nullptr;  // one-stream batches only: nlead bytes in front of the stream's input, counted in in_len[0]
     size_t nlead = 0;
     bool exact_out = false;    // never the whole-extent copy-back: nothing behind out_len[i] is written (HostChunk)
     bool drop_failed = false;  // (with exact_out) a stream whose status is not TAMP_OK produces nothing: out_len = 0
-    const uint64_t* dict_off = nullptr;  // the *_dicts calls: per stream, travels with the chunks; the whole dictionary buffer is staged
     // out == nullptr (tamp_batch_decoded_size): no output bytes at all -- out_off is null, out_cap (the limits, may be null) rides
     // along as a table only and takes no part in the chunks' extents; out_len / status / in_consumed come back as always
     uint64_t slab_off(size_t i) const { return out ? out_off[i] : 0; }
@@ -1341,28 +1332,22 @@ void plan_host_chunks(const HostBatch& b, size_t min_streams, uint64_t min_bytes
     }
 }
 
-struct HostSlot {  // device views of one chunk: offsets stay absolute, the data pointers are shifted instead
-    const uint8_t* in;
-    uint8_t* out;
-    const uint64_t *in_off, *out_off, *dict_off;  // (dict_off: null without a dictionary table)
-    const uint32_t *in_len, *out_cap;
-    uint32_t *out_len, *in_consumed;
-    int8_t* status;
-    uint8_t* states;  // row 0 = stream i0 of the chunk, or null
-};
-using HostLaunch = std::function<int(const HostSlot&, size_t count, const uint8_t* d_dict, hipStream_t)>;
+// One chunk on the device: its tables (rows of the chunk; offsets stay absolute, the data pointers are shifted instead; dict: the
+// staged dictionary or null; a table the caller left out is null here too) and its state rows (row 0 = the chunk's first stream, or null).
+using HostLaunch = std::function<int(const BatchTables& d, uint8_t* d_states, hipStream_t)>;
 
-int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::vector<HostChunk>& chunks,
-                   const uint8_t* dictionary, size_t dictionary_len, const HostLaunch& launch) {
+// `dictionary_len`: the bytes of b.dict to stage (b.dict_len is what the kernels are told).
+int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::vector<HostChunk>& chunks, size_t dictionary_len,
+                   const HostLaunch& launch) {
     using Pipe = DeviceCtx::HostPipe;
     Pipe& P = ctx->pipe;
     std::lock_guard<std::mutex> call_lock(P.mu);
     const uint8_t* d_dict = nullptr;
-    if (dictionary && dictionary_len) {
+    if (b.dict && dictionary_len) {
         // one dictionary: at most a window of it; a table of them (b.dict_off): all of it, once per call (the buffer is kept and grows)
         const size_t stage = b.dict_off ? dictionary_len : std::min(dictionary_len, kSeedTable);
         HIP_OK(P.dict.need(std::max(stage, kSeedTable)));
-        HIP_OK(hipMemcpy(P.dict.p, dictionary, stage, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(P.dict.p, b.dict, stage, hipMemcpyHostToDevice));
         d_dict = static_cast<const uint8_t*>(P.dict.p);
     }
     size_t max_in = 0, max_out = 0, max_cnt = 0;
@@ -1380,57 +1365,57 @@ int run_host_batch(DeviceCtx* ctx, int device, const HostBatch& b, const std::ve
         HIP_OK(P.meta[j].need(meta_bytes));
         if (b.states) HIP_OK(P.state[j].need(max_cnt * b.state_stride));
     }
-    auto slot_of = [&](int j, const HostChunk& ch) {
-        HostSlot s;
+    auto slot_of = [&](int j, const HostChunk& ch) {  // the device record of a chunk in slot j
+        BatchTables s = b;
         uint8_t* m = static_cast<uint8_t*>(P.meta[j].p);
-        s.in_off = reinterpret_cast<uint64_t*>(m), m += max_cnt * 8;
-        s.out_off = reinterpret_cast<uint64_t*>(m), m += max_cnt * 8;
-        s.dict_off = b.dict_off ? reinterpret_cast<uint64_t*>(m) : nullptr, m += max_cnt * 8;
-        s.in_len = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
-        s.out_cap = b.out_cap ? reinterpret_cast<uint32_t*>(m) : nullptr, m += max_cnt * 4;
-        s.out_len = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
-        s.in_consumed = reinterpret_cast<uint32_t*>(m), m += max_cnt * 4;
-        s.status = reinterpret_cast<int8_t*>(m);
+        auto column = [&](auto*& p, size_t width) {  // (every column has its place, a table the caller left out stays null)
+            if (p) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(m);
+            m += max_cnt * width;
+        };
+        column(s.in_off, 8), column(s.out_off, 8), column(s.dict_off, 8), column(s.in_len, 4), column(s.out_cap, 4), column(s.out_len, 4);
+        column(s.in_consumed, 4), column(s.status, 1);
         s.in = static_cast<const uint8_t*>(P.in[j].p) - ch.in_lo;
-        s.out = static_cast<uint8_t*>(P.out[j].p) - ch.out_lo;
-        s.states = b.states ? static_cast<uint8_t*>(P.state[j].p) : nullptr;
+        s.out = b.out ? static_cast<uint8_t*>(P.out[j].p) - ch.out_lo : nullptr;
+        s.dict = d_dict;
+        s.n = ch.i1 - ch.i0;
         return s;
     };
+    auto states_of = [&](int j) { return b.states ? static_cast<uint8_t*>(P.state[j].p) : nullptr; };
     auto feed = [&](size_t k) -> int {  // copy-in + launch of chunk k
         const HostChunk& ch = chunks[k];
         const int j = (int)(k % Pipe::kDepth);
-        const HostSlot s = slot_of(j, ch);
-        const size_t cnt = ch.i1 - ch.i0;
+        const BatchTables s = slot_of(j, ch), h = b.rows(ch.i0, ch.i1 - ch.i0);  // the chunk's rows: on the device, in the caller's arrays
+        const size_t cnt = s.n;
         hipStream_t st = P.s[j];
         uint8_t* const d_in = static_cast<uint8_t*>(P.in[j].p);
         if (b.nlead) HIP_OK(hipMemcpyAsync(d_in, b.lead, b.nlead, hipMemcpyHostToDevice, st));
         if (ch.in_hi > ch.in_lo + b.nlead)
             HIP_OK(hipMemcpyAsync(d_in + b.nlead, b.in + ch.in_lo, ch.in_hi - ch.in_lo - b.nlead, hipMemcpyHostToDevice, st));
         if (b.states)
-            HIP_OK(hipMemcpyAsync(s.states, b.states + ch.i0 * b.state_stride, cnt * b.state_stride, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.in_off), b.in_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
-        if (b.out_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.out_off), b.out_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
-        if (b.dict_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.dict_off), b.dict_off + ch.i0, cnt * 8, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.in_len), b.in_len + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
-        if (b.out_cap) HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.out_cap), b.out_cap + ch.i0, cnt * 4, hipMemcpyHostToDevice, st));
-        return launch(s, cnt, d_dict, st);
+            HIP_OK(hipMemcpyAsync(states_of(j), b.states + ch.i0 * b.state_stride, cnt * b.state_stride, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.in_off), h.in_off, cnt * 8, hipMemcpyHostToDevice, st));
+        if (h.out_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.out_off), h.out_off, cnt * 8, hipMemcpyHostToDevice, st));
+        if (h.dict_off) HIP_OK(hipMemcpyAsync(const_cast<uint64_t*>(s.dict_off), h.dict_off, cnt * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.in_len), h.in_len, cnt * 4, hipMemcpyHostToDevice, st));
+        if (h.out_cap) HIP_OK(hipMemcpyAsync(const_cast<uint32_t*>(s.out_cap), h.out_cap, cnt * 4, hipMemcpyHostToDevice, st));
+        return launch(s, states_of(j), st);
     };
     auto drain = [&](size_t k) -> int {  // copy-out of chunk k, complete on return
         const HostChunk& ch = chunks[k];
         const int j = (int)(k % Pipe::kDepth);
-        const HostSlot s = slot_of(j, ch);
-        const size_t cnt = ch.i1 - ch.i0;
+        const BatchTables s = slot_of(j, ch), h = b.rows(ch.i0, ch.i1 - ch.i0);
+        const size_t cnt = s.n;
         hipStream_t st = P.s[j];
         // (a handful of streams -- ONE long stream decoded with room for its worst case: tamp.decompress(100 MB) offers 325 MB --
         // first learn what was produced and copy exactly that: the packed path below would move the whole extent)
         const bool out_packed = ch.out_packed && cnt > 16;
         if (out_packed && ch.out_hi > ch.out_lo)
             HIP_OK(hipMemcpyAsync(b.out + ch.out_lo, P.out[j].p, ch.out_hi - ch.out_lo, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(b.out_len + ch.i0, s.out_len, cnt * 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(b.status + ch.i0, s.status, cnt, hipMemcpyDeviceToHost, st));
-        if (b.in_consumed) HIP_OK(hipMemcpyAsync(b.in_consumed + ch.i0, s.in_consumed, cnt * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h.out_len, s.out_len, cnt * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h.status, s.status, cnt, hipMemcpyDeviceToHost, st));
+        if (h.in_consumed) HIP_OK(hipMemcpyAsync(h.in_consumed, s.in_consumed, cnt * 4, hipMemcpyDeviceToHost, st));
         if (b.states)
-            HIP_OK(hipMemcpyAsync(b.states + ch.i0 * b.state_stride, s.states, cnt * b.state_stride, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(b.states + ch.i0 * b.state_stride, states_of(j), cnt * b.state_stride, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         if (b.drop_failed)
             for (size_t i = ch.i0; i < ch.i1; i++)
@@ -1583,8 +1568,10 @@ int device_fanout_count() {
     return forced > 0 ? forced : count;
 }
 
-template <class Call>  // Call(device, first_stream, count) -> library-level return code
-int fan_out_over_devices(const uint32_t* in_len, size_t n_streams, const Call& call) {
+template <class Call>  // Call(device, the shard's rows) -> library-level return code
+int fan_out_over_devices(const BatchTables& t, const Call& call) {
+    const uint32_t* const in_len = t.in_len;
+    const size_t n_streams = t.n;
     const int shards = device_fanout_count();
     int devices = 0;
     (void)hipGetDeviceCount(&devices);
@@ -1611,7 +1598,7 @@ int fan_out_over_devices(const uint32_t* in_len, size_t n_streams, const Call& c
     for (int r = 0; r < shards; r++) {
         if (cut[r + 1] == cut[r]) continue;
         workers.emplace_back([&, r] {
-            rcs[r] = call(r % devices, cut[r], cut[r + 1] - cut[r]);
+            rcs[r] = call(r % devices, t.rows(cut[r], cut[r + 1] - cut[r]));
             if (rcs[r] != TAMP_OK) msgs[r] = t_last_error;
         });
     }
@@ -1623,6 +1610,149 @@ int fan_out_over_devices(const uint32_t* in_len, size_t n_streams, const Call& c
         }
     return TAMP_OK;
 }
+
+// What every batch call refuses before it looks for a device (each entry point adds its own in front of or behind this): a missing
+// table (`slabs`: the call writes output bytes, so out_off and out_cap are tables it needs), more streams than 32 bits count, a
+// memory kind there is none of -- looked at before TAMP_AMD_ALL_DEVICES, which takes host memory (device pointers belong to one device).
+int batch_refused(const BatchTables& t, bool slabs, int mem, int device) {
+    if (t.n && (!t.in_off || !t.in_len || !t.out_len || !t.status || (slabs && (!t.out_off || !t.out_cap)))) return TAMP_AMD_BAD_ARGUMENT;
+    if (t.n > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
+    if (device == TAMP_AMD_ALL_DEVICES && mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
+    return TAMP_OK;
+}
+
+// Behind the checks: `one(ctx, device, tables)` on the call's device -- or, for TAMP_AMD_ALL_DEVICES, on every device with its shard.
+template <class One>
+int on_devices(const BatchTables& t, int device, const One& one) {
+    auto on_device = [&](int dev, const BatchTables& shard) {
+        DeviceCtx* ctx = nullptr;
+        const int rc = get_ctx(dev, &ctx);
+        return rc != TAMP_OK ? rc : one(ctx, dev, shard);
+    };
+    return device == TAMP_AMD_ALL_DEVICES ? fan_out_over_devices(t, on_device) : on_device(device, t);
+}
+
+// The batch calls behind their entry points, on the record.  Each *_dicts call is the whole of its plain twin plus a per-stream
+// dictionary offset table; the plain call passes none (dict_off = null) and behaves as it always has.
+int batch_compress(const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len, int mem, int device, void* stream) {
+    if (!conf) return TAMP_AMD_BAD_ARGUMENT;
+    if (const int rc = batch_refused(t, true, mem, device)) return rc;
+    // (a table selects among CUSTOM dictionaries: the custom bit sits in the one header byte the launch shares)
+    if (t.dict_off && (!conf->use_custom_dictionary || !t.dict)) return TAMP_AMD_BAD_ARGUMENT;
+    if (mem == TAMP_AMD_MEM_HOST && !max_in_len) {  // (over the whole call: every shard and chunk takes the same build)
+        for (size_t i = 0; i < t.n; i++) max_in_len = std::max(max_in_len, t.in_len[i]);
+        if (!max_in_len) max_in_len = 16;
+    }
+    return on_devices(t, device, [&](DeviceCtx* ctx, int dev, const BatchTables& t) -> int {
+        const bool bad_conf = !conf_valid(conf) || (conf->use_custom_dictionary && !t.dict);
+        if (mem == TAMP_AMD_MEM_DEVICE) {
+            hipStream_t st = static_cast<hipStream_t>(stream);
+            if (bad_conf) {  // tamp_compressor_init would have returned TAMP_INVALID_CONF for every stream
+                HIP_OK(hipMemsetAsync(t.status, (uint8_t)(int8_t)TAMP_INVALID_CONF, t.n, st));
+                HIP_OK(hipMemsetAsync(t.out_len, 0, t.n * sizeof(uint32_t), st));
+                return TAMP_OK;
+            }
+            return launch_compress(ctx, conf, t, max_in_len, st);
+        }
+        // ---- host memory: stage, run, copy back ----
+        if (bad_conf) {
+            for (size_t i = 0; i < t.n; i++) t.status[i] = TAMP_INVALID_CONF, t.out_len[i] = 0;
+            return TAMP_OK;
+        }
+        if (t.n == 0) return TAMP_OK;
+        HostBatch b{t};
+        if (!conf->use_custom_dictionary) b.dict = nullptr;
+        std::vector<HostChunk> chunks;
+        // a chunk fills the device three times over (256 CUs x 6 workgroups = 1,536 streams at once); measured best for
+        // 4 KiB streams (DESIGN_HISTORY.md), and at least 16 MiB so that short messages do not drown in call overhead
+        plan_host_chunks(b, env_or("TAMP_AMD_HOST_CHUNK_STREAMS", (size_t)ctx->cu_count * 18),
+                         (uint64_t)env_or("TAMP_AMD_HOST_CHUNK_MB", 16) << 20, 1ull << 30, chunks);
+        return run_host_batch(ctx, dev, b, chunks, t.dict_off ? t.dict_len : (size_t)1 << conf->window,
+                              [&](const BatchTables& d, uint8_t*, hipStream_t cs) { return launch_compress(ctx, conf, d, max_in_len, cs); });
+    });
+}
+
+int batch_decompress(BatchTables t, uint8_t max_window_bits, int mem, int device, void* stream) {
+    if (const int rc = batch_refused(t, true, mem, device)) return rc;
+    if (!t.dict) t.dict_len = 0, t.dict_off = nullptr;  // (no buffer: every stream with the custom bit is TAMP_INVALID_CONF, as ever)
+    return on_devices(t, device, [&](DeviceCtx* ctx, int dev, const BatchTables& t) -> int {
+        if (mem == TAMP_AMD_MEM_DEVICE) return launch_decompress(ctx, t, max_window_bits, static_cast<hipStream_t>(stream));
+        if (t.n == 0) return TAMP_OK;
+        HostBatch b{t};
+        if (!b.dict_off) b.dict_len = std::min(b.dict_len, kSeedTable);  // (one dictionary: no window reads beyond 32 KiB of it)
+        return run_host_batch(ctx, dev, b, plan_wide_chunks(ctx, b), b.dict_len, [&](BatchTables d, uint8_t*, hipStream_t cs) {
+            if (!d.dict) d.dict_len = 0, d.dict_off = nullptr;  // (nothing staged: a dictionary of no bytes is no dictionary)
+            return launch_decompress(ctx, d, max_window_bits, cs);
+        });
+    });
+}
+
+// (no slab: out = out_off = null, the limits travel as the out_cap table; no dictionary bytes either, only their count)
+int batch_decoded_size(BatchTables t, uint8_t max_window_bits, int mem, int device, void* stream) {
+    if (const int rc = batch_refused(t, false, mem, device)) return rc;
+    if (!t.dict_len) t.dict_off = nullptr;  // (as the decode call without a buffer)
+    return on_devices(t, device, [&](DeviceCtx* ctx, int dev, const BatchTables& t) -> int {
+        if (mem == TAMP_AMD_MEM_DEVICE) return launch_decoded_size(ctx, t, max_window_bits, static_cast<hipStream_t>(stream));
+        if (t.n == 0) return TAMP_OK;
+        HostBatch b{t};
+        return run_host_batch(ctx, dev, b, plan_wide_chunks(ctx, b), 0,
+                              [&](const BatchTables& d, uint8_t*, hipStream_t cs) { return launch_decoded_size(ctx, d, max_window_bits, cs); });
+    });
+}
+
+// The two object calls behind their entry points (the reference-named objects of include/tamp_compat.h call them with a one-row
+// record): what the call alone checks, then device memory or the host pipeline with the state rows travelling with the chunks.
+template <class Launch>  // Launch(ctx, d_states, device tables, stream)
+int run_object_batch(const BatchTables& t, void* states, size_t state_stride, size_t state_size, uint8_t window_bits_max, int mem,
+                     int device, void* stream, const Launch& launch) {
+    if (const int rc = batch_refused(t, true, mem, device)) return rc;
+    if ((t.n && !states) || window_bits_max < 8 || window_bits_max > 15 || (state_stride & 15) || state_stride < state_size ||
+        (reinterpret_cast<uintptr_t>(states) & 3))
+        return TAMP_AMD_BAD_ARGUMENT;
+    DeviceCtx* ctx = nullptr;  // (objects stay on one device: TAMP_AMD_ALL_DEVICES is no device)
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch(ctx, static_cast<uint8_t*>(states), t, static_cast<hipStream_t>(stream));
+    if (t.n == 0) return TAMP_OK;
+    HostBatch b{t};
+    b.states = static_cast<uint8_t*>(states), b.state_stride = state_stride, b.exact_out = true;
+    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), 0,
+                          [&](const BatchTables& d, uint8_t* d_states, hipStream_t cs) { return launch(ctx, d_states, d, cs); });
+}
+
+int batch_decompress_resume(const BatchTables& t, void* states, size_t state_stride, uint8_t window_bits_max, int mem, int device,
+                            void* stream) {
+    return run_object_batch(t, states, state_stride, tamp_amd_decoder_state_size(window_bits_max), window_bits_max, mem, device, stream,
+                            [&](DeviceCtx* ctx, uint8_t* d_states, const BatchTables& d, hipStream_t st) {
+        return launch_decompress_resume(ctx, d_states, state_stride, window_bits_max, d, st);
+    });
+}
+
+int batch_compress_resume(const BatchTables& t, void* states, size_t state_stride, uint8_t window_bits_max, int op, int write_token,
+                          int mem, int device, void* stream) {
+    if (op < TAMP_AMD_OP_POLL || op > TAMP_AMD_OP_COMPRESS_AND_FLUSH) return TAMP_AMD_BAD_ARGUMENT;
+    return run_object_batch(t, states, state_stride, tamp_amd_encoder_state_size(window_bits_max), window_bits_max, mem, device, stream,
+                            [&](DeviceCtx* ctx, uint8_t* d_states, const BatchTables& d, hipStream_t st) {
+        return launch_compress_resume(ctx, d_states, state_stride, window_bits_max, op, write_token, d, st);
+    });
+}
+
+// One stream at offset 0 of its buffers, in host memory: the one-row batch of the one-shot, object and piece calls.
+struct OneRow {
+    uint64_t zero = 0;
+    uint32_t ilen, ocap, olen = 0, consumed = 0;
+    int8_t status = TAMP_ERROR;
+    OneRow(size_t input_size, size_t output_size, size_t most_in = 0xFFFFFFFFu, size_t most_out = 0xFFFFFFFFu)
+        : ilen((uint32_t)std::min(input_size, most_in)), ocap((uint32_t)std::min(output_size, most_out)) {}
+    BatchTables tables(const uint8_t* in, uint8_t* out) {  // (a null or empty buffer: a byte of the library's own to point at)
+        static unsigned char empty = 0;
+        BatchTables t;
+        t.in = in && ilen ? in : &empty, t.in_off = &zero, t.in_len = &ilen;
+        t.out = ocap ? out : &empty, t.out_off = &zero, t.out_cap = &ocap, t.out_len = &olen, t.status = &status;
+        t.in_consumed = &consumed, t.n = 1;
+        return t;
+    }
+};
 
 }  // namespace
 
@@ -1791,69 +1921,13 @@ float tamp_amd_last_kernel_ms(void) {
     return ms;
 }
 
-// The batch calls.  Each *_dicts call is the whole of its plain twin plus a per-stream dictionary offset table; the plain call
-// passes none (dict_off = null) and behaves as it always has.
+// The batch calls: each entry point puts its tables into one record (BatchTables) and hands it on.
 int tamp_batch_compress_dicts(const TampAmdConf* conf, const uint8_t* dictionaries, size_t dictionaries_len, const uint64_t* dict_off,
                               const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                               const uint32_t* out_cap, uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem,
                               int device, void* stream) {
-    if (!conf || (n_streams && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)))
-        return TAMP_AMD_BAD_ARGUMENT;
-    // (a table selects among CUSTOM dictionaries: the custom bit sits in the one header byte the launch shares)
-    if (dict_off && (!conf->use_custom_dictionary || !dictionaries)) return TAMP_AMD_BAD_ARGUMENT;
-    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
-    const uint8_t* const dictionary = dictionaries;
-    if (device == TAMP_AMD_ALL_DEVICES) {
-        if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;  // device pointers belong to one device
-        if (!max_in_len)
-            for (size_t i = 0; i < n_streams; i++) max_in_len = std::max(max_in_len, in_len[i]);
-        return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
-            return tamp_batch_compress_dicts(conf, dictionaries, dictionaries_len, dict_off ? dict_off + i0 : nullptr, in, in_off + i0,
-                                             in_len + i0, out, out_off + i0, out_cap + i0, out_len + i0, status + i0, cnt, max_in_len,
-                                             mem, dev, nullptr);
-        });
-    }
-    DeviceCtx* ctx = nullptr;
-    int rc = get_ctx(device, &ctx);
-    if (rc != TAMP_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool bad_conf = !conf_valid(conf) || (conf->use_custom_dictionary && !dictionary);
-
-    if (mem == TAMP_AMD_MEM_DEVICE) {
-        if (bad_conf) {  // tamp_compressor_init would have returned TAMP_INVALID_CONF for every stream
-            HIP_OK(hipMemsetAsync(status, (uint8_t)(int8_t)TAMP_INVALID_CONF, n_streams, st));
-            HIP_OK(hipMemsetAsync(out_len, 0, n_streams * sizeof(uint32_t), st));
-            return TAMP_OK;
-        }
-        return launch_compress(ctx, conf, dictionary, in, in_off, in_len, out, out_off, out_cap, out_len, status,
-                               n_streams, max_in_len, st, nullptr, nullptr, dict_off, dictionaries_len);
-    }
-
-    // ---- host memory: stage, run, copy back ----
-    if (bad_conf) {
-        for (size_t i = 0; i < n_streams; i++) status[i] = TAMP_INVALID_CONF, out_len[i] = 0;
-        return TAMP_OK;
-    }
-    if (n_streams == 0) return TAMP_OK;
-    if (!max_in_len) {
-        uint32_t maxlen = 0;
-        for (size_t i = 0; i < n_streams; i++) maxlen = std::max(maxlen, in_len[i]);
-        max_in_len = maxlen ? maxlen : 16;
-    }
-    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, n_streams};
-    b.dict_off = dict_off;
-    std::vector<HostChunk> chunks;
-    // a chunk fills the device three times over (256 CUs x 6 workgroups = 1,536 streams at once); measured best for
-    // 4 KiB streams (DESIGN_HISTORY.md), and at least 16 MiB so that short messages do not drown in call overhead
-    plan_host_chunks(b, env_or("TAMP_AMD_HOST_CHUNK_STREAMS", (size_t)ctx->cu_count * 18),
-                     (uint64_t)env_or("TAMP_AMD_HOST_CHUNK_MB", 16) << 20, 1ull << 30, chunks);
-    return run_host_batch(ctx, device, b, chunks, conf->use_custom_dictionary ? dictionary : nullptr,
-                          dict_off ? dictionaries_len : (size_t)1 << conf->window,
-                          [&](const HostSlot& s, size_t count, const uint8_t* d_dict, hipStream_t cs) {
-        return launch_compress(ctx, conf, d_dict, s.in, s.in_off, s.in_len, s.out, s.out_off, s.out_cap, s.out_len,
-                               s.status, count, max_in_len, cs, nullptr, nullptr, s.dict_off, dictionaries_len);
-    });
+    return batch_compress(conf, {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, dict_off, dictionaries, dictionaries_len, n_streams},
+                          max_in_len, mem, device, stream);
 }
 
 int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, const uint8_t* in, const uint64_t* in_off,
@@ -1868,40 +1942,8 @@ int tamp_batch_decompress_dicts(const uint8_t* dictionaries, size_t dictionaries
                                 const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                                 const uint32_t* out_cap, uint32_t* out_len, int8_t* status, uint32_t* in_consumed, size_t n_streams,
                                 int mem, int device, void* stream) {
-    if (n_streams && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return TAMP_AMD_BAD_ARGUMENT;
-    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
-    if (device == TAMP_AMD_ALL_DEVICES) {
-        if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
-        return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
-            return tamp_batch_decompress_dicts(dictionaries, dictionaries_len, dict_off ? dict_off + i0 : nullptr, max_window_bits, in,
-                                               in_off + i0, in_len + i0, out, out_off + i0, out_cap + i0, out_len + i0, status + i0,
-                                               in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev, nullptr);
-        });
-    }
-    DeviceCtx* ctx = nullptr;
-    int rc = get_ctx(device, &ctx);
-    if (rc != TAMP_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint8_t* const dictionary = dictionaries;
-    size_t dictionary_len = dictionaries_len;
-    if (!dictionary) dictionary_len = 0, dict_off = nullptr;  // (no buffer: every stream with the custom bit is TAMP_INVALID_CONF, as ever)
-
-    if (mem == TAMP_AMD_MEM_DEVICE)
-        return launch_decompress(ctx, dictionary, dictionary_len, dict_off, max_window_bits, in, in_off, in_len, out, out_off,
-                                 out_cap, out_len, status, in_consumed, n_streams, st);
-
-    if (n_streams == 0) return TAMP_OK;
-    if (!dict_off) dictionary_len = std::min(dictionary_len, kSeedTable);  // (one dictionary: no window reads beyond 32 KiB of it)
-    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams};
-    b.dict_off = dict_off;
-    uint32_t* no_consumed = nullptr;
-    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), dictionary, dictionary_len,
-                          [&](const HostSlot& s, size_t count, const uint8_t* d_dict, hipStream_t cs) {
-        return launch_decompress(ctx, d_dict, d_dict ? dictionary_len : 0, d_dict ? s.dict_off : nullptr, max_window_bits, s.in, s.in_off,
-                                 s.in_len, s.out, s.out_off, s.out_cap, s.out_len, s.status, in_consumed ? s.in_consumed : no_consumed,
-                                 count, cs);
-    });
+    return batch_decompress({in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, dict_off, dictionaries, dictionaries_len, n_streams},
+                            max_window_bits, mem, device, stream);
 }
 
 int tamp_batch_decompress(const uint8_t* dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in,
@@ -1915,35 +1957,8 @@ int tamp_batch_decompress(const uint8_t* dictionary, size_t dictionary_len, uint
 int tamp_batch_decoded_size_dicts(size_t dictionaries_len, const uint64_t* dict_off, uint8_t max_window_bits, const uint8_t* in,
                                   const uint64_t* in_off, const uint32_t* in_len, const uint32_t* limit, uint32_t* decoded_size,
                                   int8_t* status, uint32_t* in_consumed, size_t n_streams, int mem, int device, void* stream) {
-    if (n_streams && (!in_off || !in_len || !decoded_size || !status)) return TAMP_AMD_BAD_ARGUMENT;
-    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
-    if (device == TAMP_AMD_ALL_DEVICES) {
-        if (mem != TAMP_AMD_MEM_HOST) return TAMP_AMD_BAD_ARGUMENT;
-        return fan_out_over_devices(in_len, n_streams, [&](int dev, size_t i0, size_t cnt) {
-            return tamp_batch_decoded_size_dicts(dictionaries_len, dict_off ? dict_off + i0 : nullptr, max_window_bits, in, in_off + i0,
-                                                 in_len + i0, limit ? limit + i0 : nullptr, decoded_size + i0, status + i0,
-                                                 in_consumed ? in_consumed + i0 : nullptr, cnt, mem, dev, nullptr);
-        });
-    }
-    DeviceCtx* ctx = nullptr;
-    int rc = get_ctx(device, &ctx);
-    if (rc != TAMP_OK) return rc;
-    if (!dictionaries_len) dict_off = nullptr;  // (as the decode call without a buffer)
-    if (mem == TAMP_AMD_MEM_DEVICE)
-        return launch_decoded_size(ctx, dictionaries_len, dict_off, max_window_bits, in, in_off, in_len, limit, decoded_size, status,
-                                   in_consumed, n_streams, static_cast<hipStream_t>(stream));
-
-    if (n_streams == 0) return TAMP_OK;
-    // (no slab: out = out_off = null, the limits travel as the out_cap table; no dictionary bytes either, only their count)
-    HostBatch b = {in, in_off, in_len, nullptr, nullptr, limit, decoded_size, status, in_consumed, n_streams};
-    b.dict_off = dict_off;
-    uint32_t* no_consumed = nullptr;
-    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
-                          [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
-        return launch_decoded_size(ctx, dictionaries_len, s.dict_off, max_window_bits, s.in, s.in_off, s.in_len, s.out_cap, s.out_len,
-                                   s.status, in_consumed ? s.in_consumed : no_consumed, count, cs);
-    });
+    return batch_decoded_size({in, in_off, in_len, nullptr, nullptr, limit, decoded_size, status, in_consumed, dict_off, nullptr, dictionaries_len, n_streams},
+                              max_window_bits, mem, device, stream);
 }
 
 int tamp_batch_decoded_size(size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,
@@ -1978,28 +1993,8 @@ int tamp_batch_decompress_resume(void* states, size_t state_stride, uint8_t wind
                                  const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                                  const uint32_t* out_cap, uint32_t* out_len, int8_t* status, uint32_t* in_consumed,
                                  size_t n_streams, int mem, int device, void* stream) {
-    if (n_streams && (!states || !in_off || !in_len || !out_off || !out_cap || !out_len || !status))
-        return TAMP_AMD_BAD_ARGUMENT;
-    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
-    if (window_bits_max < 8 || window_bits_max > 15 || (state_stride & 15) ||
-        state_stride < tamp_amd_decoder_state_size(window_bits_max) || (reinterpret_cast<uintptr_t>(states) & 3))
-        return TAMP_AMD_BAD_ARGUMENT;
-    DeviceCtx* ctx = nullptr;
-    int rc = get_ctx(device, &ctx);
-    if (rc != TAMP_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (mem == TAMP_AMD_MEM_DEVICE)
-        return launch_decompress_resume(ctx, static_cast<uint8_t*>(states), state_stride, window_bits_max, in, in_off,
-                                        in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams, st);
-    if (n_streams == 0) return TAMP_OK;
-    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_streams};
-    b.states = static_cast<uint8_t*>(states), b.state_stride = state_stride, b.exact_out = true;
-    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
-                          [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
-        return launch_decompress_resume(ctx, s.states, state_stride, window_bits_max, s.in, s.in_off, s.in_len, s.out,
-                                        s.out_off, s.out_cap, s.out_len, s.status, s.in_consumed, count, cs);
-    });
+    return batch_decompress_resume({in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, nullptr, nullptr, 0, n_streams},
+                                   states, state_stride, window_bits_max, mem, device, stream);
 }
 
 size_t tamp_amd_encoder_state_size(uint8_t window_bits_max) {
@@ -2017,29 +2012,8 @@ int tamp_batch_compress_resume(void* states, size_t state_stride, uint8_t window
                                const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int8_t* status,
                                uint32_t* in_consumed, size_t n_objects, int mem, int device, void* stream) {
-    if (n_objects && (!states || !in_off || !in_len || !out_off || !out_cap || !out_len || !status))
-        return TAMP_AMD_BAD_ARGUMENT;
-    if (n_objects > 0xFFFFFFFFull || op < TAMP_AMD_OP_POLL || op > TAMP_AMD_OP_COMPRESS_AND_FLUSH) return TAMP_AMD_BAD_ARGUMENT;
-    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
-    if (window_bits_max < 8 || window_bits_max > 15 || (state_stride & 15) ||
-        state_stride < tamp_amd_encoder_state_size(window_bits_max) || (reinterpret_cast<uintptr_t>(states) & 3))
-        return TAMP_AMD_BAD_ARGUMENT;
-    DeviceCtx* ctx = nullptr;
-    int rc = get_ctx(device, &ctx);
-    if (rc != TAMP_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (mem == TAMP_AMD_MEM_DEVICE)
-        return launch_compress_resume(ctx, static_cast<uint8_t*>(states), state_stride, window_bits_max, op, write_token,
-                                      in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_objects,
-                                      st);
-    if (n_objects == 0) return TAMP_OK;
-    HostBatch b = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, n_objects};
-    b.states = static_cast<uint8_t*>(states), b.state_stride = state_stride, b.exact_out = true;
-    return run_host_batch(ctx, device, b, plan_wide_chunks(ctx, b), nullptr, 0,
-                          [&](const HostSlot& s, size_t count, const uint8_t*, hipStream_t cs) {
-        return launch_compress_resume(ctx, s.states, state_stride, window_bits_max, op, write_token, s.in, s.in_off,
-                                      s.in_len, s.out, s.out_off, s.out_cap, s.out_len, s.status, s.in_consumed, count, cs);
-    });
+    return batch_compress_resume({in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, nullptr, nullptr, 0, n_objects},
+                                 states, state_stride, window_bits_max, op, write_token, mem, device, stream);
 }
 
 tamp_res tamp_amd_compress(const TampAmdConf* conf, const unsigned char* dictionary, unsigned char* output,
@@ -2047,17 +2021,13 @@ tamp_res tamp_amd_compress(const TampAmdConf* conf, const unsigned char* diction
                            size_t input_size, int device) {
     if (output_written_size) *output_written_size = 0;
     if (input_size > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    const uint64_t zero = 0;
-    const uint32_t ilen = (uint32_t)input_size;
-    const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
-    uint32_t olen = 0;
-    int8_t st = TAMP_ERROR;
-    static const unsigned char empty = 0;
-    int rc = tamp_batch_compress(conf, dictionary, input ? input : &empty, &zero, &ilen, output, &zero, &ocap, &olen,
-                                 &st, 1, ilen, TAMP_AMD_MEM_HOST, device, nullptr);
+    OneRow row(input_size, output_size);
+    BatchTables t = row.tables(input, output);
+    t.in_consumed = nullptr, t.dict = dictionary;
+    const int rc = batch_compress(conf, t, row.ilen, TAMP_AMD_MEM_HOST, device, nullptr);
     if (rc != TAMP_OK) return (tamp_res)rc;
-    if (output_written_size) *output_written_size = olen;
-    return st;
+    if (output_written_size) *output_written_size = row.olen;
+    return row.status;
 }
 
 tamp_res tamp_amd_decompress(const unsigned char* dictionary, size_t dictionary_len, unsigned char* output,
@@ -2066,18 +2036,14 @@ tamp_res tamp_amd_decompress(const unsigned char* dictionary, size_t dictionary_
     if (output_written_size) *output_written_size = 0;
     if (input_consumed_size) *input_consumed_size = 0;
     if (input_size > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    const uint64_t zero = 0;
-    const uint32_t ilen = (uint32_t)input_size;
-    const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
-    uint32_t olen = 0, consumed = 0;
-    int8_t st = TAMP_ERROR;
-    static const unsigned char empty = 0;
-    int rc = tamp_batch_decompress(dictionary, dictionary_len, 15, input ? input : &empty, &zero, &ilen, output, &zero,
-                                   &ocap, &olen, &st, &consumed, 1, TAMP_AMD_MEM_HOST, device, nullptr);
+    OneRow row(input_size, output_size);
+    BatchTables t = row.tables(input, output);
+    t.dict = dictionary, t.dict_len = dictionary_len;
+    const int rc = batch_decompress(t, 15, TAMP_AMD_MEM_HOST, device, nullptr);
     if (rc != TAMP_OK) return (tamp_res)rc;
-    if (output_written_size) *output_written_size = olen;
-    if (input_consumed_size) *input_consumed_size = consumed;
-    return st;
+    if (output_written_size) *output_written_size = row.olen;
+    if (input_consumed_size) *input_consumed_size = row.consumed;
+    return row.status;
 }
 
 tamp_res tamp_amd_read_header(TampAmdConf* conf, const unsigned char* input, size_t input_size,
@@ -2133,21 +2099,15 @@ tamp_res compat_encoder_call(TampCompressor* compressor, int op, bool write_toke
     std::vector<unsigned char> slot(stride);
     std::memcpy(slot.data(), s, sizeof *s);
     std::memcpy(slot.data() + sizeof *s, compressor->window, W);
-    const uint64_t zero = 0;
-    static unsigned char empty = 0;
-    const uint32_t ilen = (uint32_t)std::min<size_t>(input_size, 0xFFFFFFFFu);
-    const uint32_t ocap = (uint32_t)std::min<size_t>(output_size, 0xFFFFFFFFu);
-    uint32_t olen = 0, icons = 0;
-    int8_t st = TAMP_ERROR;
-    const int rc = tamp_batch_compress_resume(slot.data(), stride, s->window, op, write_token, ilen ? input : &empty, &zero,
-                                              &ilen, ocap ? output : &empty, &zero, &ocap, &olen, &st, &icons, 1,
-                                              TAMP_AMD_MEM_HOST, compat_device(), nullptr);
+    OneRow row(input_size, output_size);
+    const int rc = batch_compress_resume(row.tables(input, output), slot.data(), stride, s->window, op, write_token, TAMP_AMD_MEM_HOST,
+                                         compat_device(), nullptr);
     if (rc != TAMP_OK) return (tamp_res)rc;
     std::memcpy(s, slot.data(), sizeof *s);
     std::memcpy(compressor->window, slot.data() + sizeof *s, W);
-    if (output_written_size) *output_written_size = olen;
-    if (input_consumed_size) *input_consumed_size = icons;
-    return st;
+    if (output_written_size) *output_written_size = row.olen;
+    if (input_consumed_size) *input_consumed_size = row.consumed;
+    return row.status;
 }
 
 // A whole segment on an object that is between segments (ring empty, nothing pending, output bits byte aligned) with
@@ -2567,21 +2527,17 @@ tamp_res tamp_decompressor_decompress_cb(TampDecompressor* decompressor, unsigne
     std::vector<unsigned char> slot(sizeof(TampAmdDecoderState) + wcap);
     std::memcpy(slot.data(), s, sizeof *s);
     std::memcpy(slot.data() + sizeof *s, decompressor->window, wlive);
-    const uint64_t zero = 0;
-    static unsigned char empty = 0;
     size_t written = 0, consumed = 0;
     int8_t st = TAMP_ERROR;
     for (;;) {  // one device step per 256 MiB of input / 1 GiB of output room (the kernel's counters are 32 bits wide)
-        const uint32_t ilen = (uint32_t)std::min<size_t>(input_size - consumed, 0x10000000u);
-        const uint32_t ocap = (uint32_t)std::min<size_t>(output_size - written, 0x40000000u);
-        uint32_t olen = 0, icons = 0;
-        const int rc = tamp_batch_decompress_resume(slot.data(), slot.size(), bits_max, ilen ? input + consumed : &empty,
-                                                    &zero, &ilen, ocap ? output + written : &empty, &zero, &ocap, &olen,
-                                                    &st, &icons, 1, TAMP_AMD_MEM_HOST, compat_device(), nullptr);
+        OneRow row(input_size - consumed, output_size - written, 0x10000000u, 0x40000000u);
+        const int rc = batch_decompress_resume(row.tables(input + consumed, output + written), slot.data(), slot.size(), bits_max,
+                                               TAMP_AMD_MEM_HOST, compat_device(), nullptr);
         if (rc != TAMP_OK) return (tamp_res)rc;
-        written += olen, consumed += icons;
-        const bool more_in = st == TAMP_INPUT_EXHAUSTED && icons == ilen && consumed < input_size;
-        const bool more_out = st == TAMP_OUTPUT_FULL && olen == ocap && written < output_size;
+        st = row.status;
+        written += row.olen, consumed += row.consumed;
+        const bool more_in = st == TAMP_INPUT_EXHAUSTED && row.consumed == row.ilen && consumed < input_size;
+        const bool more_out = st == TAMP_OUTPUT_FULL && row.olen == row.ocap && written < output_size;
         if (!more_in && !more_out) break;
     }
     std::memcpy(s, slot.data(), sizeof *s);
@@ -2672,21 +2628,19 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         if (output_written_size) *output_written_size = whole;
         return TAMP_OK;
     }
-    const uint64_t zero = 0;
-    const uint32_t ocap = (uint32_t)(output_size > 0xFFFFFFFFull ? 0xFFFFFFFFull : output_size);
     if (finish && !flush_token && !resume && emit_header && !append_marker && prefix.empty() && !conf->extended &&
         !conf->lazy_matching && conf->literal == 8 && conf->window <= kPackedMaxWbits && input_size >= ((size_t)256 << 10) &&
         input_size <= 0xFFFFFF00ull) {
         // A whole fresh v1 stream in one finishing call: the batch call takes it as ONE stream and spreads its blocks over
         // all workgroups (launch_compress_blocks).  The object afterwards holds what the reference's would: every consumed
         // byte was written (compressor.c:651-657), so the window is the stream's last W bytes at their ring positions.
-        const uint32_t ilen1 = (uint32_t)input_size;
-        uint32_t olen1 = 0;
-        int8_t st1 = TAMP_ERROR;
-        rc = tamp_batch_compress(conf, conf->use_custom_dictionary ? window_state : nullptr, input, &zero, &ilen1, output, &zero,
-                                 &ocap, &olen1, &st1, 1, ilen1, TAMP_AMD_MEM_HOST, device, nullptr);
+        OneRow row(input_size, output_size);
+        BatchTables t = row.tables(input, output);
+        t.in_consumed = nullptr, t.dict = conf->use_custom_dictionary ? window_state : nullptr;
+        rc = batch_compress(conf, t, row.ilen, TAMP_AMD_MEM_HOST, device, nullptr);
         if (rc != TAMP_OK) return (tamp_res)rc;
-        if (output_written_size) *output_written_size = olen1;
+        if (output_written_size) *output_written_size = row.olen;
+        const int8_t st1 = row.status;
         if (st1 == TAMP_OK) {
             const size_t first = input_size > W ? input_size - W : 0;
             for (size_t p2 = first; p2 < input_size; p2++) window_state[p2 & (W - 1)] = input[p2];
@@ -2700,21 +2654,22 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
     // did not complete leaves window and carry as they came in, so its bytes must not count either: a caller that consumed
     // them and offered the piece again would emit them twice (drop_failed).  (A finishing call keeps the reference's
     // contract -- what fitted is delivered with TAMP_OUTPUT_FULL, compressor.c:65-75.)
-    const uint32_t ilen = (uint32_t)(prefix.size() + input_size);
-    uint32_t olen = 0;
-    int8_t status = TAMP_ERROR;
-    HostBatch b = {input, &zero, &ilen, output, &zero, &ocap, &olen, &status, nullptr, 1};
+    OneRow row(prefix.size() + input_size, output_size);
+    const uint32_t ilen = row.ilen;
+    HostBatch b{row.tables(input, output)};
+    b.in = input, b.out = output;  // (as given: the lead bytes count in in_len[0], the input itself may be empty)
+    b.in_consumed = nullptr;
+    b.dict = !resume && conf->use_custom_dictionary ? window_state : nullptr;  // (a fresh stream with a custom dictionary: window_state holds it)
     b.states = stbuf.data(), b.state_stride = stbuf.size(), b.lead = prefix.data(), b.nlead = prefix.size();
     b.exact_out = true, b.drop_failed = !finish;
     std::vector<HostChunk> one;
     plan_host_chunks(b, 1, 0, ~0ull, one);
-    // (a fresh stream with a custom dictionary: window_state holds it)
-    rc = run_host_batch(ctx, device, b, one, !resume && conf->use_custom_dictionary ? window_state : nullptr, W,
-                        [&](const HostSlot& s, size_t, const uint8_t* d_dict, hipStream_t cs) {
-        return launch_compress(ctx, conf, d_dict, s.in, s.in_off, s.in_len, s.out, s.out_off, s.out_cap, s.out_len, s.status, 1,
-                               ilen ? ilen : 16, cs, &seg, s.states);
+    rc = run_host_batch(ctx, device, b, one, W, [&](const BatchTables& d, uint8_t* d_state, hipStream_t cs) {
+        return launch_compress(ctx, conf, d, ilen ? ilen : 16, cs, &seg, d_state);
     });
     if (rc != TAMP_OK) return (tamp_res)rc;
+    const uint32_t olen = row.olen;
+    const int8_t status = row.status;
     if (output_written_size) *output_written_size = olen;
     if (status == TAMP_OK) {
         std::memcpy(window_state, stbuf.data(), W);
