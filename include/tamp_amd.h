@@ -322,6 +322,77 @@ int tamp_batch_decoded_size_dicts(size_t dictionaries_len, const uint64_t *dict_
                                   uint32_t *in_consumed /* may be NULL */, size_t n_streams, int mem, int device,
                                   void *stream);
 
+/* ---- one long buffer as dictionary-reset segments --------------------------------------------------
+ *
+ * A stream whose header has the dictionary_reset bit may hold RESETS (tamp_compressor_reset_dictionary, compressor.c:847-881;
+ * decoder: decompressor.c:501-513): two FLUSH tokens, after which the output is byte aligned and the window is the seeded
+ * dictionary again.  The pieces between resets do not depend on each other, so a buffer cut every reset_interval bytes is a
+ * BATCH, and the whole device compresses ONE stream of the default (extended) format -- which tamp_batch_compress gives to one
+ * workgroup.  The price is compression ratio: every segment starts from the seeded window (profiles/reset_segments_ratio.txt).
+ * This is NOT a parallel form of the un-segmented stream: tamp.compress(data) without resets stays one workgroup, and its bytes
+ * differ from this call's.
+ *
+ * With K = ceil(in_len / reset_interval) segments (K = 1 for an empty input) the output is byte for byte what ONE reference
+ * object writes for
+ *     tamp_compressor_init(&c, &conf, window)                                   (conf.dictionary_reset = 1)
+ *     K - 1 times:  tamp_compressor_compress(reset_interval bytes) ... ; tamp_compressor_reset_dictionary(&c, ...)
+ *     tamp_compressor_compress(the rest) ... ; tamp_compressor_flush(&c, ..., write_token = false)
+ * -- K - 1 resets, none behind the last segment, no FLUSH token at the end -- an ordinary `.tamp` stream for any decoder.
+ *
+ *   conf            dictionary_reset must be 1 and use_custom_dictionary 0 (a reset restores the SEEDED window); window, literal,
+ *                   extended and lazy_matching as for tamp_batch_compress
+ *   in, in_len      the buffer; in_len <= 0xFFFFFFFF, and the worst case of ONE segment (2 + 9/8 of min(reset_interval, in_len) bytes at
+ *                   literal 8) must fit 32 bits: reset_interval above ~3.8e9 on a buffer that long is TAMP_AMD_BAD_ARGUMENT
+ *   reset_interval  >= 1: input bytes per segment
+ *   out, out_cap    room for the stream; tamp_amd_compress_resets_bound() bytes always suffice
+ *   out_len, status one element each.  TAMP_OK and the stream's length; or -- two deviations from the reference, on failure only --
+ *                   TAMP_EXCESS_BITS when any segment holds a byte that does not fit conf->literal bits, TAMP_OUTPUT_FULL when
+ *                   the stream is longer than out_cap (the reference would leave a prefix): out_len = 0 in both cases, the
+ *                   bytes of out[0 .. out_cap) are unspecified and nothing is written at or behind out + out_cap
+ *   reset_off       optional (may be NULL): K - 1 offsets into the stream, the byte behind each reset (where the next segment's
+ *                   tokens begin)
+ *   mem, device, stream   as for tamp_batch_compress: every pointer but conf lives where `mem` says; a device-memory call is
+ *                   asynchronous on `stream` and waits for nothing, a host-memory call is synchronous (`stream` is not used)
+ * Returns TAMP_OK when the call was launched, TAMP_AMD_BAD_ARGUMENT for a call outside the contract above (nothing is written),
+ * TAMP_AMD_NO_DEVICE.
+ *
+ * The segments' outputs are gathered from slabs of tamp_amd_compress_resets_slab() bytes each in scratch memory kept per HIP
+ * stream (tamp_amd_trim releases it); a call whose slabs outgrow a quarter of the free device memory (8 GiB at most) runs in
+ * slices of at most 2^20 segments.  TAMP_AMD_RESETS_SCAN_TILE segments are scanned per step of the one workgroup that places them.
+ */
+#define TAMP_AMD_RESETS_SCAN_TILE 1024
+int tamp_amd_compress_resets(const TampAmdConf *conf, const uint8_t *in, uint64_t in_len, uint32_t reset_interval, uint8_t *out,
+                             uint64_t out_cap, uint64_t *out_len, int8_t *status, uint64_t *reset_off /* may be NULL */,
+                             int mem, int device, void *stream);
+/* Host only.  Worst-case length of that stream: per segment the 2-byte lead, every byte a literal and the FLUSH token. */
+size_t tamp_amd_compress_resets_bound(size_t n, uint32_t reset_interval, uint8_t literal);
+/* DIAGNOSTICS, host only; this function and TAMP_AMD_RESETS_SCAN_TILE describe the implementation's geometry and may change or go
+ * between releases.  Stride of the segments' slabs in the call's scratch (segment k of a slice is gathered from byte k * slab of a
+ * 256-byte aligned buffer): diagnostics, and what the tests compute the gather's source alignments from. */
+size_t tamp_amd_compress_resets_slab(size_t n, uint32_t reset_interval, uint8_t literal);
+
+/*
+ * Reading such a stream back with the whole device.  For ONE stream whose header has the dictionary_reset bit and no custom bit the
+ * call returns out_len, status and in_consumed exactly as tamp_batch_decompress does for that stream with the given max_window_bits
+ * and out_cap -- and, with out == NULL, exactly as tamp_batch_decoded_size does with limit = out_cap, writing no bytes.  The resets are
+ * found on the device (the token grammar does not depend on them), the segments between them are decoded as a batch of independent
+ * streams into `out`.  That fast path is taken only when everything is clean: a stream shorter than TAMP_AMD_RESETS_MIN bytes
+ * (environment, default 262144, at least 64) or of 2^29 - 512 bytes and more, without the reset bit, with the custom bit, with a window
+ * above max_window_bits, with an offset out of its window, with more than four resets inside 512 (extended format: 128) compressed
+ * bytes, with a segment that does not end byte aligned at normal completion, or whose size reaches out_cap is handed to the exact
+ * path BEFORE anything is written -- same results, the speed of tamp_batch_decompress.  tamp_batch_decompress itself is unchanged.
+ *   in, out              where `mem` says; out_len, status, in_consumed (may be NULL): HOST memory, one element each
+ *   mem, device, stream  device memory: the kernels run on `stream`, and the call WAITS for them (it reads tables back as it goes)
+ *                        host memory: the device staging buffer for the output is out_cap bytes -- ask for the size first
+ *                        (out = NULL) and pass a little more than it, as tamp_amd.decompress() does, not a generous bound
+ * Returns TAMP_OK, TAMP_AMD_BAD_ARGUMENT, TAMP_AMD_NO_DEVICE -- or TAMP_ERROR, the one case in which bytes were written and no answer is
+ * given: the batch decode of a segment did not produce the size the size pass found for it (the two passes disagree: a defect of
+ * the library, never a property of the stream; out_len / status / in_consumed are not written).
+ */
+int tamp_amd_decompress_resets(uint8_t max_window_bits, const uint8_t *in, uint32_t in_len, uint8_t *out /* NULL: the size only */,
+                               uint32_t out_cap, uint32_t *out_len, int8_t *status, uint32_t *in_consumed /* may be NULL */,
+                               int mem, int device, void *stream);
+
 /* ---- resumable decoding: decoder OBJECTS that survive between calls ------------------------------
  *
  * What TampDecompressor is in the reference (decompressor.h:13-57): 16 bytes of state next to a window buffer,
@@ -488,14 +559,14 @@ tamp_res tamp_amd_read_header(TampAmdConf *conf, const unsigned char *input, siz
 
 /* Timing hook for bench.py: duration in milliseconds of the most recent codec kernel launched by this
  * thread on `device`, measured with hipEvents on the stream the kernel ran on; < 0 if none recorded.
- * Enabled by tamp_amd_set_timing(1). */
+ * Enabled by tamp_amd_set_timing(1).  After tamp_amd_compress_resets: all kernels of the call, as one figure. */
 void tamp_amd_set_timing(int enabled);
 float tamp_amd_last_kernel_ms(void);
 
 /* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
  * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
  * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
- * the expensive-first ordering (37 bytes per stream of the batch) and the long-stream decoder's chunk tables, tail maps and
+ * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets and the long-stream decoder's chunk tables, tail maps and
  * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.

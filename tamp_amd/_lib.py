@@ -18,6 +18,7 @@ OP_POLL, OP_COMPRESS, OP_FLUSH, OP_COMPRESS_AND_FLUSH = 1, 2, 3, 4  # include/ta
 ALL_DEVICES = -1  # include/tamp_amd.h TAMP_AMD_ALL_DEVICES
 WINDOW_BITS_EXACT = 0x80  # include/tamp_amd.h: TAMP_AMD_WINDOW_BITS_EXACT
 MEM_HOST, MEM_DEVICE = 0, 1
+RESETS_SCAN_TILE = 1024  # include/tamp_amd.h TAMP_AMD_RESETS_SCAN_TILE
 
 # every symbol include/tamp_amd.h declares (tests/test_capi_symbols.py checks header <-> library <-> this list)
 SYMBOLS = (
@@ -37,6 +38,10 @@ SYMBOLS = (
     "tamp_batch_compress_dicts",
     "tamp_batch_decompress_dicts",
     "tamp_batch_decoded_size_dicts",
+    "tamp_amd_compress_resets",
+    "tamp_amd_compress_resets_bound",
+    "tamp_amd_compress_resets_slab",
+    "tamp_amd_decompress_resets",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
     "tamp_batch_decompress_resume",
@@ -178,6 +183,14 @@ def load() -> C.CDLL:
     lib.tamp_batch_decompress_dicts.restype = i32
     lib.tamp_batch_decoded_size_dicts.argtypes = [sz, vp, u8, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
     lib.tamp_batch_decoded_size_dicts.restype = i32
+    lib.tamp_amd_compress_resets.argtypes = [C.POINTER(TampAmdConf), vp, C.c_uint64, u32, vp, C.c_uint64, vp, vp, vp, i32, i32, vp]
+    lib.tamp_amd_compress_resets.restype = i32
+    lib.tamp_amd_compress_resets_bound.argtypes = [sz, u32, u8]
+    lib.tamp_amd_compress_resets_bound.restype = sz
+    lib.tamp_amd_compress_resets_slab.argtypes = [sz, u32, u8]
+    lib.tamp_amd_compress_resets_slab.restype = sz
+    lib.tamp_amd_decompress_resets.argtypes = [u8, vp, u32, vp, u32, vp, vp, vp, i32, i32, vp]
+    lib.tamp_amd_decompress_resets.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]
     lib.tamp_amd_decoder_state_size.restype = sz
     lib.tamp_amd_decoder_state_init.argtypes = [vp, C.POINTER(TampAmdConf), u8]

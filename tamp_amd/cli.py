@@ -75,6 +75,9 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--extended", action=argparse.BooleanOptionalAction, default=True)
         if name == "compress":
             p.add_argument("--lazy-matching", action=argparse.BooleanOptionalAction, default=False)
+            p.add_argument("--reset-interval", type=int, default=None, metavar="N",
+                           help="reset the dictionary every N input bytes (sets the header's dictionary_reset bit): the "
+                                "segments between resets are compressed in parallel, at some cost in ratio")
     b = sub.add_parser("build-dictionary", help="Build a custom dictionary from a corpus of messages.")
     b.add_argument("input", metavar="INPUT", help="directory of sample files, or one file cut at --delimiter")
     b.add_argument("--output", "-o", default="dictionary.bin", help="binary dictionary file (effective bytes only)")
@@ -115,6 +118,8 @@ def main(argv=None) -> int:
         if args.dictionary is not None:
             kwargs["dictionary"] = load_dictionary(args.dictionary, args.window, args.literal, args.extended)
         if args.command == "compress":
+            if args.reset_interval is not None:
+                kwargs.update(dictionary_reset=True, reset_interval=args.reset_interval)
             out = tamp_amd.compress(data, window=args.window, literal=args.literal, lazy_matching=args.lazy_matching,
                                     extended=args.extended, **kwargs)
         else:

@@ -219,8 +219,53 @@ ONE_SHOT_MAX_IN = 0xFFFFFFFF
 ONE_SHOT_MAX_DECODE_IN = (1 << 29) - 1
 
 
-def compress(data: Union[bytes, str], *args, **kwargs) -> bytes:
-    """``tamp.compress`` (tamp/_c_compressor.pyx:189-199)."""
+def _compress_resets(data, reset_interval, args, kwargs) -> bytes:
+    """``compress(..., dictionary_reset=True, reset_interval=N)``: the bytes of ONE ``Compressor(dictionary_reset=True)`` that
+    gets ``reset_dictionary()`` after every ``N`` bytes of ``data`` but the last ones, and ``flush(write_token=False)`` at the
+    end.  The pieces between resets are independent streams, so an eligible call is one batch over the whole device
+    (``tamp_amd_compress_resets``); a call with a ``dictionary``, ``append``, ``str`` data or more than
+    ``ONE_SHOT_MAX_IN`` bytes runs the same script on the object -- same bytes, one workgroup."""
+    if isinstance(reset_interval, bool) or not isinstance(reset_interval, int) or reset_interval < 1:
+        raise ValueError("reset_interval must be a positive integer")
+    if not kwargs.get("dictionary_reset"):
+        raise ValueError("reset_interval needs dictionary_reset=True")  # (as reset_dictionary() on such an object)
+    known = {"window", "literal", "dictionary", "extended", "lazy_matching", "dictionary_reset", "append", "device"}
+    if (not args and isinstance(data, (bytes, bytearray, memoryview)) and set(kwargs) <= known and kwargs.get("dictionary") is None
+            and not kwargs.get("append") and len(data) <= ONE_SHOT_MAX_IN and reset_interval <= 0xFFFFFFFF):
+        window, literal = kwargs.get("window", 10), kwargs.get("literal", 8)
+        if not 8 <= window <= 15:
+            raise ValueError(f"window must be in 8..15, not {window!r}")
+        if not 5 <= literal <= 8:
+            raise ValueError(f"literal must be in 5..8, not {literal!r}")
+        lib = _lib.load()
+        conf = TampAmdConf(window, literal, 0, int(bool(kwargs.get("extended", True))), 1, int(bool(kwargs.get("lazy_matching"))))
+        src = np.frombuffer(bytes(data), dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+        cap = lib.tamp_amd_compress_resets_bound(len(data), reset_interval, literal)
+        out = np.empty(cap, dtype=np.uint8)
+        out_len, status = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.int8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = lib.tamp_amd_compress_resets(C.byref(conf), p(src), len(data), reset_interval, p(out), cap, p(out_len), p(status),
+                                          None, _lib.MEM_HOST, kwargs.get("device", 0), None)
+        _lib.check_launch(rc)
+        if int(status[0]) != _lib.OK:
+            _raise_for(int(status[0]))
+        return out[: int(out_len[0])].tobytes()
+    with BytesIO() as f:
+        c = TextCompressor(f, *args, **kwargs) if isinstance(data, str) else Compressor(f, *args, **kwargs)
+        # (str data: the interval counts characters, each piece is encoded on its own)
+        for at in range(0, max(len(data), 1), reset_interval):
+            if at:
+                c.reset_dictionary()
+            c.write(data[at : at + reset_interval])
+        c.flush(write_token=False)
+        f.seek(0)
+        return f.read()
+
+
+def compress(data: Union[bytes, str], *args, reset_interval=None, **kwargs) -> bytes:
+    """``tamp.compress`` (tamp/_c_compressor.pyx:189-199).  ``reset_interval`` (not in the reference): see ``_compress_resets``."""
+    if reset_interval is not None:
+        return _compress_resets(data, reset_interval, args, kwargs)
     if (not args and isinstance(data, (bytes, bytearray, memoryview)) and ONE_SHOT_BLOCK_MIN <= len(data) <= ONE_SHOT_MAX_IN
             and kwargs.get("extended", True) is False and kwargs.get("literal", 8) == 8
             and not kwargs.get("lazy_matching") and not kwargs.get("dictionary_reset") and not kwargs.get("append")
@@ -370,6 +415,36 @@ class TextDecompressor(Decompressor):
         return super().read(*args, **kwargs).decode()
 
 
+def _resets_min() -> int:
+    """Shortest blob ``decompress`` hands to ``tamp_amd_decompress_resets`` (the library's own threshold: TAMP_AMD_RESETS_MIN)."""
+    import os
+
+    try:
+        v = int(os.environ.get("TAMP_AMD_RESETS_MIN", ""))
+    except ValueError:
+        v = 0
+    return v if v >= 64 else ONE_SHOT_BLOCK_MIN
+
+
+def _decompress_resets(blob: bytes, device: int = 0):
+    """Size query, then the decode with that much room; None when either does not end with the normal end-of-input status
+    (the decoder object then says what is wrong)."""
+    lib = _lib.load()
+    src = np.frombuffer(blob, dtype=np.uint8)
+    out_len, consumed, status = np.zeros(1, np.uint32), np.zeros(1, np.uint32), np.zeros(1, np.int8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _lib.check_launch(lib.tamp_amd_decompress_resets(15, p(src), len(blob), None, 0xFFFFFFFF, p(out_len), p(status), p(consumed),
+                                                     _lib.MEM_HOST, device, None))
+    if int(status[0]) != _lib.INPUT_EXHAUSTED:
+        return None
+    out = np.empty(int(out_len[0]) + 64, dtype=np.uint8)
+    _lib.check_launch(lib.tamp_amd_decompress_resets(15, p(src), len(blob), p(out), len(out), p(out_len), p(status), p(consumed),
+                                                     _lib.MEM_HOST, device, None))
+    if int(status[0]) != _lib.INPUT_EXHAUSTED:
+        return None
+    return bytearray(memoryview(out)[: int(out_len[0])])
+
+
 def decompress(data: bytes, *args, **kwargs) -> bytearray:
     """``tamp.decompress`` (tamp/_c_decompressor.pyx:184-187).
 
@@ -378,6 +453,15 @@ def decompress(data: bytes, *args, **kwargs) -> bytearray:
     decodes ONE long stream with the whole device; everything else -- and whatever either call does not
     finish with the normal end-of-input status -- takes the decoder object below."""
     blob = bytes(data)
+    if (blob and (blob[0] & 1) and (blob[0] & 4) == 0 and not args and not kwargs
+            and _resets_min() <= len(blob) <= ONE_SHOT_MAX_DECODE_IN):
+        # a stream with dictionary resets: its segments as a batch over the whole device (tamp_amd_decompress_resets, DESIGN.md 3.13)
+        try:
+            out = _decompress_resets(blob)
+            if out is not None:
+                return out
+        except (MemoryError, OverflowError, _lib.NativeLibraryError):
+            pass
     if (ONE_SHOT_BLOCK_MIN <= len(blob) <= ONE_SHOT_MAX_DECODE_IN and not args and set(kwargs) <= {"dictionary"}
             and (blob[0] & 1) == 0):
         from .batch import decoded_size_batch, decompress_batch

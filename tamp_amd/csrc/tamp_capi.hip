@@ -31,6 +31,7 @@
 #include "tamp_decompress_plan.hpp"
 #include "tamp_decompress_resume_kernel.hpp"
 #include "tamp_compress_resume_kernel.hpp"
+#include "tamp_reset_segments_kernel.hpp"
 
 using namespace tamp_amd;
 
@@ -72,9 +73,9 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress and launch_decompress and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets and launch_decompress and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
-// lock -- and the record is passed down (launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
+// lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
 // with nor what a launched kernel still uses.
 struct StreamScratch {
@@ -87,6 +88,7 @@ struct StreamScratch {
     DeviceBuf long_tab;    // one long stream decoded by the whole device: chunk tables, records, group tables
     DeviceBuf long_tails;  // ... the groups' tail maps (groups x window x 2 bytes)
     DeviceBuf long_lags;   // ... extended format: the list of tokens that can lag, the lag lists
+    DeviceBuf resets;      // one buffer as dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets)
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -98,7 +100,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets}) n += b->release();
         return n;
     }
 };
@@ -528,12 +530,11 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
 }
 
 // `t`: device memory.  `seg` / `d_state`: a piece of one stream (segment_core), its state row.
-int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len, hipStream_t st,
-                    const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr) {
+// `rec`: the stream's scratch record, locked by the caller (launch_compress; launch_compress_resets, which holds it over its slices).
+int launch_compress_locked(DeviceCtx* ctx, StreamScratch& rec, const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len,
+                           hipStream_t st, const SegmentSpec* seg, uint8_t* d_state) {
     const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
-    StreamScratch& rec = ctx->scratch(st);
-    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
     CompressCall call = compress_call(conf, max_in_len, reinterpret_cast<uintptr_t>(t.dict));
     if (seg) call.nlead = seg->nlead, call.lead = seg->lead, call.seg_flags = seg->flags, call.has_state = d_state != nullptr;
     call.dict_table = t.dict_off != nullptr;
@@ -626,6 +627,13 @@ int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const BatchTables& 
     HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
+int launch_compress(DeviceCtx* ctx, const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len, hipStream_t st,
+                    const SegmentSpec* seg = nullptr, uint8_t* d_state = nullptr) {
+    if (t.n == 0) return TAMP_OK;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    return launch_compress_locked(ctx, rec, conf, t, max_in_len, st, seg, d_state);
+}
 
 // Largest window (bits) any stream header of the batch asks for, among those the caller's limit admits.  LDS rows of the
 // decoders are sized from it instead of from the limit: a caller that passes the API default (15) for 1 KiB-window
@@ -706,15 +714,18 @@ struct LongFront {
     bool dbg;              // TAMP_AMD_LONGDEC_DEBUG
 };
 // A stream behind the length gate that goes to the exact decoders after all: -> 1, and under TAMP_AMD_LONGDEC_DEBUG one line that says why.
-static int long_declined(bool dbg, const char* who, const char* why) {
-    if (dbg) fprintf(stderr, "[tamp_amd long %s] declined: %s\n", who, why);
+static int long_declined(bool dbg, const char* who, const char* why, const char* tag = "long") {
+    if (dbg) fprintf(stderr, "[tamp_amd %s %s] declined: %s\n", tag, who, why);
     return 1;
 }
 // -> 1 when the stream is not one for this path (or anything is off: the exact decoders take it), TAMP_OK with `f` filled in and
 // timing begun, an error code otherwise.  `who` names the caller in the debug lines.  `t`: the stream's single row; out_off and
 // out_cap may be null.  `has_dict`: a stream with the custom bit has a dictionary (the size query: its length alone, t.dict is null).
 int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate, const BatchTables& t, bool has_dict, uint8_t max_wbits,
-                      bool with_records, const char* who, hipStream_t st, LongFront& f) {
+                      bool with_records, const char* who, hipStream_t st, LongFront& f, bool resets = false) {
+    // `resets` (launch_decompress_resets): the front alone, for a stream WITH the dictionary_reset bit -- the token grammar does not
+    // depend on resets -- under its own tag and debug variable; every other caller keeps its gates and its lines
+    const char* const tag = resets ? "resets" : "long";
     uint64_t in_off = 0, out_off = 0, dict_off = 0;  // (dict_off: the stream's row of a dictionary table, 0 without one)
     uint32_t n = 0, cap = 0xFFFFFFFFu;
     HIP_OK(hipMemcpyAsync(&n, t.in_len, 4, hipMemcpyDeviceToHost, st));
@@ -722,7 +733,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     // (the chunk kernels count bits in 32-bit registers: (i + 1) * kLongChunkBits wraps for the last chunk of the top 512 bytes of
     // the accepted range -- those streams stay with the exact decoder)
     if (n < gate.min_len || n > kMaxDecodeIn - 512) return 1;
-    const bool dbg = f.dbg = getenv("TAMP_AMD_LONGDEC_DEBUG") != nullptr;
+    const bool dbg = f.dbg = getenv(resets ? "TAMP_AMD_RESETS_DEBUG" : "TAMP_AMD_LONGDEC_DEBUG") != nullptr;
     HIP_OK(hipMemcpyAsync(&in_off, t.in_off, 8, hipMemcpyDeviceToHost, st));
     if (t.out_off) HIP_OK(hipMemcpyAsync(&out_off, t.out_off, 8, hipMemcpyDeviceToHost, st));
     if (t.out_cap) HIP_OK(hipMemcpyAsync(&cap, t.out_cap, 4, hipMemcpyDeviceToHost, st));
@@ -734,11 +745,12 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     const StreamHeader hd = decode_header(hdr[0]);
     const uint32_t hs = 1 + (hdr[0] & 1), wbits = hd.wbits, lbits = hd.lbits;
     const bool extended = hd.extended;
-    if (hd.dreset || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15) return long_declined(dbg, who, "header");
-    if (extended && !gate.extended) return long_declined(dbg, who, "extended off");  // (tests: the exact decoder)
+    if ((resets ? !hd.dreset || hd.custom : hd.dreset) || (hs == 2 && hdr[1]) || wbits > (uint32_t)(max_wbits & 0x7F) || (max_wbits & 0x7F) > 15)
+        return long_declined(dbg, who, "header", tag);
+    if (extended && !gate.extended) return long_declined(dbg, who, "extended off", tag);  // (tests: the exact decoder)
     const uint32_t W = 1u << wbits;
     // (its own row's length; a misaligned row is the exact decoders' to report as well)
-    if (hd.custom && (!has_dict || !dict_off_aligned(dict_off) || !dict_off_in_bounds(dict_off, W, t.dict_len))) return long_declined(dbg, who, "dictionary");
+    if (hd.custom && (!has_dict || !dict_off_aligned(dict_off) || !dict_off_in_bounds(dict_off, W, t.dict_len))) return long_declined(dbg, who, "dictionary", tag);
     f.n = n, f.cap = cap, f.out_off = out_off, f.in = in, f.hd = hd, f.hs = hs;
     f.dict0 = hd.custom ? t.dict + dict_off : ctx->seed_dicts + ((size_t)hd.table << 15);
 
@@ -753,7 +765,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
         const size_t max_tok = (size_t)(total_bits / (1 + lbits)) + 4096;
         const size_t b_groups = ((size_t)(max_tok / 256 + N + 64) * (16 + sizeof(LongGroup) + 4) + 255) & ~(size_t)255;
         const size_t bytes = with_records ? b_tab + max_tok * 4 + b_groups + 4 * (size_t)(1u << 15) + 4096 : b_tab;
-        if (rec.long_tab.need(bytes) != hipSuccess) return long_declined(dbg, who, "scratch");
+        if (rec.long_tab.need(bytes) != hipSuccess) return long_declined(dbg, who, "scratch", tag);
     }
     uint8_t* const tab = static_cast<uint8_t*>(rec.long_tab.p);
     uint32_t* const g0 = reinterpret_cast<uint32_t*>(tab);
@@ -804,8 +816,8 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
         std::swap(cur, nxt);
         settled = changed == 0;
     }
-    if (dbg) fprintf(stderr, "[tamp_amd long %s] %u bytes, %u chunks, %d sync rounds, settled %d\n", who, n, N, rounds, (int)settled);
-    if (!settled) { timing_end(st); return long_declined(dbg, who, "not settled"); }
+    if (dbg) fprintf(stderr, "[tamp_amd %s %s] %u bytes, %u chunks, %d sync rounds, settled %d\n", tag, who, n, N, rounds, (int)settled);
+    if (!settled) { timing_end(st); return long_declined(dbg, who, "not settled", tag); }
     la.g = cur, la.g_next = nullptr, la.write = 0;
     HIP_OK(hipMemsetAsync(flags, 0, 8, st));
     hipLaunchKernelGGL(tamp_long_parse_kernel, dim3(lg), dim3(64), 0, st, la);
@@ -815,7 +827,7 @@ int long_decode_front(DeviceCtx* ctx, StreamScratch& rec, const DecodeLong& gate
     HIP_OK(hipMemcpyAsync(f.outb.data(), d_outb, (size_t)N * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(fl, flags, 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if (fl[1]) { timing_end(st); return long_declined(dbg, who, "offset out of window"); }  // an out-of-bounds offset: the exact decoder reports where
+    if (fl[1]) { timing_end(st); return long_declined(dbg, who, "offset out of window", tag); }  // an out-of-bounds offset: the exact decoder reports where
     return TAMP_OK;
 }
 
@@ -1135,12 +1147,11 @@ int each_long_stream(const BatchTables& t, hipStream_t st, const One& one) {
 }
 
 // `t`: device memory.  A stream with the custom bit starts from its row of the dictionary table, or from t.dict without one.
-int launch_decompress(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
+// `rec`: the stream's scratch record, locked by the caller (launch_decompress; launch_decompress_resets, which holds it over its steps).
+int launch_decompress_locked(DeviceCtx* ctx, StreamScratch& rec, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
     const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
     const DecompressArgs a = decompress_args(ctx, t);
-    StreamScratch& rec = ctx->scratch(st);
-    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
     const DecodeCall call = {n_streams, max_wbits, t.dict != nullptr};
     if (const DecodeLong gate = decode_wants_long(call); gate.attempt) {  // (tamp_decompress_long_kernel.hpp)
         const int rc = each_long_stream(t, st, [&](const BatchTables& row) { return launch_decompress_long(ctx, rec, gate, row, max_wbits, st); });
@@ -1169,6 +1180,12 @@ int launch_decompress(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, h
     }
     return run_decode_plan(ctx, rec, a, call, scan, dev, plan, st);
 }
+int launch_decompress(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
+    if (t.n == 0) return TAMP_OK;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    return launch_decompress_locked(ctx, rec, t, max_wbits, st);
+}
 
 // The size of ONE long stream: the long decoder's front counts output bytes per chunk, their sum is the answer (status 2, all of
 // the input consumed) as long as it stays below the stream's limit.  -> 1 when the lane kernel has to answer: the stream fails the
@@ -1192,15 +1209,13 @@ int launch_decoded_size_long(DeviceCtx* ctx, StreamScratch& rec, const DecodeLon
 // no pre-pass, nothing that waits for `st` -- except for a handful of long streams, which the long decoder's front counts with the
 // whole device (and waits as the long decoder does).  `t`: device memory, no slab -- out and out_off are null, out_cap holds the
 // limits (may be null), out_len takes the sizes; of the dictionary only the length matters (dict is null).
-int launch_decoded_size(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
+int launch_decoded_size_locked(DeviceCtx* ctx, StreamScratch& rec, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
     const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
     SplitArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.d = decompress_args(ctx, t);
     sa.d.max_wbits = max_wbits & 0x7F;  // (TAMP_AMD_WINDOW_BITS_EXACT: there is no pre-pass to skip)
-    StreamScratch& rec = ctx->scratch(st);
-    std::lock_guard<std::mutex> call_lock(rec.mu);  // (one library call at a time enqueues on a stream: the lock rule above StreamScratch)
     if (const DecodeLong gate = decode_wants_long({n_streams, max_wbits, t.dict_len != 0}); gate.attempt) {
         const int rc = each_long_stream(t, st, [&](const BatchTables& row) { return launch_decoded_size_long(ctx, rec, gate, row, max_wbits, st); });
         if (rc != 1) return rc;
@@ -1212,6 +1227,12 @@ int launch_decoded_size(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits,
     timing_end(st);
     HIP_OK(hipGetLastError());
     return TAMP_OK;
+}
+int launch_decoded_size(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits, hipStream_t st) {
+    if (t.n == 0) return TAMP_OK;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (one library call at a time enqueues on a stream: the lock rule above StreamScratch)
+    return launch_decoded_size_locked(ctx, rec, t, max_wbits, st);
 }
 
 // Resumable decoding: one wavefront per decoder object (tamp_decompress_resume_kernel.hpp).
@@ -1673,6 +1694,282 @@ int batch_compress(const TampAmdConf* conf, const BatchTables& t, uint32_t max_i
     });
 }
 
+// One long buffer as dictionary-reset segments (tamp_amd_compress_resets; kernels and format facts: tamp_reset_segments_kernel.hpp).
+// Segment k = input bytes [k * interval, (k + 1) * interval), compressed by the batch kernel as a stream of its own into slab k of
+// the stream's scratch: opened by the append lead, closed by a FLUSH token -- all but the call's last one, which a second launch
+// of one stream closes without (tamp.compress ends with flush(write_token = False)).  Scan + gather pack the slabs into the
+// caller's buffer.  When the slabs outgrow the scratch budget (the split decoder's rule: a quarter of the free memory, what the
+// record already holds counting as free, 8 GiB at most) the call runs in slices of at most 2^20 segments; the output base and the
+// status so far ride from slice to slice in device memory, so a device-memory call waits for nothing.
+// All pointers: device memory.  out_len / status: one element each; reset_off: K - 1 elements or null.
+int launch_compress_resets(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_t* d_in, uint64_t in_len, uint32_t interval,
+                           uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_len, int8_t* d_status, uint64_t* d_reset_off,
+                           hipStream_t st) {
+    const uint64_t K = reset_segment_count(in_len, interval);
+    const uint32_t slab = reset_slab_bytes(in_len, interval, conf->literal);
+    // (what sizes the compress kernel's block: the longest segment, with the floor of 16 the one-stream calls give plan_compress)
+    const uint32_t longest = (uint32_t)std::min<uint64_t>(interval, std::max<uint64_t>(in_len, 16));
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const size_t row_bytes = 8 + 8 + 8 + 4 + 4 + 4 + 1;  // in_off, out_off, dst_off, in_len, out_cap, out_len, status
+    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max((free_b + rec.resets.bytes) / 4, rec.resets.bytes));
+    else (void)hipGetLastError();
+    size_t slice = (size_t)std::min<uint64_t>(K, (uint64_t)1 << 20);
+    slice = std::min(slice, std::max<size_t>(budget / ((size_t)slab + row_bytes), 1));
+    if (const char* e = getenv("TAMP_AMD_RESETS_SLICE")) { const long v = atol(e); if (v > 0) slice = std::min(slice, (size_t)v); }  // (tuning / tests)
+    const size_t tab_bytes = (256 + slice * row_bytes + 64 + 255) & ~(size_t)255;
+    HIP_OK(rec.resets.need(tab_bytes + slice * (size_t)slab + 64));
+    uint8_t* const base = static_cast<uint8_t*>(rec.resets.p);
+    ResetCarry* const carry = reinterpret_cast<ResetCarry*>(base);
+    uint64_t* const in_off = reinterpret_cast<uint64_t*>(base + 256);
+    uint64_t* const out_off = in_off + slice;
+    uint64_t* const dst_off = out_off + slice;
+    uint32_t* const seg_in = reinterpret_cast<uint32_t*>(dst_off + slice);
+    uint32_t* const seg_cap = seg_in + slice;
+    uint32_t* const seg_len = seg_cap + slice;
+    int8_t* const seg_status = reinterpret_cast<int8_t*>(seg_len + slice);
+    uint8_t* const slabs = base + tab_bytes;
+    HIP_OK(hipMemsetAsync(carry, 0, sizeof(ResetCarry), st));
+    BatchTables t;
+    t.in = in_len ? d_in : base;  // (an empty input: memory of the library's own to point at)
+    t.in_off = in_off, t.in_len = seg_in, t.out = slabs, t.out_off = out_off, t.out_cap = seg_cap, t.out_len = seg_len, t.status = seg_status;
+    const SegmentSpec with_token = {2, (uint16_t)(0xABu << 7), kSegFlushToken}, without = {2, (uint16_t)(0xABu << 7), 0};
+    const uint8_t header = header_byte(conf, true);
+    if (getenv("TAMP_AMD_RESETS_DEBUG"))
+        fprintf(stderr, "[tamp_amd resets] compress: %llu segments of %u bytes, slab %u, %zu per slice\n", (unsigned long long)K, interval, slab, slice);
+    timing_begin(st);  // (one event pair around the call's kernels: the inner launches do not open their own)
+    t_timing_outer = true;
+    struct OuterTiming { ~OuterTiming() { t_timing_outer = false; } } outer_timing;
+    for (uint64_t k0 = 0; k0 < K; k0 += slice) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(slice, K - k0);
+        const bool last = k0 + cnt == K;
+        const ResetRowsArgs rows = {k0, cnt, interval, in_len, slab, in_off, seg_in, out_off, seg_cap};
+        hipLaunchKernelGGL(tamp_reset_rows_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, rows);
+        t.n = cnt;
+        const uint32_t closed = last ? cnt - 1 : cnt;  // segments that end with a reset
+        if (const int rc = launch_compress_locked(ctx, rec, conf, t.rows(0, closed), longest, st, &with_token, nullptr)) return rc;
+        if (last)
+            if (const int rc = launch_compress_locked(ctx, rec, conf, t.rows(closed, 1), longest, st, &without, nullptr)) return rc;
+        const ResetScanArgs scan = {seg_len, seg_status, cnt, k0, dst_off, d_reset_off, carry, last ? 1u : 0u, out_cap, d_out_len, d_status};
+        hipLaunchKernelGGL(tamp_reset_scan_kernel, dim3(1), dim3(kResetScanTile), 0, st, scan);
+        const ResetGatherArgs gather = {slabs, slab, cnt, seg_len, dst_off, d_out, out_cap, k0 == 0 ? 1u : 0u, (uint32_t)header};
+        const uint32_t grid = (uint32_t)std::min<size_t>(cnt, (size_t)ctx->cu_count * 8);
+        hipLaunchKernelGGL(tamp_reset_gather_kernel, dim3(grid), dim3(256), 0, st, gather);
+    }
+    timing_end(st);
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
+// tamp_amd_compress_resets behind its checks.  Host memory: the input goes to the device in one piece and exactly the produced
+// bytes, the results and the reset offsets come back, on the host pipeline's first stream (one host-memory call per device at a time).
+int compress_resets(const TampAmdConf* conf, const uint8_t* in, uint64_t in_len, uint32_t interval, uint8_t* out, uint64_t out_cap,
+                    uint64_t* out_len, int8_t* status, uint64_t* reset_off, int mem, int device, void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE)
+        return launch_compress_resets(ctx, conf, in, in_len, interval, out, out_cap, out_len, status, reset_off, static_cast<hipStream_t>(stream));
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> call_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    const uint64_t K = reset_segment_count(in_len, interval);
+    const uint64_t room = std::min<uint64_t>(out_cap, tamp_amd_compress_resets_bound(in_len, interval, conf->literal));
+    HIP_OK(P.in[0].need(in_len + 64));  // the kernels' vector loads may run past the last byte
+    HIP_OK(P.out[0].need(room + 1));
+    HIP_OK(P.meta[0].need(16 + (reset_off ? 8 * (size_t)K : 0)));  // (the offsets only when asked for: K can be 2^32 - 1)
+    uint8_t* const d_in = static_cast<uint8_t*>(P.in[0].p);
+    uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
+    uint64_t* const d_len = static_cast<uint64_t*>(P.meta[0].p);
+    int8_t* const d_status = reinterpret_cast<int8_t*>(d_len + 1);
+    uint64_t* const d_reset = d_len + 2;
+    if (in_len) HIP_OK(hipMemcpyAsync(d_in, in, in_len, hipMemcpyHostToDevice, st));
+    // (`room` instead of out_cap: a total above the bound does not exist, one above out_cap is above `room` as well)
+    if (const int rc = launch_compress_resets(ctx, conf, d_in, in_len, interval, d_out, room, d_len, d_status, reset_off ? d_reset : nullptr, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(out_len, d_len, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(status, d_status, 1, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (*status != TAMP_OK || *out_len == 0) return TAMP_OK;
+    HIP_OK(hipMemcpyAsync(out, d_out, *out_len, hipMemcpyDeviceToHost, st));
+    if (reset_off && K > 1) HIP_OK(hipMemcpyAsync(reset_off, d_reset, 8 * (size_t)(K - 1), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return TAMP_OK;
+}
+
+// Reading a stream with dictionary resets back (tamp_amd_decompress_resets): the long-stream decoder's front settles the token
+// starts of every chunk, tamp_reset_find_kernel reports the FLUSH pairs, the host merges the reports into the resets' positions
+// (tamp_reset_merge.hpp), the segments between them are staged behind the stream's two header bytes as K streams of their own,
+// the size build of the split decoder's parse sizes them, and ONE decode call of K streams writes them back to back into the
+// caller's buffer.  -> TAMP_OK: done, results in *out_len / *status / *consumed (host memory); 1: declined BEFORE anything was
+// written (the caller runs the exact path); an error code (TAMP_ERROR: the batch decode disagreed with the size build).  `rec`: locked by the caller.  d_out == null: the size alone.
+int decompress_resets_declined(bool dbg, const char* why) {
+    if (dbg) fprintf(stderr, "[tamp_amd resets] declined: %s\n", why);
+    return 1;
+}
+int launch_decompress_resets(DeviceCtx* ctx, StreamScratch& rec, const uint8_t* d_in, uint32_t n, uint8_t* d_out, uint32_t cap,
+                             uint8_t max_wbits, hipStream_t st, uint32_t* out_len, int8_t* status, uint32_t* consumed) {
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    DecodeLong gate = {true, 256u << 10, true, true};
+    if (const char* e = getenv("TAMP_AMD_RESETS_MIN")) { const long v = atol(e); if (v >= 64) gate.min_len = (uint32_t)v; }
+    if (n < gate.min_len || n > kMaxDecodeIn - 512) return decompress_resets_declined(dbg, "length");
+    // the stream's row for the front, in device memory
+    HIP_OK(rec.resets.need(256));
+    {
+        const uint64_t zero = 0;
+        uint8_t* const row = static_cast<uint8_t*>(rec.resets.p);
+        HIP_OK(hipMemcpyAsync(row, &zero, 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(row + 8, &n, 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(row + 12, &cap, 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));  // (the sources are locals)
+    }
+    BatchTables row;
+    {
+        uint8_t* const r = static_cast<uint8_t*>(rec.resets.p);
+        row.in = d_in, row.in_off = reinterpret_cast<const uint64_t*>(r), row.in_len = reinterpret_cast<const uint32_t*>(r + 8);
+        row.out_cap = reinterpret_cast<const uint32_t*>(r + 12), row.n = 1;
+    }
+    LongFront f;
+    if (const int rc = long_decode_front(ctx, rec, gate, row, false, max_wbits, false, "front", st, f, true); rc != TAMP_OK) return rc;
+    timing_end(st);  // (the front began the pair; the steps below make their own)
+    // where the resets are
+    const uint32_t N = f.N;
+    HIP_OK(rec.resets.need((size_t)N * sizeof(ResetChunkReport) + 256));
+    ResetChunkReport* const d_rep = static_cast<ResetChunkReport*>(rec.resets.p);
+    const ResetFindArgs find = {f.la, d_rep};
+    hipLaunchKernelGGL(tamp_reset_find_kernel, dim3(f.lg), dim3(64), 0, st, find);
+    std::vector<ResetChunkReport> rep(N);
+    HIP_OK(hipMemcpyAsync(rep.data(), d_rep, (size_t)N * sizeof(ResetChunkReport), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    std::vector<uint32_t> boundaries, seg_start, seg_len;
+    if (!reset_merge(rep.data(), N, boundaries)) return decompress_resets_declined(dbg, "resets per chunk");
+    if (!reset_segments_of(boundaries, f.hs, n, seg_start, seg_len)) return decompress_resets_declined(dbg, "positions");
+    const size_t K = seg_start.size();
+    // the staged streams and their tables: in_off, out_off (u64), src_off, src_len, in_len, out_cap, size, consumed (u32), status
+    std::vector<uint64_t> in_off(K), out_off(K);
+    std::vector<uint32_t> in_len(K), size(K), used(K);
+    std::vector<int8_t> st8(K);
+    uint64_t staged = 0;
+    for (size_t k = 0; k < K; k++) in_off[k] = staged, in_len[k] = seg_len[k] + 2, staged += ((uint64_t)seg_len[k] + 2 + 3) & ~3ull;
+    const size_t tab_bytes = (K * (8 + 8 + 6 * 4 + 1) + 64 + 255) & ~(size_t)255;
+    if (rec.resets.need(tab_bytes + staged + 64) != hipSuccess) { (void)hipGetLastError(); return decompress_resets_declined(dbg, "scratch"); }
+    uint8_t* const base = static_cast<uint8_t*>(rec.resets.p);
+    uint64_t* const d_in_off = reinterpret_cast<uint64_t*>(base);
+    uint64_t* const d_out_off = d_in_off + K;
+    uint32_t* const d_src_off = reinterpret_cast<uint32_t*>(d_out_off + K);
+    uint32_t* const d_src_len = d_src_off + K;
+    uint32_t* const d_in_len = d_src_len + K;
+    uint32_t* const d_cap = d_in_len + K;
+    uint32_t* const d_size = d_cap + K;
+    uint32_t* const d_used = d_size + K;
+    int8_t* const d_st = reinterpret_cast<int8_t*>(d_used + K);
+    uint8_t* const stage = base + tab_bytes;
+    HIP_OK(hipMemcpyAsync(d_in_off, in_off.data(), K * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_src_off, seg_start.data(), K * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_src_len, seg_len.data(), K * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_len, in_len.data(), K * 4, hipMemcpyHostToDevice, st));
+    const ResetStageArgs sa = {d_in, d_src_off, d_src_len, d_in_off, stage, (uint32_t)K, ((f.hd.wbits - 8) << 5) | ((f.hd.lbits - 5) << 3) | ((uint32_t)f.hd.extended << 1) | 1u}  /* header byte 0; byte 1 is zero */;
+    hipLaunchKernelGGL(tamp_reset_stage_kernel, dim3((uint32_t)std::min<size_t>(K, (size_t)ctx->cu_count * 8)), dim3(256), 0, st, sa);
+    BatchTables t;
+    t.in = stage, t.in_off = d_in_off, t.in_len = d_in_len, t.out_len = d_size, t.status = d_st, t.in_consumed = d_used, t.n = K;
+    if (const int rc = launch_decoded_size_locked(ctx, rec, t, max_wbits, st)) return rc;
+    HIP_OK(hipMemcpyAsync(size.data(), d_size, K * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(used.data(), d_used, K * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(st8.data(), d_st, K, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t total = 0;
+    for (size_t k = 0; k < K; k++) {
+        if (st8[k] != TAMP_INPUT_EXHAUSTED || used[k] != in_len[k]) return decompress_resets_declined(dbg, "segment");
+        out_off[k] = total, total += size[k];
+    }
+    // (room that is used up exactly is the exact decoder's to judge, as in the long-stream decoder)
+    if (total >= cap) return decompress_resets_declined(dbg, "output room");
+    if (d_out) {
+        HIP_OK(hipMemcpyAsync(d_out_off, out_off.data(), K * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_cap, size.data(), K * 4, hipMemcpyHostToDevice, st));
+        t.out = d_out, t.out_off = d_out_off, t.out_cap = d_cap;
+        if (const int rc = launch_decompress_locked(ctx, rec, t, max_wbits, st)) return rc;
+        std::vector<uint32_t> got(K);
+        HIP_OK(hipMemcpyAsync(got.data(), d_size, K * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(st8.data(), d_st, K, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (size_t k = 0; k < K; k++)  // (a segment's room is its exact size: padding bits left read as TAMP_OUTPUT_FULL)
+            if (got[k] != size[k] || (st8[k] != TAMP_INPUT_EXHAUSTED && st8[k] != TAMP_OUTPUT_FULL)) {
+                if (dbg) fprintf(stderr, "[tamp_amd resets] segment %zu decoded to status %d, %u of %u bytes\n", k, (int)st8[k], got[k], size[k]);
+                return TAMP_ERROR;
+            }
+    }
+    if (dbg) fprintf(stderr, "[tamp_amd resets] %s: %zu segments, %llu bytes out\n", d_out ? "decoded" : "sized", K, (unsigned long long)total);
+    *out_len = (uint32_t)total, *status = TAMP_INPUT_EXHAUSTED, *consumed = n;
+    return TAMP_OK;
+}
+
+// The entry point behind its checks: the fast path, or -- declined -- the exact path of tamp_batch_decompress / _decoded_size for
+// the one stream, under the same lock.  in / out: device memory; the three results: host memory.
+int decompress_resets_device(DeviceCtx* ctx, const uint8_t* d_in, uint32_t n, uint8_t* d_out, uint32_t cap, uint8_t max_wbits,
+                             hipStream_t st, uint32_t* out_len, int8_t* status, uint32_t* consumed) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    // (TAMP_ERROR: a staged segment did not decode to the size the size build gave it -- the two disagree, which is a defect of the
+    // library and not a property of the stream; bytes have been written by then, so it is reported, not handed to the exact path)
+    int rc = launch_decompress_resets(ctx, rec, d_in, n, d_out, cap, max_wbits, st, out_len, status, consumed);
+    if (rc != 1) return rc;
+    HIP_OK(rec.resets.need(256));
+    uint8_t* const r = static_cast<uint8_t*>(rec.resets.p);
+    const uint64_t zero = 0;
+    HIP_OK(hipMemcpyAsync(r, &zero, 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(r + 8, &n, 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(r + 12, &cap, 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));
+    BatchTables t;
+    t.in = d_in, t.in_off = reinterpret_cast<const uint64_t*>(r), t.in_len = reinterpret_cast<const uint32_t*>(r + 8);
+    t.out_cap = reinterpret_cast<const uint32_t*>(r + 12), t.out_len = reinterpret_cast<uint32_t*>(r + 16);
+    t.in_consumed = reinterpret_cast<uint32_t*>(r + 20), t.status = reinterpret_cast<int8_t*>(r + 24), t.n = 1;
+    if (d_out) {
+        t.out = d_out, t.out_off = reinterpret_cast<const uint64_t*>(r);
+        rc = launch_decompress_locked(ctx, rec, t, max_wbits, st);
+    } else {
+        rc = launch_decoded_size_locked(ctx, rec, t, max_wbits, st);
+    }
+    if (rc != TAMP_OK) return rc;
+    HIP_OK(hipMemcpyAsync(out_len, r + 16, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(consumed, r + 20, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(status, r + 24, 1, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return TAMP_OK;
+}
+
+int decompress_resets(uint8_t max_wbits, const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* out_len, int8_t* status,
+                      uint32_t* consumed, int mem, int device, void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE)
+        return decompress_resets_device(ctx, in, n, out, cap, max_wbits, static_cast<hipStream_t>(stream), out_len, status, consumed);
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> call_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    HIP_OK(P.in[0].need((size_t)n + 64));
+    if (out) HIP_OK(P.out[0].need((size_t)cap + 1));
+    uint8_t* const d_in = static_cast<uint8_t*>(P.in[0].p);
+    uint8_t* const d_out = out ? static_cast<uint8_t*>(P.out[0].p) : nullptr;
+    if (n) HIP_OK(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, st));
+    if (const int rc = decompress_resets_device(ctx, d_in, n, d_out, cap, max_wbits, st, out_len, status, consumed)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (out && *out_len) {
+        HIP_OK(hipMemcpyAsync(out, d_out, *out_len, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    return TAMP_OK;
+}
+
 int batch_decompress(BatchTables t, uint8_t max_window_bits, int mem, int device, void* stream) {
     if (const int rc = batch_refused(t, true, mem, device)) return rc;
     if (!t.dict) t.dict_len = 0, t.dict_off = nullptr;  // (no buffer: every stream with the custom bit is TAMP_INVALID_CONF, as ever)
@@ -1783,6 +2080,39 @@ void tamp_window_copy(unsigned char* window, uint16_t* window_pos, uint16_t wind
 
 size_t tamp_amd_compress_bound(size_t n, uint8_t literal, int dictionary_reset) {
     return 1 + (dictionary_reset ? 1 : 0) + (n * ((size_t)literal + 1) + 7) / 8;
+}
+
+size_t tamp_amd_compress_resets_bound(size_t n, uint32_t reset_interval, uint8_t literal) {
+    if (!reset_interval) return 0;
+    return (size_t)reset_stream_bound(n, reset_interval, literal);
+}
+
+size_t tamp_amd_compress_resets_slab(size_t n, uint32_t reset_interval, uint8_t literal) {
+    return reset_interval ? reset_slab_bytes(n, reset_interval, literal) : 0;
+}
+
+int tamp_amd_compress_resets(const TampAmdConf* conf, const uint8_t* in, uint64_t in_len, uint32_t reset_interval, uint8_t* out,
+                             uint64_t out_cap, uint64_t* out_len, int8_t* status, uint64_t* reset_off, int mem, int device,
+                             void* stream) {
+    if (!conf || !out_len || !status || (in_len && !in) || (out_cap && !out)) return TAMP_AMD_BAD_ARGUMENT;
+    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
+    if (!conf_valid(conf) || conf->lazy_matching > 1 || !conf->dictionary_reset || conf->use_custom_dictionary || !reset_interval ||
+        in_len > 0xFFFFFFFFull)
+        return TAMP_AMD_BAD_ARGUMENT;
+    // (a table row's capacity is 32 bits wide: a segment whose worst case does not fit one is not taken)
+    if (reset_segment_bound(std::min<uint64_t>(reset_interval, std::max<uint64_t>(in_len, 1)), conf->literal, true) > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    return compress_resets(conf, in, in_len, reset_interval, out, out_cap, out_len, status, reset_off, mem, device, stream);
+}
+
+int tamp_amd_decompress_resets(uint8_t max_window_bits, const uint8_t* in, uint32_t in_len, uint8_t* out, uint32_t out_cap,
+                               uint32_t* out_len, int8_t* status, uint32_t* in_consumed, int mem, int device, void* stream) {
+    if (!out_len || !status || (in_len && !in)) return TAMP_AMD_BAD_ARGUMENT;
+    if (mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) return TAMP_AMD_BAD_ARGUMENT;
+    uint32_t consumed = 0;
+    static const unsigned char empty = 0;
+    const int rc = decompress_resets(max_window_bits, in_len ? in : &empty, in_len, out, out_cap, out_len, status, &consumed, in_len ? mem : TAMP_AMD_MEM_HOST, device, stream);
+    if (rc == TAMP_OK && in_consumed) *in_consumed = consumed;
+    return rc;
 }
 
 int tamp_amd_device_count(void) {
