@@ -372,6 +372,34 @@ size_t tamp_amd_compress_resets_bound(size_t n, uint32_t reset_interval, uint8_t
 size_t tamp_amd_compress_resets_slab(size_t n, uint32_t reset_interval, uint8_t literal);
 
 /*
+ * The batch form: EVERY stream of a batch cut into segments of reset_interval bytes, one interval for the whole call.  The segments of
+ * all streams are the units of work, each about as long as the next, so a ragged batch with a few long streams no longer waits for
+ * its longest stream on one workgroup.  Stream i, with K_i = max(1, ceil(in_len[i] / reset_interval)) segments, is byte for byte
+ * what tamp_amd_compress_resets returns for that buffer alone (the script above); an empty stream is one empty segment.
+ *
+ *   conf, reset_interval   as above: dictionary_reset 1, use_custom_dictionary 0, reset_interval >= 1, and the worst case of ONE
+ *                   segment of reset_interval bytes must fit 32 bits; otherwise TAMP_AMD_BAD_ARGUMENT and nothing is written
+ *   in .. status, n_streams, max_in_len, mem, device, stream   the tables of tamp_batch_compress, with its meaning of every one;
+ *                   TAMP_AMD_ALL_DEVICES is not taken.  n_streams == 0: TAMP_OK, nothing is done
+ *   max_in_len      a hint, as there: it sizes the compress kernel's block (for segments: min(reset_interval, max(max_in_len, 16))
+ *                   positions), and a stale one costs speed, never bytes -- the slabs are sized from in_len[] itself.  0 = unknown:
+ *                   the longest stream of the tables stands in.  A host-memory call reads the tables and ignores the hint
+ *   out_cap[i]      tamp_amd_compress_resets_bound(in_len[i], reset_interval, conf->literal) bytes always suffice
+ *   out_len[i], status[i]   TAMP_OK and the stream's length; TAMP_EXCESS_BITS when any of its segments holds a byte outside
+ *                   conf->literal bits, TAMP_OUTPUT_FULL when its stream is longer than out_cap[i]: out_len[i] = 0 for both, the bytes
+ *                   of its slab are unspecified, nothing is written in front of out + out_off[i] or at or behind
+ *                   out + out_off[i] + out_cap[i], and no other stream is affected
+ * A host-memory call is synchronous and writes exactly the produced bytes and the two result tables.  A device-memory call runs on
+ * `stream` and WAITS once, early, for one 16-byte record it reads back -- how many segments the batch has and how long its longest
+ * stream is, which size its scratch (the slabs of tamp_amd_compress_resets, per HIP stream, in slices by the same rule); everything
+ * behind that is asynchronous.
+ */
+int tamp_batch_compress_resets(const TampAmdConf *conf, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                               uint32_t reset_interval, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                               uint32_t *out_len, int8_t *status, size_t n_streams, uint32_t max_in_len,
+                               int mem, int device, void *stream);
+
+/*
  * Reading such a stream back with the whole device.  For ONE stream whose header has the dictionary_reset bit and no custom bit the
  * call returns out_len, status and in_consumed exactly as tamp_batch_decompress does for that stream with the given max_window_bits
  * and out_cap -- and, with out == NULL, exactly as tamp_batch_decoded_size does with limit = out_cap, writing no bytes.  The resets are

@@ -41,6 +41,7 @@ SYMBOLS = (
     "tamp_amd_compress_resets",
     "tamp_amd_compress_resets_bound",
     "tamp_amd_compress_resets_slab",
+    "tamp_batch_compress_resets",
     "tamp_amd_decompress_resets",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
@@ -189,6 +190,8 @@ def load() -> C.CDLL:
     lib.tamp_amd_compress_resets_bound.restype = sz
     lib.tamp_amd_compress_resets_slab.argtypes = [sz, u32, u8]
     lib.tamp_amd_compress_resets_slab.restype = sz
+    lib.tamp_batch_compress_resets.argtypes = [C.POINTER(TampAmdConf), vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp]
+    lib.tamp_batch_compress_resets.restype = i32
     lib.tamp_amd_decompress_resets.argtypes = [u8, vp, u32, vp, u32, vp, vp, vp, i32, i32, vp]
     lib.tamp_amd_decompress_resets.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]

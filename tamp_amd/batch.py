@@ -27,6 +27,28 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+def compress_resets_bound(n, reset_interval: int, literal: int = 8):
+    """Not part of the package's surface: how ``compress_batch(..., reset_interval=N, out_cap=None)`` sizes its slabs -- the
+    arithmetic of ``tamp_amd_compress_resets_bound`` (tests pin the two together) for whole tables at once, on the device for CUDA
+    tensors, where a C call per stream would take a copy and a sync.  Worst-case size of an ``n``-byte stream: per segment
+    the 2-byte lead and every byte a literal, a FLUSH token behind every segment but the last.  ``n``: an int, or per-stream lengths
+    as a numpy array or torch tensor (-> uint64 array / int64 tensor)."""
+    if _is_torch(n):
+        import torch
+
+        n = n.to(torch.int64) & 0xFFFFFFFF  # (lengths are uint32 values, whatever the storage)
+        closed = (torch.clamp(n, min=1) - 1) // reset_interval
+    elif isinstance(n, np.ndarray):
+        n = n.astype(np.uint64)
+        closed = (np.maximum(n, np.uint64(1)) - np.uint64(1)) // np.uint64(reset_interval)
+        reset_interval, literal = np.uint64(reset_interval), np.uint64(literal)
+        return (closed * (np.uint64(2) + (reset_interval * (literal + np.uint64(1)) + np.uint64(16)) // np.uint64(8)) + np.uint64(2)
+                + ((n - closed * reset_interval) * (literal + np.uint64(1)) + np.uint64(7)) // np.uint64(8))
+    else:
+        closed = (max(n, 1) - 1) // reset_interval
+    return closed * (2 + (reset_interval * (literal + 1) + 16) // 8) + 2 + ((n - closed * reset_interval) * (literal + 1) + 7) // 8
+
+
 @dataclass
 class BatchResult:
     out: object          # uint8 buffer (numpy array or torch tensor) holding every stream's slab
@@ -200,7 +222,7 @@ def trim(device: int = 0) -> int:
 def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal: int = 8, extended: bool = True,
                    dictionary=None, dictionary_reset: bool = False, lazy_matching: bool = False, out_cap=None,
                    max_in_len: int = 0, device: int = 0, stream=None, timing: bool = False,
-                   run_aware=None, reuse=None, dictionaries=None, dictionary_index=None) -> BatchResult:
+                   run_aware=None, reuse=None, dictionaries=None, dictionary_index=None, reset_interval=None) -> BatchResult:
     """Compress many independent streams in one launch.
 
     ``data`` is a list of bytes-likes (host), a flat numpy uint8 array + ``in_off``/``in_len`` (host), or a flat
@@ -218,7 +240,26 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
     ``dictionaries`` is K bytes objects of ``1 << window`` bytes each, or a uint8 array / CUDA tensor of shape
     ``(K, 1 << window)``; stream ``i`` is compressed as ``dictionary=dictionaries[dictionary_index[i]]`` would compress it
     (``dictionary=DictionaryTable(dictionaries, dictionary_index)`` says the same).
+    ``reset_interval`` (with ``dictionary_reset=True``; not in the reference): every stream is cut every ``reset_interval`` bytes
+    and the segments of ALL streams are the units of work (``tamp_batch_compress_resets``), so a ragged batch does
+    not wait for its longest stream.  Stream ``i`` is ``tamp_amd.compress(stream_i, dictionary_reset=True, reset_interval=...)``;
+    ``out_cap=None`` sizes the slabs with the bound of ``tamp_amd_compress_resets_bound``.  ``max_in_len`` stays a hint, as without resets.  Not with a dictionary of any form, nor with ``reuse``.
     """
+    if reset_interval is not None:  # (the rules and wording of codec._compress_resets; all decided before the library is looked for)
+        if isinstance(reset_interval, bool) or not isinstance(reset_interval, int) or reset_interval < 1:
+            raise ValueError("reset_interval must be a positive integer")
+        if not dictionary_reset:
+            raise ValueError("reset_interval needs dictionary_reset=True")
+        if dictionary is not None or dictionaries is not None or dictionary_index is not None:
+            raise ValueError("reset_interval excludes dictionaries: a reset restores the seeded window")
+        if reuse is not None:
+            raise ValueError("reset_interval excludes reuse")
+        if reset_interval > 0xFFFFFFFF:
+            raise ValueError("reset_interval must fit 32 bits")
+        if not 8 <= window <= 15:
+            raise ValueError(f"window must be in 8..15, not {window!r}")
+        if not 5 <= literal <= 8:
+            raise ValueError(f"literal must be in 5..8, not {literal!r}")
     dictionary, table = _dict_table(dictionary, dictionaries, dictionary_index, window)
     if stream is not None and _is_torch(data):
         # The call makes its tables (capacities, offsets) and its output slab with torch: they have to come into being on the
@@ -230,7 +271,8 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
             return compress_batch(data, in_off, in_len, window=window, literal=literal, extended=extended,
                                   dictionary=dictionary if table is None else table,
                                   dictionary_reset=dictionary_reset, lazy_matching=lazy_matching, out_cap=out_cap,
-                                  max_in_len=max_in_len, device=device, stream=None, timing=timing, run_aware=run_aware, reuse=reuse)
+                                  max_in_len=max_in_len, device=device, stream=None, timing=timing, run_aware=run_aware, reuse=reuse,
+                                  reset_interval=reset_interval)
     lib = _lib.load()
     conf = _conf(window, literal, extended, dictionary if table is None else table, dictionary_reset, lazy_matching, run_aware)
     if dictionary is not None and not _is_torch(dictionary) and len(dictionary) != (1 << window):
@@ -248,6 +290,13 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
             # previous call are written again -- no allocation, no fill kernels, nothing on the host but the launch
             ws = reuse
             out, out_off_t, out_len_t, status_t, out_cap_t = ws.out, ws.out_off, ws.out_len, ws.status, ws._keep[3]
+        elif out_cap is None and reset_interval is not None:
+            cap64 = compress_resets_bound(in_len, reset_interval, literal)
+            total, largest = (int(x) for x in torch.stack((cap64.sum(), cap64.max())).tolist()) if n else (0, 0)
+            if largest > 0xFFFFFFFF:
+                raise ValueError("a stream's bound does not fit 32 bits: pass out_cap")
+            out_cap_t = cap64.to(torch.int32)  # (the low 32 bits: what the library reads as uint32)
+            out_off_t = torch.cumsum(cap64, 0) - cap64
         elif out_cap is None or _is_int(out_cap):
             if _is_int(out_cap):
                 cap1 = int(out_cap)  # one capacity for every stream: no device round trip to lay the slabs out
@@ -281,6 +330,10 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                                _ptr(in_off_t), _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
                                                _ptr(out_len_t), _ptr(status_t), n, int(max_in_len), _lib.MEM_DEVICE,
                                                dev.index or 0, C.c_void_p(st))
+        elif reset_interval is not None:
+            rc = lib.tamp_batch_compress_resets(C.byref(conf), _ptr(data), _ptr(in_off_t), _ptr(in_len_t), reset_interval, _ptr(out),
+                                                _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t), _ptr(status_t), n, int(max_in_len),
+                                                _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st))
         else:
             rc = lib.tamp_batch_compress(C.byref(conf), _ptr(dict_t), _ptr(data), _ptr(in_off_t),
                                          _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
@@ -299,7 +352,11 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
     n = len(in_len)
-    if out_cap is None:
+    if out_cap is None and reset_interval is not None:
+        out_cap = compress_resets_bound(in_len, reset_interval, literal)
+        if n and int(out_cap.max()) > 0xFFFFFFFF:
+            raise ValueError("a stream's bound does not fit 32 bits: pass out_cap")
+    elif out_cap is None:
         out_cap = np.array([compress_bound(int(x), literal, dictionary_reset) for x in in_len], dtype=np.uint32)
     elif _is_int(out_cap):
         out_cap = np.full(n, int(out_cap), dtype=np.uint32)
@@ -315,6 +372,10 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                            _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len), _ptr(out),
                                            _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), n, int(max_in_len),
                                            _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
+    elif reset_interval is not None:
+        rc = lib.tamp_batch_compress_resets(C.byref(conf), _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len),
+                                            reset_interval, _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), n,
+                                            int(max_in_len), _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
     else:
         rc = lib.tamp_batch_compress(C.byref(conf), _ptr(d), _ptr(flat if flat.size else np.zeros(1, np.uint8)),
                                      _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),

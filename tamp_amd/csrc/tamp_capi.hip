@@ -73,7 +73,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets and launch_decompress and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets and launch_decompress and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -88,7 +88,7 @@ struct StreamScratch {
     DeviceBuf long_tab;    // one long stream decoded by the whole device: chunk tables, records, group tables
     DeviceBuf long_tails;  // ... the groups' tail maps (groups x window x 2 bytes)
     DeviceBuf long_lags;   // ... extended format: the list of tokens that can lag, the lag lists
-    DeviceBuf resets;      // one buffer as dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets)
+    DeviceBuf resets;      // dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets), a batch's per-stream words in front (launch_compress_batch_resets)
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -218,6 +218,15 @@ void timing_end(hipStream_t st) {
     (void)hipEventRecord(t_ev1, st);
     t_ev_valid = true;
 }
+
+// One event pair around all kernels of a call that makes inner launches (they do not open their own), ended on every way out of it.
+struct CallTiming {
+    hipStream_t st;
+    explicit CallTiming(hipStream_t s) : st(s) { timing_begin(st), t_timing_outer = true; }
+    ~CallTiming() { t_timing_outer = false, timing_end(st); }
+    CallTiming(const CallTiming&) = delete;
+    CallTiming& operator=(const CallTiming&) = delete;
+};
 
 struct SegmentSpec {  // streaming Compressor over the engine: how this piece of the stream opens and closes
     uint8_t nlead;
@@ -530,7 +539,7 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
 }
 
 // `t`: device memory.  `seg` / `d_state`: a piece of one stream (segment_core), its state row.
-// `rec`: the stream's scratch record, locked by the caller (launch_compress; launch_compress_resets, which holds it over its slices).
+// `rec`: the stream's scratch record, locked by the caller (launch_compress; launch_compress_resets and launch_compress_batch_resets, which hold it over their slices).
 int launch_compress_locked(DeviceCtx* ctx, StreamScratch& rec, const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len,
                            hipStream_t st, const SegmentSpec* seg, uint8_t* d_state) {
     const size_t n_streams = t.n;
@@ -1738,9 +1747,7 @@ int launch_compress_resets(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_
     const uint8_t header = header_byte(conf, true);
     if (getenv("TAMP_AMD_RESETS_DEBUG"))
         fprintf(stderr, "[tamp_amd resets] compress: %llu segments of %u bytes, slab %u, %zu per slice\n", (unsigned long long)K, interval, slab, slice);
-    timing_begin(st);  // (one event pair around the call's kernels: the inner launches do not open their own)
-    t_timing_outer = true;
-    struct OuterTiming { ~OuterTiming() { t_timing_outer = false; } } outer_timing;
+    const CallTiming call_timing(st);
     for (uint64_t k0 = 0; k0 < K; k0 += slice) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(slice, K - k0);
         const bool last = k0 + cnt == K;
@@ -1757,7 +1764,6 @@ int launch_compress_resets(DeviceCtx* ctx, const TampAmdConf* conf, const uint8_
         const uint32_t grid = (uint32_t)std::min<size_t>(cnt, (size_t)ctx->cu_count * 8);
         hipLaunchKernelGGL(tamp_reset_gather_kernel, dim3(grid), dim3(256), 0, st, gather);
     }
-    timing_end(st);
     HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
@@ -1797,6 +1803,181 @@ int compress_resets(const TampAmdConf* conf, const uint8_t* in, uint64_t in_len,
     if (*status != TAMP_OK || *out_len == 0) return TAMP_OK;
     HIP_OK(hipMemcpyAsync(out, d_out, *out_len, hipMemcpyDeviceToHost, st));
     if (reset_off && K > 1) HIP_OK(hipMemcpyAsync(reset_off, d_reset, 8 * (size_t)(K - 1), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return TAMP_OK;
+}
+
+// A batch of buffers, every one cut into dictionary-reset segments (tamp_batch_compress_resets; kernels and the two-table order:
+// tamp_reset_segments_kernel.hpp).  The segments of ALL streams are the units of work: the closed ones (a reset behind them) run
+// first, in slices of the budget rule above, then every stream's open one, each slice as rows -> compress -> place / finish ->
+// gather.  What a stream's closed segments took rides per stream in device memory, so a stream may straddle slices.
+// `t`: device memory.  `counted`: the closed segments of the batch (sum of K_i - 1) and its longest stream when the caller has them
+// from host tables, else null: the one 16-byte record a device-memory call reads back, once, and waits for.  The slabs are sized
+// from that longest stream, never from `max_in_len`: the caller's hint sizes the compress kernel's block alone (a stale one costs
+// speed, never bytes, as for tamp_batch_compress) -- longest = min(N, max(max_in_len, 16)), the true longest stream standing in
+// for a hint of 0 (unknown).
+struct BatchResetCounted { uint64_t closed, longest; };
+int launch_compress_batch_resets(DeviceCtx* ctx, const TampAmdConf* conf, const BatchTables& t, uint32_t interval, uint32_t max_in_len,
+                                 const BatchResetCounted* counted, hipStream_t st) {
+    const uint64_t n = t.n;
+    if (n == 0) return TAMP_OK;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    // per stream: closed_first (n + 1) and the longest stream, start, end, lowest, highest, behind the carry
+    const size_t streams_bytes = (256 + (n + 2) * 8 + n * (8 + 8 + 4 + 4) + 255) & ~(size_t)255;
+    auto count_streams = [&]() -> int {  // the per-stream part of the scratch: zeroed, the closed segments counted and scanned
+        uint8_t* const base = static_cast<uint8_t*>(rec.resets.p);
+        HIP_OK(hipMemsetAsync(base, 0, streams_bytes, st));
+        const BatchResetCountArgs count = {t.in_len, n, interval, reinterpret_cast<uint64_t*>(base + 256)};
+        hipLaunchKernelGGL(tamp_batch_reset_count_kernel, dim3(1), dim3(kResetScanTile), 0, st, count);
+        return TAMP_OK;
+    };
+    BatchResetCounted have = counted ? *counted : BatchResetCounted{0, 0};
+    if (!counted) {
+        HIP_OK(rec.resets.need(streams_bytes + 64));
+        if (const int rc = count_streams()) return rc;
+        HIP_OK(hipMemcpyAsync(&have, static_cast<uint8_t*>(rec.resets.p) + 256 + n * 8, sizeof have, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    const uint32_t slab = batch_reset_slab_bytes((uint32_t)std::max<uint64_t>(have.longest, 1), interval, conf->literal);
+    const uint32_t longest = (uint32_t)std::min<uint64_t>(interval, std::max<uint64_t>(max_in_len ? max_in_len : have.longest, 16));
+    const uint64_t closed = have.closed;
+    const size_t row_bytes = 8 + 8 + 8 + 4 + 4 + 4 + 4 + 1;  // in_off, out_off, pos, in_len, out_cap, out_len, owner, status
+    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max((free_b + rec.resets.bytes) / 4, rec.resets.bytes));
+    else (void)hipGetLastError();
+    size_t slice = (size_t)std::min<uint64_t>(std::max<uint64_t>(closed, n), (uint64_t)1 << 20);
+    slice = std::min(slice, std::max<size_t>(budget / ((size_t)slab + row_bytes), 1));
+    if (const char* e = getenv("TAMP_AMD_RESETS_SLICE")) { const long v = atol(e); if (v > 0) slice = std::min(slice, (size_t)v); }  // (tuning / tests)
+    const size_t tab_bytes = (slice * row_bytes + 64 + 255) & ~(size_t)255;
+    const size_t all_bytes = streams_bytes + tab_bytes + slice * (size_t)slab + 64;
+    // (growth loses the contents: the count is then taken again, a tiny kernel)
+    const bool recount = counted || all_bytes > rec.resets.bytes;
+    HIP_OK(rec.resets.need(all_bytes));
+    if (recount)
+        if (const int rc = count_streams()) return rc;
+    uint8_t* const base = static_cast<uint8_t*>(rec.resets.p);
+    ResetCarry* const carry = reinterpret_cast<ResetCarry*>(base);
+    uint64_t* const closed_first = reinterpret_cast<uint64_t*>(base + 256);
+    BatchResetStreams per;
+    per.start = closed_first + n + 2, per.end = per.start + n;
+    per.lowest = reinterpret_cast<int32_t*>(per.end + n), per.highest = per.lowest + n;
+    uint8_t* const tab = base + streams_bytes;
+    uint64_t* const in_off = reinterpret_cast<uint64_t*>(tab);
+    uint64_t* const out_off = in_off + slice;
+    uint64_t* const pos = out_off + slice;
+    uint32_t* const seg_in = reinterpret_cast<uint32_t*>(pos + slice);
+    uint32_t* const seg_cap = seg_in + slice;
+    uint32_t* const seg_len = seg_cap + slice;
+    uint32_t* const owner = seg_len + slice;
+    int8_t* const seg_status = reinterpret_cast<int8_t*>(owner + slice);
+    uint8_t* const slabs = tab + tab_bytes;
+    BatchTables seg;
+    seg.in = t.in ? t.in : base, seg.in_off = in_off, seg.in_len = seg_in;  // (no input at all: memory of the library's own to point at)
+    seg.out = slabs, seg.out_off = out_off, seg.out_cap = seg_cap, seg.out_len = seg_len, seg.status = seg_status;
+    const SegmentSpec with_token = {2, (uint16_t)(0xABu << 7), kSegFlushToken}, without = {2, (uint16_t)(0xABu << 7), 0};
+    const uint32_t header = header_byte(conf, true);
+    if (getenv("TAMP_AMD_RESETS_DEBUG"))
+        fprintf(stderr, "[tamp_amd resets] batch compress: %llu streams, %llu closed segments of %u bytes, slab %u, %zu per slice, %llu slices\n",
+                (unsigned long long)n, (unsigned long long)closed, interval, slab, slice,
+                (unsigned long long)((closed + slice - 1) / slice + (n + slice - 1) / slice));
+    const CallTiming call_timing(st);
+    for (int open = 0; open < 2; open++) {
+        const uint64_t rows_total = open ? n : closed;
+        for (uint64_t r0 = 0; r0 < rows_total; r0 += slice) {
+            const uint32_t cnt = (uint32_t)std::min<uint64_t>(slice, rows_total - r0);
+            const BatchResetRowsArgs rows = {closed_first, t.in_off, t.in_len, n, r0, cnt, (uint32_t)open, interval, slab,
+                                             in_off, seg_in, out_off, seg_cap, owner};
+            hipLaunchKernelGGL(tamp_batch_reset_rows_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, rows);
+            seg.n = cnt;
+            if (const int rc = launch_compress_locked(ctx, rec, conf, seg, longest, st, open ? &without : &with_token, nullptr)) return rc;
+            if (open) {
+                const BatchResetFinishArgs finish = {seg_len, seg_status, cnt, r0, per, t.out_cap, t.out_len, t.status};
+                hipLaunchKernelGGL(tamp_batch_reset_finish_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, finish);
+            } else {
+                const BatchResetPlaceArgs place = {seg_len, seg_status, owner, cnt, r0, closed_first, pos, per, carry};
+                hipLaunchKernelGGL(tamp_batch_reset_place_kernel, dim3(1), dim3(kResetScanTile), 0, st, place);
+            }
+            const BatchResetGatherArgs gather = {slabs, slab, cnt, (uint32_t)open, r0, seg_len, owner, pos, closed_first, per,
+                                                 t.out, t.out_off, t.out_cap, header};
+            const uint32_t grid = (uint32_t)std::min<size_t>(cnt, (size_t)ctx->cu_count * 8);
+            hipLaunchKernelGGL(tamp_batch_reset_gather_kernel, dim3(grid), dim3(256), 0, st, gather);
+        }
+    }
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
+// tamp_batch_compress_resets behind its checks.  Host memory, on the host pipeline's kept buffers and first stream (one host-memory
+// call per device at a time): the tables and the input's extent go to the device in one piece each; the output slabs lie back to
+// back there, each as long as its stream can get or as the caller allows, whichever is less; the two result tables come back, then
+// exactly the produced bytes of every stream -- through one pinned transfer of the slabs when that is at most 512 MiB, else stream
+// by stream.
+int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_t interval, uint32_t max_in_len, int mem, int device,
+                          void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_compress_batch_resets(ctx, conf, t, interval, max_in_len, nullptr, static_cast<hipStream_t>(stream));
+    const size_t n = t.n;
+    if (n == 0) return TAMP_OK;
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> call_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    uint64_t in_lo = ~0ull, in_hi = 0, closed = 0, room = 0;
+    uint32_t longest = 0;
+    std::vector<uint64_t> h_in_off(n), h_out_off(n);
+    std::vector<uint32_t> h_cap(n);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t len = t.in_len[i];
+        if (len) in_lo = std::min(in_lo, t.in_off[i]), in_hi = std::max(in_hi, t.in_off[i] + len);
+        longest = std::max(longest, len);
+        closed += batch_reset_closed_count(len, interval);
+        h_cap[i] = (uint32_t)std::min<uint64_t>(t.out_cap[i], reset_stream_bound(len, interval, conf->literal));
+        h_out_off[i] = room, room += h_cap[i];
+    }
+    if (in_hi < in_lo) in_lo = in_hi = 0;
+    for (size_t i = 0; i < n; i++) h_in_off[i] = t.in_len[i] ? t.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
+    HIP_OK(P.in[0].need(in_hi - in_lo + 64));  // the kernels' vector loads may run past the last byte
+    HIP_OK(P.out[0].need(room + 1));
+    HIP_OK(P.meta[0].need(n * (8 + 8 + 4 + 4 + 4 + 1) + 64));
+    BatchTables d;
+    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
+    uint64_t* const d_out_off = d_in_off + n;
+    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_out_off + n);
+    uint32_t* const d_cap = d_in_len + n;
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = d_in_off, d.in_len = d_in_len;
+    d.out = static_cast<uint8_t*>(P.out[0].p), d.out_off = d_out_off, d.out_cap = d_cap;
+    d.out_len = d_cap + n, d.status = reinterpret_cast<int8_t*>(d.out_len + n), d.n = n;
+    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, t.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_len, t.in_len, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_cap, h_cap.data(), n * 4, hipMemcpyHostToDevice, st));
+    (void)max_in_len;  // (the tables are here: the longest stream is known exactly and stands for the caller's hint)
+    const BatchResetCounted counted = {closed, longest};
+    if (const int rc = launch_compress_batch_resets(ctx, conf, d, interval, std::max(longest, 1u), &counted, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(t.out_len, d.out_len, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(t.status, d.status, n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t produced = 0;
+    for (size_t i = 0; i < n; i++) produced += t.out_len[i];
+    if (!produced) return TAMP_OK;
+    if (room <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(room) == hipSuccess) {
+        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
+        HIP_OK(hipMemcpyAsync(P.stage[0].p, d.out, room, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < n; i++)
+            if (t.out_len[i]) memcpy(t.out + t.out_off[i], stg + h_out_off[i], t.out_len[i]);
+        return TAMP_OK;
+    }
+    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
+    for (size_t i = 0; i < n; i++)
+        if (t.out_len[i]) HIP_OK(hipMemcpyAsync(t.out + t.out_off[i], d.out + h_out_off[i], t.out_len[i], hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return TAMP_OK;
 }
@@ -2266,6 +2447,20 @@ int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, cons
                         void* stream) {
     return tamp_batch_compress_dicts(conf, dictionary, 0, nullptr, in, in_off, in_len, out, out_off, out_cap, out_len, status, n_streams,
                                      max_in_len, mem, device, stream);
+}
+
+int tamp_batch_compress_resets(const TampAmdConf* conf, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                               uint32_t reset_interval, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                               uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem, int device,
+                               void* stream) {
+    const BatchTables t = {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, nullptr, nullptr, 0, n_streams};
+    if (!conf) return TAMP_AMD_BAD_ARGUMENT;
+    if (const int rc = batch_refused(t, true, mem, device)) return rc;
+    if (!conf_valid(conf) || conf->lazy_matching > 1 || !conf->dictionary_reset || conf->use_custom_dictionary || !reset_interval)
+        return TAMP_AMD_BAD_ARGUMENT;
+    // (a table row's capacity is 32 bits wide: an interval whose worst case does not fit one is not taken)
+    if (reset_segment_bound(reset_interval, conf->literal, true) > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    return batch_compress_resets(conf, t, reset_interval, max_in_len, mem, device, stream);
 }
 
 int tamp_batch_decompress_dicts(const uint8_t* dictionaries, size_t dictionaries_len, const uint64_t* dict_off, uint8_t max_window_bits,
