@@ -400,6 +400,24 @@ int tamp_batch_compress_resets(const TampAmdConf *conf, const uint8_t *in, const
                                int mem, int device, void *stream);
 
 /*
+ * The same call, and the same bytes, with a RESET INDEX on top: where every reset of every stream lies.  The compressor knows
+ * these positions (they are what places its segments); a reader that has them need not search the stream for its resets.
+ *   reset_first     n_streams + 1 entries, may be NULL: reset_first[i] = sum of K_j - 1 over j < i, so stream i's K_i - 1 entries are
+ *                   reset_off[reset_first[i] .. reset_first[i + 1]) and reset_first[n_streams] is their number in the whole batch
+ *   reset_off       one entry per reset: the offset, from out + out_off[i], of the byte behind it -- where the next segment's tokens
+ *                   begin, the values tamp_amd_compress_resets gives for that stream alone.  The entries of a stream whose
+ *                   status is not TAMP_OK are unspecified.  NULL (with reset_cap 0): no index, which is tamp_batch_compress_resets
+ *   reset_cap       the entries reset_off has room for.  A batch with more resets than that is refused with TAMP_AMD_BAD_ARGUMENT
+ *                   before anything is written: sum max(1, ceil(in_len[i] / reset_interval)) - 1 over the streams always suffices
+ * Both tables lie where `mem` says.  A host-memory call writes them with the results; n_streams == 0 writes nothing at all.
+ */
+int tamp_batch_compress_resets_index(const TampAmdConf *conf, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                                     uint32_t reset_interval, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                                     uint32_t *out_len, int8_t *status, size_t n_streams, uint32_t max_in_len,
+                                     int mem, int device, void *stream, uint64_t *reset_first, uint32_t *reset_off,
+                                     uint64_t reset_cap);
+
+/*
  * Reading such a stream back with the whole device.  For ONE stream whose header has the dictionary_reset bit and no custom bit the
  * call returns out_len, status and in_consumed exactly as tamp_batch_decompress does for that stream with the given max_window_bits
  * and out_cap -- and, with out == NULL, exactly as tamp_batch_decoded_size does with limit = out_cap, writing no bytes.  The resets are
@@ -420,6 +438,35 @@ int tamp_batch_compress_resets(const TampAmdConf *conf, const uint8_t *in, const
 int tamp_amd_decompress_resets(uint8_t max_window_bits, const uint8_t *in, uint32_t in_len, uint8_t *out /* NULL: the size only */,
                                uint32_t out_cap, uint32_t *out_len, int8_t *status, uint32_t *in_consumed /* may be NULL */,
                                int mem, int device, void *stream);
+
+/*
+ * Reading a BATCH of such streams back, the segments of all streams as the units of work, with the reset index of
+ * tamp_batch_compress_resets_index as a HINT.  For every stream out_len[i], status[i], in_consumed[i] and the bytes
+ * out[out_off[i] .. + out_len[i]) are exactly what tamp_batch_decompress gives for it with no dictionary, the same max_window_bits
+ * and the same out_cap[i] -- and, with out == NULL, what tamp_batch_decoded_size gives with limit = out_cap -- for ANY contents of
+ * the index; nothing is written outside [out_off[i], out_off[i] + out_cap[i]).  The index is verified on the device: a stream is
+ * SPLIT into its segments only when its header has the reset bit, no custom bit and a window of at most max_window_bits, when it
+ * has at least one entry, its entries are strictly increasing, behind the header and at or before in_len[i], when walking every
+ * segment token by token from its start ends exactly at its boundary behind two FLUSH tokens (the last segment: as a stream ends)
+ * with no offset out of the window, and when the stream's size stays below out_cap[i].  Every other stream is decoded WHOLE, as
+ * tamp_batch_decompress decodes it.  There is no minimum length and no environment switch.
+ *   reset_first     n_streams + 1 entries, a running sum from 0 (a table that is none: the call goes without an index)
+ *   reset_off       reset_first[n_streams] entries; may be NULL when there are none
+ *   out_cap         required with and without `out`; the other tables as for tamp_batch_decompress; in_consumed may be NULL
+ *   mem, device, stream   as there, TAMP_AMD_ALL_DEVICES is not taken.  A device-memory call WAITS once, early, for one 16-byte
+ *                   record (how many entries the batch has, how many bytes it may stage); everything behind that is asynchronous on
+ *                   `stream`.  A host-memory call is synchronous and writes exactly the produced bytes and the result tables.
+ * The segments are staged in scratch kept per HIP stream (a quarter of the free device memory at most, 8 GiB at most; streams are
+ * split in stream order until it is full).  With TAMP_AMD_RESETS_DEBUG set the call writes one line to stderr:
+ * "[tamp_amd resets] batch decode: <n> streams, <s> split into <u> units, <w> whole" (and waits for the device to say so).
+ * status[i] = TAMP_ERROR: a segment of stream i did not decode to the size the walk found -- a defect of the library.
+ * Returns TAMP_OK, TAMP_AMD_BAD_ARGUMENT (a null required table, a bad memory kind, n_streams >= 2^32), TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_decompress_resets(uint8_t max_window_bits, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                                 const uint64_t *reset_first, const uint32_t *reset_off,
+                                 uint8_t *out /* NULL: sizes only */, const uint64_t *out_off, const uint32_t *out_cap,
+                                 uint32_t *out_len, int8_t *status, uint32_t *in_consumed /* may be NULL */,
+                                 size_t n_streams, int mem, int device, void *stream);
 
 /* ---- resumable decoding: decoder OBJECTS that survive between calls ------------------------------
  *

@@ -42,6 +42,8 @@ SYMBOLS = (
     "tamp_amd_compress_resets_bound",
     "tamp_amd_compress_resets_slab",
     "tamp_batch_compress_resets",
+    "tamp_batch_compress_resets_index",
+    "tamp_batch_decompress_resets",
     "tamp_amd_decompress_resets",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
@@ -192,6 +194,11 @@ def load() -> C.CDLL:
     lib.tamp_amd_compress_resets_slab.restype = sz
     lib.tamp_batch_compress_resets.argtypes = [C.POINTER(TampAmdConf), vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp]
     lib.tamp_batch_compress_resets.restype = i32
+    lib.tamp_batch_compress_resets_index.argtypes = [C.POINTER(TampAmdConf), vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp,
+                                                     vp, vp, C.c_uint64]
+    lib.tamp_batch_compress_resets_index.restype = i32
+    lib.tamp_batch_decompress_resets.argtypes = [u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.tamp_batch_decompress_resets.restype = i32
     lib.tamp_amd_decompress_resets.argtypes = [u8, vp, u32, vp, u32, vp, vp, vp, i32, i32, vp]
     lib.tamp_amd_decompress_resets.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]

@@ -50,6 +50,16 @@ def compress_resets_bound(n, reset_interval: int, literal: int = 8):
 
 
 @dataclass
+class ResetIndex:
+    """Where the dictionary resets of a batch lie (``compress_batch(..., reset_index=True)`` makes one, ``decompress_batch(...,
+    reset_index=...)`` takes one as a hint): ``first`` has one entry per stream and one more, stream ``i``'s entries are
+    ``off[first[i]:first[i + 1]]``, each the offset, in the stream's compressed bytes, of the byte behind a reset.  numpy arrays
+    (uint64, uint32) or CUDA tensors (int64, int32), like the other tables."""
+    first: object
+    off: object
+
+
+@dataclass
 class BatchResult:
     out: object          # uint8 buffer (numpy array or torch tensor) holding every stream's slab
     out_off: object      # uint64/int64 [n]
@@ -59,6 +69,7 @@ class BatchResult:
     kernel_ms: float = -1.0
     _keep: object = None  # device tensors the asynchronous launch still reads (converted tables, the dictionary)
     _ws_key: object = None  # (streams, capacity, device) when the slab may serve as the next call's workspace (``reuse=``)
+    reset_index: Optional[ResetIndex] = None  # compress_batch(..., reset_index=True)
 
     def stream(self, i: int) -> bytes:
         o, n = int(self.out_off[i]), int(self.out_len[i])
@@ -222,7 +233,8 @@ def trim(device: int = 0) -> int:
 def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal: int = 8, extended: bool = True,
                    dictionary=None, dictionary_reset: bool = False, lazy_matching: bool = False, out_cap=None,
                    max_in_len: int = 0, device: int = 0, stream=None, timing: bool = False,
-                   run_aware=None, reuse=None, dictionaries=None, dictionary_index=None, reset_interval=None) -> BatchResult:
+                   run_aware=None, reuse=None, dictionaries=None, dictionary_index=None, reset_interval=None,
+                   reset_index: bool = False) -> BatchResult:
     """Compress many independent streams in one launch.
 
     ``data`` is a list of bytes-likes (host), a flat numpy uint8 array + ``in_off``/``in_len`` (host), or a flat
@@ -244,7 +256,12 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
     and the segments of ALL streams are the units of work (``tamp_batch_compress_resets``), so a ragged batch does
     not wait for its longest stream.  Stream ``i`` is ``tamp_amd.compress(stream_i, dictionary_reset=True, reset_interval=...)``;
     ``out_cap=None`` sizes the slabs with the bound of ``tamp_amd_compress_resets_bound``.  ``max_in_len`` stays a hint, as without resets.  Not with a dictionary of any form, nor with ``reuse``.
+    ``reset_index=True`` (with ``reset_interval``): the result's ``reset_index`` says where every reset of every stream lies
+    (``ResetIndex``, ``tamp_batch_compress_resets_index``) -- the same bytes, and what ``decompress_batch(..., reset_index=...)``
+    reads the batch back with.  Device tensors: one more sync, for the number of entries.
     """
+    if reset_index and reset_interval is None:
+        raise ValueError("reset_index needs reset_interval")
     if reset_interval is not None:  # (the rules and wording of codec._compress_resets; all decided before the library is looked for)
         if isinstance(reset_interval, bool) or not isinstance(reset_interval, int) or reset_interval < 1:
             raise ValueError("reset_interval must be a positive integer")
@@ -272,7 +289,7 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                   dictionary=dictionary if table is None else table,
                                   dictionary_reset=dictionary_reset, lazy_matching=lazy_matching, out_cap=out_cap,
                                   max_in_len=max_in_len, device=device, stream=None, timing=timing, run_aware=run_aware, reuse=reuse,
-                                  reset_interval=reset_interval)
+                                  reset_interval=reset_interval, reset_index=reset_index)
     lib = _lib.load()
     conf = _conf(window, literal, extended, dictionary if table is None else table, dictionary_reset, lazy_matching, run_aware)
     if dictionary is not None and not _is_torch(dictionary) and len(dictionary) != (1 << window):
@@ -330,6 +347,15 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                                _ptr(in_off_t), _ptr(in_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t),
                                                _ptr(out_len_t), _ptr(status_t), n, int(max_in_len), _lib.MEM_DEVICE,
                                                dev.index or 0, C.c_void_p(st))
+        elif reset_index:
+            # (the entries: the `closed` of compress_resets_bound, summed on the device; one sync for the total)
+            closed = (torch.clamp(in_len_t.to(torch.int64) & 0xFFFFFFFF, min=1) - 1) // reset_interval
+            entries = int(closed.sum().item()) if n else 0
+            index = ResetIndex(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(max(entries, 1), dtype=torch.int32, device=dev)[:entries])
+            rc = lib.tamp_batch_compress_resets_index(C.byref(conf), _ptr(data), _ptr(in_off_t), _ptr(in_len_t), reset_interval, _ptr(out),
+                                                      _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t), _ptr(status_t), n, int(max_in_len),
+                                                      _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st), _ptr(index.first),
+                                                      _ptr(index.off) if entries else None, entries)
         elif reset_interval is not None:
             rc = lib.tamp_batch_compress_resets(C.byref(conf), _ptr(data), _ptr(in_off_t), _ptr(in_len_t), reset_interval, _ptr(out),
                                                 _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t), _ptr(status_t), n, int(max_in_len),
@@ -343,6 +369,7 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
         ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
         res = BatchResult(out, out_off_t, out_len_t, status_t, None, ms, (data, in_off_t, in_len_t, out_cap_t, dict_t, dict_off_t))
         res._ws_key = (n, int(out_cap), str(dev)) if (out_cap is not None and _is_int(out_cap)) else None
+        res.reset_index = index if reset_index else None
         return res
 
     if in_off is None:
@@ -372,6 +399,14 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                            _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len), _ptr(out),
                                            _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), n, int(max_in_len),
                                            _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
+    elif reset_index:
+        entries = int(((np.maximum(in_len.astype(np.uint64), np.uint64(1)) - np.uint64(1)) // np.uint64(reset_interval)).sum())
+        index = ResetIndex(np.zeros(n + 1, dtype=np.uint64), np.zeros(entries, dtype=np.uint32))
+        rc = lib.tamp_batch_compress_resets_index(C.byref(conf), _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off),
+                                                  _ptr(in_len), reset_interval, _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),
+                                                  _ptr(status), n, int(max_in_len), _lib.MEM_HOST, device,
+                                                  C.c_void_p(stream) if stream else None, _ptr(index.first),
+                                                  _ptr(index.off) if entries else None, entries)
     elif reset_interval is not None:
         rc = lib.tamp_batch_compress_resets(C.byref(conf), _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off), _ptr(in_len),
                                             reset_interval, _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), n,
@@ -383,7 +418,7 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                      C.c_void_p(stream) if stream else None)
     _lib.check_launch(rc)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
-    return BatchResult(out, out_off, out_len, status, None, ms)
+    return BatchResult(out, out_off, out_len, status, None, ms, reset_index=index if reset_index else None)
 
 
 @dataclass
@@ -485,7 +520,7 @@ def decoded_size_batch(data, in_off=None, in_len=None, *, limit=None, dictionary
 
 def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: int = 0xFFFFFFFF, dictionary=None,
                      max_window_bits: int = 15, scan_headers: bool = True, device: int = 0, stream=None,
-                     timing: bool = False, dictionaries=None, dictionary_index=None) -> BatchResult:
+                     timing: bool = False, dictionaries=None, dictionary_index=None, reset_index=None) -> BatchResult:
     """Decompress many independent ``.tamp`` streams in one launch (configuration read from each header).
 
     ``out_cap=None``: the sizes are not known.  ``decoded_size_batch(limit=max_out)`` finds them and stream ``i`` is decoded
@@ -506,7 +541,20 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
     ``dictionaries`` is K bytes objects of equal length D, or a uint8 array / CUDA tensor of shape ``(K, D)``, D a multiple of
     16; a stream whose header has the custom bit is decoded as ``dictionary=dictionaries[dictionary_index[i]]`` would decode
     it, one without the bit ignores its selector (``dictionary=DictionaryTable(dictionaries, dictionary_index)`` says the same).
+
+    ``reset_index`` (the ``ResetIndex`` of ``compress_batch(..., reset_interval=N, reset_index=True)``; not in the reference): the
+    segments between the resets of ALL streams are the units of work (``tamp_batch_decompress_resets``), so a ragged
+    batch does not wait for its longest stream.  The index is a hint that the library verifies on the device: status, bytes and
+    consumed count of every stream are those of the call without it, whatever the index holds.  Not with a dictionary of any form.
     """
+    if reset_index is not None:  # (all decided before the library is looked for)
+        if dictionary is not None or dictionaries is not None or dictionary_index is not None:
+            raise ValueError("reset_index excludes dictionaries: a reset restores the seeded window")
+        if not isinstance(reset_index, ResetIndex):
+            raise ValueError("reset_index: a ResetIndex expected")
+        n_streams = len(data) if in_off is None and not _is_torch(data) else len(in_len)
+        if len(reset_index.first) != n_streams + 1:
+            raise ValueError("reset_index.first: one entry per stream and one more expected")
     dictionary, table = _dict_table(dictionary, dictionaries, dictionary_index)
     dict_arg = dictionary if table is None else table  # (what the calls below pass on)
     if stream is not None and _is_torch(data):
@@ -514,7 +562,11 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
 
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
             return decompress_batch(data, in_off, in_len, out_cap=out_cap, max_out=max_out, dictionary=dict_arg,
-                                    max_window_bits=max_window_bits, scan_headers=scan_headers, device=device, stream=None, timing=timing)
+                                    max_window_bits=max_window_bits, scan_headers=scan_headers, device=device, stream=None, timing=timing,
+                                    reset_index=reset_index)
+    if reset_index is not None:
+        return _decompress_batch_resets(data, in_off, in_len, reset_index, out_cap, max_out, max_window_bits, scan_headers, device, stream,
+                                        timing)
     if out_cap is None:
         if not 0 <= int(max_out) <= 0xFFFFFFFF:
             raise ValueError("max_out must fit 32 bits")
@@ -604,6 +656,88 @@ def decompress_batch(data, in_off=None, in_len=None, *, out_cap=None, max_out: i
                                        _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status),
                                        _ptr(consumed), n, _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
     _lib.check_launch(rc)
+    ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+    return BatchResult(out, out_off, out_len, status, consumed, ms)
+
+
+def _decompress_batch_resets(data, in_off, in_len, index, out_cap, max_out, max_window_bits, scan_headers, device, stream, timing):
+    """``decompress_batch(..., reset_index=index)`` behind its checks: with ``out_cap=None`` the call is made twice, first for the
+    sizes (no output buffer, ``max_out`` as every stream's limit), then into ``min(size + 1, max_out)`` bytes per stream."""
+    if out_cap is None and not 0 <= int(max_out) <= 0xFFFFFFFF:
+        raise ValueError("max_out must fit 32 bits")
+    lib = _lib.load()
+    lib.tamp_amd_set_timing(1 if timing else 0)
+    if not scan_headers:
+        max_window_bits |= _lib.WINDOW_BITS_EXACT
+    if _is_torch(data):
+        import torch
+
+        n = int(in_len.numel())
+        dev = data.device
+        as_t = lambda x, dt: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.int64))).to(device=dev, dtype=dt)  # noqa: E731
+        first_t, off_t = as_t(index.first, torch.int64), as_t(index.off, torch.int32)
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+
+        def call(out, out_off_t, out_cap_t):
+            out_len_t = torch.empty(n, dtype=torch.int32, device=dev)
+            status_t = torch.empty(n, dtype=torch.int8, device=dev)
+            consumed_t = torch.empty(n, dtype=torch.int32, device=dev)
+            _lib.check_launch(lib.tamp_batch_decompress_resets(
+                max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(first_t), _ptr(off_t) if off_t.numel() else None,
+                _ptr(out), _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t), _ptr(status_t), _ptr(consumed_t), n, _lib.MEM_DEVICE,
+                dev.index or 0, C.c_void_p(st)))
+            return out_len_t, status_t, consumed_t
+
+        if out_cap is None:
+            limit = int(max_out)  # (the table holds uint32 values in int32 storage)
+            limit_t = torch.full((n,), limit - (1 << 32) if limit >= 1 << 31 else limit, dtype=torch.int32, device=dev)
+            size_t, _, _ = call(None, None, limit_t)
+            out_cap = torch.clamp((size_t.to(torch.int64) & 0xFFFFFFFF) + 1, max=limit)  # (int64: sizes are uint32 values)
+        if _is_int(out_cap):
+            out_cap = int(out_cap)
+            out_cap_t = torch.full((n,), out_cap, dtype=torch.int32, device=dev)
+            out_off_t = torch.arange(n, dtype=torch.int64, device=dev) * out_cap
+            total = n * out_cap
+        else:
+            cap64 = out_cap.to(device=dev, dtype=torch.int64)
+            out_cap_t = cap64.to(torch.int32)  # (the low 32 bits: what the library reads as uint32)
+            out_off_t = torch.cumsum(cap64, 0) - cap64
+            total = int(cap64.sum().item())
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        out_len_t, status_t, consumed_t = call(out, out_off_t, out_cap_t)
+        ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+        return BatchResult(out, out_off_t, out_len_t, status_t, consumed_t, ms, (data, in_off_t, in_len_t, out_cap_t, first_t, off_t))
+
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    n = len(in_len)
+    to_np = lambda x, dt: np.ascontiguousarray((x.cpu().numpy() if _is_torch(x) else np.asarray(x)).astype(dt))  # noqa: E731
+    first, off = to_np(index.first, np.uint64), to_np(index.off, np.uint32)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+
+    def call(out, out_off, out_cap):
+        out_len, status, consumed = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int8), np.zeros(n, dtype=np.uint32)
+        _lib.check_launch(lib.tamp_batch_decompress_resets(
+            max_window_bits, _ptr(flat), _ptr(in_off), _ptr(in_len), _ptr(first), _ptr(off) if off.size else None, _ptr(out),
+            _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), _ptr(consumed), n, _lib.MEM_HOST, device,
+            C.c_void_p(stream) if stream else None))
+        return out_len, status, consumed
+
+    if out_cap is None:
+        size, _, _ = call(None, None, np.full(n, int(max_out), dtype=np.uint32))
+        out_cap = np.minimum(size.astype(np.uint64) + 1, np.uint64(int(max_out))).astype(np.uint32)
+    if _is_int(out_cap):
+        out_cap = np.full(n, int(out_cap), dtype=np.uint32)
+    out_cap = np.ascontiguousarray(out_cap, dtype=np.uint32)
+    out_off, total = _slab_offsets(out_cap)
+    out = np.zeros(total + 1, dtype=np.uint8)
+    out_len, status, consumed = call(out, out_off, out_cap)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
     return BatchResult(out, out_off, out_len, status, consumed, ms)
 

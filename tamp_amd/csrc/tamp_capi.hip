@@ -1816,9 +1816,14 @@ int compress_resets(const TampAmdConf* conf, const uint8_t* in, uint64_t in_len,
 // from that longest stream, never from `max_in_len`: the caller's hint sizes the compress kernel's block alone (a stale one costs
 // speed, never bytes, as for tamp_batch_compress) -- longest = min(N, max(max_in_len, 16)), the true longest stream standing in
 // for a hint of 0 (unknown).
+// `index`: the reset index of tamp_batch_compress_resets_index, all of it optional.  first: n + 1 entries, the closed_first table
+// (copied from the scratch on the call's stream); off: per closed segment of the batch the offset, in its stream, of the byte behind
+// its reset (the gather's store); cap: the entries `off` has room for -- a batch with more closed segments is refused before anything
+// is launched that writes to the caller's memory.
 struct BatchResetCounted { uint64_t closed, longest; };
+struct BatchResetIndex { uint64_t* first; uint32_t* off; uint64_t cap; };
 int launch_compress_batch_resets(DeviceCtx* ctx, const TampAmdConf* conf, const BatchTables& t, uint32_t interval, uint32_t max_in_len,
-                                 const BatchResetCounted* counted, hipStream_t st) {
+                                 const BatchResetCounted* counted, const BatchResetIndex& index, hipStream_t st) {
     const uint64_t n = t.n;
     if (n == 0) return TAMP_OK;
     StreamScratch& rec = ctx->scratch(st);
@@ -1838,6 +1843,10 @@ int launch_compress_batch_resets(DeviceCtx* ctx, const TampAmdConf* conf, const 
         if (const int rc = count_streams()) return rc;
         HIP_OK(hipMemcpyAsync(&have, static_cast<uint8_t*>(rec.resets.p) + 256 + n * 8, sizeof have, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
+    }
+    if (index.off && have.closed > index.cap) {
+        snprintf(t_last_error, sizeof t_last_error, "reset index: %llu entries, room for %llu", (unsigned long long)have.closed, (unsigned long long)index.cap);
+        return TAMP_AMD_BAD_ARGUMENT;
     }
     const uint32_t slab = batch_reset_slab_bytes((uint32_t)std::max<uint64_t>(have.longest, 1), interval, conf->literal);
     const uint32_t longest = (uint32_t)std::min<uint64_t>(interval, std::max<uint64_t>(max_in_len ? max_in_len : have.longest, 16));
@@ -1859,6 +1868,7 @@ int launch_compress_batch_resets(DeviceCtx* ctx, const TampAmdConf* conf, const 
     uint8_t* const base = static_cast<uint8_t*>(rec.resets.p);
     ResetCarry* const carry = reinterpret_cast<ResetCarry*>(base);
     uint64_t* const closed_first = reinterpret_cast<uint64_t*>(base + 256);
+    if (index.first) HIP_OK(hipMemcpyAsync(index.first, closed_first, (n + 1) * 8, hipMemcpyDeviceToDevice, st));
     BatchResetStreams per;
     per.start = closed_first + n + 2, per.end = per.start + n;
     per.lowest = reinterpret_cast<int32_t*>(per.end + n), per.highest = per.lowest + n;
@@ -1899,7 +1909,7 @@ int launch_compress_batch_resets(DeviceCtx* ctx, const TampAmdConf* conf, const 
                 hipLaunchKernelGGL(tamp_batch_reset_place_kernel, dim3(1), dim3(kResetScanTile), 0, st, place);
             }
             const BatchResetGatherArgs gather = {slabs, slab, cnt, (uint32_t)open, r0, seg_len, owner, pos, closed_first, per,
-                                                 t.out, t.out_off, t.out_cap, header};
+                                                 t.out, t.out_off, t.out_cap, header, index.off};
             const uint32_t grid = (uint32_t)std::min<size_t>(cnt, (size_t)ctx->cu_count * 8);
             hipLaunchKernelGGL(tamp_batch_reset_gather_kernel, dim3(grid), dim3(256), 0, st, gather);
         }
@@ -1913,11 +1923,11 @@ int launch_compress_batch_resets(DeviceCtx* ctx, const TampAmdConf* conf, const 
 // back there, each as long as its stream can get or as the caller allows, whichever is less; the two result tables come back, then
 // exactly the produced bytes of every stream -- through one pinned transfer of the slabs when that is at most 512 MiB, else stream
 // by stream.
-int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_t interval, uint32_t max_in_len, int mem, int device,
-                          void* stream) {
+int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_t interval, uint32_t max_in_len, const BatchResetIndex& index,
+                          int mem, int device, void* stream) {
     DeviceCtx* ctx = nullptr;
     if (const int rc = get_ctx(device, &ctx)) return rc;
-    if (mem == TAMP_AMD_MEM_DEVICE) return launch_compress_batch_resets(ctx, conf, t, interval, max_in_len, nullptr, static_cast<hipStream_t>(stream));
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_compress_batch_resets(ctx, conf, t, interval, max_in_len, nullptr, index, static_cast<hipStream_t>(stream));
     const size_t n = t.n;
     if (n == 0) return TAMP_OK;
     using Pipe = DeviceCtx::HostPipe;
@@ -1937,11 +1947,13 @@ int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_
         h_cap[i] = (uint32_t)std::min<uint64_t>(t.out_cap[i], reset_stream_bound(len, interval, conf->literal));
         h_out_off[i] = room, room += h_cap[i];
     }
+    if (index.off && closed > index.cap) return TAMP_AMD_BAD_ARGUMENT;  // (before anything is written, the device path's rule)
     if (in_hi < in_lo) in_lo = in_hi = 0;
     for (size_t i = 0; i < n; i++) h_in_off[i] = t.in_len[i] ? t.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
     HIP_OK(P.in[0].need(in_hi - in_lo + 64));  // the kernels' vector loads may run past the last byte
     HIP_OK(P.out[0].need(room + 1));
-    HIP_OK(P.meta[0].need(n * (8 + 8 + 4 + 4 + 4 + 1) + 64));
+    const size_t index_at = (n * (8 + 8 + 4 + 4 + 4 + 1) + 3) & ~(size_t)3;  // the reset index, behind the tables
+    HIP_OK(P.meta[0].need(index_at + (index.off ? closed * 4 : 0) + 64));
     BatchTables d;
     uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
     uint64_t* const d_out_off = d_in_off + n;
@@ -1957,13 +1969,21 @@ int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_
     HIP_OK(hipMemcpyAsync(d_cap, h_cap.data(), n * 4, hipMemcpyHostToDevice, st));
     (void)max_in_len;  // (the tables are here: the longest stream is known exactly and stands for the caller's hint)
     const BatchResetCounted counted = {closed, longest};
-    if (const int rc = launch_compress_batch_resets(ctx, conf, d, interval, std::max(longest, 1u), &counted, st)) {
+    uint32_t* const d_reset_off = index.off ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(P.meta[0].p) + index_at) : nullptr;
+    // (the first table is the host's own count below; the entries come back with the results)
+    if (const int rc = launch_compress_batch_resets(ctx, conf, d, interval, std::max(longest, 1u), &counted, {nullptr, d_reset_off, closed}, st)) {
         (void)hipStreamSynchronize(st);
         return rc;
     }
     HIP_OK(hipMemcpyAsync(t.out_len, d.out_len, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(t.status, d.status, n, hipMemcpyDeviceToHost, st));
+    if (index.off && closed) HIP_OK(hipMemcpyAsync(index.off, d_reset_off, closed * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    if (index.first) {
+        uint64_t run = 0;
+        for (size_t i = 0; i < n; i++) index.first[i] = run, run += batch_reset_closed_count(t.in_len[i], interval);
+        index.first[n] = run;
+    }
     uint64_t produced = 0;
     for (size_t i = 0; i < n; i++) produced += t.out_len[i];
     if (!produced) return TAMP_OK;
@@ -2148,6 +2168,186 @@ int decompress_resets(uint8_t max_wbits, const uint8_t* in, uint32_t n, uint8_t*
         HIP_OK(hipMemcpyAsync(out, d_out, *out_len, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
     }
+    return TAMP_OK;
+}
+
+// Reading a batch back with the compressor's reset index (tamp_batch_decompress_resets; kernels and steps:
+// tamp_reset_segments_kernel.hpp).  The index is checked on the device; the segments of the streams that hold up are staged as
+// streams of their own in the stream's scratch and decoded as ONE batch by the existing launch path, each into its place in the
+// caller's buffer with exactly its decoded size as room; every other stream is decoded as it lies, by a second launch over the
+// caller's tables in which the split streams are empty (in_len 0): the stage and the caller's input are two allocations, so the
+// two kinds of unit cannot share a launch, and rows that stay in place need no compaction and no scatter.  The walk's sizes stand
+// alone -- there is no size build over the staged segments beside it; a unit that decodes to another size is TAMP_ERROR for its
+// stream.  `t`, d_first, d_off: device memory; t.out null: the sizes only (nothing is staged).  `counted`: closed = reset_first[n]
+// (0 for a table out of order) and the bound of the staged bytes when the caller has them from host tables, else null: the one
+// 16-byte record a device-memory call reads back, once, and waits for.
+struct BatchResetIndexCounted { uint64_t closed, staged_bound; };
+int launch_decompress_batch_resets(DeviceCtx* ctx, const BatchTables& t, const uint64_t* d_first, const uint32_t* d_off, uint8_t max_wbits,
+                                   const BatchResetIndexCounted* counted, hipStream_t st) {
+    const uint64_t n = t.n;
+    if (n == 0) return TAMP_OK;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    auto exact = [&](const BatchTables& rows) {
+        return t.out ? launch_decompress_locked(ctx, rec, rows, max_wbits, st) : launch_decoded_size_locked(ctx, rec, rows, max_wbits, st);
+    };
+    auto all_whole = [&]() {
+        if (dbg) fprintf(stderr, "[tamp_amd resets] batch decode: %llu streams, 0 split into 0 units, %llu whole\n", (unsigned long long)n, (unsigned long long)n);
+        return exact(t);
+    };
+    BatchResetIndexCounted have = counted ? *counted : BatchResetIndexCounted{0, 0};
+    if (!counted) {
+        HIP_OK(rec.resets.need(256));
+        const BatchResetBoundArgs bound = {d_first, t.in_len, n, static_cast<BatchResetRecord*>(rec.resets.p)};
+        hipLaunchKernelGGL(tamp_batch_reset_bound_kernel, dim3(1), dim3(kResetScanTile), 0, st, bound);
+        HIP_OK(hipMemcpyAsync(&have, rec.resets.p, sizeof have, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    const uint64_t C = have.closed, R = C + n;
+    if (C == 0 || R > 0xFFFFFFFFull) return all_whole();  // (no entry anywhere, or more rows than a launch's tables count)
+    if (!d_off) return TAMP_AMD_BAD_ARGUMENT;
+    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max((free_b + rec.resets.bytes) / 4, rec.resets.bytes));
+    else (void)hipGetLastError();
+    const size_t stage_bytes = (size_t)std::min<uint64_t>(have.staged_bound, budget);
+    const size_t tab_bytes = (256 + 8 * (2 * (C + 1) + n + 3 * R) + 4 * (2 * n + 5 * R) + (2 * R + n) + 255) & ~(size_t)255;
+    if (rec.resets.need(tab_bytes + stage_bytes + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        return all_whole();
+    }
+    uint8_t* const base = static_cast<uint8_t*>(rec.resets.p);
+    BatchResetRecord* const record = reinterpret_cast<BatchResetRecord*>(base);
+    uint64_t* const size_scan = reinterpret_cast<uint64_t*>(base + 256);
+    uint64_t* const fail_scan = size_scan + C + 1;
+    uint64_t* const stage_base = fail_scan + C + 1;
+    BatchResetUnits u;
+    u.in_off = stage_base + n, u.out_off = u.in_off + R, u.src_off = u.out_off + R;
+    uint32_t* const size = reinterpret_cast<uint32_t*>(u.src_off + R);
+    uint32_t* const total = size + R;
+    uint32_t* const whole_len = total + n;
+    u.in_len = whole_len + n, u.out_cap = u.in_len + R, u.out_len = u.out_cap + R, u.owner = u.out_len + R;
+    uint8_t* const failed = reinterpret_cast<uint8_t*>(u.owner + R);
+    uint8_t* const split = failed + R;
+    u.status = reinterpret_cast<int8_t*>(split + n);
+    uint8_t* const stage = base + tab_bytes;
+    const uint32_t wbits = max_wbits & 0x7F;
+    const CallTiming call_timing(st);
+    const BatchResetCheckArgs check = {t.in, t.in_off, t.in_len, d_first, d_off, n, C, wbits, size, failed};
+    hipLaunchKernelGGL(tamp_batch_reset_check_kernel, dim3((uint32_t)((R + 63) / 64)), dim3(64), 0, st, check);
+    const BatchResetSizesArgs sizes = {size, failed, C, size_scan, fail_scan};
+    hipLaunchKernelGGL(tamp_batch_reset_sizes_kernel, dim3(1), dim3(kResetScanTile), 0, st, sizes);
+    const BatchResetPlanArgs plan = {t.in, t.in_off, t.in_len, t.out_cap, d_first, n, C, wbits, size, failed, size_scan, fail_scan,
+                                     stage_bytes, split, stage_base, total, whole_len, record};
+    hipLaunchKernelGGL(tamp_batch_reset_plan_kernel, dim3(1), dim3(kResetScanTile), 0, st, plan);
+    const uint32_t row_grid = (uint32_t)((R + 255) / 256);
+    if (t.out) {
+        const BatchResetUnitsArgs units = {t.in_off, t.in_len, t.out_off, d_first, d_off, n, C, size, size_scan, split, stage_base, u};
+        hipLaunchKernelGGL(tamp_batch_reset_units_kernel, dim3(row_grid), dim3(256), 0, st, units);
+        const BatchResetStageArgs sa = {t.in, t.in_off, u, stage, R};
+        hipLaunchKernelGGL(tamp_batch_reset_stage_kernel, dim3((uint32_t)std::min<uint64_t>(R, (uint64_t)ctx->cu_count * 8)), dim3(256), 0, st, sa);
+        HIP_OK(hipGetLastError());
+        BatchTables ut;
+        ut.in = stage, ut.in_off = u.in_off, ut.in_len = u.in_len, ut.out = t.out, ut.out_off = u.out_off, ut.out_cap = u.out_cap;
+        ut.out_len = u.out_len, ut.status = u.status, ut.n = R;
+        if (const int rc = launch_decompress_locked(ctx, rec, ut, max_wbits, st)) return rc;
+    }
+    BatchTables wt = t;  // the streams that stay whole, where they lie
+    wt.in_len = whole_len;
+    if (const int rc = exact(wt)) return rc;
+    BatchResetDoneArgs done = {t.in_len, t.out_len, t.status, t.in_consumed, n, C, split, total, u, 0};
+    hipLaunchKernelGGL(tamp_batch_reset_done_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, done);
+    if (t.out) {
+        done.units = 1;
+        hipLaunchKernelGGL(tamp_batch_reset_done_kernel, dim3(row_grid), dim3(256), 0, st, done);
+    }
+    HIP_OK(hipGetLastError());
+    if (dbg) {  // (the line waits for the plan's record; a call without the variable does not)
+        BatchResetRecord r;
+        HIP_OK(hipMemcpyAsync(&r, record, sizeof r, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        fprintf(stderr, "[tamp_amd resets] batch decode: %llu streams, %llu split into %llu units, %llu whole\n", (unsigned long long)n,
+                (unsigned long long)r.split, (unsigned long long)r.units, (unsigned long long)(n - r.split));
+    }
+    return TAMP_OK;
+}
+
+// tamp_batch_decompress_resets behind its checks.  Host memory, on the host pipeline's kept buffers and first stream (one host-memory
+// call per device at a time): the input's extent, the tables and the index go to the device in one piece each; the output slabs
+// lie back to back there; the three result tables come back, then exactly the produced bytes of every stream.
+int batch_decompress_resets(const BatchTables& t, const uint64_t* first, const uint32_t* off, uint8_t max_wbits, int mem, int device,
+                            void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_decompress_batch_resets(ctx, t, first, off, max_wbits, nullptr, static_cast<hipStream_t>(stream));
+    const size_t n = t.n;
+    if (n == 0) return TAMP_OK;
+    BatchResetIndexCounted counted = {first[n], 0};
+    for (size_t i = 0; i < n; i++) {
+        if (!reset_first_in_order(first, i)) counted.closed = 0;
+        if (const uint64_t E = reset_index_entries(first, n, i)) counted.staged_bound += (uint64_t)t.in_len[i] + kResetHeaderBytes * (E + 1);
+    }
+    const uint64_t C = counted.closed;
+    if (C && !off) return TAMP_AMD_BAD_ARGUMENT;
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> call_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    uint64_t in_lo = ~0ull, in_hi = 0, room = 0;
+    std::vector<uint64_t> h_in_off(n), h_out_off(n);
+    for (size_t i = 0; i < n; i++) {
+        if (t.in_len[i]) in_lo = std::min(in_lo, t.in_off[i]), in_hi = std::max(in_hi, t.in_off[i] + t.in_len[i]);
+        h_out_off[i] = room, room += t.out ? t.out_cap[i] : 0;
+    }
+    if (in_hi < in_lo) in_lo = in_hi = 0;
+    for (size_t i = 0; i < n; i++) h_in_off[i] = t.in_len[i] ? t.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
+    HIP_OK(P.in[0].need(in_hi - in_lo + 64));  // the kernels' vector loads may run past the last byte
+    if (t.out) HIP_OK(P.out[0].need(room + 1));
+    const size_t index_at = (n * (8 + 8 + 4 + 4 + 4 + 4) + 7) & ~(size_t)7, status_at = index_at + (n + 1) * 8 + C * 4;
+    HIP_OK(P.meta[0].need(status_at + n + 64));
+    uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
+    uint64_t* const d_in_off = reinterpret_cast<uint64_t*>(m);
+    uint64_t* const d_out_off = d_in_off + n;
+    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_out_off + n);
+    uint32_t* const d_cap = d_in_len + n;
+    uint64_t* const d_first = reinterpret_cast<uint64_t*>(m + index_at);
+    uint32_t* const d_off = reinterpret_cast<uint32_t*>(d_first + n + 1);
+    BatchTables d;
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = d_in_off, d.in_len = d_in_len;
+    d.out = t.out ? static_cast<uint8_t*>(P.out[0].p) : nullptr, d.out_off = t.out ? d_out_off : nullptr, d.out_cap = d_cap;
+    d.out_len = d_cap + n, d.in_consumed = d.out_len + n, d.status = reinterpret_cast<int8_t*>(m + status_at), d.n = n;
+    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, t.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_len, t.in_len, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_cap, t.out_cap, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_first, first, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (C) HIP_OK(hipMemcpyAsync(d_off, off, C * 4, hipMemcpyHostToDevice, st));
+    if (const int rc = launch_decompress_batch_resets(ctx, d, d_first, d_off, max_wbits, &counted, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(t.out_len, d.out_len, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(t.status, d.status, n, hipMemcpyDeviceToHost, st));
+    if (t.in_consumed) HIP_OK(hipMemcpyAsync(t.in_consumed, d.in_consumed, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (!t.out) return TAMP_OK;
+    uint64_t produced = 0;
+    for (size_t i = 0; i < n; i++) produced += t.out_len[i];
+    if (!produced) return TAMP_OK;
+    if (room <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(room) == hipSuccess) {
+        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
+        HIP_OK(hipMemcpyAsync(P.stage[0].p, d.out, room, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < n; i++)
+            if (t.out_len[i]) memcpy(t.out + t.out_off[i], stg + h_out_off[i], t.out_len[i]);
+        return TAMP_OK;
+    }
+    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
+    for (size_t i = 0; i < n; i++)
+        if (t.out_len[i]) HIP_OK(hipMemcpyAsync(t.out + t.out_off[i], d.out + h_out_off[i], t.out_len[i], hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
     return TAMP_OK;
 }
 
@@ -2449,10 +2649,11 @@ int tamp_batch_compress(const TampAmdConf* conf, const uint8_t* dictionary, cons
                                      max_in_len, mem, device, stream);
 }
 
-int tamp_batch_compress_resets(const TampAmdConf* conf, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                               uint32_t reset_interval, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                               uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem, int device,
-                               void* stream) {
+// (one implementation for both forms: the plain call asks for no index)
+int tamp_batch_compress_resets_index(const TampAmdConf* conf, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                     uint32_t reset_interval, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                     uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem, int device,
+                                     void* stream, uint64_t* reset_first, uint32_t* reset_off, uint64_t reset_cap) {
     const BatchTables t = {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, nullptr, nullptr, 0, n_streams};
     if (!conf) return TAMP_AMD_BAD_ARGUMENT;
     if (const int rc = batch_refused(t, true, mem, device)) return rc;
@@ -2460,7 +2661,27 @@ int tamp_batch_compress_resets(const TampAmdConf* conf, const uint8_t* in, const
         return TAMP_AMD_BAD_ARGUMENT;
     // (a table row's capacity is 32 bits wide: an interval whose worst case does not fit one is not taken)
     if (reset_segment_bound(reset_interval, conf->literal, true) > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
-    return batch_compress_resets(conf, t, reset_interval, max_in_len, mem, device, stream);
+    if (!reset_off && reset_cap) return TAMP_AMD_BAD_ARGUMENT;  // (room for entries and nowhere to put them)
+    return batch_compress_resets(conf, t, reset_interval, max_in_len, {reset_first, reset_off, reset_cap}, mem, device, stream);
+}
+
+int tamp_batch_compress_resets(const TampAmdConf* conf, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                               uint32_t reset_interval, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                               uint32_t* out_len, int8_t* status, size_t n_streams, uint32_t max_in_len, int mem, int device,
+                               void* stream) {
+    return tamp_batch_compress_resets_index(conf, in, in_off, in_len, reset_interval, out, out_off, out_cap, out_len, status, n_streams,
+                                            max_in_len, mem, device, stream, nullptr, nullptr, 0);
+}
+
+int tamp_batch_decompress_resets(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                 const uint64_t* reset_first, const uint32_t* reset_off, uint8_t* out, const uint64_t* out_off,
+                                 const uint32_t* out_cap, uint32_t* out_len, int8_t* status, uint32_t* in_consumed, size_t n_streams,
+                                 int mem, int device, void* stream) {
+    const BatchTables t = {in, in_off, in_len, out, out ? out_off : nullptr, out_cap, out_len, status, in_consumed, nullptr, nullptr, 0, n_streams};
+    // (out_cap is read with and without a slab: it is what decides whether a stream's segments may be decoded on their own)
+    if (const int rc = batch_refused(t, out != nullptr, mem, device)) return rc;
+    if (device == TAMP_AMD_ALL_DEVICES || (n_streams && (!reset_first || !out_cap))) return TAMP_AMD_BAD_ARGUMENT;
+    return batch_decompress_resets(t, reset_first, reset_off, max_window_bits, mem, device, stream);
 }
 
 int tamp_batch_decompress_dicts(const uint8_t* dictionaries, size_t dictionaries_len, const uint64_t* dict_off, uint8_t max_window_bits,

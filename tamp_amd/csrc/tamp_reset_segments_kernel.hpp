@@ -183,7 +183,8 @@ __global__ void __launch_bounds__(256) tamp_reset_gather_kernel(ResetGatherArgs 
 //                                   segment starts and its last one ends in that scan, and the worst status
 //   tamp_batch_reset_finish_kernel  open slices: out_len and status of every stream
 //   tamp_batch_reset_gather_kernel  a workgroup per segment: its slab to out + out_off[owner] + what the stream's segments in front
-//                                   of it took, clipped at out_cap[owner]; the header over the lead of each stream's segment 0
+//                                   of it took, clipped at out_cap[owner]; the header over the lead of each stream's segment 0;
+//                                   on request the RESET INDEX (tamp_batch_compress_resets_index): one store per closed segment
 // A device-memory call reads ONE 16-byte record back, once: closed_first[n] and the longest stream behind it, which size the slices,
 // the slabs and the scratch -- from the tables themselves, never from the caller's max_in_len hint.
 
@@ -330,6 +331,8 @@ struct BatchResetGatherArgs {
     const uint64_t* out_off;
     const uint32_t* out_cap;  // nothing is written at or behind dst + out_off[i] + out_cap[i]
     uint32_t header;          // byte 0 in bits 0-7, byte 1 in bits 8-15
+    uint32_t* reset_off;      // optional, closed slices: the reset index -- entry c for closed segment c of the batch (the streams'
+                              // entries stand in stream order, stream i's from closed_first[i] on)
 };
 __global__ void __launch_bounds__(256) tamp_batch_reset_gather_kernel(BatchResetGatherArgs a) {
     for (uint32_t k = blockIdx.x; k < a.count; k += gridDim.x) {
@@ -337,6 +340,9 @@ __global__ void __launch_bounds__(256) tamp_batch_reset_gather_kernel(BatchReset
         const uint64_t c0 = a.closed_first[o], from = a.s.start[o];
         const uint64_t at = a.open ? a.s.end[o] - from : a.pos[k] - from;  // in front of it in its stream
         const bool head = a.open ? a.closed_first[o + 1] == c0 : a.first + k == c0;  // the stream's segment 0
+        // the byte behind this segment's reset, in its stream: behind the next segment's lead (the reset's last 16 bits).  Of a
+        // stream that fails the value means nothing.
+        if (!a.open && a.reset_off && threadIdx.x == 0) a.reset_off[a.first + k] = (uint32_t)(at + a.seg_len[k] + 2);
         const uint64_t cap = a.out_cap[o];
         if (at >= cap) continue;
         const uint64_t room = cap - at;
@@ -401,6 +407,263 @@ __global__ void __launch_bounds__(256) tamp_reset_stage_kernel(ResetStageArgs a)
         if (threadIdx.x == 64) dst[0] = (uint8_t)a.header, dst[1] = (uint8_t)(a.header >> 8);
         reset_copy(dst + 2, a.in + a.src_off[k], a.src_len[k], false, 0);
     }
+}
+
+// ---- reading a BATCH back with the compressor's reset index (tamp_batch_decompress_resets; the rows: tamp_reset_segments.hpp) ----
+//
+// The index is a hint, checked here: a stream all of whose claimed segments hold up is SPLIT into units, every other one stays one
+// WHOLE unit for the exact decoders.  R = C + n rows (C closed segments, n open ones).  No workgroup waits for another: the steps
+// are kernels of their own on the call's stream.
+//   tamp_batch_reset_bound_kernel   C and an upper bound of the staged bytes: the 16-byte record a device-memory call reads back
+//   tamp_batch_reset_check_kernel   a lane per row: range and order of its entries, then the WALK of its segment, token by token
+//                                   (long_token): decoded size, ends at its boundary, last two tokens FLUSH, no offset out of window
+//   tamp_batch_reset_sizes_kernel   exclusive scans over the closed rows: decoded sizes, rows that failed
+//   tamp_batch_reset_plan_kernel    a lane per stream: split or whole, its size; the scan that places the split streams in the stage
+//   tamp_batch_reset_units_kernel   a lane per row: the unit's table row (a row of a whole stream: an empty stream)
+//   tamp_batch_reset_stage_kernel   a workgroup per unit: header + segment into the stage (reset_copy)
+//   tamp_batch_reset_done_kernel    per split stream out_len / status / in_consumed, then per unit: decoded to the walk's size?
+
+// What a stream must look like to be split: the reset bit (with it the second header byte, which must be zero), no custom
+// dictionary, a window the call accepts, a length the 32-bit bit positions of the walk can count.
+__device__ __forceinline__ bool reset_split_header(const uint8_t* s, uint32_t len, uint32_t max_wbits) {
+    if (len < kResetHeaderBytes || len > kMaxDecodeIn - 512 || max_wbits > 15) return false;
+    const uint32_t h0 = s[0];
+    const StreamHeader hd = decode_header(h0);
+    return hd.dreset && !hd.custom && s[1] == 0 && hd.wbits <= max_wbits;
+}
+
+struct BatchResetRecord {  // in device memory; a device-memory call reads the first two words back
+    uint64_t closed;        // C = reset_first[n]
+    uint64_t staged_bound;  // no verdict can stage more bytes than this
+    uint64_t split, units, staged;  // the plan: streams split, their units, the bytes staged (TAMP_AMD_RESETS_DEBUG reads these)
+};
+
+struct BatchResetBoundArgs {
+    const uint64_t* first;
+    const uint32_t* in_len;
+    uint64_t n;
+    BatchResetRecord* rec;
+};
+__global__ void __launch_bounds__(kResetScanTile) tamp_batch_reset_bound_kernel(BatchResetBoundArgs a) {
+    __shared__ uint64_t wave_sum[kResetScanTile / kWave];
+    uint64_t bound = 0, disorder = 0;
+    for (uint64_t t0 = 0; t0 < a.n; t0 += kResetScanTile) {  // (uniform bounds: every lane takes part in the shuffles)
+        const uint64_t i = t0 + threadIdx.x;
+        const uint64_t E = i < a.n ? reset_index_entries(a.first, a.n, i) : 0;
+        uint64_t tile;
+        (void)reset_tile_scan(E ? (uint64_t)a.in_len[i] + kResetHeaderBytes * (E + 1) : 0, wave_sum, tile);
+        bound += tile;
+        (void)reset_tile_scan(i < a.n && !reset_first_in_order(a.first, i) ? 1 : 0, wave_sum, tile);
+        disorder += tile;
+    }
+    // (a table that is no running sum from 0 gives no row one owner: the call then has no index at all)
+    if (threadIdx.x == 0) a.rec->closed = disorder ? 0 : a.first[a.n], a.rec->staged_bound = bound;
+}
+
+struct BatchResetCheckArgs {
+    const uint8_t* in;  // the caller's tables
+    const uint64_t* in_off;
+    const uint32_t* in_len;
+    const uint64_t* first;
+    const uint32_t* off;
+    uint64_t n, closed;
+    uint32_t max_wbits;
+    uint32_t* size;   // -> per row: bytes the segment decodes to
+    uint8_t* failed;  // -> per row: 0 = the segment holds up
+};
+__global__ void __launch_bounds__(64) tamp_batch_reset_check_kernel(BatchResetCheckArgs a) {
+    __shared__ uint8_t lut[128];
+    build_prefix_lut(lut);
+    __syncthreads();
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.closed + a.n) return;
+    const bool open = r >= a.closed;
+    const ResetIndexCut u = open ? reset_index_open_cut(a.first, a.off, a.in_len, a.n, r - a.closed)
+                                 : reset_index_closed_cut(a.first, a.off, a.in_len, a.n, r);
+    uint64_t bytes = 0;
+    bool ok = u.stream != kResetNoOwner;
+    if (ok) {
+        const uint8_t* const s = a.in + a.in_off[u.stream];
+        ok = reset_split_header(s, a.in_len[u.stream], a.max_wbits);
+        if (ok) {
+            const StreamHeader hd = decode_header(s[0]);
+            // the walk: token aligned at u.start by induction from the header, and never a bit read at or behind u.end.  The
+            // reference keeps "the last token was a FLUSH" across a reset, so segments behind one start with it set
+            const uint32_t end = 8 * u.end;
+            uint32_t t = 8 * u.start;
+            bool last = u.seg != 0, before = last, bad = false;
+            while (t < end) {  // (long_token: at least one bit, or 0)
+                uint32_t rec;
+                const uint32_t k = long_token(s, u.end, t, lut, hd.wbits, hd.lbits, hd.minp, hd.extended, rec, bad);
+                if (!k) break;
+                t += k;
+                before = last, last = rec == 0xFFFFFFFFu;
+                if (!last) bytes += (rec >> 2) & 0xFFu;
+            }
+            // a closed segment ends exactly at its boundary behind FLUSH, FLUSH; the open one ends as a stream ends: out of tokens
+            ok = !bad && bytes <= 0xFFFFFFFFull && (open || (t == end && last && before));
+        }
+    }
+    a.size[r] = ok ? (uint32_t)bytes : 0, a.failed[r] = ok ? 0 : 1;
+}
+
+struct BatchResetSizesArgs {
+    const uint32_t* size;  // per closed row
+    const uint8_t* failed;
+    uint64_t closed;
+    uint64_t* size_scan;  // -> closed + 1 entries each
+    uint64_t* fail_scan;
+};
+__global__ void __launch_bounds__(kResetScanTile) tamp_batch_reset_sizes_kernel(BatchResetSizesArgs a) {
+    __shared__ uint64_t wave_sum[kResetScanTile / kWave];
+    uint64_t bytes = 0, fails = 0;
+    for (uint64_t t0 = 0; t0 < a.closed; t0 += kResetScanTile) {  // (uniform bounds)
+        const uint64_t c = t0 + threadIdx.x;
+        const bool live = c < a.closed;
+        uint64_t tile;
+        const uint64_t at = bytes + reset_tile_scan(live ? a.size[c] : 0, wave_sum, tile);
+        bytes += tile;
+        const uint64_t fat = fails + reset_tile_scan(live ? a.failed[c] : 0, wave_sum, tile);
+        fails += tile;
+        if (live) a.size_scan[c] = at, a.fail_scan[c] = fat;
+    }
+    if (threadIdx.x == 0) a.size_scan[a.closed] = bytes, a.fail_scan[a.closed] = fails;
+}
+
+struct BatchResetPlanArgs {
+    const uint8_t* in;  // the caller's tables
+    const uint64_t* in_off;
+    const uint32_t* in_len;
+    const uint32_t* out_cap;
+    const uint64_t* first;
+    uint64_t n, closed;
+    uint32_t max_wbits;
+    const uint32_t* size;  // per row
+    const uint8_t* failed;
+    const uint64_t* size_scan;
+    const uint64_t* fail_scan;
+    uint64_t budget;       // bytes of the stage: streams are split in stream order until it is full
+    uint8_t* split;        // -> per stream
+    uint64_t* stage_base;  // -> per split stream: its first staged byte
+    uint32_t* total;       // -> per split stream: its decoded size
+    uint32_t* whole_len;   // -> per stream: in_len of a whole stream, 0 for a split one (the exact decoders' table)
+    BatchResetRecord* rec;
+};
+__global__ void __launch_bounds__(kResetScanTile) tamp_batch_reset_plan_kernel(BatchResetPlanArgs a) {
+    __shared__ uint64_t wave_sum[kResetScanTile / kWave];
+    uint64_t wanted = 0, staged = 0, n_split = 0, units = 0;
+    for (uint64_t t0 = 0; t0 < a.n; t0 += kResetScanTile) {  // (uniform bounds)
+        const uint64_t i = t0 + threadIdx.x;
+        const bool live = i < a.n;
+        const uint64_t E = live ? reset_index_entries(a.first, a.n, i) : 0;
+        bool ok = E != 0 && !a.failed[a.closed + i] && a.fail_scan[a.first[i + 1]] == a.fail_scan[a.first[i]];
+        uint64_t bytes = 0;
+        if (ok) {
+            // (room that is used up exactly is the exact decoder's to judge)
+            bytes = a.size_scan[a.first[i + 1]] - a.size_scan[a.first[i]] + a.size[a.closed + i];
+            ok = bytes < a.out_cap[i] && reset_split_header(a.in + a.in_off[i], a.in_len[i], a.max_wbits);
+        }
+        const uint64_t want = ok ? reset_staged_bytes(a.in_len[i], E) : 0;
+        uint64_t tile;
+        const uint64_t at = wanted + reset_tile_scan(want, wave_sum, tile);
+        wanted += tile;
+        ok = ok && at + want <= a.budget;  // (the sums only grow: behind the first stream that does not fit none fits)
+        if (ok) staged += want, n_split += 1, units += E + 1;  // (this lane's own streams; summed behind the loop)
+        if (live) {
+            a.split[i] = ok ? 1 : 0, a.stage_base[i] = at, a.total[i] = (uint32_t)bytes;
+            a.whole_len[i] = ok ? 0 : a.in_len[i];
+        }
+    }
+    uint64_t all_staged, all_split, all_units;
+    (void)reset_tile_scan(staged, wave_sum, all_staged);
+    (void)reset_tile_scan(n_split, wave_sum, all_split);
+    (void)reset_tile_scan(units, wave_sum, all_units);
+    if (threadIdx.x == 0) a.rec->split = all_split, a.rec->units = all_units, a.rec->staged = all_staged;
+}
+
+// The units' table, one row per claimed segment; a row whose stream stays whole is an empty stream (no input, no room).
+struct BatchResetUnits {
+    uint64_t* in_off;   // where the unit's staged stream starts in the stage
+    uint64_t* out_off;  // where it decodes to in the caller's buffer
+    uint64_t* src_off;  // where its segment starts in the caller's input
+    uint32_t* in_len;   // segment + header bytes (0: no unit)
+    uint32_t* out_cap;  // exactly its decoded size
+    uint32_t* out_len;  // <- the decode
+    uint32_t* owner;    // kResetNoOwner: no unit
+    int8_t* status;     // <- the decode
+};
+struct BatchResetUnitsArgs {
+    const uint64_t* in_off;  // the caller's tables
+    const uint32_t* in_len;
+    const uint64_t* out_off;  // (null: sizes only, no units)
+    const uint64_t* first;
+    const uint32_t* off;
+    uint64_t n, closed;
+    const uint32_t* size;
+    const uint64_t* size_scan;
+    const uint8_t* split;
+    const uint64_t* stage_base;
+    BatchResetUnits u;
+};
+__global__ void __launch_bounds__(256) tamp_batch_reset_units_kernel(BatchResetUnitsArgs a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.closed + a.n) return;
+    ResetIndexCut u = r >= a.closed ? reset_index_open_cut(a.first, a.off, a.in_len, a.n, r - a.closed)
+                                    : reset_index_closed_cut(a.first, a.off, a.in_len, a.n, r);
+    if (u.stream != kResetNoOwner && !a.split[u.stream]) u.stream = kResetNoOwner;
+    const bool unit = u.stream != kResetNoOwner;
+    a.u.owner[r] = u.stream;
+    a.u.in_off[r] = unit ? reset_unit_stage_off(a.stage_base[u.stream], u) : 0;
+    a.u.in_len[r] = unit ? u.end - u.start + kResetHeaderBytes : 0;
+    a.u.src_off[r] = unit ? a.in_off[u.stream] + u.start : 0;
+    a.u.out_off[r] = unit ? a.out_off[u.stream] + reset_unit_out_off(a.first, a.size_scan, u) : 0;
+    a.u.out_cap[r] = unit ? a.size[r] : 0;
+}
+
+struct BatchResetStageArgs {
+    const uint8_t* in;  // the caller's input
+    const uint64_t* in_off;
+    BatchResetUnits u;
+    uint8_t* stage;
+    uint64_t rows;
+};
+__global__ void __launch_bounds__(256) tamp_batch_reset_stage_kernel(BatchResetStageArgs a) {
+    for (uint64_t r = blockIdx.x; r < a.rows; r += gridDim.x) {
+        const uint32_t o = a.u.owner[r];
+        if (o == kResetNoOwner) continue;
+        uint8_t* const dst = a.stage + a.u.in_off[r];
+        // (the stream's own two header bytes: the second one is zero)
+        if (threadIdx.x == 64) dst[0] = a.in[a.in_off[o]], dst[1] = 0;
+        reset_copy(dst + kResetHeaderBytes, a.in + a.u.src_off[r], a.u.in_len[r] - kResetHeaderBytes, false, 0);
+    }
+}
+
+struct BatchResetDoneArgs {
+    const uint32_t* in_len;  // the caller's tables
+    uint32_t* out_len;
+    int8_t* status;
+    uint32_t* in_consumed;  // may be null
+    uint64_t n, closed;
+    const uint8_t* split;
+    const uint32_t* total;
+    BatchResetUnits u;  // (u.owner null: sizes only, no units were decoded)
+    uint32_t units;     // 0: the split streams' results; 1: the units against the walk
+};
+// Launched twice, one behind the other: a unit that did not decode to the size the walk found makes its stream TAMP_ERROR -- the two
+// disagree, which is a defect of the library and not a property of the stream (several units may store that same value).
+__global__ void __launch_bounds__(256) tamp_batch_reset_done_kernel(BatchResetDoneArgs a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!a.units) {
+        if (r >= a.n || !a.split[r]) return;
+        a.out_len[r] = a.total[r], a.status[r] = (int8_t)kInputExhausted;
+        if (a.in_consumed) a.in_consumed[r] = a.in_len[r];
+        return;
+    }
+    if (r >= a.closed + a.n) return;
+    const uint32_t o = a.u.owner[r];
+    if (o == kResetNoOwner) return;
+    const int8_t st = a.u.status[r];
+    if (a.u.out_len[r] != a.u.out_cap[r] || (st != (int8_t)kInputExhausted && st != (int8_t)kOutputFull)) a.status[o] = (int8_t)kError;
 }
 
 }  // namespace tamp_amd

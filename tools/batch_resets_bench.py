@@ -13,6 +13,16 @@ the median of all but the first two (of all but the first below four).  New and 
 tree).
 
     python tools/batch_resets_bench.py [--out profiles/batch_resets_bench.txt] [--before-root ../parent-checkout]
+
+`--decode`: the way BACK on the same batch, compressed once per process by the call under test's own library (DESIGN.md 3.13,
+"Reading a batch back"), every stream with room for its size + 1:
+  index, device / host   tamp_batch_decompress_resets with the index of tamp_batch_compress_resets_index
+  plain, device / host   tamp_batch_decompress as it stands, on this tree and -- with `--before-root` -- on a build of the parent
+  compress, device / host   the `new` rows above, on both builds (the index store and the shared entry point must cost nothing)
+Median of the last ten of twelve calls in a fresh process, `--rounds` alternating runs; SHA-256 over all decoded streams must be the
+input's on every row.  Written to profiles/batch_reset_decode_bench.txt.
+
+    python tools/batch_resets_bench.py --decode [--before-root ../parent-checkout]
 """
 import argparse
 import hashlib
@@ -132,6 +142,118 @@ def child(which, reps):
                           calls=reps, out_len=int(h_len.astype(np.uint64).sum()), sha256=digest.hexdigest(), lib=_lib.LIB_PATH)))
 
 
+def decode_child(which, reps):
+    """One decode row: `index-device`, `index-host`, `plain-device`, `plain-host`."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from tamp_amd import _lib
+
+    lib = _lib.load()
+    kind, route = which.split("-")
+    flat, in_off, in_len = workload()
+    n, total = len(in_len), int(flat.size)
+    conf = _lib.TampAmdConf(10, 8, 0, 1, 1, 0)
+    cap = np.array([lib.tamp_amd_compress_resets_bound(int(x), INTERVAL, 8) for x in in_len], dtype=np.uint32)
+    c_off = np.zeros(n, dtype=np.uint64)
+    c_off[1:] = np.cumsum(cap.astype(np.uint64))[:-1]
+    entries = int(((np.maximum(in_len.astype(np.uint64), 1) - 1) // INTERVAL).sum())
+    room = np.minimum(in_len.astype(np.uint64) + 1, 0xFFFFFFFF).astype(np.uint32)  # (size + 1: a stream that fits ends with status 2)
+    d_off = np.zeros(n, dtype=np.uint64)
+    d_off[1:] = np.cumsum(room.astype(np.uint64))[:-1]
+    dev = torch.device("cuda:0")
+    host = route == "host"
+    mem = _lib.MEM_HOST if host else _lib.MEM_DEVICE
+    arrays = dict(flat=flat, in_off=in_off.view(np.int64), in_len=in_len.view(np.int32), comp=np.zeros(int(cap.astype(np.uint64).sum()) + 1, np.uint8),
+                  c_off=c_off.view(np.int64), cap=cap.view(np.int32), c_len=np.zeros(n, np.int32), c_status=np.full(n, 99, np.int8),
+                  first=np.zeros(n + 1, np.int64), off=np.zeros(max(entries, 1), np.int32), out=np.zeros(int(room.astype(np.uint64).sum()) + 1, np.uint8),
+                  d_off=d_off.view(np.int64), room=room.view(np.int32), d_len=np.zeros(n, np.int32), d_status=np.full(n, 99, np.int8),
+                  used=np.zeros(n, np.int32))
+    held = arrays if host else {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+    p = {k: C.c_void_p(v.ctypes.data if host else v.data_ptr()) for k, v in held.items()}
+    if kind == "index":
+        rc = lib.tamp_batch_compress_resets_index(C.byref(conf), p["flat"], p["in_off"], p["in_len"], INTERVAL, p["comp"], p["c_off"], p["cap"],
+                                                  p["c_len"], p["c_status"], n, LONGEST, mem, 0, None, p["first"], p["off"], entries)
+    else:
+        rc = lib.tamp_batch_compress_resets(C.byref(conf), p["flat"], p["in_off"], p["in_len"], INTERVAL, p["comp"], p["c_off"], p["cap"],
+                                            p["c_len"], p["c_status"], n, LONGEST, mem, 0, None)
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    ms, wall = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        if kind == "index":
+            rc = lib.tamp_batch_decompress_resets(15, p["comp"], p["c_off"], p["c_len"], p["first"], p["off"], p["out"], p["d_off"], p["room"],
+                                                  p["d_len"], p["d_status"], p["used"], n, mem, 0, None)
+        else:
+            rc = lib.tamp_batch_decompress(None, 0, 15, p["comp"], p["c_off"], p["c_len"], p["out"], p["d_off"], p["room"], p["d_len"],
+                                           p["d_status"], p["used"], n, mem, 0, None)
+        e1.record()
+        e1.synchronize()
+        torch.cuda.synchronize()
+        assert rc == 0, rc
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(e0.elapsed_time(e1))
+    back = held if host else {k: held[k].cpu().numpy() for k in ("out", "d_len", "d_status", "used", "c_len", "c_status")}
+    assert (back["c_status"] == 0).all() and (back["d_status"] == 2).all(), back["d_status"][back["d_status"] != 2][:8]
+    assert (back["d_len"].view(np.uint32) == in_len).all() and (back["used"] == back["c_len"]).all()
+    digest, source = hashlib.sha256(), hashlib.sha256()
+    for i in range(n):
+        digest.update(back["out"][int(d_off[i]) : int(d_off[i]) + int(in_len[i])].tobytes())
+        source.update(flat[int(in_off[i]) : int(in_off[i]) + int(in_len[i])].tobytes())
+    assert digest.hexdigest() == source.hexdigest(), "the decoded streams are not the input"
+    kept, kept_wall = sorted(ms[2:]), sorted(wall[2:])
+    med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2  # noqa: E731
+    print(json.dumps(dict(which=which, streams=n, bytes=total, median_ms=med(kept), min_ms=kept[0], max_ms=kept[-1], wall_ms=med(kept_wall),
+                          calls=reps, comp_len=int(back["c_len"].astype(np.uint64).sum()), sha256=digest.hexdigest(), lib=_lib.LIB_PATH)))
+
+
+def decode_main(args):
+    me = os.path.abspath(__file__)
+
+    def run(flag, which, parent):
+        env = dict(os.environ)
+        if parent:
+            env["BATCH_RESETS_BENCH_ROOT"] = os.path.abspath(args.before_root)
+        p = subprocess.run([sys.executable, me, flag, which, str(REPS)], env=env, capture_output=True, text=True, timeout=1100)
+        if p.returncode != 0:
+            raise SystemExit(f"{which}: exit {p.returncode}\n{p.stderr[-2000:]}")
+        return json.loads([ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")][-1])
+
+    lines = [f"# tools/batch_resets_bench.py --decode: prose corpus tiled into {STREAMS:,} streams, lengths log-uniform in {SHORTEST:,} .. {LONGEST:,} bytes",
+             f"# (seed {SEED}), window 10, literal 8, extended, a reset every 65,536 bytes, compressed once per process; every stream decoded into",
+             "# its size + 1 bytes.  hipEvents around each call, wall clock around the same span, the device drained at both ends; median of the",
+             "# last ten of twelve calls in a fresh process (min .. max in brackets).  index = tamp_batch_decompress_resets with the compressor's",
+             "# reset index; plain = tamp_batch_decompress; compress = tamp_batch_compress_resets.  'parent': a build of the parent commit."
+             if args.before_root else "# reset index; plain = tamp_batch_decompress; compress = tamp_batch_compress_resets.",
+             "# SHA-256 over all decoded streams equals the input's on every row (asserted).  ratio = plain / index on the same route.", ""]
+    fmt = lambda r: (f"{r['median_ms']:10.2f} ms [{r['min_ms']:.2f} .. {r['max_ms']:.2f}]  wall {r['wall_ms']:10.2f} ms "  # noqa: E731
+                     f"{r['bytes'] / r['median_ms'] / 1e6:8.2f} GB/s")
+    sides = [("this tree", False)] + ([("parent", True)] if args.before_root else [])
+    for rnd in range(args.rounds):
+        lines.append(f"run {rnd + 1}")
+        for route in ("device", "host"):
+            index = run("--decode-child", f"index-{route}", False)
+            lines.append(f"    index, {route:<7} this tree  {fmt(index)}")
+            digests = {index["sha256"]}
+            for name, parent in sides:
+                plain = run("--decode-child", f"plain-{route}", parent)
+                digests.add(plain["sha256"])
+                lines.append(f"    plain, {route:<7} {name:<9}  {fmt(plain)}   ratio {plain['median_ms'] / index['median_ms']:6.2f}")
+            assert len(digests) == 1, digests
+            for name, parent in sides:
+                lines.append(f"    compress, {route:<4} {name:<9}  {fmt(run('--child', f'new-{route}', parent))}")
+        print("\n".join(lines[-(1 + 2 * (1 + 2 * len(sides))):]), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:  # (after every run: a session that is cut short keeps what it measured)
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_resets_bench.txt"))
@@ -139,9 +261,17 @@ def main():
     ap.add_argument("--old-reps", type=int, default=REPS)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--child", nargs=2, default=None)
+    ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--decode-child", nargs=2, default=None)
     args = ap.parse_args()
     if args.child:
         return child(args.child[0], int(args.child[1]))
+    if args.decode_child:
+        return decode_child(args.decode_child[0], int(args.decode_child[1]))
+    if args.decode:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "batch_reset_decode_bench.txt")
+        return decode_main(args)
 
     def run(which):
         env = dict(os.environ)
