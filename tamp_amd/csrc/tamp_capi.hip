@@ -445,20 +445,21 @@ CompressArgs fill_compress_args(const DeviceCtx* ctx, const CompressCall& call, 
 // a work-counter slot, zeroed, and the launch over it.  (Two steps: the grid is sized, checked and used between them.)
 int prepare_compress_kernel(const CompressPlan& p, int* per_cu) {
     const void* const kernel = reinterpret_cast<const void*>(compress_kernel_of(p.build, p.dicts));
-    HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds.total));
+    const uint32_t dyn = dynamic_lds(p);  // (0 for the fixed-geometry builds: their LDS is a static array of the kernel's)
+    if (dyn) HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     if (!p.persistent) return TAMP_OK;
     static std::mutex occ_mu;
     static std::map<std::pair<const void*, uint64_t>, int> occ;  // (0: not asked yet)
     std::lock_guard<std::mutex> lock(occ_mu);
-    int& cached = occ[std::make_pair(kernel, (uint64_t)p.lds.total << 16 | p.threads)];
-    if (cached == 0) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kernel, (int)p.threads, p.lds.total));
+    int& cached = occ[std::make_pair(kernel, (uint64_t)dyn << 16 | p.threads)];
+    if (cached == 0) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cached, kernel, (int)p.threads, dyn));
     *per_cu = cached = std::max(cached, 1);
     return TAMP_OK;
 }
 int launch_on_counter(DeviceCtx* ctx, const CompressPlan& p, uint32_t grid, CompressArgs& a, hipStream_t st) {
     a.work_counter = ctx->work_counters + ctx->next_counter.fetch_add(1) % DeviceCtx::kCounters;
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(compress_kernel_of(p.build, p.dicts), dim3(grid), dim3(p.threads), p.lds.total, st, a);
+    hipLaunchKernelGGL(compress_kernel_of(p.build, p.dicts), dim3(grid), dim3(p.threads), dynamic_lds(p), st, a);
     return TAMP_OK;
 }
 
@@ -629,7 +630,7 @@ int launch_compress_locked(DeviceCtx* ctx, StreamScratch& rec, const TampAmdConf
         for (size_t first = 0; first < n_streams; first += launch_step) {  // one stream per workgroup
             a.first_stream = (uint32_t)first;
             const uint32_t g = (uint32_t)std::min<size_t>(launch_step, n_streams - first);
-            hipLaunchKernelGGL(compress_kernel_of(p.build, p.dicts), dim3(g), dim3(p.threads), p.lds.total, st, a);
+            hipLaunchKernelGGL(compress_kernel_of(p.build, p.dicts), dim3(g), dim3(p.threads), dynamic_lds(p), st, a);
         }
     }
     timing_end(st);

@@ -186,6 +186,7 @@ __device__ __forceinline__ uint32_t ffbl_or_ones(uint32_t x) {
     asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
     return r;
 }
+template <bool OR_TAIL = false>
 __device__ __forceinline__ uint32_t prefix_len16(const uint8_t* ebuf, uint32_t c, const uint32_t (&P)[4]) {
     // Round 6: ONE hardware-unaligned ds_read_b128 (gfx950's LDS serves it) instead of five aligned dwords + four funnel shifts:
     // with the rest of the loop slimmed down the LDS pipe has the room (synthetic 5.64 -> 5.51 ms; in rounds 1-2 it was the bound:
@@ -198,9 +199,11 @@ __device__ __forceinline__ uint32_t prefix_len16(const uint8_t* ebuf, uint32_t c
     // iteration (some lane's first eight bytes agree) with two exec-mask regions: synthetic 5.96 -> 5.81 ms, prose 9.96 -> 9.63,
     // markup 9.88 -> 9.53, Python sources 22.24 -> 21.74 (profiles/ab/r6_experiments.log).
     const uint32_t t0 = ffbl_or_ones(x0);
-    const uint32_t t1 = __builtin_elementwise_add_sat(ffbl_or_ones(x1), 32u);
-    const uint32_t t2 = __builtin_elementwise_add_sat(ffbl_or_ones(x2), 64u);
-    const uint32_t t3 = __builtin_elementwise_add_sat(ffbl_or_ones(x3), 96u);
+    // OR_TAIL (the fixed-geometry builds): the first set bit is 0..31 or all ones, so `| 32` (64, 96) IS the saturating add for
+    // every value it can take -- a plain v_or_b32, in the 2.2-cycle issue class where v_add_u32 ... clamp is in the 4.1-cycle one
+    const uint32_t t1 = OR_TAIL ? ffbl_or_ones(x1) | 32u : __builtin_elementwise_add_sat(ffbl_or_ones(x1), 32u);
+    const uint32_t t2 = OR_TAIL ? ffbl_or_ones(x2) | 64u : __builtin_elementwise_add_sat(ffbl_or_ones(x2), 64u);
+    const uint32_t t3 = OR_TAIL ? ffbl_or_ones(x3) | 96u : __builtin_elementwise_add_sat(ffbl_or_ones(x3), 96u);
     return min(min(min(t0, t1), min(t2, t3)) >> 3, 16u);
 }
 
@@ -836,6 +839,22 @@ constexpr uint32_t kFixWbits = 10, kFixBlk = 1024, kFixLbits = 8, kFixThreads = 
 constexpr CompressLds kLdsFixed(1u << kFixWbits, kFixBlk, true, false, true, kHb1024);
 static_assert(kLdsFixed.total == 19616 && kLdsFixed.tokcap == 1376 && kLdsFixed.obuf_words == 516,
               "the fixed builds' LDS layout is the generic build's for window 2^10, block 1,024, 1,024 buckets");
+// The workgroup's LDS.  Generic builds: the dynamic allocation, sized by the launcher from the plan's layout.  Fixed-geometry
+// builds: a STATIC array of the same kLdsFixed.total bytes, and no dynamic LDS at the launch (dynamic_lds in
+// tamp_compress_plan.hpp).  The dynamic allocation starts behind the kernel's static LDS, and the compiler only learns that this
+// is address 0 after instruction selection: every LDS address computed from it kept a v_add_u32 v, 0, v -- 115 of the 2,927 VALU
+// instructions of the extended fixed build.  A static array's address is a link-time constant that folds into the ds_ offsets
+// (profiles/static_lds_static.txt).  (Not a literal address 0: address-space inference is lost and every access becomes FLAT.)
+template <bool FX>
+__device__ __forceinline__ uint8_t* lds_base() {
+    if constexpr (FX) {
+        __shared__ __attribute__((aligned(16))) uint8_t smem_fx[kLdsFixed.total];
+        return smem_fx;
+    } else {
+        extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+        return smem;
+    }
+}
 // (the body is this one function for every build; the two kernels behind it -- tamp_compress_kernel for the generic builds,
 // tamp_compress_fixed::compress_kernel for the fixed ones -- only name its instantiations)
 // DICTS: a dictionary table (CompressArgs::dict_off) selects each stream's dictionary; the generic builds have a twin each
@@ -846,6 +865,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     static_assert(!BLOCKM || (LOOP && PACKED && !LAZY), "block mode: a persistent build of the default parse");
     // FX: constant geometry, no segment / piece machinery, constant format (made in these three steps: profiles/fixed_build_static.txt)
     constexpr bool FX = FIX != kFixNone;
+    // ... and two changes that stay with the fixed builds (the generic builds' code objects are what they were): the query sort's
+    // lengths are counted inside the scatter (kFoldSort, see there), and the 16-byte compare's tail is three ORs (kOrTail,
+    // prefix_len16).  Each was judged alone against the build without it: profiles/static_lds_ab.txt.
+    constexpr bool kFoldSort = FX, kOrTail = FX;
     static_assert(!FX || (PACKED && !LAZY && RUNS && WSCAN == (1u << kFixWbits) && HB == kHb1024 && LOOP && !BLOCKM),
                   "fixed geometry: the run-aware persistent build of the 2^10 window");
     // HB: bucket bits of the bigram index (2,048 buckets; 512 for the short-message build, whose blocks hold a few hundred
@@ -864,7 +887,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     constexpr uint32_t kPB = WSCAN == 1024 ? 12u : 16u, kLB = 32u - kRem - kPB;
     static_assert(!kEntV2 || kLB >= 9, "the third byte and at least one bit of the fourth");
     static_assert(!(RUNS && LAZY), "the run list serves the default parse only");
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t* const smem = lds_base<FX>();
     // LOOP builds: this workgroup's claim on the work counter (next stream, end of the claim, the stream in hand, start of
     // the claim after this one once fetched) lives in the first four words of LDS -- the slack in front of `ebuf`, which is only ever read under a mask -- at an address
     // that does not depend on the configuration
@@ -1259,6 +1282,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 // Two cursor snapshots bracket what a query must scan: the cursor of its bucket when the tile holding
                 // its oldest window byte starts (qstart) and after the tile holding its own position (top, in bidx).
                 if (tid < nvalid) qstart[tid] = cnt16[qstart[tid]];  // queries of tile 0: bucket start (the slot held the bucket's number)
+                // kFoldSort (the fixed-geometry builds): the scan length of a query, Lq = min(top - start, 63), is final where its `top` is stored below (its start was
+                // settled at least a tile earlier): it is counted into the query sort's bins there and kept in blen[q] -- free
+                // until the match phase stores the query's result -- for the sort's placing pass and the deferral test.
+                // (The bins: 64 words behind the control words that nothing else uses; last touched by the previous epoch's sort,
+                // barriers back.  A TAMP_PROF repeat of the index phase comes through here again.)
+                if (kFoldSort && tid < 64) bins[tid] = 0;
                 __syncthreads();
                 for (uint32_t t0 = 0; t0 < NE; t0 += nt) {
                     const uint32_t c = t0 + tid;
@@ -1281,21 +1310,34 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         }
                     }
                     __syncthreads();
-                    if (c < NE && c >= W) bidx[c - W] = cnt16[h];
+                    if constexpr (!kFoldSort) {
+                        if (c < NE && c >= W) bidx[c - W] = cnt16[h];
+                    } else if (c < NE && c >= W) {
+                        const uint32_t top = cnt16[h];
+                        bidx[c - W] = (uint16_t)top;
+                        if (c - W >= e_pending) {  // a query of this epoch (c < NE: below nvalid, in front of the sentinels)
+                            const uint32_t Lq = min(top - (uint32_t)qstart[c - W], 63u);
+                            atomicAdd(&bins[63 - Lq], 1u);
+                            blen[c - W] = (uint8_t)Lq;
+                        }
+                    }
                     const uint32_t q2 = t0 + nt + tid;  // queries whose oldest window byte lies in the next tile
                     if (q2 < nvalid) qstart[q2] = cnt16[qstart[q2]];
                     __syncthreads();
                 }
                 // Order the queries by scan length (counting sort, longest first) so that the 64 lanes of a wave
                 // loop about equally often: the greedy per-lane scan is otherwise paced by its longest bucket.
-                if (tid < 64) bins[tid] = 0;
+                // (kFoldSort: the lengths were counted by the scatter, and its last barrier is behind us)
+                if (!kFoldSort && tid < 64) bins[tid] = 0;
                 if (tid == 0) ctl[cCut] = nvalid;  // (everybody has read the cut position: several barriers back)
-                __syncthreads();
-                for (uint32_t q = e_pending + tid; q < nvalid; q += nt) {
-                    const uint32_t Lq = min((uint32_t)bidx[q] - (uint32_t)qstart[q], 63u);
-                    atomicAdd(&bins[63 - Lq], 1u);
+                if constexpr (!kFoldSort) {
+                    __syncthreads();
+                    for (uint32_t q = e_pending + tid; q < nvalid; q += nt) {
+                        const uint32_t Lq = min((uint32_t)bidx[q] - (uint32_t)qstart[q], 63u);
+                        atomicAdd(&bins[63 - Lq], 1u);
+                    }
+                    __syncthreads();
                 }
-                __syncthreads();
                 if (wave == 0) {
                     const uint32_t v = bins[lane];
                     const uint32_t incl = wave_scan_add(v);
@@ -1303,7 +1345,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 }
                 __syncthreads();
                 for (uint32_t q = e_pending + tid; q < nvalid; q += nt) {
-                    const uint32_t Lq = min((uint32_t)bidx[q] - (uint32_t)qstart[q], 63u);
+                    const uint32_t Lq = kFoldSort ? (uint32_t)blen[q] : min((uint32_t)bidx[q] - (uint32_t)qstart[q], 63u);
                     sorted[atomicAdd(&bins[63 - Lq], 1u)] = (uint16_t)q;
                 }
                 __syncthreads();
@@ -1359,7 +1401,8 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         in_run = r >= 7 || r >= R;  // the run reaches past the arbitration limit or to the end of the ring
                         // a short run, with a crowded bucket: the walk asks when -- if -- it gets here (kDeferred)
                         // (the marker travels in `key`: length field kDeferred, slow by the bytes' own rule below)
-                        if (!in_run && r >= 2 && (uint32_t)bidx[q] - (uint32_t)qstart[q] >= kDeferMin) in_run = true, key = kDeferred << 16;
+                        // (kFoldSort: blen[q] still holds the scan length the scatter left there, min(top - start, 63))
+                        if (!in_run && r >= 2 && (kFoldSort ? (uint32_t)blen[q] : (uint32_t)bidx[q] - (uint32_t)qstart[q]) >= kDeferMin) in_run = true, key = kDeferred << 16;
                     }
                     if (R >= minp && !in_run) {
                         const uint32_t cap_len = R < maxp ? R : maxp;
@@ -1389,10 +1432,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                     const uint32_t low = y & ((1u << kLB) - 1);
                                     uint32_t len = (low & 0xFFu) ? 2u : 3u;
                                     if (low == 0) {  // the next two bytes agree too (the entry's bits of the second)
-                                        len = prefix_len16(ebuf, q + d, P);
+                                        len = prefix_len16<kOrTail>(ebuf, q + d, P);
                                         if (TAMP_DBG(0x1000000u)) {  // (the compare once more -- same result -- for its exact count)
                                             asm volatile("" ::: "memory");
-                                            len = max(len, prefix_len16(ebuf, q + d, P));
+                                            len = max(len, prefix_len16<kOrTail>(ebuf, q + d, P));
                                         }
                                     }
                                     // (the wrap zone and the key: as in the generic loop below.  One test: the compare reaches the
@@ -1666,7 +1709,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                 if (cs >= (int32_t)lo && cs <= (int32_t)hi) {  // cs itself
                                     const uint32_t x2 = (rx >> 8) ^ pb2;
                                     uint32_t len = rq;
-                                    if (rq < 16 && !(x2 & 0xFFu)) len = (x2 >> 8) ? rq + 1 : prefix_len16(ebuf, (uint32_t)cs, P);
+                                    if (rq < 16 && !(x2 & 0xFFu)) len = (x2 >> 8) ? rq + 1 : prefix_len16<kOrTail>(ebuf, (uint32_t)cs, P);
                                     const uint32_t lim_i = W - (((uint32_t)cs + e_wp) & mask);
                                     key = max(key, (min(len, min(cap_len, lim_i)) << 16) | lim_i);
                                 }

@@ -76,6 +76,15 @@ struct CompressPlan {  // (in the order plan_compress decides them)
     bool dicts;                // a dictionary-table call: the build's DICTS twin (compress_kernel_of(build, dicts))
 };
 
+// Dynamic LDS of a launch of `p`'s kernel (and of the occupancy query about it).  The generic builds take the plan's whole layout
+// this way.  The fixed-geometry builds declare the same bytes as a static array (lds_base in tamp_compress_kernel.hpp) and take
+// none: handed over a second time they would count twice and halve the workgroups per CU.  What the plan REPORTS is one figure
+// for both -- p.lds.total bytes per workgroup, p.per_cu workgroups -- however the bytes reach the kernel.
+static inline uint32_t dynamic_lds(const CompressPlan& p) {
+    if (p.build == CompressBuild::kFixedExt || p.build == CompressBuild::kFixedV1) return 0;
+    return p.lds.total;
+}
+
 // Workgroups per CU: what the registers allow (8 for the run-aware builds, 6 lean, 5 lazy), and the estimate for a layout of `lds`
 // bytes: 160 KiB per CU, handed out in coarse granules (26,960 B per workgroup measured as five per CU, 25,424 B as six).
 static inline uint32_t register_cap(bool lazy, bool runlist) { return lazy ? kLazyPerCu : (runlist ? kWgPerCu : kLeanPerCu); }
