@@ -468,6 +468,32 @@ int tamp_batch_decompress_resets(uint8_t max_window_bits, const uint8_t *in, con
                                  uint32_t *out_len, int8_t *status, uint32_t *in_consumed /* may be NULL */,
                                  size_t n_streams, int mem, int device, void *stream);
 
+/* ---- a batch's streams packed densely on the device -----------------------------------------------
+ *
+ * The batch calls return their streams in slabs of worst-case size (tamp_batch_compress: 1 + ceil(9n/8) bytes for n input bytes), of
+ * which about half is data.  This call copies n_streams byte ranges of one device buffer back to back into another -- what a caller
+ * ships off the device, or keeps instead of the slabs.  No codec work; not in the reference.  The decoders read streams at any
+ * offset, so (dst, dst_off, src_len) is an input of tamp_batch_decompress / tamp_batch_decoded_size as it stands.
+ *
+ *   src, src_off, src_len   stream i is src[src_off[i] .. + src_len[i]); any order, gaps and overlaps are fine; only read
+ *   dst, dst_cap            room for the packed bytes; dst may have any alignment.  dst == NULL with dst_cap == 0: the size query,
+ *                           only dst_off is written
+ *   dst_off                 n_streams + 1 entries, ALWAYS written: dst_off[0] = 0, dst_off[i + 1] = dst_off[i] + src_len[i] rounded
+ *                           up to a multiple of `align`; dst_off[n_streams] is the packed size
+ *   align                   a power of two in 1 .. 4096; offsets are aligned relative to dst
+ * When dst_off[n_streams] <= dst_cap: dst[dst_off[i] .. + src_len[i]) holds stream i, the bytes from there to dst_off[i + 1] are
+ * zero, and no other byte is written -- none in front of dst, none at or behind dst + dst_off[n_streams].  Otherwise no byte of dst
+ * is written at all (the caller compares dst_off[n_streams] with dst_cap).
+ * The ranges of src that are read and dst[0 .. dst_cap) MUST NOT OVERLAP: there is no in-place packing.
+ * All pointers are device memory on `device`.  The call is asynchronous on `stream` (NULL: the default stream), waits for nothing
+ * and reads nothing back; its one allocation is 8 KiB of scratch kept per HIP stream (tamp_amd_trim releases it).
+ * Returns TAMP_OK when the kernels were launched; TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null src_off, src_len
+ * or dst_off, a null src with n_streams > 0, a null dst with dst_cap > 0, n_streams >= 2^32 or a bad align; TAMP_AMD_NO_DEVICE.
+ * n_streams == 0 stores dst_off[0] = 0 and nothing else.
+ */
+int tamp_batch_pack(const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len, uint8_t *dst, uint64_t dst_cap,
+                    uint64_t *dst_off /* n_streams + 1 entries */, size_t n_streams, uint32_t align, int device, void *stream);
+
 /* ---- resumable decoding: decoder OBJECTS that survive between calls ------------------------------
  *
  * What TampDecompressor is in the reference (decompressor.h:13-57): 16 bytes of state next to a window buffer,
@@ -641,7 +667,7 @@ float tamp_amd_last_kernel_ms(void);
 /* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
  * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
  * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
- * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets and the long-stream decoder's chunk tables, tail maps and
+ * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
  * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.

@@ -45,6 +45,7 @@ SYMBOLS = (
     "tamp_batch_compress_resets_index",
     "tamp_batch_decompress_resets",
     "tamp_amd_decompress_resets",
+    "tamp_batch_pack",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
     "tamp_batch_decompress_resume",
@@ -201,6 +202,8 @@ def load() -> C.CDLL:
     lib.tamp_batch_decompress_resets.restype = i32
     lib.tamp_amd_decompress_resets.argtypes = [u8, vp, u32, vp, u32, vp, vp, vp, i32, i32, vp]
     lib.tamp_amd_decompress_resets.restype = i32
+    lib.tamp_batch_pack.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, sz, u32, i32, vp]
+    lib.tamp_batch_pack.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]
     lib.tamp_amd_decoder_state_size.restype = sz
     lib.tamp_amd_decoder_state_init.argtypes = [vp, C.POINTER(TampAmdConf), u8]

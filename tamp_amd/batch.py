@@ -79,6 +79,10 @@ class BatchResult:
     def streams(self):
         return [self.stream(i) for i in range(len(self.out_len))]
 
+    def packed(self, align: int = 1, out=None, stream=None) -> "PackedBatch":
+        """The batch's streams back to back instead of in their slabs: ``pack_batch(self.out, self.out_off, self.out_len, ...)``."""
+        return pack_batch(self.out, self.out_off, self.out_len, align=align, out=out, stream=stream)
+
 
 def _conf(window, literal, extended, dictionary, dictionary_reset=False, lazy_matching=False, run_aware=None) -> TampAmdConf:
     # run_aware: None = TAMP_AMD_HINT_AUTO (by stream length), False = PLAIN, True = RUNS
@@ -740,6 +744,106 @@ def _decompress_batch_resets(data, in_off, in_len, index, out_cap, max_out, max_
     out_len, status, consumed = call(out, out_off, out_cap)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
     return BatchResult(out, out_off, out_len, status, consumed, ms)
+
+
+@dataclass
+class PackedBatch:
+    """A batch's streams back to back in one buffer (``pack_batch``, ``BatchResult.packed``): stream ``i`` is
+    ``data[off[i] : off[i] + len[i]]``, and ``off[-1]`` is the packed size.  numpy arrays (uint8, uint64, uint32) or CUDA tensors
+    (uint8, int64, int32), like the other tables.  With ``out=`` the caller compares ``off[-1]`` with ``out.numel()``: a batch that
+    did not fit left ``data`` untouched."""
+    data: object  # uint8
+    off: object   # n + 1 entries
+    len: object   # n entries
+    _keep: object = None  # device tensors the asynchronous launch still reads (the source, converted tables)
+
+    def stream(self, i: int) -> bytes:
+        o, n = int(self.off[i]), int(self.len[i])
+        chunk = self.data[o : o + n]
+        return bytes(chunk.cpu().numpy()) if _is_torch(chunk) else chunk.tobytes()
+
+    def streams(self):
+        """Every stream's bytes: ONE device-to-host copy of the packed bytes (and one of each table), sliced on the host."""
+        h = self.cpu()
+        flat = h.data.tobytes()
+        return [flat[o : o + n] for o, n in zip(h.off[:-1].tolist(), h.len.tolist())]
+
+    def triple(self):
+        """``(data, in_off, in_len)``: what ``decompress_batch`` / ``decoded_size_batch`` take positionally."""
+        return self.data, self.off[:-1], self.len
+
+    def cpu(self) -> "PackedBatch":
+        """The same batch in numpy arrays (itself when it is there already)."""
+        if not _is_torch(self.data):
+            return self
+        off = self.off.cpu().numpy().astype(np.uint64)
+        data = self.data[: min(int(off[-1]), int(self.data.numel()))].cpu().numpy()
+        return PackedBatch(data, off, self.len.cpu().numpy().view(np.uint32))
+
+
+def pack_batch(data, off, length, *, align: int = 1, out=None, device: int = 0, stream=None) -> PackedBatch:
+    """Streams ``data[off[i] : off[i] + length[i]]``, in any order and with any gaps, copied back to back (``tamp_batch_pack``).
+
+    Stream ``i`` lands at ``result.off[i]``, the running sum of the lengths rounded up to ``align`` (a power of two in 1..4096);
+    the bytes between its end and ``result.off[i + 1]`` are zero.  No codec work: the result's ``triple()`` decodes like the slabs.
+    With CUDA tensors (``off`` int64, ``length`` int32) the copy is a kernel on torch's current stream (or ``stream``): the sizes
+    are found first, ONE ``.item()`` reads the total, exactly that is allocated and then filled.  ``out=`` (a CUDA uint8 tensor)
+    takes the place of the allocation: one asynchronous call and no sync, and the caller compares ``result.off[-1]`` with
+    ``out.numel()`` -- a batch that does not fit leaves ``out`` untouched.  ``data`` and ``out`` must not overlap.
+    With numpy arrays the streams are packed on the host, by numpy.
+    """
+    if isinstance(align, bool) or not isinstance(align, numbers.Integral) or not 1 <= align <= 4096 or align & (align - 1):
+        raise ValueError(f"align must be a power of two in 1..4096, not {align!r}")
+    align = int(align)
+    if len(off) != len(length):
+        raise ValueError("one offset and one length per stream expected")
+    if not _is_torch(data):
+        if out is not None:
+            raise ValueError("out= needs CUDA tensors: host arrays are packed into a new array")
+        flat = _np_u8(data)
+        src_off = np.ascontiguousarray(off, dtype=np.uint64)
+        src_len = np.ascontiguousarray(length, dtype=np.uint32)
+        if len(src_len) and int((src_off + src_len.astype(np.uint64)).max()) > flat.size:
+            raise ValueError("a stream ends behind the data")
+        dst_off = np.zeros(len(src_len) + 1, dtype=np.uint64)
+        np.cumsum((src_len.astype(np.uint64) + np.uint64(align - 1)) & ~np.uint64(align - 1), out=dst_off[1:])
+        packed = np.zeros(int(dst_off[-1]), dtype=np.uint8)
+        for o, s, n in zip(dst_off[:-1].tolist(), src_off.tolist(), src_len.tolist()):
+            packed[o : o + n] = flat[s : s + n]
+        return PackedBatch(packed, dst_off, src_len)
+    if not data.is_cuda:
+        raise ValueError("data: a CUDA tensor or a host array expected")
+    if out is not None and not (_is_torch(out) and out.is_cuda and "uint8" in str(out.dtype) and out.dim() == 1 and out.is_contiguous()):
+        raise ValueError("out: a contiguous 1-D CUDA uint8 tensor expected")
+    import torch
+
+    if stream is not None:  # (tables and the packed buffer on the launch stream: see compress_batch)
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return pack_batch(data, off, length, align=align, out=out, device=device, stream=None)
+    lib = _lib.load()
+    dev = data.device
+    n = int(length.numel())
+    src = data.contiguous().reshape(-1)
+    if not src.numel():
+        src = torch.zeros(1, dtype=torch.uint8, device=dev)  # (a batch of empty streams: a byte to point at)
+    src_off_t = off.to(device=dev, dtype=torch.int64).contiguous()
+    src_len_t = length.to(device=dev, dtype=torch.int32).contiguous()
+    dst_off_t = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    # (no streams: the tables are empty tensors without an address, and the call refuses null tables)
+    tables = (_ptr(src_off_t), _ptr(src_len_t)) if n else (_ptr(dst_off_t), _ptr(dst_off_t))
+
+    def call(dst, cap):
+        _lib.check_launch(lib.tamp_batch_pack(_ptr(src), *tables, _ptr(dst) if cap else None, cap, _ptr(dst_off_t), n, align,
+                                              dev.index or 0, st))
+
+    if out is None:
+        call(None, 0)
+        out = torch.empty(int(dst_off_t[-1].item()), dtype=torch.uint8, device=dev)
+    call(out, int(out.numel()))
+    # the launch is asynchronous: the source and the converted tables must outlive it (they ride on the result)
+    return PackedBatch(out, dst_off_t, src_len_t, (src, src_off_t, src_len_t))
 
 
 class DecoderBatch:

@@ -32,6 +32,7 @@
 #include "tamp_decompress_resume_kernel.hpp"
 #include "tamp_compress_resume_kernel.hpp"
 #include "tamp_reset_segments_kernel.hpp"
+#include "tamp_pack_kernel.hpp"
 
 using namespace tamp_amd;
 
@@ -73,7 +74,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets and launch_decompress and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress and launch_pack and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -89,6 +90,7 @@ struct StreamScratch {
     DeviceBuf long_tails;  // ... the groups' tail maps (groups x window x 2 bytes)
     DeviceBuf long_lags;   // ... extended format: the list of tokens that can lag, the lag lists
     DeviceBuf resets;      // dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets), a batch's per-stream words in front (launch_compress_batch_resets)
+    DeviceBuf pack;        // tamp_batch_pack: the scan's per-workgroup sums (8 KiB, allocated once)
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -100,7 +102,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack}) n += b->release();
         return n;
     }
 };
@@ -2416,6 +2418,32 @@ int batch_compress_resume(const BatchTables& t, void* states, size_t state_strid
     });
 }
 
+// tamp_batch_pack behind its checks: the scan of the padded lengths (tamp_pack_kernel.hpp), then the copy unless the call only asks
+// for the offsets.  Nothing is read back and the stream is never waited for: the grids come from n and the CU count (the copy's is
+// cut down by what dst_cap can hold in tiles), and whatever depends on the lengths the kernels take from dst_off.
+int launch_pack(DeviceCtx* ctx, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint8_t* dst, uint64_t dst_cap,
+                uint64_t* dst_off, uint64_t n, uint32_t align, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    constexpr uint32_t kMaxRanges = kResetScanTile;  // (the offsets kernel sums the ranges in front of its own in one step)
+    HIP_OK(rec.pack.need(kMaxRanges * sizeof(uint64_t), false));
+    const uint64_t steps = (n + kResetScanTile - 1) / kResetScanTile;
+    const uint64_t ranges = std::max<uint64_t>(1, std::min<uint64_t>({steps, (uint64_t)ctx->cu_count * 4, kMaxRanges}));
+    const uint64_t per = std::max<uint64_t>(1, (steps + ranges - 1) / ranges) * kResetScanTile;
+    const uint32_t scan_grid = (uint32_t)std::max<uint64_t>(1, (n + per - 1) / per);
+    const PackScanArgs scan = {src_len, n, per, align, static_cast<uint64_t*>(rec.pack.p), dst_off};
+    if (scan_grid > 1) hipLaunchKernelGGL(tamp_pack_sums_kernel, dim3(scan_grid), dim3(kResetScanTile), 0, st, scan);
+    hipLaunchKernelGGL(tamp_pack_offsets_kernel, dim3(scan_grid), dim3(kResetScanTile), 0, st, scan);
+    if (dst && n) {
+        const uint64_t most_tiles = dst_cap / kPackTile + 2;  // (a destination at any address: a cut tile at either end)
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(most_tiles, (uint64_t)ctx->cu_count * 8);
+        hipLaunchKernelGGL(tamp_pack_copy_kernel, dim3(grid), dim3(kPackCopyThreads), 0, st, src, src_off, src_len, dst, dst_cap,
+                           (const uint64_t*)dst_off, n);
+    }
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
 // One stream at offset 0 of its buffers, in host memory: the one-row batch of the one-shot, object and piece calls.
 struct OneRow {
     uint64_t zero = 0;
@@ -2683,6 +2711,16 @@ int tamp_batch_decompress_resets(uint8_t max_window_bits, const uint8_t* in, con
     if (const int rc = batch_refused(t, out != nullptr, mem, device)) return rc;
     if (device == TAMP_AMD_ALL_DEVICES || (n_streams && (!reset_first || !out_cap))) return TAMP_AMD_BAD_ARGUMENT;
     return batch_decompress_resets(t, reset_first, reset_off, max_window_bits, mem, device, stream);
+}
+
+int tamp_batch_pack(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint8_t* dst, uint64_t dst_cap,
+                    uint64_t* dst_off, size_t n_streams, uint32_t align, int device, void* stream) {
+    // (refused before a device is looked for, in the manner of batch_refused)
+    if (!src_off || !src_len || !dst_off || (!src && n_streams) || (!dst && dst_cap)) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || !pack_align_ok(align)) return TAMP_AMD_BAD_ARGUMENT;
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    return launch_pack(ctx, src, src_off, src_len, dst, dst_cap, dst_off, n_streams, align, static_cast<hipStream_t>(stream));
 }
 
 int tamp_batch_decompress_dicts(const uint8_t* dictionaries, size_t dictionaries_len, const uint64_t* dict_off, uint8_t max_window_bits,
