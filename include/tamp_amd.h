@@ -190,10 +190,31 @@ int tamp_amd_decompress_plan(const TampAmdDecodeQuery *query, TampAmdDecodePlan 
  *                                               memory: the results come back in one transfer per chunk); with gaps
  *                                               between slabs or permuted offsets only the out_len[i] produced bytes
  *                                               of each slab are written, nothing else in the caller's buffer
- *   status[i]                                   TAMP_OK, TAMP_OUTPUT_FULL (slab too small; out_len[i] <= out_cap[i]
- *                                               bytes of valid prefix), TAMP_EXCESS_BITS (a literal does not fit
- *                                               conf->literal bits, compressor.c:629-631; out_len[i] = whole bytes
- *                                               emitted before it), or TAMP_INVALID_CONF
+ *   status[i]                                   TAMP_OK, TAMP_OUTPUT_FULL (slab too small), TAMP_EXCESS_BITS (a literal
+ *                                               does not fit conf->literal bits, compressor.c:629-631; out_len[i] =
+ *                                               whole bytes emitted before it), or TAMP_INVALID_CONF.
+ *                                               TOO LITTLE ROOM, the rule of every build of the kernel -- this call,
+ *                                               tamp_batch_compress_dicts, tamp_amd_compress and the segment / piece
+ *                                               calls that finish a segment: let T be the stream's length and S
+ *                                               its status with ample room (S = TAMP_EXCESS_BITS: T = the whole bytes
+ *                                               in front of the offending literal).  Then
+ *                                                 out_cap[i] <  T:  TAMP_OUTPUT_FULL, out_len[i] = out_cap[i], the
+ *                                                                   slab holds the first out_cap[i] of the T bytes
+ *                                                 out_cap[i] >= T:  S, out_len[i] = T, all T bytes
+ *                                               -- room comes first: a stream with an offending literal behind more
+ *                                               bytes than fit is TAMP_OUTPUT_FULL, and exact room (out_cap[i] == T)
+ *                                               is enough.  Nothing is written at or behind
+ *                                               out + out_off[i] + out_cap[i], in either memory kind.
+ *                                               The REFERENCE with the same room is never more lenient and never
+ *                                               ahead: whenever the rule says TAMP_OUTPUT_FULL so does it, its status
+ *                                               is the rule's or TAMP_OUTPUT_FULL, and its bytes are a prefix of the
+ *                                               bytes above.  But it gives up early: it asks for six free bytes before
+ *                                               an extended-match token and one before every parse step, so with
+ *                                               TAMP_OUTPUT_FULL it delivers up to 5 bytes fewer than min(out_cap[i],
+ *                                               T), and it still reports TAMP_OUTPUT_FULL for out_cap[i] = T .. T + 3
+ *                                               on some streams (also where S is TAMP_EXCESS_BITS).  From T + 4 on it
+ *                                               and the rule agree (measured, tests/test_oracle_vs_reference.py; the
+ *                                               bound is 8: its 32-bit bit buffer and one more token).
  *   dictionary                                  1<<window bytes shared by every stream when
  *                                               conf->use_custom_dictionary, else NULL (each stream starts from
  *                                               its own pristine copy)
@@ -617,7 +638,9 @@ tamp_res tamp_amd_decompress(const unsigned char *dictionary, size_t dictionary_
  *   resume                        0: fresh stream (window_state holds the custom dictionary if conf says so, else it is
  *                                 ignored on input); 1: continue from window_state / *window_pos
  *   flush_token                   write_token of tamp_compressor_flush; *token_written tells whether one was emitted
- * window_state / *window_pos are updated on TAMP_OK.  Host buffers, one stream, device `device`.
+ * window_state / *window_pos are updated on TAMP_OK.  TAMP_OUTPUT_FULL leaves them byte-identical to what they were: the
+ * output holds what fitted (the rule of tamp_batch_compress) and the same call with enough room gives the whole segment.
+ * Host buffers, one stream, device `device`.
  */
 tamp_res tamp_amd_compress_segment(const TampAmdConf *conf, int emit_header, int append_marker, int resume,
                                    int flush_token, unsigned char *window_state, uint16_t *window_pos,
@@ -635,7 +658,8 @@ tamp_res tamp_amd_compress_segment(const TampAmdConf *conf, int emit_header, int
  * built from: tamp_amd.Compressor.write() sends a piece whenever it has gathered enough and returns the bytes written,
  * as tamp/_c_compressor.pyx:74-118 does.  Not offered with conf->lazy_matching (the cached match of compressor.c:576-619
  * is not carried): TAMP_AMD_BAD_ARGUMENT.  Give a piece tamp_amd_compress_bound(input_size + 271, ...) bytes of room;
- * TAMP_OUTPUT_FULL leaves window_state / carry as they were.
+ * TAMP_OUTPUT_FULL leaves window_state / *window_pos / *carry byte-identical to what they were, and a piece with finish = 0
+ * then delivers nothing (*output_written_size = 0: offered again it emits all its bytes); exact room is enough.
  */
 typedef struct TampAmdCarry {
     uint8_t rle_count;   /* bytes consumed by a run that has not ended yet */

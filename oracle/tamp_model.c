@@ -312,6 +312,8 @@ int model_compress(const OracleConf *conf, const uint8_t *dict, const uint8_t *i
         if (m.bs.nacc) put_bits(&m.bs, 0, 8 - m.bs.nacc);
         whole = m.bs.nbytes;
         if (m.bs.overflow) res = ORACLE_OUTPUT_FULL;
+    } else if (whole > cap) {
+        res = ORACLE_OUTPUT_FULL; /* room comes before the offending literal, as in oracle_compress */
     }
     if (out_len) *out_len = whole < cap ? whole : cap;
     if (n_epochs) *n_epochs = m.n_epochs;

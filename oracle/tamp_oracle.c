@@ -340,6 +340,14 @@ static int enc_step(Enc *e, unsigned R) {
     return ORACLE_OK;
 }
 
+/* A literal that does not fit `literal` bits ends the stream after the whole bytes before it.  Room comes first,
+ * as for a stream that ends normally: with fewer than `whole` bytes of room the result is OUTPUT_FULL and the
+ * first `cap` bytes, whatever the literal was. */
+static int stop_at_literal(int res, size_t whole, size_t cap, size_t *out_len) {
+    if (out_len) *out_len = whole < cap ? whole : cap;
+    return whole > cap ? ORACLE_OUTPUT_FULL : res;
+}
+
 /* Core of every compress entry point: one SEGMENT = lead bits (header, append marker or nothing), the
  * reference's sink/poll loop over `in`, then tamp_compressor_flush(write_token).  `win` is the caller's window
  * (already seeded or carried over), *wp its write cursor. */
@@ -374,10 +382,7 @@ static int compress_core(const OracleConf *conf, uint8_t *win, uint32_t *wp, uin
         if (sunk - e.p == RING) {
             size_t whole_before = e.bs.nbytes;
             res = enc_step(&e, RING);
-            if (res != ORACLE_OK) {
-                if (out_len) *out_len = whole_before < cap ? whole_before : cap;
-                return res;
-            }
+            if (res != ORACLE_OK) return stop_at_literal(res, whole_before, cap, out_len);
         }
     }
     /* tamp_compressor_flush (compressor.c:728-810): drain with shrinking look-ahead. */
@@ -385,10 +390,7 @@ static int compress_core(const OracleConf *conf, uint8_t *win, uint32_t *wp, uin
         if (e.p < n) {
             size_t whole_before = e.bs.nbytes;
             res = enc_step(&e, (unsigned)(n - e.p));
-            if (res != ORACLE_OK) {
-                if (out_len) *out_len = whole_before < cap ? whole_before : cap;
-                return res;
-            }
+            if (res != ORACLE_OK) return stop_at_literal(res, whole_before, cap, out_len);
         } else if (e.extended && e.rle_count >= 1) {
             if (e.rle_count == 1) {
                 uint8_t c = last_window_byte(&e);

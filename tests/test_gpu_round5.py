@@ -235,7 +235,7 @@ def test_expensive_streams_first_changes_the_schedule_not_the_results(ta, checke
     assert res["0"][0] == res["1"][0] and (res["0"][1] == res["1"][1]).all() and (res["0"][2] == res["1"][2]).all()
     wantr = checker.compress_batch(blob, offs, lens, out_cap=caps, window=10, literal=8, extended=True)
     # (streams that ran out of room: the status is the reference's; how many bytes of the cut-off stream are delivered is
-    # pinned elsewhere -- tests/test_gpu_parity.py::test_restricted_output)
+    # pinned elsewhere -- tests/test_gpu_tight_output.py, this ordering included)
     assert (res["1"][1] == wantr.status).all()
     assert all(res["1"][0][i] == wantr.stream(i) for i in range(len(lens)) if wantr.status[i] == 0 and i % 5 == 0)
 

@@ -52,6 +52,52 @@ def test_differential_compress_decompress(oracle, ref):
             assert oracle.decompress(bad, dictionary=d, cap=n + 300) == ref.decompress(bad, dictionary=d, cap=n + 300)
 
 
+def test_compress_with_too_little_room_is_the_rule_and_the_reference_stays_inside_it(oracle, ref):
+    """Every capacity 0..T+8 of every stream of tests/tight_output_input.cpu_inputs at windows 8/10/12/15 x literals 5..8 x both
+    formats x lazy on/off.  The rule (include/tamp_amd.h; T and S from the REFERENCE's ample-room result): cap < T gives
+    (OUTPUT_FULL, first cap bytes), otherwise (S, all T bytes).
+      (a) the oracle is the rule, exactly;
+      (b) the rule says OUTPUT_FULL => the reference says OUTPUT_FULL;
+      (c) the reference's bytes are a prefix of the rule's;
+      (d) the reference's status is the rule's or OUTPUT_FULL.
+    Measured slack of the reference (INTEGRATION.md quotes the pair): `agree_from` = the smallest k with the reference equal to
+    the rule at every cap >= T + k, `shortfall` = the most bytes it delivers fewer than min(cap, T).  Both at most 8: the
+    reference holds back at most its 32-bit bit buffer and one further token of at most 32 bits.  Measured: 4 and 5."""
+    import tight_output_input as toi
+    from concurrent.futures import ThreadPoolExecutor
+
+    jobs = [(dict(window=w, literal=lit, extended=ext, lazy_matching=lazy), x)
+            for w in (8, 10, 12, 15) for lit in (5, 6, 7, 8) for ext in (True, False) for lazy in (False, True)
+            for x in toi.cpu_inputs(lit)]
+
+    def sweep(kw, x):
+        status, full = ref.compress(x, **kw)
+        assert status in (toi.OK, toi.EXCESS_BITS), (kw, len(x), status)
+        T, agree_from, shortfall, statuses = len(full), 0, 0, set()
+        for cap in range(T + 9):
+            want = toi.rule(status, full, cap)
+            got, r = oracle.compress(x, cap=cap, **kw), ref.compress(x, cap=cap, **kw)
+            tag = (kw, len(x), status, T, cap)
+            assert got == want, tag + ("oracle", got[0], len(got[1]))                           # (a)
+            assert want[0] != toi.OUTPUT_FULL or r[0] == toi.OUTPUT_FULL, tag + ("ref", r[0])   # (b)
+            assert want[1].startswith(r[1]), tag + ("ref bytes", len(r[1]))                     # (c)
+            assert r[0] in (want[0], toi.OUTPUT_FULL), tag + ("ref", r[0])                      # (d)
+            if r != want and cap >= T:
+                agree_from = cap - T + 1
+            shortfall = max(shortfall, min(cap, T) - len(r[1]))
+            statuses.add(want[0])
+        return agree_from, shortfall, statuses, status, T
+
+    with ThreadPoolExecutor(16) as ex:  # (both libraries' calls release the GIL)
+        results = list(ex.map(lambda j: sweep(*j), jobs))
+    agree_from, shortfall = max(r[0] for r in results), max(r[1] for r in results)
+    print(f"reference vs rule over {sum(r[4] + 9 for r in results)} cases: agrees from T + {agree_from}, "
+          f"delivers up to {shortfall} bytes fewer")
+    assert set().union(*(r[2] for r in results)) == {toi.OK, toi.OUTPUT_FULL, toi.EXCESS_BITS}
+    assert sum(r[3] == toi.EXCESS_BITS and r[4] > 1 for r in results) >= 100  # (streams that fail behind some output)
+    assert agree_from <= 8 and shortfall <= 8, (agree_from, shortfall)
+
+
 def test_struct_sizes(ref):
     # SURVEY.md section 8(b): sizeof(TampConf)=2, TampCompressor=48, TampDecompressor=24 on x86-64
     assert ref.sizes() == (2, 48, 24)
