@@ -265,6 +265,28 @@ int tamp_batch_compress(const TampAmdConf *conf, const uint8_t *dictionary, cons
  *                                 one actually present; OR in TAMP_AMD_WINDOW_BITS_EXACT to skip that and stay fully
  *                                 asynchronous (windows are then sized for max_window_bits itself)
  *   in_consumed                   optional (may be NULL): compressed bytes consumed per stream
+ *   out_cap[i], TOO LITTLE ROOM   the rule of every batch decoder (wave, LDS lanes, slab lanes, split and what it hands back),
+ *                                 and through it of tamp_batch_decoded_size with limit = out_cap: let (S, X, K) be the stream's
+ *                                 status, bytes and in_consumed with ample room and N the length of X.  Then
+ *                                   out_cap[i] <  N:  TAMP_OUTPUT_FULL, out_len[i] = out_cap[i], the slab holds the first
+ *                                                     out_cap[i] bytes of X (a match, an RLE run or an extended match that
+ *                                                     straddles the slab's end is delivered as far as it fits)
+ *                                   out_cap[i] >  N:  exactly (S, X, K)
+ *                                   out_cap[i] == N:  all of X, with status S or TAMP_OUTPUT_FULL: the reference asks whether
+ *                                                     the output is full BEFORE it looks at the next token, so a stream that
+ *                                                     ends in TAMP_OOB reports TAMP_OUTPUT_FULL here, and so does a clean
+ *                                                     stream with pad bits left in its last byte; one whose last token ends
+ *                                                     on a byte reports S
+ *                                 in_consumed[i] never decreases as out_cap[i] grows, and never exceeds K.  All of it is the
+ *                                 reference's own behaviour, capacity by capacity (tests/test_oracle_vs_reference.py).
+ *   out, WHAT IS WRITTEN          nothing in front of a slab and nothing at or behind out + out_off[i] + out_cap[i], in either
+ *                                 memory kind; only the out_len[i] produced bytes of a slab are written -- slab bytes behind
+ *                                 out_len[i], gaps between slabs and whatever surrounds them keep their contents.  ONE
+ *                                 EXCEPTION, as for tamp_batch_compress: a host-memory call whose slabs tile the output
+ *                                 buffer back to back brings each chunk's extent home in one transfer and leaves the slab
+ *                                 bytes behind out_len[i] unspecified; with gaps between slabs or permuted offsets only the
+ *                                 produced bytes arrive.  (tests/test_gpu_tight_decode.py: every capacity 0 .. N + 2 of a
+ *                                 stream at every slab alignment, the buffer compared whole, on every build of every decoder.)
  *   in_len[i]                     below 2^29 bytes (512 MiB) per stream: the decoders count bits in 32-bit registers;
  *                                 a longer stream gets status TAMP_AMD_BAD_ARGUMENT and produces nothing.  Feed longer
  *                                 streams in pieces through tamp_batch_decompress_resume, which looks at 2^28 bytes per

@@ -24,12 +24,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tight_output_input as toi  # noqa: E402
+from tight_check import LEAD, TAIL, check_call, env, pattern, slab_layout  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 OK, OUTPUT_FULL, EXCESS_BITS = toi.OK, toi.OUTPUT_FULL, toi.EXCESS_BITS
 MEM_HOST, MEM_DEVICE = 0, 1
-LEAD, TAIL = 3, 64  # guard bytes in front of the first slab and behind the last
 BUILD_GENERIC, BUILD_FIXED_EXT, BUILD_FIXED_V1 = 0, 1, 2
 CALL_DICT_TABLE = 128  # include/tamp_amd.h TAMP_AMD_CALL_DICT_TABLE
 HINT_AUTO, HINT_RUNS = 0, 2
@@ -42,24 +42,6 @@ def lib():
     lib = _lib.load()  # raises if the native library is missing: no silent fallback
     assert lib.tamp_amd_device_count() >= 1, "no HIP device visible"
     return lib
-
-
-@contextlib.contextmanager
-def env(name, value):
-    """(set and restored the way tests/test_gpu_fixed_build.py does it)"""
-    old = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ[name]
-        else:
-            os.environ[name] = old
-
-
-def pattern(n):
-    return ((np.arange(n, dtype=np.uint32) * 37 + 11) & 0xFF).astype(np.uint8)
 
 
 def make_conf(window, literal, extended, lazy=False, custom=False, hint=HINT_AUTO):
@@ -126,9 +108,7 @@ def batch_call(lib, mem, conf, streams, caps, max_in_len, gap=0, dictionary=None
     flat, in_off, in_len = pack_streams(streams)
     caps = np.asarray(caps, dtype=np.uint32)
     n = len(caps)
-    pitch = caps.astype(np.uint64) + np.uint64(gap)
-    out_off = (np.uint64(LEAD) + np.cumsum(pitch) - pitch).astype(np.uint64)
-    out = pattern(LEAD + int(pitch.sum()) + TAIL)
+    out_off, out = slab_layout(caps, gap)
     out_len, status = np.full(n, 0x7FFFFFFF, np.uint32), np.full(n, 99, np.int8)
     dict_buf = dict_off = None
     if table is not None:
@@ -162,29 +142,6 @@ def batch_call(lib, mem, conf, streams, caps, max_in_len, gap=0, dictionary=None
         torch.cuda.synchronize()
         out, out_len, status = held[3].cpu().numpy(), held[6].cpu().numpy().view(np.uint32), held[7].cpu().numpy()
     return status.astype(np.int64), out_len.astype(np.int64), out, out_off
-
-
-def check_call(got, caps, want_status, want_len, want_streams, tag, behind_len_unspecified=False):
-    """Per slab: status, length, bytes.  Then the whole buffer: the expected prefixes in a buffer of pattern() -- guard bytes, gaps
-    and the slab bytes behind out_len untouched (``behind_len_unspecified``: all but the latter -- a host-memory call whose
-    slabs tile the buffer brings them back in one transfer, and the header leaves those bytes open)."""
-    status, out_len, out, out_off = got
-    bad = np.flatnonzero((status != want_status) | (out_len != want_len))
-    assert bad.size == 0, (tag, "slab", int(bad[0]), "status", int(status[bad[0]]), int(want_status[bad[0]]),
-                           "out_len", int(out_len[bad[0]]), int(want_len[bad[0]]))
-    expected, care = pattern(out.size), np.ones(out.size, dtype=bool)
-    for j, s in enumerate(want_streams):
-        o = int(out_off[j])
-        assert out[o : o + len(s)].tobytes() == s, (tag, "slab", j, "bytes")
-        expected[o : o + len(s)] = np.frombuffer(s, dtype=np.uint8)
-        if behind_len_unspecified:
-            care[o + len(s) : o + int(caps[j])] = False
-    diff = np.flatnonzero((out != expected) & care)
-    if diff.size:
-        at = int(diff[0])
-        j = int(np.searchsorted(out_off, at, side="right")) - 1
-        raise AssertionError((tag, "byte", at, "written outside the produced bytes; slab", j, "starts at",
-                              int(out_off[max(j, 0)]), "cap", int(caps[max(j, 0)])))
 
 
 def run_sweep(lib, mem, conf, sw, max_in_len, tag, gap=0, dictionary=None):

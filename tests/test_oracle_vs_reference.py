@@ -98,6 +98,39 @@ def test_compress_with_too_little_room_is_the_rule_and_the_reference_stays_insid
     assert agree_from <= 8 and shortfall <= 8, (agree_from, shortfall)
 
 
+def test_decode_with_too_little_room_is_the_rule_at_every_capacity(oracle, ref):
+    """Every stream of tests/tight_decode_input.py at every capacity 0..N+8 (N = its output with ample room): the oracle and the
+    reference agree on (status, bytes, consumed), the result obeys tight_decode_input.rule -- cap < N: (OUTPUT_FULL, X[:cap]);
+    cap > N: the ample-room result; cap == N: all of X with the end status or OUTPUT_FULL -- and the consumed count never
+    decreases as the capacity grows.  tests/test_gpu_tight_decode.py expects the oracle's result of every decoder, capacity by
+    capacity; this test pins that expectation to the reference."""
+    import tight_decode_input as tdi
+    from concurrent.futures import ThreadPoolExecutor
+
+    def sweep(c):
+        full = ref.decompress(c.blob, dictionary=c.dictionary, cap=1 << 16)
+        N = len(full[1])
+        statuses, exact, last = set(), None, 0
+        for cap in range(N + 9):
+            got = oracle.decompress(c.blob, dictionary=c.dictionary, cap=cap)
+            r = ref.decompress(c.blob, dictionary=c.dictionary, cap=cap)
+            tag = (c.name, cap, N)
+            assert got == r, tag + (got[0], r[0], len(got[1]), len(r[1]), got[2], r[2])
+            assert tdi.obeys(full, cap, got), tag + (got[0], len(got[1]), got[2])
+            assert got[2] >= last, tag + ("consumed", got[2], last)
+            last = got[2]
+            statuses.add(got[0])
+            if cap == N:
+                exact = got[0] == full[0]
+        return N + 9, statuses, exact
+
+    with ThreadPoolExecutor(16) as ex:  # (both libraries' calls release the GIL)
+        results = list(ex.map(sweep, tdi.cases(oracle).values()))
+    print(f"decode, oracle vs reference vs rule: {sum(r[0] for r in results)} (stream, capacity) pairs over {len(results)} streams")
+    assert set().union(*(r[1] for r in results)) >= {tdi.OUTPUT_FULL, tdi.INPUT_EXHAUSTED, tdi.OOB}
+    assert {r[2] for r in results} == {True, False}  # exact room: the end status on some streams, OUTPUT_FULL on others
+
+
 def test_struct_sizes(ref):
     # SURVEY.md section 8(b): sizeof(TampConf)=2, TampCompressor=48, TampDecompressor=24 on x86-64
     assert ref.sizes() == (2, 48, 24)
