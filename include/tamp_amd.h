@@ -34,6 +34,7 @@ enum {
     /* library-level failures of this implementation (outside the reference's range) */
     TAMP_AMD_NO_DEVICE = -20, /* no HIP device / HIP runtime error: nothing was computed */
     TAMP_AMD_BAD_ARGUMENT = -21,
+    TAMP_AMD_BAD_INDEX = -22, /* tamp_batch_read_ranges: the reset index does not hold up on the segments a range touches */
 };
 typedef int8_t tamp_res;
 
@@ -511,6 +512,67 @@ int tamp_batch_decompress_resets(uint8_t max_window_bits, const uint8_t *in, con
                                  uint32_t *out_len, int8_t *status, uint32_t *in_consumed /* may be NULL */,
                                  size_t n_streams, int mem, int device, void *stream);
 
+/*
+ * Reading byte RANGES of such streams without decoding the rest: random access.  The compressor cuts every stream into segments of
+ * reset_interval decoded bytes that do not depend on each other and its index says where each one's tokens start, so decoded byte b
+ * of a stream lies in segment b / reset_interval.  Range q asks for the decoded bytes [range_begin[q], range_begin[q] + range_len[q])
+ * of stream i = range_stream[q]; they go to out + out_off[q], where the room is exactly range_len[q] bytes (there is no capacity
+ * table).  Only the segments a range touches are looked at: k0 = begin / N through k1 = min((begin + len - 1) / N, E) for a stream
+ * with E index entries (segments 0 .. E, the last one open; E = 0: the whole stream is one open segment), all in 64 bits.  Ranges
+ * may come in any order, repeat, overlap and share segments; each is answered on its own, and a segment two ranges touch is
+ * decoded twice (nothing is de-duplicated).
+ *   in, in_off, in_len      the streams, as for tamp_batch_decompress_resets
+ *   reset_first, reset_off  their reset index (tamp_batch_compress_resets_index); reset_off may be NULL only when reset_first[n_streams]
+ *                           is 0 (a host-memory call refuses the call otherwise, a device-memory call the ranges of streams with entries)
+ *   reset_interval          the N the streams were compressed with, > 0
+ *   range_stream, range_begin, range_len, out_off   n_ranges entries each, where `mem` says; only read
+ *   out_len[q], status[q]   per range, the first rule that applies:
+ *       range_stream[q] >= n_streams ........................................ TAMP_AMD_BAD_ARGUMENT, 0
+ *       range_len[q] == 0 .................................................... TAMP_OK, 0 (the stream is not looked at)
+ *       the header has no reset bit, a non-zero second byte, the custom bit
+ *       or a window above max_window_bits .................................... TAMP_INVALID_CONF, 0
+ *       the stream's rows of reset_first are no running sum from 0 ........... TAMP_AMD_BAD_INDEX, 0
+ *       k0 > E: the range starts behind the stream's last segment ............ TAMP_INPUT_EXHAUSTED, 0
+ *       an offset out of the window in a touched segment ..................... TAMP_OOB, 0
+ *       an entry a touched segment uses is out of range or order (inside the
+ *       header, beyond in_len[i], not behind the one in front of it), a touched
+ *       segment of 2^29 - 512 compressed bytes or more, a closed one that does not
+ *       end exactly at its entry behind FLUSH, FLUSH or does not decode to exactly
+ *       N bytes, the open one decoding to more than N .......................... TAMP_AMD_BAD_INDEX, 0
+ *       the range alone outgrows the scratch budget (below) .................. TAMP_AMD_BAD_ARGUMENT, 0
+ *       a segment did not decode to what the walk found (a defect of the library) TAMP_ERROR, 0
+ *       otherwise: TAMP_OK and range_len[q] when all bytes were delivered, TAMP_INPUT_EXHAUSTED and the bytes delivered when
+ *       the stream ended first
+ *   Exactly out_len[q] bytes are written at out + out_off[q] and nothing else of `out`; a failing range writes nothing and affects
+ *   no other range.  With the compressor's own index and interval the bytes are those of the whole stream decoded, sliced.
+ * WHAT THE INDEX IS TRUSTED FOR.  Unlike tamp_batch_decompress_resets, which takes the index as a hint and checks every segment
+ * from the header on, this call trusts it for POSITION: a segment's start is no longer token aligned by induction from the header.
+ * The checks above are made on the touched segments only; the two size conditions are what make k * N an address, and they also
+ * catch a call made with the wrong interval.  A forged index whose touched segments happen to parse can deliver other bytes, and a
+ * range that touches only the open segment has no closed segment to check N against.  Memory safety holds for any contents of
+ * every table (reset_off must have reset_first[n_streams] entries, as ever).
+ *   mem, device, stream   TAMP_AMD_ALL_DEVICES is not taken.  A device-memory call WAITS once, early, for one 16-byte record (how many
+ *                   units the ranges come to and what they ask of the scratch); everything behind that is asynchronous on `stream`
+ *                   (the decode step is tamp_batch_decompress's: without TAMP_AMD_WINDOW_BITS_EXACT in max_window_bits it waits for its
+ *                   header pre-pass).  A host-memory call is synchronous; it copies ONLY the touched segments' compressed bytes to the
+ *                   device -- sum of (segment + 2) over the touched segments, never the whole streams -- and writes exactly the
+ *                   delivered bytes and the two result tables.
+ * The touched segments are staged and decoded, each with its room trimmed to the last byte asked for, in scratch kept per HIP
+ * stream (tamp_amd_trim releases it): a quarter of the free device memory at most, 8 GiB at most, TAMP_AMD_RANGES_SCRATCH_MB (environment)
+ * instead of both.  Ranges are processed in slices, in range order, each of which fits that budget (a device-memory call that needs
+ * more than one slice reads three more tables back to cut them).  With TAMP_AMD_RESETS_DEBUG set the call writes one line to stderr:
+ * "[tamp_amd resets] read ranges: <r> ranges, <u> units, <s> slices, <b> bytes staged".
+ * Returns TAMP_OK (n_ranges == 0: at once, nothing is touched); TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null
+ * in_off, in_len, reset_first, range_stream, range_begin, range_len, out_off, out_len or status, a null `in` with n_streams > 0, a
+ * null `out` with n_ranges > 0, reset_interval == 0, a bad memory kind, TAMP_AMD_ALL_DEVICES, n_streams or n_ranges >= 2^32;
+ * TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                           const uint64_t *reset_first, const uint32_t *reset_off, uint32_t reset_interval,
+                           const uint32_t *range_stream, const uint64_t *range_begin, const uint32_t *range_len,
+                           uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int8_t *status,
+                           size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
+
 /* ---- a batch's streams packed densely on the device -----------------------------------------------
  *
  * The batch calls return their streams in slabs of worst-case size (tamp_batch_compress: 1 + ceil(9n/8) bytes for n input bytes), of
@@ -713,7 +775,7 @@ float tamp_amd_last_kernel_ms(void);
 /* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
  * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
  * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
- * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
+ * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
  * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("TAMP_AMD_LIB") or os.path.join(_HERE, "libtamp_amd.so
 OK, OUTPUT_FULL, INPUT_EXHAUSTED = 0, 1, 2
 ERROR, EXCESS_BITS, INVALID_CONF, OOB = -1, -2, -3, -4
 NO_DEVICE, BAD_ARGUMENT = -20, -21
+BAD_INDEX = -22  # include/tamp_amd.h TAMP_AMD_BAD_INDEX: a range's status (tamp_batch_read_ranges)
 OP_POLL, OP_COMPRESS, OP_FLUSH, OP_COMPRESS_AND_FLUSH = 1, 2, 3, 4  # include/tamp_amd.h TAMP_AMD_OP_*
 ALL_DEVICES = -1  # include/tamp_amd.h TAMP_AMD_ALL_DEVICES
 WINDOW_BITS_EXACT = 0x80  # include/tamp_amd.h: TAMP_AMD_WINDOW_BITS_EXACT
@@ -45,6 +46,7 @@ SYMBOLS = (
     "tamp_batch_compress_resets_index",
     "tamp_batch_decompress_resets",
     "tamp_amd_decompress_resets",
+    "tamp_batch_read_ranges",
     "tamp_batch_pack",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
@@ -202,6 +204,8 @@ def load() -> C.CDLL:
     lib.tamp_batch_decompress_resets.restype = i32
     lib.tamp_amd_decompress_resets.argtypes = [u8, vp, u32, vp, u32, vp, vp, vp, i32, i32, vp]
     lib.tamp_amd_decompress_resets.restype = i32
+    lib.tamp_batch_read_ranges.argtypes = [u8, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, vp]
+    lib.tamp_batch_read_ranges.restype = i32
     lib.tamp_batch_pack.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, sz, u32, i32, vp]
     lib.tamp_batch_pack.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]
@@ -251,4 +255,6 @@ def check_launch(rc: int) -> None:
                                  f"[{detail}]; the codec only runs on the GPU")
     if rc == BAD_ARGUMENT:
         raise ValueError("tamp_amd: bad argument (invalid pointers / sizes / configuration)")
+    if rc == BAD_INDEX:
+        raise ValueError("tamp_amd: the reset index does not hold up")
     raise RuntimeError(f"tamp_amd: unexpected return code {rc}")

@@ -54,9 +54,11 @@ class ResetIndex:
     """Where the dictionary resets of a batch lie (``compress_batch(..., reset_index=True)`` makes one, ``decompress_batch(...,
     reset_index=...)`` takes one as a hint): ``first`` has one entry per stream and one more, stream ``i``'s entries are
     ``off[first[i]:first[i + 1]]``, each the offset, in the stream's compressed bytes, of the byte behind a reset.  numpy arrays
-    (uint64, uint32) or CUDA tensors (int64, int32), like the other tables."""
+    (uint64, uint32) or CUDA tensors (int64, int32), like the other tables.  ``interval``: the decoded bytes per segment the
+    streams were compressed with, which ``read_ranges`` needs (``compress_batch`` fills it)."""
     first: object
     off: object
+    interval: Optional[int] = None
 
 
 @dataclass
@@ -355,7 +357,8 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
             # (the entries: the `closed` of compress_resets_bound, summed on the device; one sync for the total)
             closed = (torch.clamp(in_len_t.to(torch.int64) & 0xFFFFFFFF, min=1) - 1) // reset_interval
             entries = int(closed.sum().item()) if n else 0
-            index = ResetIndex(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(max(entries, 1), dtype=torch.int32, device=dev)[:entries])
+            index = ResetIndex(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(max(entries, 1), dtype=torch.int32, device=dev)[:entries],
+                               int(reset_interval))
             rc = lib.tamp_batch_compress_resets_index(C.byref(conf), _ptr(data), _ptr(in_off_t), _ptr(in_len_t), reset_interval, _ptr(out),
                                                       _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t), _ptr(status_t), n, int(max_in_len),
                                                       _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st), _ptr(index.first),
@@ -405,7 +408,7 @@ def compress_batch(data, in_off=None, in_len=None, *, window: int = 10, literal:
                                            _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None)
     elif reset_index:
         entries = int(((np.maximum(in_len.astype(np.uint64), np.uint64(1)) - np.uint64(1)) // np.uint64(reset_interval)).sum())
-        index = ResetIndex(np.zeros(n + 1, dtype=np.uint64), np.zeros(entries, dtype=np.uint32))
+        index = ResetIndex(np.zeros(n + 1, dtype=np.uint64), np.zeros(entries, dtype=np.uint32), int(reset_interval))
         rc = lib.tamp_batch_compress_resets_index(C.byref(conf), _ptr(flat if flat.size else np.zeros(1, np.uint8)), _ptr(in_off),
                                                   _ptr(in_len), reset_interval, _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),
                                                   _ptr(status), n, int(max_in_len), _lib.MEM_HOST, device,
@@ -744,6 +747,117 @@ def _decompress_batch_resets(data, in_off, in_len, index, out_cap, max_out, max_
     out_len, status, consumed = call(out, out_off, out_cap)
     ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
     return BatchResult(out, out_off, out_len, status, consumed, ms)
+
+
+@dataclass
+class RangeResult:
+    out: object          # uint8 buffer (numpy array or torch tensor): the ranges back to back
+    out_off: object      # uint64/int64 [n_ranges] -- the running sum of ``length``
+    out_len: object      # uint32/int32 [n_ranges] -- bytes delivered
+    status: object       # int8 [n_ranges] -- per range (include/tamp_amd.h, tamp_batch_read_ranges)
+    kernel_ms: float = -1.0
+    _keep: object = None  # device tensors the asynchronous launch still reads
+
+    def range(self, q: int) -> bytes:
+        o, n = int(self.out_off[q]), int(self.out_len[q]) & 0xFFFFFFFF
+        chunk = self.out[o : o + n]
+        return bytes(chunk.cpu().numpy()) if _is_torch(chunk) else chunk.tobytes()
+
+    def ranges(self):
+        return [self.range(q) for q in range(len(self.out_len))]
+
+
+def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, begin, length, reset_interval=None,
+                max_window_bits: int = 15, device: int = 0, stream=None, timing: bool = False) -> RangeResult:
+    """Byte ranges of reset-segmented streams, without decoding the rest (``tamp_batch_read_ranges``; not in the
+    reference).  ``data`` as for ``decompress_batch``: the streams of ``compress_batch(..., reset_interval=N, reset_index=True)``,
+    ``reset_index`` their index.  Range ``q`` is ``decompress(stream stream_index[q])[begin[q] : begin[q] + length[q]]``; only the
+    segments it touches are staged and decoded.  The three range tables are sequences, numpy arrays or CUDA tensors.  The output is
+    the ranges back to back; ``status[q]`` is 0 when all of range ``q`` was delivered, 2 when the stream ended first (``out_len[q]``
+    bytes are there), negative otherwise -- -22 when the index does not hold up on the touched segments.  The index is trusted
+    for position: pass the compressor's own.  ``reset_interval`` defaults to ``reset_index.interval``."""
+    if not isinstance(reset_index, ResetIndex):  # (all decided before the library is looked for)
+        raise ValueError("reset_index: a ResetIndex expected")
+    n_streams = len(data) if in_off is None and not _is_torch(data) else len(in_len)
+    if len(reset_index.first) != n_streams + 1:
+        raise ValueError("reset_index.first: one entry per stream and one more expected")
+    if not len(stream_index) == len(begin) == len(length):
+        raise ValueError("stream_index, begin and length: one entry per range each")
+    interval = reset_interval if reset_interval is not None else reset_index.interval
+    if interval is None:
+        raise ValueError("reset_interval: not given and not in the index")
+    if not _is_int(interval) or not 1 <= int(interval) <= 0xFFFFFFFF:
+        raise ValueError("reset_interval: a positive integer that fits 32 bits expected")
+    interval = int(interval)
+    n_ranges = len(stream_index)
+    on_device = _is_torch(data)
+    tables = (stream_index, begin, length)
+    if not (on_device and all(_is_torch(t) for t in tables)):  # (CUDA tables of a CUDA call are checked by nobody: no sync)
+        def host_table(t, what, most, dt):  # -> numpy array of dt; a sequence goes through Python integers (2^64 - 1 is one)
+            a = t.cpu().numpy() if _is_torch(t) else (t if isinstance(t, np.ndarray) else np.array([int(x) for x in t] or [0], dtype=object)[: len(t)])
+            if a.dtype.kind not in "iuO":
+                raise ValueError(what + ": integers expected")
+            if len(a) and int(a.min()) < 0 and what == "begin":
+                raise ValueError(what + ": negative")
+            if len(a) and (int(a.min()) < 0 or int(a.max()) > most):
+                raise ValueError(what + ": does not fit %d bits" % most.bit_length())
+            return np.ascontiguousarray(a.astype(dt))
+
+        h_stream = host_table(stream_index, "stream_index", 0xFFFFFFFF, np.uint32)
+        h_begin = host_table(begin, "begin", (1 << 64) - 1, np.uint64)
+        h_length = host_table(length, "length", 0xFFFFFFFF, np.uint32)
+        if on_device:
+            stream_index, begin, length = h_stream, h_begin, h_length
+    if stream is not None and on_device:
+        import torch  # (tables and output on the launch stream: see compress_batch)
+
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return read_ranges(data, in_off, in_len, reset_index=reset_index, stream_index=stream_index, begin=begin, length=length,
+                               reset_interval=interval, max_window_bits=max_window_bits, device=device, stream=None, timing=timing)
+    lib = _lib.load()
+    lib.tamp_amd_set_timing(1 if timing else 0)
+    if on_device:
+        import torch
+
+        dev = data.device
+        as_t = lambda x, dt: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.uint64).view(np.int64))).to(device=dev, dtype=dt)  # noqa: E731
+        first_t, off_t = as_t(reset_index.first, torch.int64), as_t(reset_index.off, torch.int32)
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        stream_t, begin_t, length_t = as_t(stream_index, torch.int32), as_t(begin, torch.int64), as_t(length, torch.int32)
+        len64 = length_t.to(torch.int64) & 0xFFFFFFFF  # (lengths are uint32 values, whatever the storage)
+        out_off_t = torch.cumsum(len64, 0) - len64
+        total = int(len64.sum().item()) if n_ranges else 0
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        out_len_t = torch.empty(n_ranges, dtype=torch.int32, device=dev)
+        status_t = torch.empty(n_ranges, dtype=torch.int8, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check_launch(lib.tamp_batch_read_ranges(
+            max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(first_t), _ptr(off_t) if off_t.numel() else None, interval,
+            _ptr(stream_t), _ptr(begin_t), _ptr(length_t), _ptr(out), _ptr(out_off_t), _ptr(out_len_t), _ptr(status_t), n_streams,
+            n_ranges, _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st)))
+        ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+        return RangeResult(out, out_off_t, out_len_t, status_t, ms,
+                           (data, in_off_t, in_len_t, first_t, off_t, stream_t, begin_t, length_t))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    to_np = lambda x, dt: np.ascontiguousarray((x.cpu().numpy() if _is_torch(x) else np.asarray(x)).astype(dt))  # noqa: E731
+    first, off = to_np(reset_index.first, np.uint64), to_np(reset_index.off, np.uint32)
+    range_stream, range_begin, range_len = h_stream, h_begin, h_length
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    out_off, total = _slab_offsets(range_len)
+    out = np.zeros(total + 1, dtype=np.uint8)
+    out_len, status = np.zeros(n_ranges, dtype=np.uint32), np.zeros(n_ranges, dtype=np.int8)
+    _lib.check_launch(lib.tamp_batch_read_ranges(
+        max_window_bits, _ptr(flat), _ptr(in_off), _ptr(in_len), _ptr(first), _ptr(off) if off.size else None, interval, _ptr(range_stream),
+        _ptr(range_begin), _ptr(range_len), _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(status), n_streams, n_ranges, _lib.MEM_HOST,
+        device, C.c_void_p(stream) if stream else None))
+    ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+    return RangeResult(out, out_off, out_len, status, ms)
 
 
 @dataclass

@@ -32,6 +32,7 @@
 #include "tamp_decompress_resume_kernel.hpp"
 #include "tamp_compress_resume_kernel.hpp"
 #include "tamp_reset_segments_kernel.hpp"
+#include "tamp_read_ranges_kernel.hpp"
 #include "tamp_pack_kernel.hpp"
 
 using namespace tamp_amd;
@@ -74,7 +75,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress and launch_pack and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges and launch_pack and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -91,6 +92,7 @@ struct StreamScratch {
     DeviceBuf long_lags;   // ... extended format: the list of tokens that can lag, the lag lists
     DeviceBuf resets;      // dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets), a batch's per-stream words in front (launch_compress_batch_resets)
     DeviceBuf pack;        // tamp_batch_pack: the scan's per-workgroup sums (8 KiB, allocated once)
+    DeviceBuf ranges;      // tamp_batch_read_ranges: the per-range scans and verdicts (the units, stage and scratch of a slice: `resets`)
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -102,7 +104,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges}) n += b->release();
         return n;
     }
 };
@@ -2354,6 +2356,234 @@ int batch_decompress_resets(const BatchTables& t, const uint64_t* first, const u
     return TAMP_OK;
 }
 
+// Reading byte ranges of reset-segmented streams (tamp_batch_read_ranges; kernels and steps: tamp_read_ranges_kernel.hpp, the
+// arithmetic: tamp_reset_segments.hpp).  The ranges are processed in SLICES, in range order, each of which fits the budget with its
+// units' rows, stage and scratch (one region of the stream's `resets` buffer); the per-range tables of the whole call lie in `ranges`.
+size_t read_ranges_budget(const StreamScratch& rec) {
+    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, std::max((free_b + rec.resets.bytes) / 4, (size_t)1 << 20));
+    else (void)hipGetLastError();
+    if (const char* e = getenv("TAMP_AMD_RANGES_SCRATCH_MB")) { const long v = atol(e); if (v >= 1) budget = (size_t)v << 20; }
+    return budget;
+}
+constexpr size_t kReadRangesHead = 256;  // the record, in front of the per-range tables
+size_t read_ranges_bytes(uint64_t nr) { return kReadRangesHead + 24 * (nr + 1) + 2 * nr + 64; }
+ReadRanges read_ranges_at(uint8_t* base, uint64_t nr) {
+    ReadRanges r;
+    r.unit_first = reinterpret_cast<uint64_t*>(base + kReadRangesHead), r.scratch_first = r.unit_first + nr + 1;
+    r.stage_first = r.scratch_first + nr + 1;
+    r.verdict = reinterpret_cast<int8_t*>(r.stage_first + nr + 1), r.failed = reinterpret_cast<uint8_t*>(r.verdict + nr);
+    return r;
+}
+// The slices of a call from the scans of its ranges' costs and units (host copies, nr + 1 entries each): as many ranges as fit the
+// budget, one at least (a range that alone outgrows the budget has no units and costs nothing: it was refused when it was counted).
+struct ReadSliceSpan { uint64_t q0, q1; };
+std::vector<ReadSliceSpan> read_ranges_slices(const uint64_t* cost_first, const uint64_t* unit_first, uint64_t nr, uint64_t budget) {
+    std::vector<ReadSliceSpan> slices;
+    for (uint64_t q0 = 0; q0 < nr;) {
+        uint64_t q1 = q0 + 1;
+        while (q1 < nr && cost_first[q1 + 1] - cost_first[q0] <= budget && unit_first[q1 + 1] - unit_first[q0] < 0xFFFFFFFFull) q1++;
+        slices.push_back({q0, q1});
+        q0 = q1;
+    }
+    return slices;
+}
+// The steps of a slice behind its staged units: the walk, the decode of the unit rows by the existing launch path, the gather.
+// `c`: what the gather reads of the caller's tables (interval, range_begin, range_len).
+int launch_read_tail(DeviceCtx* ctx, StreamScratch& rec, const ReadCaller& c, const ReadRanges& r, const ReadSlice& s, uint8_t max_wbits,
+                     uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int8_t* status, hipStream_t st) {
+    if (s.U) {
+        const ReadWalkArgs walk = {s, r.failed, c.interval};
+        hipLaunchKernelGGL(tamp_read_walk_kernel, dim3((uint32_t)((s.U + 63) / 64)), dim3(64), 0, st, walk);
+        HIP_OK(hipGetLastError());
+        const ReadUnits u = read_units_at(s.region, s.U);
+        BatchTables ut;
+        ut.in = s.region, ut.in_off = u.in_off, ut.in_len = u.in_len, ut.out = s.region, ut.out_off = u.out_off, ut.out_cap = u.out_cap;
+        ut.out_len = u.out_len, ut.status = u.status, ut.n = s.U;
+        if (const int rc = launch_decompress_locked(ctx, rec, ut, max_wbits, st)) return rc;
+    }
+    const ReadGatherArgs gather = {c, r, s, out, out_off, out_len, status};
+    hipLaunchKernelGGL(tamp_read_gather_kernel, dim3((uint32_t)std::min<uint64_t>(s.q1 - s.q0, (uint64_t)ctx->cu_count * 8)), dim3(256), 0, st, gather);
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+void read_ranges_debug(uint64_t ranges, uint64_t units, size_t slices, uint64_t staged) {
+    fprintf(stderr, "[tamp_amd resets] read ranges: %llu ranges, %llu units, %zu slices, %llu bytes staged\n", (unsigned long long)ranges,
+            (unsigned long long)units, slices, (unsigned long long)staged);
+}
+
+// Device memory: everything is counted, cut and staged on the device; the call waits once, for the 16-byte record that sizes the
+// region -- and, only when the call does not fit ONE slice, for the three scans that say where to cut it.
+int launch_read_ranges(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                       int8_t* status, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    const uint64_t nr = c.n_ranges, budget = read_ranges_budget(rec);
+    HIP_OK(rec.ranges.need(read_ranges_bytes(nr)));
+    uint8_t* const tabs = static_cast<uint8_t*>(rec.ranges.p);
+    const ReadRanges r = read_ranges_at(tabs, nr);
+    const CallTiming call_timing(st);
+    const ReadCountArgs count = {c, budget, r, reinterpret_cast<ReadRecord*>(tabs)};
+    hipLaunchKernelGGL(tamp_read_count_kernel, dim3(1), dim3(kResetScanTile), 0, st, count);
+    HIP_OK(hipGetLastError());
+    ReadRecord have = {0, 0};
+    HIP_OK(hipMemcpyAsync(&have, tabs, sizeof have, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    std::vector<ReadSliceSpan> slices = {{0, nr}};
+    std::vector<uint64_t> cost_first, unit_first;
+    if (have.cost > budget || have.units >= 0xFFFFFFFFull) {
+        std::vector<uint64_t> scans(3 * (nr + 1));  // (unit_first, scratch_first, stage_first lie one behind the other)
+        HIP_OK(hipMemcpyAsync(scans.data(), r.unit_first, scans.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        cost_first.resize(nr + 1), unit_first.assign(scans.begin(), scans.begin() + nr + 1);
+        for (uint64_t q = 0; q <= nr; q++) cost_first[q] = scans[nr + 1 + q] + scans[2 * (nr + 1) + q] + kReadUnitRow * scans[q];
+        slices = read_ranges_slices(cost_first.data(), unit_first.data(), nr, budget);
+    }
+    // one region for every slice: the largest.  (A slice's cost counts kReadUnitRow bytes of rows per unit; what it stages and
+    // decodes is the rest, and the paddings between the three parts come on top.)
+    auto units_of = [&](const ReadSliceSpan& s) { return unit_first.empty() ? have.units : unit_first[s.q1] - unit_first[s.q0]; };
+    auto payload_of = [&](const ReadSliceSpan& s) { return (cost_first.empty() ? have.cost : cost_first[s.q1] - cost_first[s.q0]) - kReadUnitRow * units_of(s); };
+    size_t region_bytes = 256;
+    for (const ReadSliceSpan& s : slices) region_bytes = std::max<size_t>(region_bytes, read_region_bytes(units_of(s), payload_of(s), 0) + 512);
+    HIP_OK(rec.resets.need(region_bytes));
+    for (const ReadSliceSpan& span : slices) {
+        const ReadSlice s = {span.q0, span.q1, units_of(span), static_cast<uint8_t*>(rec.resets.p)};
+        if (s.U) {
+            const ReadUnitsArgs units = {c, budget, r, s};
+            hipLaunchKernelGGL(tamp_read_units_kernel, dim3((uint32_t)((s.U + 255) / 256)), dim3(256), 0, st, units);
+            const ReadStageArgs stage = {c, s};
+            hipLaunchKernelGGL(tamp_read_stage_kernel, dim3((uint32_t)std::min<uint64_t>(s.U, (uint64_t)ctx->cu_count * 8)), dim3(256), 0, st, stage);
+            HIP_OK(hipGetLastError());
+        }
+        if (const int rc = launch_read_tail(ctx, rec, c, r, s, max_wbits, out, out_off, out_len, status, st)) return rc;
+    }
+    if (dbg) {  // (the line waits for the count's last entry; a call without the variable does not)
+        uint64_t staged = 0;
+        HIP_OK(hipMemcpyAsync(&staged, r.stage_first + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        read_ranges_debug(nr, have.units, slices.size(), staged);
+    }
+    return TAMP_OK;
+}
+
+// Host memory, on the host pipeline's first stream (one host-memory call per device at a time): the host counts and cuts with the
+// functions the kernels use and copies ONLY the touched segments, a header in front of each, into pinned staging; per slice the
+// units' rows and that stage go up, the result tables and the packed ranges come back, and the delivered bytes are placed.
+int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                     int8_t* status) {
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> pipe_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    const uint64_t nr = c.n_ranges, budget = read_ranges_budget(rec);
+    // the count, on the host
+    std::vector<ReadPlan> plan(nr);
+    std::vector<uint64_t> unit_first(nr + 1), cost_first(nr + 1), packed_off(nr);
+    std::vector<int8_t> verdict(nr);
+    std::vector<uint8_t> failed(nr, 0);
+    uint64_t units_all = 0, cost_all = 0, staged_all = 0;
+    for (uint64_t q = 0; q < nr; q++) {
+        plan[q] = read_range_plan(c.in, c.in_off, c.in_len, c.first, c.off, c.n, c.interval, c.max_wbits, budget, c.range_stream[q],
+                                  c.range_begin[q], c.range_len[q]);
+        unit_first[q] = units_all, cost_first[q] = cost_all, verdict[q] = (int8_t)plan[q].verdict;
+        units_all += plan[q].units, cost_all += plan[q].units ? read_plan_cost(plan[q]) : 0;
+    }
+    unit_first[nr] = units_all, cost_first[nr] = cost_all;
+    const std::vector<ReadSliceSpan> slices = read_ranges_slices(cost_first.data(), unit_first.data(), nr, budget);
+    // the per-range tables of the device steps: unit_first and the verdicts in `ranges` (the walk's `failed` follows per slice), what
+    // the gather reads of the caller's tables and the results in the pipeline's meta buffer
+    HIP_OK(rec.ranges.need(read_ranges_bytes(nr)));
+    const ReadRanges r = read_ranges_at(static_cast<uint8_t*>(rec.ranges.p), nr);
+    HIP_OK(P.meta[0].need(nr * (8 + 8 + 4 + 4 + 1) + 64));
+    uint64_t* const d_begin = static_cast<uint64_t*>(P.meta[0].p);
+    uint64_t* const d_out_off = d_begin + nr;
+    uint32_t* const d_len = reinterpret_cast<uint32_t*>(d_out_off + nr);
+    uint32_t* const d_out_len = d_len + nr;
+    int8_t* const d_status = reinterpret_cast<int8_t*>(d_out_len + nr);
+    ReadCaller d = {};
+    d.interval = c.interval, d.max_wbits = c.max_wbits, d.range_begin = d_begin, d.range_len = d_len, d.n_ranges = nr;
+    const CallTiming call_timing(st);
+    HIP_OK(hipMemcpyAsync(r.unit_first, unit_first.data(), (nr + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(r.verdict, verdict.data(), nr, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_begin, c.range_begin, nr * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_len, c.range_len, nr * 4, hipMemcpyHostToDevice, st));
+    for (const ReadSliceSpan& span : slices) {
+        const uint64_t U = unit_first[span.q1] - unit_first[span.q0];
+        uint64_t staged = 0, scratch = 0, packed = 0;
+        for (uint64_t q = span.q0; q < span.q1; q++) {
+            // (a range delivers no more than its units are given room for)
+            packed_off[q] = packed, packed += std::min<uint64_t>(c.range_len[q], plan[q].scratch);
+            staged += plan[q].staged, scratch += plan[q].scratch;
+        }
+        HIP_OK(rec.resets.need(read_region_bytes(U, staged, scratch)));
+        const ReadSlice s = {span.q0, span.q1, U, static_cast<uint8_t*>(rec.resets.p)};
+        const uint64_t rows_bytes = read_units_upload_bytes(U);
+        if (U) {
+            HIP_OK(P.stage[0].need(rows_bytes + staged));
+            uint8_t* const h = static_cast<uint8_t*>(P.stage[0].p);
+            uint8_t* const h_stage = h + rows_bytes;
+            const ReadUnits u = read_units_at(h, U);  // (the uploaded rows alone)
+            uint64_t x = 0, stage_at = 0, scratch_at = 0;
+            for (uint64_t q = span.q0; q < span.q1; q++) {
+                const uint64_t i = c.range_stream[q];
+                for (uint64_t j = 0; j < plan[q].units; j++, x++) {
+                    const ReadUnit w = read_range_unit(c.first, c.off, c.in_len, c.interval, i, plan[q], j);
+                    u.in_off[x] = read_stage_at(U) + stage_at + w.place, u.out_off[x] = read_scratch_at(U, staged) + scratch_at + w.room;
+                    u.in_len[x] = w.in_len, u.need[x] = w.need, u.owner[x] = (uint32_t)(q - span.q0);
+                    u.flags[x] = (uint8_t)((w.cut.closed ? kReadUnitClosed : 0) | (plan[q].k0 + j ? kReadUnitBehindReset : 0));
+                    u.verdict[x] = w.cut.ok ? kReadWalkOk : kReadWalkBad;
+                    if (!w.cut.ok) { failed[q] = 1; continue; }
+                    uint8_t* const dst = h_stage + stage_at + w.place;
+                    dst[0] = c.in[c.in_off[i]], dst[1] = 0;  // (the stream's own two header bytes: the second one is zero)
+                    memcpy(dst + kResetHeaderBytes, c.in + c.in_off[i] + w.cut.start, w.cut.end - w.cut.start);
+                    staged_all += w.in_len;
+                }
+                stage_at += plan[q].staged, scratch_at += plan[q].scratch;
+            }
+            HIP_OK(hipMemcpyAsync(s.region, h, rows_bytes, hipMemcpyHostToDevice, st));
+            if (staged) HIP_OK(hipMemcpyAsync(s.region + read_stage_at(U), h_stage, staged, hipMemcpyHostToDevice, st));
+        }
+        const uint64_t nq = span.q1 - span.q0;
+        HIP_OK(hipMemcpyAsync(r.failed + span.q0, failed.data() + span.q0, nq, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_out_off + span.q0, packed_off.data() + span.q0, nq * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(P.out[0].need(packed + 1));
+        uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
+        if (const int rc = launch_read_tail(ctx, rec, d, r, s, max_wbits, d_out, d_out_off, d_out_len, d_status, st)) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        HIP_OK(hipMemcpyAsync(out_len + span.q0, d_out_len + span.q0, nq * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(status + span.q0, d_status + span.q0, nq, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        uint64_t extent = 0;  // of the packed ranges: behind the last delivered byte
+        for (uint64_t q = span.q0; q < span.q1; q++)
+            if (out_len[q]) extent = std::max(extent, packed_off[q] + out_len[q]);
+        if (!extent) continue;
+        HIP_OK(P.stage[1].need(extent));
+        HIP_OK(hipMemcpyAsync(P.stage[1].p, d_out, extent, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        const uint8_t* const back = static_cast<const uint8_t*>(P.stage[1].p);
+        for (uint64_t q = span.q0; q < span.q1; q++)
+            if (out_len[q]) memcpy(out + out_off[q], back + packed_off[q], out_len[q]);
+    }
+    if (dbg) read_ranges_debug(nr, units_all, slices.size(), staged_all);
+    return TAMP_OK;
+}
+
+int batch_read_ranges(const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int8_t* status,
+                      int mem, int device, void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_read_ranges(ctx, c, max_wbits, out, out_off, out_len, status, static_cast<hipStream_t>(stream));
+    if (!c.off && c.n && c.first[c.n] != 0) return TAMP_AMD_BAD_ARGUMENT;  // (entries and no table to hold them)
+    return read_ranges_host(ctx, c, max_wbits, out, out_off, out_len, status);
+}
+
 int batch_decompress(BatchTables t, uint8_t max_window_bits, int mem, int device, void* stream) {
     if (const int rc = batch_refused(t, true, mem, device)) return rc;
     if (!t.dict) t.dict_len = 0, t.dict_off = nullptr;  // (no buffer: every stream with the custom bit is TAMP_INVALID_CONF, as ever)
@@ -2711,6 +2941,22 @@ int tamp_batch_decompress_resets(uint8_t max_window_bits, const uint8_t* in, con
     if (const int rc = batch_refused(t, out != nullptr, mem, device)) return rc;
     if (device == TAMP_AMD_ALL_DEVICES || (n_streams && (!reset_first || !out_cap))) return TAMP_AMD_BAD_ARGUMENT;
     return batch_decompress_resets(t, reset_first, reset_off, max_window_bits, mem, device, stream);
+}
+
+int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                           const uint64_t* reset_first, const uint32_t* reset_off, uint32_t reset_interval, const uint32_t* range_stream,
+                           const uint64_t* range_begin, const uint32_t* range_len, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                           int8_t* status, size_t n_streams, size_t n_ranges, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!in_off || !in_len || !reset_first || !range_stream || !range_begin || !range_len || !out_off || !out_len || !status)
+        return TAMP_AMD_BAD_ARGUMENT;
+    if ((!in && n_streams) || (!out && n_ranges) || !reset_interval) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || n_ranges > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_ranges == 0) return TAMP_OK;  // (nothing is touched)
+    const ReadCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
+                          range_stream, range_begin, range_len, n_ranges};
+    return batch_read_ranges(c, max_window_bits, out, out_off, out_len, status, mem, device, stream);
 }
 
 int tamp_batch_pack(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint8_t* dst, uint64_t dst_cap,

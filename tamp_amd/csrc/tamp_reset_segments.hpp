@@ -1,10 +1,10 @@
 // tamp_reset_segments.hpp -- the segment table of a dictionary-reset call (tamp_amd_compress_resets): how a buffer
 // is cut into segments, what a segment's slab holds, what the whole stream can take -- and, for a batch of such buffers
 // (tamp_batch_compress_resets), which stream and cut a row of its two segment tables stands for, and the same for the rows a reset
-// index claims on the way back (tamp_batch_decompress_resets).  Arithmetic only, for the host and the device: no HIP type, so that
-// tests/test_reset_segments_host.py, tests/test_batch_resets_host.py and tests/test_batch_reset_index_host.py compile it into
-// stand-alone host programs.  The kernels that use it:
-// tamp_reset_segments_kernel.hpp.
+// index claims on the way back (tamp_batch_decompress_resets), and what a byte range of such a stream touches
+// (tamp_batch_read_ranges).  Arithmetic only, for the host and the device: no HIP type, so that tests/test_reset_segments_host.py,
+// tests/test_batch_resets_host.py, tests/test_batch_reset_index_host.py and tests/test_read_ranges_host.py compile it into
+// stand-alone host programs.  The kernels that use it: tamp_reset_segments_kernel.hpp, tamp_read_ranges_kernel.hpp.
 #pragma once
 #include <stdint.h>
 
@@ -139,6 +139,121 @@ TAMP_HD constexpr uint64_t reset_unit_stage_off(uint64_t stage_base, const Reset
 }
 TAMP_HD inline uint64_t reset_unit_out_off(const uint64_t* first, const uint64_t* size_scan, const ResetIndexCut& u) {
     return size_scan[first[u.stream] + u.seg] - size_scan[first[u.stream]];  // (the open segment: seg = E, the stream's closed total)
+}
+
+// ---- reading byte RANGES of such a batch (tamp_batch_read_ranges) ----
+// Every closed segment decodes to exactly N = reset_interval bytes, so decoded byte b of a stream lies in segment b / N and the index
+// says where that segment's tokens start.  Range q asks for `len` decoded bytes from `begin` of stream i (E entries, segments 0 .. E,
+// the last one open): it touches segments k0 = begin / N through k1 = min((begin + len - 1) / N, E), each one a UNIT that is staged
+// behind a copy of the stream's header as a stream of its own and decoded into the range's scratch at j * N for unit j -- the
+// range's bytes are then `skip` = begin - k0 * N bytes into that scratch, in one piece.  Here the index is TRUSTED for position
+// (a segment's start is no longer token aligned by induction from the header); what is checked is what memory safety and the
+// address k * N need.  All of it in 64 bits.
+constexpr int32_t kReadGo = 127;  // a range's verdict: no result yet, its units are decoded (every other value is its status)
+constexpr int32_t kReadOk = 0, kReadInputExhausted = 2, kReadInvalidConf = -3, kReadBadArgument = -21, kReadBadIndex = -22;
+constexpr uint32_t kReadMaxSegment = (1u << 29) - 1 - 512;  // the walk counts a segment's bits in 32 bits (kMaxDecodeIn - 512)
+constexpr uint64_t kReadUnitRow = 64;  // bytes of table rows a unit takes in the call's scratch (at least; the budget counts them)
+
+// The header conditions of a stream that may be read by ranges: the reset bit (with it the second header byte, which must be
+// zero), no custom dictionary, a window the call accepts.
+TAMP_HD inline bool read_header_eligible(const uint8_t* s, uint32_t len, uint32_t max_wbits) {
+    if (len < kResetHeaderBytes || max_wbits > 15) return false;
+    const uint32_t h0 = s[0];
+    return (h0 & 1u) && !((h0 >> 2) & 1u) && s[1] == 0 && ((h0 >> 5) & 7u) + 8 <= max_wbits;
+}
+// Stream i's rows of reset_first make sense: in order, inside the table, and the table starts at 0.
+TAMP_HD inline bool read_index_usable(const uint64_t* first, uint64_t n, uint64_t i) {
+    return reset_first_in_order(first, i) && first[i + 1] <= first[n];
+}
+// Segment k <= E of stream i (E = first[i + 1] - first[i], which may be 0: the whole stream is one open segment): its cut, with the
+// range and order check of the entries it uses.  ok = false: an entry out of range or order, or a segment too long to walk.
+struct ReadCut {
+    uint32_t start, end;
+    bool closed, ok;
+};
+TAMP_HD inline ReadCut read_segment_cut(const uint64_t* first, const uint32_t* off, const uint32_t* in_len, uint64_t i, uint64_t k) {
+    const uint64_t f = first[i], E = first[i + 1] - f;
+    const bool closed = k < E;
+    const uint32_t start = k ? off[f + k - 1] : kResetHeaderBytes, end = closed ? off[f + k] : in_len[i];
+    // a closed segment holds its FLUSH, FLUSH at least: it is never empty; the open one may be (a stream that ends with a reset)
+    const bool ok = start >= kResetHeaderBytes && end <= in_len[i] && (closed ? start < end : start <= end) && end - start <= kReadMaxSegment;
+    return {start, end, closed, ok};
+}
+TAMP_HD constexpr uint64_t read_sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
+
+// What a range comes to before anything is decoded.  verdict != kReadGo: the range's status, it has no units.
+struct ReadPlan {
+    int32_t verdict;
+    uint64_t k0;       // its first segment
+    uint64_t units;    // segments it touches
+    uint64_t scratch;  // decoded bytes its units are given room for: N for every unit but the last, `last_need` for that
+    uint64_t staged;   // bytes its units take in the stage: the segments and a header each
+    uint32_t last_need;
+    uint32_t span_start;  // where its first unit starts in the stream
+};
+TAMP_HD inline ReadPlan read_range_plan(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* first,
+                                        const uint32_t* off, uint64_t n, uint32_t N, uint32_t max_wbits, uint64_t budget,
+                                        uint32_t stream, uint64_t begin, uint32_t len) {
+    ReadPlan p = {kReadBadArgument, 0, 0, 0, 0, 0, 0};
+    if (stream >= n) return p;
+    p.verdict = kReadOk;
+    if (len == 0) return p;  // (the stream is not looked at)
+    const uint64_t i = stream;
+    p.verdict = kReadInvalidConf;
+    if (!read_header_eligible(in + in_off[i], in_len[i], max_wbits)) return p;
+    p.verdict = kReadBadIndex;
+    if (!read_index_usable(first, n, i) || (!off && first[i + 1] != first[i])) return p;  // (entries and no table to hold them)
+    const uint64_t E = first[i + 1] - first[i], k0 = begin / N;
+    p.k0 = k0;
+    p.verdict = kReadInputExhausted;
+    if (k0 > E) return p;
+    // k1 = min((begin + len - 1) / N, E) without the sum, which 64 bits may not hold, and with ONE 64-bit division: from the first
+    // byte of segment k0 the range ends rem + len bytes on, and len - 1 = more * N + r2
+    const uint64_t rem = begin - k0 * N;
+    const uint32_t more = (len - 1) / N, r2 = (len - 1) % N;
+    const bool carry = rem + r2 >= N;
+    const uint64_t beyond = (uint64_t)more + (carry ? 1 : 0);  // segments behind k0 that the range reaches into, were there enough
+    const bool clipped = beyond > E - k0;                       // ... it runs past the open segment
+    const uint64_t units = (clipped ? E - k0 : beyond) + 1, k1 = k0 + units - 1;
+    // the span of the touched segments: from the entry in front of the first to the entry behind the last (the units kernel
+    // checks every entry between them)
+    const ReadCut a = read_segment_cut(first, off, in_len, i, k0), b = read_segment_cut(first, off, in_len, i, k1);
+    p.verdict = kReadBadIndex;
+    if (!a.ok || !b.ok || b.end < a.start) return p;
+    // what is asked of the last unit: up to the range's last byte, or all of it when the range runs on
+    const uint32_t last_need = clipped ? N : (uint32_t)(rem + r2 - (carry ? N : 0) + 1);
+    const uint64_t scratch = (units - 1) * N + last_need, staged = (uint64_t)(b.end - a.start) + kResetHeaderBytes * units;
+    p.verdict = kReadBadArgument;  // the range alone outgrows what the call may take
+    if (units > budget / kReadUnitRow || read_sat_add(read_sat_add(scratch, staged), units * kReadUnitRow) > budget) return p;
+    p.verdict = kReadGo, p.units = units, p.scratch = scratch, p.staged = staged, p.last_need = last_need, p.span_start = a.start;
+    return p;
+}
+TAMP_HD constexpr uint64_t read_plan_cost(const ReadPlan& p) { return p.scratch + p.staged + p.units * kReadUnitRow; }
+
+// Unit j < units of a range: segment k0 + j.  Its cut must hold up and lie inside the range's span (then its place in the stage
+// does, too); place: from the range's first staged byte; room: from the range's first scratch byte.
+struct ReadUnit {
+    ReadCut cut;
+    uint32_t need;     // decoded bytes asked of it
+    uint32_t in_len;   // segment + header bytes, 0: no unit (cut.ok false)
+    uint64_t place, room;
+};
+TAMP_HD inline ReadUnit read_range_unit(const uint64_t* first, const uint32_t* off, const uint32_t* in_len, uint32_t N, uint64_t i,
+                                        const ReadPlan& p, uint64_t j) {
+    ReadUnit u;
+    u.cut = read_segment_cut(first, off, in_len, i, p.k0 + j);
+    u.need = j + 1 == p.units ? p.last_need : N;
+    const uint64_t span = p.staged - kResetHeaderBytes * p.units;  // span_start .. span_start + span
+    if (u.cut.ok && (u.cut.start < p.span_start || (uint64_t)u.cut.end - p.span_start > span)) u.cut.ok = false;
+    u.in_len = u.cut.ok ? u.cut.end - u.cut.start + kResetHeaderBytes : 0;
+    u.place = u.cut.ok ? (uint64_t)(u.cut.start - p.span_start) + kResetHeaderBytes * j : 0;
+    u.room = j * N;
+    return u;
+}
+// Bytes a range delivers when its units decoded to `total` bytes in all: what lies behind `skip` = begin - k0 * N, `len` at most.
+TAMP_HD constexpr uint64_t read_range_skip(uint64_t begin, uint64_t k0, uint32_t N) { return begin - k0 * N; }
+TAMP_HD constexpr uint32_t read_range_delivered(uint64_t total, uint64_t skip, uint32_t len) {
+    return total > skip ? (total - skip < len ? (uint32_t)(total - skip) : len) : 0;
 }
 
 }  // namespace tamp_amd
