@@ -573,6 +573,50 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t *in, const uin
                            uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int8_t *status,
                            size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
 
+/*
+ * FINDING the resets of streams that came without an index: a blob of tamp_amd_compress_resets, a file, a batch whose index was not
+ * kept, anything a reference Compressor(dictionary_reset=True) wrote with reset_dictionary() calls of its own or in append mode.
+ * The call returns the table tamp_batch_compress_resets_index writes, found on the device: the compressed bits of every stream are
+ * cut into chunks of TAMP_AMD_INDEX_RESETS_CHUNK_BITS, and the chunks of ALL streams are the units of work (a lane each).
+ *   in, in_off, in_len   the streams, as for tamp_batch_decompress_resets; only read
+ *   reset_first          n_streams + 1 entries, ALWAYS written: the running sum of the streams' entry counts, from 0
+ *   reset_off            reset_cap entries, or NULL with reset_cap == 0 (count only).  Stream i's entries are
+ *                        reset_off[reset_first[i] .. reset_first[i + 1]): the offset of the byte behind each reset, counted in the
+ *                        stream's own bytes, ascending.  A reset is a FLUSH token whose predecessor token is a FLUSH
+ *                        (decompressor.c:501-513): three in a row are two resets with an empty segment between them, a lone one is none
+ *   closed_size          optional, parallel to reset_off: the decoded bytes of the segment each reset closes
+ *   open_size            optional, n_streams entries: the decoded bytes of each stream's last (open) segment; a stream's decoded size
+ *                        is the sum of its closed sizes and this.  Sizes come from the token grammar alone -- the bytes every token
+ *                        produces, summed between resets; one that does not fit 32 bits saturates at 0xFFFFFFFF
+ *   status[i]            the first rule that applies:
+ *       the stream is shorter than its header ................................. TAMP_INPUT_EXHAUSTED, no entries
+ *       a header tamp_amd_read_header refuses, a window above max_window_bits .. TAMP_INVALID_CONF, no entries
+ *       more than 2^29 - 513 bytes (32-bit bit positions) ...................... TAMP_AMD_BAD_ARGUMENT, no entries
+ *       any token whose offset runs out of the window .......................... TAMP_OOB, entries and sizes still as the grammar says
+ *       anything else, a stream that ends inside a token included (it is walked
+ *       up to its last complete token) ......................................... TAMP_OK
+ *     A header without the reset bit cannot hold resets: no entries, TAMP_OK, the whole size in open_size[i].  The custom-dictionary
+ *     bit does not change where tokens lie: such a stream is indexed all the same (the calls that take the index refuse it themselves).
+ * CAPACITY.  More entries than reset_cap holds: the call returns 1, reset_first, open_size and status are complete and no byte of
+ * reset_off or closed_size is written; call again with room for reset_first[n_streams] entries.
+ * WHAT THE RESULT IS CHECKED FOR.  Positions come from the grammar alone: nothing is decoded, no window is kept.  The consumers
+ * verify -- tamp_batch_decompress_resets walks every segment from the header on, tamp_batch_read_ranges checks the segments it touches.
+ *   mem, device, stream   TAMP_AMD_ALL_DEVICES is not taken.  A device-memory call WAITS for one 16-byte record (the chunks of the batch),
+ *                   for a 4-byte changed-flag per round of the start search -- text settles in two or three; ceil(c / 64) + 2 at most for
+ *                   a longest stream of c chunks, more is TAMP_ERROR, a defect -- and for the 8-byte entry count; everything else is
+ *                   asynchronous on `stream`.  A host-memory call is synchronous: the streams go up once, the tables alone come back.
+ * Scratch is kept per HIP stream (about 40 bytes per chunk, 8 per entry; tamp_amd_trim releases it).  With TAMP_AMD_RESETS_DEBUG set
+ * the call writes one line to stderr: "[tamp_amd resets] index: <n> streams, <c> chunks, <r> rounds, <e> entries".
+ * Returns TAMP_OK, 1 (above); TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null in_off, in_len, reset_first or status, a
+ * null `in` with n_streams > 0, a null reset_off with reset_cap > 0, a bad memory kind, TAMP_AMD_ALL_DEVICES, n_streams >= 2^32 (and
+ * for a batch of 2^32 chunks or more); TAMP_AMD_NO_DEVICE.
+ */
+#define TAMP_AMD_INDEX_RESETS_CHUNK_BITS 1024
+int tamp_batch_index_resets(uint8_t max_window_bits, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                            uint64_t *reset_first, uint32_t *reset_off /* NULL with reset_cap == 0 */,
+                            uint32_t *closed_size /* may be NULL */, uint32_t *open_size /* may be NULL */, uint64_t reset_cap,
+                            int8_t *status, size_t n_streams, int mem, int device, void *stream);
+
 /* ---- a batch's streams packed densely on the device -----------------------------------------------
  *
  * The batch calls return their streams in slabs of worst-case size (tamp_batch_compress: 1 + ceil(9n/8) bytes for n input bytes), of

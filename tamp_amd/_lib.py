@@ -20,6 +20,7 @@ ALL_DEVICES = -1  # include/tamp_amd.h TAMP_AMD_ALL_DEVICES
 WINDOW_BITS_EXACT = 0x80  # include/tamp_amd.h: TAMP_AMD_WINDOW_BITS_EXACT
 MEM_HOST, MEM_DEVICE = 0, 1
 RESETS_SCAN_TILE = 1024  # include/tamp_amd.h TAMP_AMD_RESETS_SCAN_TILE
+INDEX_RESETS_CHUNK_BITS = 1024  # include/tamp_amd.h TAMP_AMD_INDEX_RESETS_CHUNK_BITS
 
 # every symbol include/tamp_amd.h declares (tests/test_capi_symbols.py checks header <-> library <-> this list)
 SYMBOLS = (
@@ -47,6 +48,7 @@ SYMBOLS = (
     "tamp_batch_decompress_resets",
     "tamp_amd_decompress_resets",
     "tamp_batch_read_ranges",
+    "tamp_batch_index_resets",
     "tamp_batch_pack",
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
@@ -206,6 +208,8 @@ def load() -> C.CDLL:
     lib.tamp_amd_decompress_resets.restype = i32
     lib.tamp_batch_read_ranges.argtypes = [u8, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, vp]
     lib.tamp_batch_read_ranges.restype = i32
+    lib.tamp_batch_index_resets.argtypes = [u8, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, sz, i32, i32, vp]
+    lib.tamp_batch_index_resets.restype = i32
     lib.tamp_batch_pack.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, sz, u32, i32, vp]
     lib.tamp_batch_pack.restype = i32
     lib.tamp_amd_decoder_state_size.argtypes = [u8]

@@ -861,6 +861,129 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
 
 
 @dataclass
+class ResetScan:
+    """What ``index_resets`` found: the batch's ``ResetIndex`` and, from the token grammar alone, the decoded sizes."""
+    index: ResetIndex
+    status: object       # int8 [n] -- per stream (include/tamp_amd.h, tamp_batch_index_resets)
+    closed_size: object  # uint32/int32 [entries] -- decoded bytes of the segment each reset closes (0xFFFFFFFF: 2^32 - 1 or more)
+    open_size: object    # uint32/int32 [n] -- decoded bytes of each stream's last (open) segment
+    kernel_ms: float = -1.0
+    _keep: object = None  # device tensors the asynchronous launch still reads
+
+    def size(self, i: int) -> int:
+        """Decoded bytes of stream ``i``: its closed segments and its open one."""
+        a, b = int(self.index.first[i]), int(self.index.first[i + 1])
+        closed = self.closed_size[a:b]
+        closed = closed.cpu().numpy() if _is_torch(closed) else np.asarray(closed)
+        return int((closed.astype(np.int64) & 0xFFFFFFFF).sum()) + (int(self.open_size[i]) & 0xFFFFFFFF)
+
+
+def _detect_interval(first, closed, open_size, status):
+    """``ResetIndex.interval`` of a found index (numpy tables): the one size of all closed segments of the ``TAMP_OK`` streams,
+    when there is a closed segment and no open segment is larger -- else ``None``."""
+    counts = np.diff(first.astype(np.int64))
+    ok = np.repeat(status == 0, counts)
+    sizes = closed[ok]
+    if not sizes.size or int(sizes.min()) != int(sizes.max()):
+        return None
+    return int(sizes[0]) if not open_size.size or int(open_size.max()) <= int(sizes[0]) else None
+
+
+def index_resets(data, in_off=None, in_len=None, *, max_window_bits: int = 15, device: int = 0, stream=None,
+                 timing: bool = False) -> ResetScan:
+    """The reset index of streams that came without one (``tamp_batch_index_resets``; not in the reference): a blob
+    of ``compress(..., dictionary_reset=True, reset_interval=N)``, a file, a batch whose index was not kept, anything a reference
+    ``Compressor(dictionary_reset=True)`` wrote with ``reset_dictionary()`` calls of its own.  ``data`` as for ``decompress_batch``:
+    a list of bytes, numpy tables or CUDA tensors.  The resets are found on the device, from the token grammar alone; nothing is
+    decoded.  ``status[i]`` is 0, 2 (shorter than its header), -3 (header), -4 (an offset out of the window: entries and sizes still
+    as the grammar says) or -21 (too long); a refused stream has no entries.  ``index`` goes to ``read_ranges`` and
+    ``decompress_batch(..., reset_index=)`` as it stands: they verify what they use.  ``index.interval`` is filled when the batch has
+    a closed segment, all closed segments of the status-0 streams decode to the same number of bytes and no open segment is larger.
+    The first call has room for ``max(n, total_bytes >> 12)`` entries; when there are more, the library says how many and ONE more
+    call is made with exactly that room.  CUDA tensors: the entry count and the interval check are the only waits beyond the
+    library's own (one per round of its start search)."""
+    if not _is_int(max_window_bits) or not 8 <= int(max_window_bits) <= 15:  # (all decided before the library is looked for)
+        raise ValueError("max_window_bits: 8 .. 15 expected")
+    if (in_off is None) != (in_len is None):
+        raise ValueError("in_off and in_len: both or neither")
+    if in_off is not None and len(in_off) != len(in_len):
+        raise ValueError("in_off and in_len: one entry per stream each")
+    on_device = _is_torch(data)
+    if on_device and in_off is None:
+        raise ValueError("a CUDA buffer needs in_off and in_len")
+    if stream is not None and on_device:
+        import torch  # (tables and output on the launch stream: see compress_batch)
+
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return index_resets(data, in_off, in_len, max_window_bits=max_window_bits, device=device, stream=None, timing=timing)
+    lib = _lib.load()
+    lib.tamp_amd_set_timing(1 if timing else 0)
+    total_ms = 0.0
+
+    def call(args, first_n, cap, make):  # -> (reset_off, closed_size), the retry included
+        nonlocal total_ms
+        for attempt in (0, 1):
+            off, closed = make(cap)
+            rc = lib.tamp_batch_index_resets(*args(off if cap else None, closed if cap else None, cap))
+            total_ms += lib.tamp_amd_last_kernel_ms() if timing else 0.0
+            if rc != 1 or attempt:
+                break
+            cap = first_n()
+        if rc == 1:
+            raise RuntimeError("tamp_amd: the entry count changed between two calls")
+        _lib.check_launch(rc)
+        return off, closed
+
+    if on_device:
+        import torch
+
+        dev = data.device
+        n = len(in_len)
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        first_t = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        open_t = torch.empty(n, dtype=torch.int32, device=dev)
+        status_t = torch.empty(n, dtype=torch.int8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        off_t, closed_t = call(
+            lambda off, closed, cap: (max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(first_t), _ptr(off), _ptr(closed),
+                                      _ptr(open_t), cap, _ptr(status_t), n, _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st)),
+            lambda: int(first_t[n].item()), max(n, data.numel() >> 12),
+            lambda cap: (torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)))
+        entries = int(first_t[n].item())
+        off_t, closed_t = off_t[:entries], closed_t[:entries]
+        interval = None
+        if entries:
+            ok = torch.repeat_interleave(status_t == 0, first_t[1:] - first_t[:-1], output_size=entries)
+            sizes = closed_t.to(torch.int64) & 0xFFFFFFFF  # (masked without a compaction: that would be one more wait)
+            lo, hi = torch.where(ok, sizes, 1 << 32).min(), torch.where(ok, sizes, -1).max()
+            found = torch.where((lo == hi) & ((open_t.to(torch.int64) & 0xFFFFFFFF).max() <= lo), lo, -1)
+            found = int(found.item())
+            interval = found if found >= 0 else None
+        return ResetScan(ResetIndex(first_t, off_t, interval), status_t, closed_t, open_t, total_ms if timing else -1.0,
+                         (data, in_off_t, in_len_t))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    n = len(in_len)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    first = np.zeros(n + 1, dtype=np.uint64)
+    open_size, status = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int8)
+    off, closed = call(
+        lambda off, closed, cap: (max_window_bits, _ptr(flat), _ptr(in_off), _ptr(in_len), _ptr(first), _ptr(off), _ptr(closed),
+                                  _ptr(open_size), cap, _ptr(status), n, _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None),
+        lambda: int(first[n]), max(n, int(in_len.sum(dtype=np.uint64)) >> 12),
+        lambda cap: (np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)))
+    entries = int(first[n])
+    off, closed = off[:entries], closed[:entries]
+    return ResetScan(ResetIndex(first, off, _detect_interval(first, closed, open_size, status)), status, closed, open_size,
+                     total_ms if timing else -1.0)
+
+
+@dataclass
 class PackedBatch:
     """A batch's streams back to back in one buffer (``pack_batch``, ``BatchResult.packed``): stream ``i`` is
     ``data[off[i] : off[i] + len[i]]``, and ``off[-1]`` is the packed size.  numpy arrays (uint8, uint64, uint32) or CUDA tensors

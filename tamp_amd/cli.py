@@ -1,4 +1,4 @@
-"""Command line of the package: ``python -m tamp_amd compress|decompress|build-dictionary`` with the options of the reference's CLI.
+"""Command line of the package: ``python -m tamp_amd compress|decompress|index|build-dictionary`` with the options of the reference's CLI.
 
 Mirrors ``tamp/cli/main.py:115-232`` (``tamp compress`` / ``tamp decompress``: ``--input/-i``, ``--output/-o``,
 ``--window/-w``, ``--literal/-l``, ``--dictionary/-d``, ``--lazy-matching``, ``--extended`` / ``--no-extended``; stdin /
@@ -78,6 +78,8 @@ def build_parser() -> argparse.ArgumentParser:
             p.add_argument("--reset-interval", type=int, default=None, metavar="N",
                            help="reset the dictionary every N input bytes (sets the header's dictionary_reset bit): the "
                                 "segments between resets are compressed in parallel, at some cost in ratio")
+    x = sub.add_parser("index", help="Find the dictionary resets of compressed files: entries, interval, decoded size.")
+    x.add_argument("files", nargs="+", metavar="FILE")
     b = sub.add_parser("build-dictionary", help="Build a custom dictionary from a corpus of messages.")
     b.add_argument("input", metavar="INPUT", help="directory of sample files, or one file cut at --delimiter")
     b.add_argument("--output", "-o", default="dictionary.bin", help="binary dictionary file (effective bytes only)")
@@ -109,6 +111,16 @@ def main(argv=None) -> int:
         except ValueError as e:
             print(f"tamp_amd: {type(e).__name__}: {e}", file=sys.stderr)
             return 1
+        return 0
+    if args.command == "index":
+        scan = tamp_amd.index_resets([Path(f).read_bytes() for f in args.files])
+        from tamp_amd.batch import _detect_interval
+
+        for i, f in enumerate(args.files):  # (the interval of each file's own segments; scan.index.interval is the batch's)
+            a, b = int(scan.index.first[i]), int(scan.index.first[i + 1])
+            own = _detect_interval(scan.index.first[i:i + 2] - scan.index.first[i], scan.closed_size[a:b], scan.open_size[i:i + 1],
+                                   scan.status[i:i + 1])
+            print(f"{f}: status {int(scan.status[i])}, {b - a} resets, interval {own or 'none'}, {scan.size(i)} bytes decoded")
         return 0
     src = args.input if args.input is not None else args.input_pos
     dst = args.output if args.output is not None else args.output_pos

@@ -33,6 +33,7 @@
 #include "tamp_compress_resume_kernel.hpp"
 #include "tamp_reset_segments_kernel.hpp"
 #include "tamp_read_ranges_kernel.hpp"
+#include "tamp_reset_index_kernel.hpp"
 #include "tamp_pack_kernel.hpp"
 
 using namespace tamp_amd;
@@ -75,7 +76,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges and launch_pack and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_index_resets and launch_pack and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -93,6 +94,7 @@ struct StreamScratch {
     DeviceBuf resets;      // dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets), a batch's per-stream words in front (launch_compress_batch_resets)
     DeviceBuf pack;        // tamp_batch_pack: the scan's per-workgroup sums (8 KiB, allocated once)
     DeviceBuf ranges;      // tamp_batch_read_ranges: the per-range scans and verdicts (the units, stage and scratch of a slice: `resets`)
+    DeviceBuf index_streams, index_chunks, index_entries;  // tamp_batch_index_resets: its tables per stream, per chunk, per entry
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -104,7 +106,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &index_streams, &index_chunks, &index_entries}) n += b->release();
         return n;
     }
 };
@@ -2584,6 +2586,167 @@ int batch_read_ranges(const ReadCaller& c, uint8_t max_wbits, uint8_t* out, cons
     return read_ranges_host(ctx, c, max_wbits, out, out_off, out_len, status);
 }
 
+// The reset index of a batch that came without one (tamp_batch_index_resets; kernels and steps: tamp_reset_index_kernel.hpp, the
+// arithmetic: tamp_reset_index.hpp).  All tables in device memory.  The call waits for the 16 bytes that size the chunk tables, for the
+// 4-byte changed-flag of every round, and for the entry count that decides whether the entries fit.  -> TAMP_OK, 1 (more entries than
+// reset_cap holds: reset_first, open_size and status are complete, reset_off and closed_size untouched) or an error code.
+int launch_index_resets(DeviceCtx* ctx, const IndexCaller& c, uint64_t* reset_first, uint32_t* reset_off, uint32_t* closed_size,
+                        uint32_t* open_size, uint64_t reset_cap, int8_t* status, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const uint64_t n = c.n;
+    const size_t first_at = 256, pre_at = first_at + (n + 1) * 8;
+    HIP_OK(rec.index_streams.need(pre_at + 2 * n + 64));
+    uint8_t* const sb = static_cast<uint8_t*>(rec.index_streams.p);
+    IndexStreams s;
+    s.rec = reinterpret_cast<IndexRecord*>(sb), s.chunk_first = reinterpret_cast<uint64_t*>(sb + first_at);
+    s.pre = reinterpret_cast<int8_t*>(sb + pre_at), s.bad = reinterpret_cast<uint8_t*>(sb + pre_at + n);
+    const CallTiming call_timing(st);
+    const IndexChunksArgs count = {c, s};
+    hipLaunchKernelGGL(tamp_index_chunks_kernel, dim3(1), dim3(kResetScanTile), 0, st, count);
+    HIP_OK(hipGetLastError());
+    IndexRecord have = {};
+    HIP_OK(hipMemcpyAsync(&have, s.rec, 16, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (have.chunks > 0xFFFF0000ull) return TAMP_AMD_BAD_ARGUMENT;  // (the chunks are numbered in 32 bits: 512 GiB of streams)
+    const uint32_t C = (uint32_t)have.chunks, tiles = (C + kResetScanTile - 1) / kResetScanTile, lg = (C + 63) / 64;
+    // per chunk: two rows of starts, the report, the place and the running byte count; per tile of the scan its value and what lies in front
+    const size_t g_bytes = (((size_t)C + 1) * 4 + 15) & ~(size_t)15, sum_bytes = ((size_t)tiles + 1) * sizeof(IndexSum);
+    const size_t rep_at = 2 * g_bytes, place_at = rep_at + (size_t)C * sizeof(IndexChunkReport), bytes_at = place_at + ((size_t)C + 1) * 8;
+    const size_t sum_at = bytes_at + ((size_t)C + 1) * 8;
+    HIP_OK(rec.index_chunks.need(sum_at + 2 * sum_bytes));
+    uint8_t* const cb = static_cast<uint8_t*>(rec.index_chunks.p);
+    uint32_t* cur = reinterpret_cast<uint32_t*>(cb);
+    uint32_t* nxt = reinterpret_cast<uint32_t*>(cb + g_bytes);
+    uint64_t* const place = reinterpret_cast<uint64_t*>(cb + place_at);
+    uint64_t* const bytes = reinterpret_cast<uint64_t*>(cb + bytes_at);
+    uint64_t rounds = 0, entries = 0;
+    if (C == 0) {  // (no stream has chunks: an empty index)
+        HIP_OK(hipMemsetAsync(place, 0, 8, st));
+        HIP_OK(hipMemsetAsync(bytes, 0, 8, st));
+    } else {
+        IndexChunkArgs ca = {};
+        ca.c = c, ca.s = s, ca.chunks = C;
+        const uint64_t bound = index_round_bound(have.longest);
+        for (bool settled = false; !settled; rounds++) {
+            if (rounds == bound) {  // a defect of the library, not a property of the input
+                snprintf(t_last_error, sizeof t_last_error, "tamp_batch_index_resets: the starts did not settle in %llu rounds", (unsigned long long)bound);
+                return TAMP_ERROR;
+            }
+            if (rounds) HIP_OK(hipMemsetAsync(&s.rec->moved, 0, 4, st));
+            ca.round0 = rounds == 0, ca.g = cur, ca.g_next = nxt;
+            hipLaunchKernelGGL(tamp_index_sync_kernel, dim3(lg), dim3(64), 0, st, ca);
+            HIP_OK(hipGetLastError());
+            uint32_t moved = 1;
+            HIP_OK(hipMemcpyAsync(&moved, &s.rec->moved, 4, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            std::swap(cur, nxt);
+            settled = moved == 0;
+        }
+        ca.g = cur, ca.g_next = nullptr, ca.rep = reinterpret_cast<IndexChunkReport*>(cb + rep_at), ca.write = 0;
+        hipLaunchKernelGGL(tamp_index_find_kernel, dim3(lg), dim3(64), 0, st, ca);
+        IndexMergeArgs m = {ca.rep, C, tiles, 0, reinterpret_cast<IndexSum*>(cb + sum_at), reinterpret_cast<IndexSum*>(cb + sum_at + sum_bytes),
+                            place, bytes, s.rec};
+        hipLaunchKernelGGL(tamp_index_merge_kernel, dim3(tiles), dim3(kResetScanTile), 0, st, m);
+        m.step = 1;
+        hipLaunchKernelGGL(tamp_index_merge_kernel, dim3(1), dim3(kResetScanTile), 0, st, m);
+        m.step = 2;
+        hipLaunchKernelGGL(tamp_index_merge_kernel, dim3(tiles), dim3(kResetScanTile), 0, st, m);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(&entries, &s.rec->entries, 8, hipMemcpyDeviceToHost, st));
+    }
+    const IndexStreamsArgs sa = {c, s, cur, place, bytes, reset_first, open_size, status};
+    hipLaunchKernelGGL(tamp_index_streams_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, st, sa);
+    HIP_OK(hipGetLastError());
+    if (C) HIP_OK(hipStreamSynchronize(st));  // (the entry count)
+    const bool fits = entries <= reset_cap;
+    if (fits && entries) {
+        if (entries > 0xFFFFFFFFull * 255) return TAMP_AMD_BAD_ARGUMENT;  // (the grid of the lane-per-entry step)
+        uint64_t* d_count = nullptr;
+        if (closed_size) {
+            HIP_OK(rec.index_entries.need(entries * 8));
+            d_count = static_cast<uint64_t*>(rec.index_entries.p);
+        }
+        IndexChunkArgs wa = {};
+        wa.c = c, wa.s = s, wa.chunks = C, wa.g = cur, wa.write = 1, wa.place = place, wa.bytes = bytes, wa.reset_off = reset_off, wa.count = d_count;
+        hipLaunchKernelGGL(tamp_index_find_kernel, dim3(lg), dim3(64), 0, st, wa);
+        if (closed_size) {
+            const IndexSizesArgs za = {reset_first, n, entries, s.chunk_first, bytes, d_count, closed_size};
+            hipLaunchKernelGGL(tamp_index_sizes_kernel, dim3((uint32_t)((entries + 255) / 256)), dim3(256), 0, st, za);
+        }
+        HIP_OK(hipGetLastError());
+    }
+    if (getenv("TAMP_AMD_RESETS_DEBUG"))
+        fprintf(stderr, "[tamp_amd resets] index: %llu streams, %llu chunks, %llu rounds, %llu entries\n", (unsigned long long)n,
+                (unsigned long long)C, (unsigned long long)rounds, (unsigned long long)entries);
+    return fits ? TAMP_OK : 1;
+}
+
+// Host memory, on the host pipeline's first stream (one host-memory call per device at a time): the streams go up once, in one
+// transfer of their extent, and the tables alone come back.
+int index_resets_host(DeviceCtx* ctx, const IndexCaller& c, uint64_t* reset_first, uint32_t* reset_off, uint32_t* closed_size,
+                      uint32_t* open_size, uint64_t reset_cap, int8_t* status) {
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> pipe_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    const size_t n = c.n;
+    uint64_t in_lo = ~0ull, in_hi = 0, total = 0;
+    std::vector<uint64_t> h_in_off(n);
+    for (size_t i = 0; i < n; i++)
+        if (c.in_len[i]) in_lo = std::min(in_lo, c.in_off[i]), in_hi = std::max(in_hi, c.in_off[i] + c.in_len[i]), total += c.in_len[i];
+    if (in_hi < in_lo) in_lo = in_hi = 0;
+    for (size_t i = 0; i < n; i++) h_in_off[i] = c.in_len[i] ? c.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
+    const uint64_t cap = std::min<uint64_t>(reset_cap, total);  // (every reset ends on a byte of its own)
+    HIP_OK(P.in[0].need(in_hi - in_lo + 64));
+    HIP_OK(P.meta[0].need(n * (8 + 4) + 64));
+    const size_t off_at = (n + 1) * 8, closed_at = off_at + cap * 4, open_at = closed_at + cap * 4, status_at = open_at + n * 4;
+    HIP_OK(P.out[0].need(status_at + n + 64));
+    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
+    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_in_off + n);
+    uint8_t* const o = static_cast<uint8_t*>(P.out[0].p);
+    uint64_t* const d_first = reinterpret_cast<uint64_t*>(o);
+    uint32_t* const d_off = reinterpret_cast<uint32_t*>(o + off_at);
+    uint32_t* const d_closed = reinterpret_cast<uint32_t*>(o + closed_at);
+    uint32_t* const d_open = reinterpret_cast<uint32_t*>(o + open_at);
+    int8_t* const d_status = reinterpret_cast<int8_t*>(o + status_at);
+    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_len, c.in_len, n * 4, hipMemcpyHostToDevice, st));
+    const IndexCaller d = {static_cast<const uint8_t*>(P.in[0].p), d_in_off, d_in_len, c.n, c.max_wbits};
+    const int rc = launch_index_resets(ctx, d, d_first, cap ? d_off : nullptr, closed_size && cap ? d_closed : nullptr,
+                                       open_size ? d_open : nullptr, cap, d_status, st);
+    if (rc != TAMP_OK && rc != 1) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(reset_first, d_first, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
+    if (open_size) HIP_OK(hipMemcpyAsync(open_size, d_open, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t E = reset_first[n];
+    if (rc == TAMP_OK && E) {
+        HIP_OK(hipMemcpyAsync(reset_off, d_off, E * 4, hipMemcpyDeviceToHost, st));
+        if (closed_size) HIP_OK(hipMemcpyAsync(closed_size, d_closed, E * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    return rc;
+}
+
+int batch_index_resets(const IndexCaller& c, uint64_t* reset_first, uint32_t* reset_off, uint32_t* closed_size, uint32_t* open_size,
+                       uint64_t reset_cap, int8_t* status, int mem, int device, void* stream) {
+    if (c.n == 0 && mem == TAMP_AMD_MEM_HOST) {  // (nothing to look at: the table's one entry)
+        reset_first[0] = 0;
+        return TAMP_OK;
+    }
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE)
+        return launch_index_resets(ctx, c, reset_first, reset_off, closed_size, open_size, reset_cap, status, static_cast<hipStream_t>(stream));
+    return index_resets_host(ctx, c, reset_first, reset_off, closed_size, open_size, reset_cap, status);
+}
+
 int batch_decompress(BatchTables t, uint8_t max_window_bits, int mem, int device, void* stream) {
     if (const int rc = batch_refused(t, true, mem, device)) return rc;
     if (!t.dict) t.dict_len = 0, t.dict_off = nullptr;  // (no buffer: every stream with the custom bit is TAMP_INVALID_CONF, as ever)
@@ -2957,6 +3120,17 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t* in, const uin
     const ReadCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
                           range_stream, range_begin, range_len, n_ranges};
     return batch_read_ranges(c, max_window_bits, out, out_off, out_len, status, mem, device, stream);
+}
+
+int tamp_batch_index_resets(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                            uint64_t* reset_first, uint32_t* reset_off, uint32_t* closed_size, uint32_t* open_size, uint64_t reset_cap,
+                            int8_t* status, size_t n_streams, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!in_off || !in_len || !reset_first || !status || (!in && n_streams) || (!reset_off && reset_cap)) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    const IndexCaller c = {in, in_off, in_len, n_streams, (uint32_t)(max_window_bits & 0x7F)};
+    return batch_index_resets(c, reset_first, reset_off, closed_size, open_size, reset_cap, status, mem, device, stream);
 }
 
 int tamp_batch_pack(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint8_t* dst, uint64_t dst_cap,

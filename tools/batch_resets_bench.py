@@ -23,6 +23,15 @@ Median of the last ten of twelve calls in a fresh process, `--rounds` alternatin
 input's on every row.  Written to profiles/batch_reset_decode_bench.txt.
 
     python tools/batch_resets_bench.py --decode [--before-root ../parent-checkout]
+
+`--index`: the same batch read back WITHOUT its index ("Finding the resets of a batch"):
+  find, device / host    (a) tamp_batch_index_resets alone, with the rounds of its start search
+  both, device / host    (b) (a) followed by tamp_batch_decompress_resets with the found index
+  plain, device / host   (c) tamp_batch_decompress of the same blobs, on this tree and -- with `--before-root` -- on a build of the parent
+(d) the found index equals the compressor's and the decoded streams the input (SHA-256, asserted in every find / both process).
+Written to profiles/index_resets_bench.txt.
+
+    python tools/batch_resets_bench.py --index [--before-root ../parent-checkout]
 """
 import argparse
 import hashlib
@@ -254,6 +263,132 @@ def decode_main(args):
             f.write("\n".join(lines) + "\n")
 
 
+def index_child(which, reps):
+    """One row of --index: `find-device`, `find-host`, `both-device`, `both-host`."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from tamp_amd import _lib
+
+    lib = _lib.load()
+    kind, route = which.split("-")
+    flat, in_off, in_len = workload()
+    n, total = len(in_len), int(flat.size)
+    conf = _lib.TampAmdConf(10, 8, 0, 1, 1, 0)
+    cap = np.array([lib.tamp_amd_compress_resets_bound(int(x), INTERVAL, 8) for x in in_len], dtype=np.uint32)
+    c_off = np.zeros(n, dtype=np.uint64)
+    c_off[1:] = np.cumsum(cap.astype(np.uint64))[:-1]
+    entries = int(((np.maximum(in_len.astype(np.uint64), 1) - 1) // INTERVAL).sum())
+    room = np.minimum(in_len.astype(np.uint64) + 1, 0xFFFFFFFF).astype(np.uint32)
+    d_off = np.zeros(n, dtype=np.uint64)
+    d_off[1:] = np.cumsum(room.astype(np.uint64))[:-1]
+    dev = torch.device("cuda:0")
+    host = route == "host"
+    mem = _lib.MEM_HOST if host else _lib.MEM_DEVICE
+    E = max(entries, 1)
+    arrays = dict(flat=flat, in_off=in_off.view(np.int64), in_len=in_len.view(np.int32), comp=np.zeros(int(cap.astype(np.uint64).sum()) + 1, np.uint8),
+                  c_off=c_off.view(np.int64), cap=cap.view(np.int32), c_len=np.zeros(n, np.int32), c_status=np.full(n, 99, np.int8),
+                  first=np.zeros(n + 1, np.int64), off=np.zeros(E, np.int32), found_first=np.zeros(n + 1, np.int64), found_off=np.zeros(E, np.int32),
+                  closed=np.zeros(E, np.int32), open=np.zeros(n, np.int32), f_status=np.full(n, 99, np.int8),
+                  out=np.zeros(int(room.astype(np.uint64).sum()) + 1, np.uint8), d_off=d_off.view(np.int64), room=room.view(np.int32),
+                  d_len=np.zeros(n, np.int32), d_status=np.full(n, 99, np.int8), used=np.zeros(n, np.int32))
+    held = arrays if host else {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+    p = {k: C.c_void_p(v.ctypes.data if host else v.data_ptr()) for k, v in held.items()}
+    rc = lib.tamp_batch_compress_resets_index(C.byref(conf), p["flat"], p["in_off"], p["in_len"], INTERVAL, p["comp"], p["c_off"], p["cap"],
+                                              p["c_len"], p["c_status"], n, LONGEST, mem, 0, None, p["first"], p["off"], entries)
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    ms, wall = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        rc = lib.tamp_batch_index_resets(15, p["comp"], p["c_off"], p["c_len"], p["found_first"], p["found_off"], p["closed"], p["open"], entries,
+                                         p["f_status"], n, mem, 0, None)
+        if kind == "both" and rc == 0:
+            rc = lib.tamp_batch_decompress_resets(15, p["comp"], p["c_off"], p["c_len"], p["found_first"], p["found_off"], p["out"], p["d_off"],
+                                                  p["room"], p["d_len"], p["d_status"], p["used"], n, mem, 0, None)
+        e1.record()
+        e1.synchronize()
+        torch.cuda.synchronize()
+        assert rc == 0, rc
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(e0.elapsed_time(e1))
+    back = held if host else {k: v.cpu().numpy() for k, v in held.items() if k not in ("flat", "comp")}
+    assert (back["c_status"] == 0).all() and (back["f_status"] == 0).all()
+    index = hashlib.sha256(back["first"].tobytes() + back["off"][:entries].tobytes()).hexdigest()
+    found = hashlib.sha256(back["found_first"].tobytes() + back["found_off"][:entries].tobytes()).hexdigest()
+    assert found == index, "the found index is not the compressor's"
+    run_sum = np.concatenate([[0], np.cumsum(back["closed"][:entries].view(np.uint32).astype(np.uint64))])
+    sizes = run_sum[back["first"][1:]] - run_sum[back["first"][:-1]] + back["open"].view(np.uint32)
+    assert (sizes == in_len).all(), "the sizes of the scan are not the inputs'"
+    digest = None
+    if kind == "both":
+        assert (back["d_status"] == 2).all() and (back["d_len"].view(np.uint32) == in_len).all()
+        digest, source = hashlib.sha256(), hashlib.sha256()
+        for i in range(n):
+            digest.update(back["out"][int(d_off[i]) : int(d_off[i]) + int(in_len[i])].tobytes())
+            source.update(flat[int(in_off[i]) : int(in_off[i]) + int(in_len[i])].tobytes())
+        assert digest.hexdigest() == source.hexdigest(), "the decoded streams are not the input"
+        digest = digest.hexdigest()
+    kept, kept_wall = sorted(ms[2:]), sorted(wall[2:])
+    med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2  # noqa: E731
+    print(json.dumps(dict(which=which, streams=n, bytes=total, median_ms=med(kept), min_ms=kept[0], max_ms=kept[-1], wall_ms=med(kept_wall),
+                          calls=reps, comp_len=int(back["c_len"].astype(np.uint64).sum()), entries=entries, index_sha256=found, sha256=digest,
+                          lib=_lib.LIB_PATH)))
+
+
+def index_main(args):
+    import re
+
+    me = os.path.abspath(__file__)
+    line = re.compile(r"index: (\d+) streams, (\d+) chunks, (\d+) rounds, (\d+) entries")
+
+    def run(flag, which, parent):
+        env = dict(os.environ, TAMP_AMD_RESETS_DEBUG="1") if flag == "--index-child" else dict(os.environ)
+        if parent:
+            env["BATCH_RESETS_BENCH_ROOT"] = os.path.abspath(args.before_root)
+        p = subprocess.run([sys.executable, me, flag, which, str(REPS)], env=env, capture_output=True, text=True, timeout=1100)
+        if p.returncode != 0:
+            raise SystemExit(f"{which}: exit {p.returncode}\n{p.stderr[-2000:]}")
+        r = json.loads([ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")][-1])
+        m = line.search(p.stderr)
+        if m:
+            r["chunks"], r["rounds"] = int(m[2]), int(m[3])
+        return r
+
+    lines = [f"# tools/batch_resets_bench.py --index: prose corpus tiled into {STREAMS:,} streams, lengths log-uniform in {SHORTEST:,} .. {LONGEST:,} bytes",
+             f"# (seed {SEED}), window 10, literal 8, extended, a reset every 65,536 bytes, compressed once per process.  hipEvents around each call or",
+             "# pair of calls, wall clock around the same span, the device drained at both ends; median of the last ten of twelve in a fresh process",
+             "# (min .. max in brackets).  find = (a) tamp_batch_index_resets alone; both = (b) find, then tamp_batch_decompress_resets with the FOUND",
+             "# index; plain = (c) tamp_batch_decompress of the same blobs without an index" + (", 'parent': a build of the parent commit." if args.before_root else "."),
+             "# (d) asserted in every find / both process: SHA-256 of the found index equals the compressor's, the scan's sizes are the inputs', and",
+             "# (both) SHA-256 over all decoded streams equals the input's.  gain = plain / both on the same route.", ""]
+    fmt = lambda r: (f"{r['median_ms']:10.2f} ms [{r['min_ms']:.2f} .. {r['max_ms']:.2f}]  wall {r['wall_ms']:10.2f} ms")  # noqa: E731
+    sides = [("this tree", False)] + ([("parent", True)] if args.before_root else [])
+    for rnd in range(args.rounds):
+        lines.append(f"run {rnd + 1}")
+        for route in ("device", "host"):
+            find = run("--index-child", f"find-{route}", False)
+            both = run("--index-child", f"both-{route}", False)
+            assert find["index_sha256"] == both["index_sha256"]
+            lines.append(f"    find, {route:<7} this tree  {fmt(find)}   {find.get('chunks', 0):,} chunks, {find.get('rounds', 0)} rounds, {find['entries']:,} entries")
+            lines.append(f"    both, {route:<7} this tree  {fmt(both)}")
+            for name, parent in sides:
+                plain = run("--decode-child", f"plain-{route}", parent)
+                assert plain["sha256"] == both["sha256"]
+                spread = max(both["max_ms"] - both["min_ms"], plain["max_ms"] - plain["min_ms"])
+                lines.append(f"    plain, {route:<6} {name:<9}  {fmt(plain)}   gain {plain['median_ms'] / both['median_ms']:5.2f}, plain - both "
+                             f"{plain['median_ms'] - both['median_ms']:.2f} ms against a spread of {spread:.2f} ms")
+        print("\n".join(lines[-(1 + 2 * (2 + len(sides))):]), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:  # (after every run: a session that is cut short keeps what it measured)
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_resets_bench.txt"))
@@ -263,11 +398,19 @@ def main():
     ap.add_argument("--child", nargs=2, default=None)
     ap.add_argument("--decode", action="store_true")
     ap.add_argument("--decode-child", nargs=2, default=None)
+    ap.add_argument("--index", action="store_true")
+    ap.add_argument("--index-child", nargs=2, default=None)
     args = ap.parse_args()
     if args.child:
         return child(args.child[0], int(args.child[1]))
     if args.decode_child:
         return decode_child(args.decode_child[0], int(args.decode_child[1]))
+    if args.index_child:
+        return index_child(args.index_child[0], int(args.index_child[1]))
+    if args.index:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "index_resets_bench.txt")
+        return index_main(args)
     if args.decode:
         if args.out == ap.get_default("out"):
             args.out = os.path.join(ROOT, "profiles", "batch_reset_decode_bench.txt")

@@ -1,5 +1,7 @@
 """Randomised differential run on the GPU box: compress (all modes) and decompress (both decoders) against the oracle.
-   usage: python tools/fuzz_gpu.py [seconds]   -- prints a summary line; exits 1 on the first mismatch."""
+   usage: python tools/fuzz_gpu.py [seconds]   -- prints a summary line; exits 1 on the first mismatch.
+          python tools/fuzz_gpu.py [seconds] index   -- random token streams with resets through tamp_amd.index_resets against the
+                                                        CPU token reader (tests/long_stream_writer.py) instead."""
 import os, random, sys, time
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
 import numpy as np
@@ -12,6 +14,58 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = random.Random(int(os.environ.get('FUZZ_SEED', '1')))
 t0 = time.time()
 rounds = streams = 0
+
+
+def index_mode():
+    """Batches of random token streams (every window, literal width and format; resets spliced in; some cut anywhere) ->
+    offsets, closed and open sizes and status of index_resets against read_tokens."""
+    global rounds, streams
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, 'tests'))
+    from long_stream_writer import TokenWriter, mixed, oob, read_tokens
+
+    def truth(blob):
+        if len(blob) < 2:
+            return 2, [], [], 0
+        toks, window = read_tokens(blob)[:2]
+        offs, closed, seg, prev = [], [], 0, False
+        for tk in toks:
+            flush = tk.kind == 'F'
+            if flush and prev:
+                offs.append((tk.bit + tk.nbits) >> 3), closed.append(seg)
+                seg = 0
+            seg, prev = seg + tk.produced, flush
+        return (-4 if any(oob(tk, window) for tk in toks) else 0), offs, closed, seg
+
+    while time.time() - t0 < budget:
+        blobs = []
+        for _ in range(rng.choice([1, 5, 70, 300])):
+            w = TokenWriter(rng.randrange(8, 16), rng.randrange(5, 9), rng.random() < 0.5, more=0)
+            end = w.bit + rng.choice([0, 50, 900, 1100, 5000, 70000, 140000])
+            while w.bit < end:
+                mixed(w, rng, min(end, w.bit + rng.randrange(1, 3000)))
+                for _ in range(rng.choice([0, 1, 2, 2, 3, 50])):
+                    w.flush()
+                if rng.random() < 0.02:
+                    w.match(w.W - 1, w.minp, check=False)
+            blob = w.blob()
+            blobs.append(blob[: rng.randrange(len(blob) + 1)] if rng.random() < 0.2 else blob)
+        scan = tamp_amd.index_resets(blobs)
+        for i, blob in enumerate(blobs):
+            a, b = int(scan.index.first[i]), int(scan.index.first[i + 1])
+            got = (int(scan.status[i]), scan.index.off[a:b].tolist(), scan.closed_size[a:b].tolist(), int(scan.open_size[i]))
+            if got != truth(blob):
+                print('INDEX MISMATCH', i, len(blob), blob[:1].hex(), got[0], truth(blob)[0], len(got[1]), len(truth(blob)[1]))
+                open('fuzz_index_fail.bin', 'wb').write(blob)  # (the stream that differs, into the working directory)
+                sys.exit(1)
+        rounds += 1
+        streams += len(blobs)
+    print(f"index fuzz ok: {rounds} rounds, {streams} streams, {time.time() - t0:.0f} s")
+    sys.exit(0)
+
+
+if len(sys.argv) > 2 and sys.argv[2] == 'index':
+    index_mode()
 gens = [lambda n, L, k: wl.synth_text(n, L, first_index=k), lambda n, L, k: wl.lcg_runs(n, L, first_index=k),
         lambda n, L, k: wl.stress(n, L, first_index=k), lambda n, L, k: wl.telemetry(n, L, first_index=k),
         lambda n, L, k: np.random.default_rng(k).integers(0, 256, (n, L), dtype=np.uint8),
