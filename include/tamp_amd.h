@@ -574,6 +574,85 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t *in, const uin
                            size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
 
 /*
+ * WRITING byte ranges into such streams: the other half of random access.  Write q replaces the decoded bytes
+ * [write_begin[q], write_begin[q] + write_len[q]) of stream write_stream[q] with src[src_off[q] .. + write_len[q]).  Only the segments
+ * a write touches are decoded (by tamp_batch_read_ranges' own steps), patched and compressed again; every other segment keeps its
+ * compressed bytes and is copied to its new place, and the index is shifted.  A stream's decoded size never changes: a write that
+ * reaches beyond the end is refused, it does not extend the stream.  Not in the reference.
+ *   conf                    how the touched segments are compressed: dictionary_reset = 1, use_custom_dictionary = 0, and window, literal
+ *                           and extended as in every written stream's header; lazy_matching is the caller's choice, as for compress
+ *   in, in_off, in_len, reset_first, reset_off, reset_interval   the streams and their index, as for tamp_batch_read_ranges; only read
+ *   write_stream, write_begin, write_len, src_off   n_writes entries each, where `mem` says; only read.  SORTED by (write_stream,
+ *                           write_begin) and, within a stream, NOT OVERLAPPING: checked on the device, write q against q - 1.  That is
+ *                           what makes patching free of races with one unit of work per write, and the touched segments of the batch
+ *                           a flag array and a scan.  Two writes in one segment make ONE unit, compressed once; a write of length 0
+ *                           touches nothing (its stream is not looked at), but it stands in the order like any other
+ *   src                     the source bytes, where `mem` says; only read
+ *   out, out_off, out_cap   the new stream i comes back in out[out_off[i] ..), out_cap[i] bytes of room
+ *   new_reset_off           optional, parallel to reset_off: the new streams' index.  The new stream has the old one's header and as many
+ *                           resets, so reset_first holds for it unchanged.  Entries of a failing stream mean nothing
+ *   out_len[i], status[i]   per stream.  Of the stream's writes the one with the lowest q that fails decides, and of the rules the
+ *                           first that applies to it:
+ *       write_stream[q] >= n_streams .......................................... the write is ignored: it has no stream to fail
+ *       write q lies in front of write q - 1 (a lower stream, or the same stream
+ *       and a begin in front of the predecessor's end) .......................... TAMP_AMD_BAD_ARGUMENT
+ *       (write_len[q] == 0: nothing more is asked of it)
+ *       the header has no reset bit, a non-zero second byte, the custom bit, a
+ *       window above max_window_bits, or window / literal / extended other than
+ *       conf's ................................................................ TAMP_INVALID_CONF
+ *       the stream's rows of reset_first are no running sum from 0 ............ TAMP_AMD_BAD_INDEX
+ *       the write begins or ends behind the stream's decoded end (the open
+ *       segment's size is known once it is walked; a write that touches closed
+ *       segments only needs no look at the open one) ........................... TAMP_INPUT_EXHAUSTED
+ *       an offset out of the window in a touched segment ...................... TAMP_OOB
+ *       a touched segment whose index entries do not hold: the conditions of
+ *       tamp_batch_read_ranges (out of range or order, a closed segment that does
+ *       not end at its entry behind FLUSH, FLUSH or does not decode to exactly
+ *       reset_interval bytes, the open one decoding to more) ................... TAMP_AMD_BAD_INDEX
+ *       a touched segment that did not decode to what the walk found (a defect
+ *       of the library) ........................................................ TAMP_ERROR
+ *       a source byte that does not fit conf->literal bits .................... TAMP_EXCESS_BITS
+ *     and, of the stream as a whole: its touched segments alone outgrow the scratch budget (below): TAMP_AMD_BAD_ARGUMENT, in front of
+ *     every rule above; an untouched segment whose entries lie outside the stream or out of order: TAMP_AMD_BAD_INDEX; the new stream
+ *     longer than out_cap[i]: TAMP_OUTPUT_FULL, behind every rule above.
+ *     A failing stream has out_len[i] = 0 and unspecified bytes in its slab; nothing is ever written outside [out_off[i], out_off[i] +
+ *     out_cap[i]), and no other stream is affected.  A stream no write touches (none, or writes of length 0 only) is copied unchanged,
+ *     whatever it holds, with TAMP_OK (TAMP_OUTPUT_FULL when it does not fit), and its entries are copied with it.
+ * THE RESULT, bit for bit: every untouched segment keeps its compressed bytes exactly; every touched segment is what
+ * tamp_batch_compress_resets writes for that segment's patched bytes under `conf`.  Hence, for streams tamp_batch_compress_resets_index
+ * made under the same conf and reset_interval, the new streams and new_reset_off are byte for byte what that call returns for the
+ * patched inputs.
+ * WHAT THE INDEX IS TRUSTED FOR.  As in tamp_batch_read_ranges the index is trusted for POSITION and checked on the TOUCHED segments
+ * only: an entry of an untouched segment that is moved but still in range and order is not noticed -- the bytes between the entries
+ * are copied whichever tokens they hold -- and the new index carries the same displacement.  Memory safety holds for any contents of
+ * every table (reset_off must have reset_first[n_streams] entries, as ever).
+ *   mem, device, stream   TAMP_AMD_ALL_DEVICES is not taken.  A device-memory call WAITS for the 8 bytes of reset_first[n_streams] (they
+ *                   size its per-segment tables), for one 16-byte record (the units of the call), and once per slice inside the decode
+ *                   step, which is tamp_batch_read_ranges' (its 16-byte record; see there for its header pre-pass); everything else is
+ *                   asynchronous on `stream`.  A host-memory call is synchronous: the streams, the tables and the sources go up, the
+ *                   result tables and exactly the produced bytes come back.
+ * SCRATCH is kept per HIP stream (tamp_amd_trim releases it): 18 bytes per segment and 32 per stream of the batch, and per unit a staging
+ * row of reset_interval bytes, a slab and 64 bytes of rows, within the budget of tamp_batch_read_ranges (a quarter of the free device
+ * memory, 8 GiB at most, TAMP_AMD_RANGES_SCRATCH_MB instead of both); the decode step takes its own scratch by the same rule.  A call
+ * whose units outgrow the budget runs in slices of whole streams (it then reads two tables of n_streams + 1 entries back to cut them).
+ * With TAMP_AMD_RESETS_DEBUG set the call writes one line to stderr:
+ * "[tamp_amd resets] write ranges: <w> writes, <u> units, <s> slices, <b> bytes staged" (b: the decoded bytes of the units).
+ * Returns TAMP_OK (n_streams == 0: at once, nothing is done; n_writes == 0: every stream is copied and new_reset_off filled from
+ * reset_off); TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null conf, in_off, in_len, reset_first, out_off, out_cap,
+ * out_len or status, a null write table, src or src_off with n_writes > 0, a null `in` or `out` with n_streams > 0, reset_interval == 0
+ * or one whose worst-case segment does not fit 32 bits, a conf that tamp_batch_compress_resets refuses, a bad memory kind,
+ * TAMP_AMD_ALL_DEVICES, n_streams or n_writes >= 2^32; TAMP_AMD_BAD_ARGUMENT for 2^32 - 1 touched segments or more; TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_write_ranges(const TampAmdConf *conf, uint8_t max_window_bits,
+                            const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                            const uint64_t *reset_first, const uint32_t *reset_off, uint32_t reset_interval,
+                            const uint32_t *write_stream, const uint64_t *write_begin, const uint32_t *write_len,
+                            const uint8_t *src, const uint64_t *src_off,
+                            uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int8_t *status,
+                            uint32_t *new_reset_off /* may be NULL */,
+                            size_t n_streams, size_t n_writes, int mem, int device, void *stream);
+
+/*
  * FINDING the resets of streams that came without an index: a blob of tamp_amd_compress_resets, a file, a batch whose index was not
  * kept, anything a reference Compressor(dictionary_reset=True) wrote with reset_dictionary() calls of its own or in append mode.
  * The call returns the table tamp_batch_compress_resets_index writes, found on the device: the compressed bits of every stream are
@@ -819,7 +898,7 @@ float tamp_amd_last_kernel_ms(void);
 /* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
  * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
  * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
- * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
+ * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the tables, staging rows and slabs of tamp_batch_write_ranges, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
  * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.

@@ -860,6 +860,191 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
     return RangeResult(out, out_off, out_len, status, ms)
 
 
+def _write_tables(stream_index, begin, length, source_off, n_streams):
+    """Not part of the package's surface: the host tables of ``write_ranges`` as the C call takes them -- checked, then sorted stably
+    by (stream, begin), writes of no bytes first among equals.  -> (stream uint32, begin uint64, length uint32, source_off uint64); ValueError on negative values, values
+    that do not fit, a stream index out of range, and writes of one stream that overlap."""
+    def table(t, what, most, dt):  # (a sequence goes through Python integers: 2^64 - 1 is one)
+        a = t.cpu().numpy() if _is_torch(t) else (t if isinstance(t, np.ndarray) else np.array([int(x) for x in t] or [0], dtype=object)[: len(t)])
+        if a.dtype.kind not in "iuO":
+            raise ValueError(what + ": integers expected")
+        if len(a) and int(a.min()) < 0:
+            raise ValueError(what + ": negative")
+        if len(a) and int(a.max()) > most:
+            raise ValueError(what + ": does not fit %d bits" % most.bit_length())
+        return np.ascontiguousarray(a.astype(dt))
+
+    w_stream = table(stream_index, "stream_index", 0xFFFFFFFF, np.uint32)
+    w_begin = table(begin, "begin", (1 << 64) - 1, np.uint64)
+    w_len = table(length, "length", 0xFFFFFFFF, np.uint32)
+    w_src = table(source_off, "source_off", (1 << 64) - 1, np.uint64)
+    if len(w_stream) and int(w_stream.max()) >= n_streams:
+        raise ValueError("stream_index: out of range")
+    # (stable: writes with the same stream and begin keep their order, but one of no bytes goes in front of one that begins where it
+    # stands -- behind it, it would stand inside its predecessor)
+    order = np.lexsort((w_len != 0, w_begin, w_stream))
+    w_stream, w_begin, w_len, w_src = (np.ascontiguousarray(a[order]) for a in (w_stream, w_begin, w_len, w_src))
+    if len(w_stream) > 1:
+        end = w_begin[:-1] + w_len[:-1].astype(np.uint64)  # (a sum 64 bits do not hold wraps: behind everything)
+        same = w_stream[1:] == w_stream[:-1]
+        if bool((same & ((w_begin[1:] < end) | (end < w_begin[:-1]))).any()):
+            raise ValueError("writes of one stream overlap")
+    return w_stream, w_begin, w_len, w_src
+
+
+def _write_bound(entries, interval: int, literal: int):
+    """``compress_resets_bound((E + 1) * interval, interval, literal)`` per stream of ``E`` entries, without the 32-bit mask that
+    function puts on lengths: ``E`` closed segments and one more full one.  ``entries``: a uint64 array or an int64 tensor."""
+    closed, last = 2 + (interval * (literal + 1) + 16) // 8, 2 + (interval * (literal + 1) + 7) // 8
+    if _is_torch(entries):
+        return entries * closed + last
+    return entries * np.uint64(closed) + np.uint64(last)
+
+
+def write_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, begin, source, source_off=None, length=None,
+                 reset_interval=None, lazy_matching: bool = False, out_cap=None, max_window_bits: int = 15, device: int = 0, stream=None,
+                 timing: bool = False, window=None, literal=None, extended=None) -> BatchResult:
+    """Write byte ranges into reset-segmented streams without compressing the rest again (``tamp_batch_write_ranges``, DESIGN.md 3.13;
+    not in the reference).  ``data``, ``reset_index`` and ``reset_interval`` as for ``read_ranges``.  Write ``q`` replaces the decoded
+    bytes ``[begin[q], begin[q] + length[q])`` of stream ``stream_index[q]``.  ``source``: a sequence of bytes-likes, one per write
+    (``source_off`` and ``length`` are then derived), or one flat uint8 buffer (numpy array or CUDA tensor) with ``source_off`` and
+    ``length``.  Only the touched segments are decoded, patched and compressed again; the others keep their bytes.  A stream's size
+    never changes: a write beyond its end fails the stream with status 2.  The result holds the new streams in slabs, and
+    ``res.reset_index`` their index.  For streams ``compress_batch(..., reset_interval=N, reset_index=True)`` made, the result is byte
+    for byte what that call makes of the patched data.  ``window``, ``literal``, ``extended``: how the touched segments are compressed;
+    they must be the streams' own -- read from the first stream's header for host data, required with CUDA tensors (no sync is hidden).
+    Host tables may come in any order (they are sorted by stream and begin; overlapping writes raise ``ValueError``, and so does a write of no bytes INSIDE another); CUDA tables of a
+    CUDA call are passed as they are and must be sorted already -- a stream whose writes are not gets status -21.
+    ``out_cap=None`` sizes the slabs from the index: no stream of ``E`` entries can take more than ``E + 1`` full segments do."""
+    if not isinstance(reset_index, ResetIndex):  # (all decided before the library is looked for)
+        raise ValueError("reset_index: a ResetIndex expected")
+    on_device = _is_torch(data)
+    n_streams = len(data) if in_off is None and not on_device else len(in_len)
+    if len(reset_index.first) != n_streams + 1:
+        raise ValueError("reset_index.first: one entry per stream and one more expected")
+    interval = reset_interval if reset_interval is not None else reset_index.interval
+    if interval is None:
+        raise ValueError("reset_interval: not given and not in the index")
+    if not _is_int(interval) or not 1 <= int(interval) <= 0xFFFFFFFF:
+        raise ValueError("reset_interval: a positive integer that fits 32 bits expected")
+    interval = int(interval)
+    pieces = not _is_torch(source) and not isinstance(source, np.ndarray)
+    if pieces:
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            raise ValueError("source: a sequence of bytes-likes, one per write, or a flat uint8 buffer with source_off and length")
+        if source_off is not None or length is not None:
+            raise ValueError("source_off and length are derived from a sequence of sources")
+        parts = [_np_u8(x) for x in source]
+        length = np.array([p.size for p in parts], dtype=np.uint64)
+        source_off = np.cumsum(length) - length
+        source = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    elif source_off is None or length is None:
+        raise ValueError("a flat source needs source_off and length")
+    if not len(stream_index) == len(begin) == len(length) == len(source_off):
+        raise ValueError("stream_index, begin, length and the sources: one entry per write each")
+    if on_device != _is_torch(source) and not (on_device and pieces):
+        raise ValueError("source: where the data is (a CUDA tensor with CUDA data)")
+    if on_device and (window is None or literal is None or extended is None):
+        raise ValueError("window, literal and extended are required with CUDA tensors")
+    for name, v, lo, hi in (("window", window, 8, 15), ("literal", literal, 5, 8)):
+        if v is not None and (not _is_int(v) or not lo <= int(v) <= hi):
+            raise ValueError(f"{name} must be in {lo}..{hi}, not {v!r}")
+    if out_cap is not None and not _is_int(out_cap) and len(out_cap) != n_streams:
+        raise ValueError("out_cap: one entry per stream expected")
+    if _is_int(out_cap) and not 0 <= int(out_cap) <= 0xFFFFFFFF:
+        raise ValueError("out_cap: does not fit 32 bits")
+    n_writes = len(stream_index)
+    tables = (stream_index, begin, length, source_off)
+    if not (on_device and all(_is_torch(t) for t in tables)):  # (CUDA tables of a CUDA call: the device check answers for them)
+        stream_index, begin, length, source_off = _write_tables(stream_index, begin, length, source_off, n_streams)
+    if stream is not None and on_device:
+        import torch  # (tables and output on the launch stream: see compress_batch)
+
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return write_ranges(data, in_off, in_len, reset_index=reset_index, stream_index=stream_index, begin=begin,
+                                source=source if _is_torch(source) else torch.from_numpy(source).to(data.device), source_off=source_off,
+                                length=length, reset_interval=interval, lazy_matching=lazy_matching, out_cap=out_cap,
+                                max_window_bits=max_window_bits, device=device, stream=None, timing=timing, window=window, literal=literal,
+                                extended=extended)
+    lib = _lib.load()
+    lib.tamp_amd_set_timing(1 if timing else 0)
+    if on_device:
+        import torch
+
+        dev = data.device
+        as_t = lambda x, dt: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.uint64).view(np.int64))).to(device=dev, dtype=dt)  # noqa: E731
+        conf = _conf(int(window), int(literal), extended, None, True, lazy_matching)
+        first_t, off_t = as_t(reset_index.first, torch.int64), as_t(reset_index.off, torch.int32)
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        stream_t, begin_t, length_t = as_t(stream_index, torch.int32), as_t(begin, torch.int64), as_t(length, torch.int32)
+        src_off_t = as_t(source_off, torch.int64)
+        src_t = source if _is_torch(source) else torch.from_numpy(source).to(dev)
+        if out_cap is None:
+            cap64 = _write_bound(first_t[1:] - first_t[:-1], interval, int(literal))
+            cap64 = torch.maximum(cap64, in_len_t.to(torch.int64) & 0xFFFFFFFF)  # (a stream no write touches is copied as it stands)
+            if n_streams and int(cap64.max().item()) > 0xFFFFFFFF:
+                raise ValueError("a stream's bound does not fit 32 bits: pass out_cap")
+        elif _is_int(out_cap):
+            cap64 = torch.full((n_streams,), int(out_cap), dtype=torch.int64, device=dev)
+        else:
+            cap64 = as_t(out_cap, torch.int64) & 0xFFFFFFFF
+        out_cap_t = cap64.to(torch.int32)  # (the low 32 bits: what the library reads as uint32)
+        out_off_t = torch.cumsum(cap64, 0) - cap64
+        total = int(cap64.sum().item()) if n_streams else 0
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        out_len_t = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+        status_t = torch.zeros(n_streams, dtype=torch.int8, device=dev)
+        new_off_t = torch.zeros(max(int(off_t.numel()), 1), dtype=torch.int32, device=dev)[: int(off_t.numel())]
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check_launch(lib.tamp_batch_write_ranges(
+            C.byref(conf), max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(first_t), _ptr(off_t) if off_t.numel() else None,
+            interval, _ptr(stream_t), _ptr(begin_t), _ptr(length_t), _ptr(src_t if src_t.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)),
+            _ptr(src_off_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t), _ptr(status_t),
+            _ptr(new_off_t) if new_off_t.numel() else None, n_streams, n_writes, _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st)))
+        ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+        return BatchResult(out, out_off_t, out_len_t, status_t, None, ms,
+                           (data, in_off_t, in_len_t, first_t, off_t, stream_t, begin_t, length_t, src_t, src_off_t, out_cap_t),
+                           reset_index=ResetIndex(first_t, new_off_t, interval))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    if n_streams and int(in_len[0]) and (window is None or literal is None or extended is None):
+        h0 = int(flat[int(in_off[0])])  # (the first stream's header: what every written stream must have)
+        window = (h0 >> 5) + 8 if window is None else window
+        literal = ((h0 >> 3) & 3) + 5 if literal is None else literal
+        extended = bool((h0 >> 1) & 1) if extended is None else extended
+    conf = _conf(int(window) if window is not None else 10, int(literal) if literal is not None else 8,
+                 True if extended is None else extended, None, True, lazy_matching)
+    to_np = lambda x, dt: np.ascontiguousarray((x.cpu().numpy() if _is_torch(x) else np.asarray(x)).astype(dt))  # noqa: E731
+    first, off = to_np(reset_index.first, np.uint64), to_np(reset_index.off, np.uint32)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    src = _np_u8(source)
+    if not src.size:
+        src = np.zeros(1, np.uint8)
+    if out_cap is None:
+        out_cap = np.maximum(_write_bound(first[1:] - first[:-1], interval, int(conf.literal)), in_len.astype(np.uint64))
+        if n_streams and int(out_cap.max()) > 0xFFFFFFFF:
+            raise ValueError("a stream's bound does not fit 32 bits: pass out_cap")
+    elif _is_int(out_cap):
+        out_cap = np.full(n_streams, int(out_cap), dtype=np.uint32)
+    out_cap = np.ascontiguousarray(out_cap, dtype=np.uint32)
+    out_off, total = _slab_offsets(out_cap)
+    out = np.zeros(total + 1, dtype=np.uint8)
+    out_len, status = np.zeros(n_streams, dtype=np.uint32), np.zeros(n_streams, dtype=np.int8)
+    new_off = np.zeros(off.size, dtype=np.uint32)
+    _lib.check_launch(lib.tamp_batch_write_ranges(
+        C.byref(conf), max_window_bits, _ptr(flat), _ptr(in_off), _ptr(in_len), _ptr(first), _ptr(off) if off.size else None, interval,
+        _ptr(stream_index), _ptr(begin), _ptr(length), _ptr(src), _ptr(source_off), _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len),
+        _ptr(status), _ptr(new_off) if off.size else None, n_streams, n_writes, _lib.MEM_HOST, device,
+        C.c_void_p(stream) if stream else None))
+    ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+    return BatchResult(out, out_off, out_len, status, None, ms, reset_index=ResetIndex(first, new_off, interval))
+
+
 @dataclass
 class ResetScan:
     """What ``index_resets`` found: the batch's ``ResetIndex`` and, from the token grammar alone, the decoded sizes."""

@@ -33,6 +33,7 @@
 #include "tamp_compress_resume_kernel.hpp"
 #include "tamp_reset_segments_kernel.hpp"
 #include "tamp_read_ranges_kernel.hpp"
+#include "tamp_write_ranges_kernel.hpp"
 #include "tamp_reset_index_kernel.hpp"
 #include "tamp_pack_kernel.hpp"
 
@@ -76,7 +77,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_index_resets and launch_pack and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_index_resets and launch_pack and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -94,6 +95,7 @@ struct StreamScratch {
     DeviceBuf resets;      // dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets), a batch's per-stream words in front (launch_compress_batch_resets)
     DeviceBuf pack;        // tamp_batch_pack: the scan's per-workgroup sums (8 KiB, allocated once)
     DeviceBuf ranges;      // tamp_batch_read_ranges: the per-range scans and verdicts (the units, stage and scratch of a slice: `resets`)
+    DeviceBuf writes, write_units;  // tamp_batch_write_ranges: its tables per stream and per segment; the rows, staging rows and slabs of a slice's units
     DeviceBuf index_streams, index_chunks, index_entries;  // tamp_batch_index_resets: its tables per stream, per chunk, per entry
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
@@ -106,7 +108,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &index_streams, &index_chunks, &index_entries}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &writes, &write_units, &index_streams, &index_chunks, &index_entries}) n += b->release();
         return n;
     }
 };
@@ -2416,16 +2418,14 @@ void read_ranges_debug(uint64_t ranges, uint64_t units, size_t slices, uint64_t 
 
 // Device memory: everything is counted, cut and staged on the device; the call waits once, for the 16-byte record that sizes the
 // region -- and, only when the call does not fit ONE slice, for the three scans that say where to cut it.
-int launch_read_ranges(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
-                       int8_t* status, hipStream_t st) {
-    StreamScratch& rec = ctx->scratch(st);
-    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
-    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+// `rec`: the stream's scratch record, locked by the caller (launch_read_ranges; launch_write_ranges, whose touched segments are read
+// as ranges of their own), who also holds the call's event pair.
+int launch_read_ranges_locked(DeviceCtx* ctx, StreamScratch& rec, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off,
+                              uint32_t* out_len, int8_t* status, bool dbg, hipStream_t st) {
     const uint64_t nr = c.n_ranges, budget = read_ranges_budget(rec);
     HIP_OK(rec.ranges.need(read_ranges_bytes(nr)));
     uint8_t* const tabs = static_cast<uint8_t*>(rec.ranges.p);
     const ReadRanges r = read_ranges_at(tabs, nr);
-    const CallTiming call_timing(st);
     const ReadCountArgs count = {c, budget, r, reinterpret_cast<ReadRecord*>(tabs)};
     hipLaunchKernelGGL(tamp_read_count_kernel, dim3(1), dim3(kResetScanTile), 0, st, count);
     HIP_OK(hipGetLastError());
@@ -2467,6 +2467,13 @@ int launch_read_ranges(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, u
         read_ranges_debug(nr, have.units, slices.size(), staged);
     }
     return TAMP_OK;
+}
+int launch_read_ranges(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                       int8_t* status, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const CallTiming call_timing(st);
+    return launch_read_ranges_locked(ctx, rec, c, max_wbits, out, out_off, out_len, status, getenv("TAMP_AMD_RESETS_DEBUG") != nullptr, st);
 }
 
 // Host memory, on the host pipeline's first stream (one host-memory call per device at a time): the host counts and cuts with the
@@ -2584,6 +2591,239 @@ int batch_read_ranges(const ReadCaller& c, uint8_t max_wbits, uint8_t* out, cons
     if (mem == TAMP_AMD_MEM_DEVICE) return launch_read_ranges(ctx, c, max_wbits, out, out_off, out_len, status, static_cast<hipStream_t>(stream));
     if (!c.off && c.n && c.first[c.n] != 0) return TAMP_AMD_BAD_ARGUMENT;  // (entries and no table to hold them)
     return read_ranges_host(ctx, c, max_wbits, out, out_off, out_len, status);
+}
+
+// Writing byte ranges into reset-segmented streams (tamp_batch_write_ranges; kernels and steps: tamp_write_ranges_kernel.hpp, the
+// arithmetic: tamp_write_ranges.hpp).  The per-stream and per-segment tables of the whole call lie in `writes`; the units run in
+// SLICES of whole streams, each of which fits the budget with its rows, staging rows and slabs (`write_units`).  The decode of a
+// slice's units is launch_read_ranges_locked over one range per unit (its own tables: `ranges`, `resets`).
+struct WriteOut {
+    uint8_t* out;
+    const uint64_t* out_off;
+    const uint32_t* out_cap;
+    uint32_t* out_len;
+    int8_t* status;
+    uint32_t* new_reset_off;  // may be null
+};
+struct WriteSliceSpan { uint64_t i0, i1, u0, U, o0, Uo; bool run; };
+// All pointers: device memory.  `segments`: reset_first[n] + n when the caller has it from host tables, else null: the call then
+// waits for the table's last entry.  It waits for the 16-byte record of the units; a call that does not fit one slice reads two
+// tables more to cut it.
+int launch_write_ranges(DeviceCtx* ctx, const TampAmdConf* conf, const WriteCaller& c, uint8_t max_wbits, const WriteOut& o,
+                        const uint64_t* segments, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    const uint64_t n = c.n, nw = c.n_writes;
+    uint64_t S = 0;
+    if (segments) S = *segments;
+    else {
+        uint64_t entries = 0;
+        HIP_OK(hipMemcpyAsync(&entries, c.first + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (entries + n < entries) return TAMP_AMD_BAD_ARGUMENT;
+        S = entries + n;
+    }
+    // the tables: 8-byte ones, 4-byte ones, bytes
+    const size_t at_fail = 256, at_fail0 = at_fail + 8 * n, at_ufirst = at_fail0 + 8 * n, at_ofirst = at_ufirst + 8 * (n + 1);
+    const size_t at_unit = at_ofirst + 8 * (n + 1), at_open = at_unit + 4 * (S + 1), at_pos = at_open + 4 * (S + 1), at_len = at_pos + 4 * S;
+    const size_t at_owner = at_len + 4 * S, at_flags = at_owner + 4 * S, at_whole = at_flags + S, all_bytes = at_whole + n + 64;
+    HIP_OK(rec.writes.need(all_bytes));
+    uint8_t* const base = static_cast<uint8_t*>(rec.writes.p);
+    WriteTables t;
+    t.S = S;
+    t.fail = reinterpret_cast<uint64_t*>(base + at_fail), t.fail0 = reinterpret_cast<uint64_t*>(base + at_fail0);
+    t.unit_first = reinterpret_cast<uint64_t*>(base + at_ufirst), t.open_first = reinterpret_cast<uint64_t*>(base + at_ofirst);
+    t.unit_at = reinterpret_cast<uint32_t*>(base + at_unit), t.open_at = reinterpret_cast<uint32_t*>(base + at_open);
+    t.new_pos = reinterpret_cast<uint32_t*>(base + at_pos), t.new_len = reinterpret_cast<uint32_t*>(base + at_len);
+    t.owner = reinterpret_cast<uint32_t*>(base + at_owner), t.flags = base + at_flags, t.whole = base + at_whole;
+    const uint32_t N = c.interval, row = write_row_bytes(N), slab = (uint32_t)reset_segment_bound(N, conf->literal, true);
+    const uint64_t budget = read_ranges_budget(rec), max_units = std::max<uint64_t>(budget / write_unit_cost(N, slab), 1);
+    const CallTiming call_timing(st);
+    HIP_OK(hipMemsetAsync(t.fail, 0xFF, 8 * n, st));
+    HIP_OK(hipMemsetAsync(t.owner, 0xFF, 4 * S, st));  // (none)
+    HIP_OK(hipMemsetAsync(t.flags, 0, S + n, st));             // (flags and whole, one behind the other)
+    if (nw) {
+        const WritePlanArgs plan = {c, t};
+        hipLaunchKernelGGL(tamp_write_plan_kernel, dim3((uint32_t)((nw + 255) / 256)), dim3(256), 0, st, plan);
+    }
+    const WriteScanArgs scan = {t, reinterpret_cast<WriteRecord*>(base)};
+    hipLaunchKernelGGL(tamp_write_scan_kernel, dim3(1), dim3(kResetScanTile), 0, st, scan);
+    const WriteStreamsArgs streams = {c, t, max_units};
+    hipLaunchKernelGGL(tamp_write_streams_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, st, streams);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(t.fail0, t.fail, 8 * n, hipMemcpyDeviceToDevice, st));
+    WriteRecord have = {0, 0};
+    HIP_OK(hipMemcpyAsync(&have, base, sizeof have, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (have.units >= 0xFFFFFFFFull) {
+        snprintf(t_last_error, sizeof t_last_error, "write ranges: %llu touched segments", (unsigned long long)have.units);
+        return TAMP_AMD_BAD_ARGUMENT;
+    }
+    std::vector<WriteSliceSpan> slices = {{0, n, 0, have.units, 0, have.open_units, true}};
+    if (have.units > max_units) {
+        std::vector<uint64_t> firsts(2 * (n + 1));  // (unit_first and open_first lie one behind the other)
+        HIP_OK(hipMemcpyAsync(firsts.data(), t.unit_first, firsts.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        uint64_t* const uf = firsts.data();
+        uint64_t* const of = uf + n + 1;
+        for (uint64_t i = 1; i <= n; i++) uf[i] = std::max(uf[i], uf[i - 1]), of[i] = std::max(of[i], of[i - 1]);  // (any table: in order)
+        slices.clear();
+        for (uint64_t i0 = 0; i0 < n;) {  // as many whole streams as fit, one at least (its units do not run when it alone is too many)
+            uint64_t i1 = i0 + 1;
+            while (i1 < n && uf[i1 + 1] - uf[i0] <= max_units) i1++;
+            const uint64_t U = uf[i1] - uf[i0];
+            slices.push_back({i0, i1, uf[i0], U, of[i0], std::min(of[i1] - of[i0], U), U <= max_units});
+            i0 = i1;
+        }
+    }
+    uint64_t most = 0;
+    for (const WriteSliceSpan& s : slices) most = std::max(most, s.run ? s.U : 0);
+    HIP_OK(rec.write_units.need(write_region_bytes(most, row, slab) + 256));
+    uint8_t* const region = static_cast<uint8_t*>(rec.write_units.p);
+    const SegmentSpec with_token = {2, (uint16_t)(0xABu << 7), kSegFlushToken}, without = {2, (uint16_t)(0xABu << 7), 0};
+    const uint32_t wide = (uint32_t)ctx->cu_count * 8;
+    uint64_t staged = 0;
+    for (const WriteSliceSpan& span : slices) {
+        const uint64_t U = span.run ? span.U : 0, Uo = span.run ? span.Uo : 0;
+        const WriteSlice s = {span.i0, span.i1, span.u0, U, span.o0, Uo, region, row, slab};
+        if (U) {
+            const WriteRows w = write_rows_at(region, U);
+            HIP_OK(hipMemsetAsync(region, 0, write_rows_bytes(U), st));
+            const WriteRowsArgs rows = {c, t, s};
+            hipLaunchKernelGGL(tamp_write_rows_kernel, dim3((uint32_t)((U + 255) / 256)), dim3(256), 0, st, rows);
+            HIP_OK(hipGetLastError());
+            const ReadCaller rc = {c.in, c.in_off, c.in_len, c.first, c.off, n, N, c.max_wbits, w.stream, w.begin, w.len, U};
+            if (const int r = launch_read_ranges_locked(ctx, rec, rc, max_wbits, region, w.row_off, w.size, w.read_status, false, st)) return r;
+            if (nw) {
+                const WritePatchArgs patch = {c, t, s};
+                hipLaunchKernelGGL(tamp_write_patch_kernel, dim3((uint32_t)std::min<uint64_t>(nw, wide)), dim3(256), 0, st, patch);
+                HIP_OK(hipGetLastError());
+            }
+            BatchTables seg;
+            seg.in = region, seg.in_off = w.row_off, seg.in_len = w.size, seg.out = region, seg.out_off = w.slab_off, seg.out_cap = w.cap;
+            seg.out_len = w.out_len, seg.status = w.status, seg.n = U;
+            if (const int r = launch_compress_locked(ctx, rec, conf, seg.rows(0, U - Uo), N, st, &with_token, nullptr)) return r;
+            if (const int r = launch_compress_locked(ctx, rec, conf, seg.rows(U - Uo, Uo), N, st, &without, nullptr)) return r;
+            if (dbg) {
+                std::vector<uint32_t> sizes(U);
+                HIP_OK(hipMemcpyAsync(sizes.data(), w.size, 4 * U, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                for (const uint32_t v : sizes) staged += v;
+            }
+        }
+        const WriteSpliceArgs splice = {c, t, s, o.out_cap, o.out_len, o.status, o.new_reset_off};
+        hipLaunchKernelGGL(tamp_write_splice_kernel, dim3((uint32_t)std::min<uint64_t>(span.i1 - span.i0, wide)), dim3(kResetScanTile), 0, st, splice);
+        const WriteGatherArgs gather = {c, t, s, o.out, o.out_off, o.out_cap, o.status};
+        hipLaunchKernelGGL(tamp_write_gather_kernel, dim3((uint32_t)std::min<uint64_t>(S + (span.i1 - span.i0), wide)), dim3(256), 0, st, gather);
+        HIP_OK(hipGetLastError());
+    }
+    if (dbg)
+        fprintf(stderr, "[tamp_amd resets] write ranges: %llu writes, %llu units, %zu slices, %llu bytes staged\n", (unsigned long long)nw,
+                (unsigned long long)have.units, slices.size(), (unsigned long long)staged);
+    return TAMP_OK;
+}
+
+// tamp_batch_write_ranges behind its checks.  Host memory, on the host pipeline's kept buffers and first stream (one host-memory
+// call per device at a time): the extents of the streams and of the sources and every table go up; the output slabs lie back to back
+// on the device, each as long as its stream can get or as the caller allows, whichever is less; the result tables come back, then
+// exactly the produced bytes of every stream.
+int batch_write_ranges(const TampAmdConf* conf, const WriteCaller& c, uint8_t max_wbits, const WriteOut& o, int mem, int device, void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_write_ranges(ctx, conf, c, max_wbits, o, nullptr, static_cast<hipStream_t>(stream));
+    const uint64_t n = c.n, nw = c.n_writes, C = c.first[n];
+    if (!c.off && C) return TAMP_AMD_BAD_ARGUMENT;  // (entries and no table to hold them)
+    if (C + n < C) return TAMP_AMD_BAD_ARGUMENT;
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> pipe_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    const uint64_t unit_bound = reset_segment_bound(c.interval, conf->literal, true);
+    uint64_t in_lo = ~0ull, in_hi = 0, src_lo = ~0ull, src_hi = 0, room = 0;
+    std::vector<uint64_t> h_in_off(n), h_out_off(n), h_src_off(nw), grow(n, 0);
+    std::vector<uint32_t> h_cap(n);
+    for (uint64_t q = 0; q < nw; q++) {
+        const uint32_t i = c.write_stream[q], len = c.write_len[q];
+        if (i >= n || !len) continue;
+        src_lo = std::min(src_lo, c.src_off[q]), src_hi = std::max(src_hi, c.src_off[q] + len);
+        grow[i] += ((uint64_t)len / c.interval + 2) * unit_bound;  // (what its touched segments can take at most)
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t len = c.in_len[i];
+        if (len) in_lo = std::min(in_lo, c.in_off[i]), in_hi = std::max(in_hi, c.in_off[i] + len);
+        // the new stream: its untouched bytes, no more than it has, and its touched segments again
+        h_cap[i] = (uint32_t)std::min<uint64_t>(o.out_cap[i], std::min<uint64_t>((uint64_t)len + kResetHeaderBytes + grow[i], 0xFFFFFFFFull));
+        h_out_off[i] = room, room += h_cap[i];
+    }
+    if (in_hi < in_lo) in_lo = in_hi = 0;
+    if (src_hi < src_lo) src_lo = src_hi = 0;
+    for (uint64_t i = 0; i < n; i++) h_in_off[i] = c.in_len[i] ? c.in_off[i] - in_lo : 0;
+    for (uint64_t q = 0; q < nw; q++) h_src_off[q] = c.write_stream[q] < n && c.write_len[q] ? c.src_off[q] - src_lo : 0;
+    HIP_OK(P.in[0].need(in_hi - in_lo + 64));
+    HIP_OK(P.in[1].need(src_hi - src_lo + 64));
+    HIP_OK(P.out[0].need(room + 1));
+    // 8-byte tables, 4-byte tables, bytes
+    const size_t meta = 8 * (n + n + (n + 1) + nw + nw) + 4 * (n + n + n + C + C + nw + nw) + n + 64;
+    HIP_OK(P.meta[0].need(meta));
+    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
+    uint64_t* const d_out_off = d_in_off + n;
+    uint64_t* const d_first = d_out_off + n;
+    uint64_t* const d_begin = d_first + n + 1;
+    uint64_t* const d_src_off = d_begin + nw;
+    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_src_off + nw);
+    uint32_t* const d_cap = d_in_len + n;
+    uint32_t* const d_out_len = d_cap + n;
+    uint32_t* const d_off = d_out_len + n;
+    uint32_t* const d_new_off = d_off + C;
+    uint32_t* const d_wstream = d_new_off + C;
+    uint32_t* const d_wlen = d_wstream + nw;
+    int8_t* const d_status = reinterpret_cast<int8_t*>(d_wlen + nw);
+    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
+    if (src_hi > src_lo) HIP_OK(hipMemcpyAsync(P.in[1].p, c.src + src_lo, src_hi - src_lo, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_first, c.first, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_len, c.in_len, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_cap, h_cap.data(), n * 4, hipMemcpyHostToDevice, st));
+    if (C) HIP_OK(hipMemcpyAsync(d_off, c.off, C * 4, hipMemcpyHostToDevice, st));
+    if (nw) {
+        HIP_OK(hipMemcpyAsync(d_begin, c.write_begin, nw * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_src_off, h_src_off.data(), nw * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_wstream, c.write_stream, nw * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_wlen, c.write_len, nw * 4, hipMemcpyHostToDevice, st));
+    }
+    WriteCaller d = c;
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = d_in_off, d.in_len = d_in_len, d.first = d_first, d.off = C ? d_off : nullptr;
+    d.write_stream = d_wstream, d.write_begin = d_begin, d.write_len = d_wlen, d.src = static_cast<const uint8_t*>(P.in[1].p), d.src_off = d_src_off;
+    uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
+    const WriteOut dout = {d_out, d_out_off, d_cap, d_out_len, d_status, o.new_reset_off ? d_new_off : nullptr};
+    const uint64_t S = C + n;
+    if (const int rc = launch_write_ranges(ctx, conf, d, max_wbits, dout, &S, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(o.out_len, d_out_len, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(o.status, d_status, n, hipMemcpyDeviceToHost, st));
+    if (o.new_reset_off && C) HIP_OK(hipMemcpyAsync(o.new_reset_off, d_new_off, C * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t produced = 0;
+    for (uint64_t i = 0; i < n; i++) produced += o.out_len[i];
+    if (!produced) return TAMP_OK;
+    if (room <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(room) == hipSuccess) {
+        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
+        HIP_OK(hipMemcpyAsync(P.stage[0].p, d_out, room, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (uint64_t i = 0; i < n; i++)
+            if (o.out_len[i]) memcpy(o.out + o.out_off[i], stg + h_out_off[i], o.out_len[i]);
+        return TAMP_OK;
+    }
+    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
+    for (uint64_t i = 0; i < n; i++)
+        if (o.out_len[i]) HIP_OK(hipMemcpyAsync(o.out + o.out_off[i], d_out + h_out_off[i], o.out_len[i], hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return TAMP_OK;
 }
 
 // The reset index of a batch that came without one (tamp_batch_index_resets; kernels and steps: tamp_reset_index_kernel.hpp, the
@@ -3120,6 +3360,26 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t* in, const uin
     const ReadCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
                           range_stream, range_begin, range_len, n_ranges};
     return batch_read_ranges(c, max_window_bits, out, out_off, out_len, status, mem, device, stream);
+}
+
+int tamp_batch_write_ranges(const TampAmdConf* conf, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,
+                            const uint32_t* in_len, const uint64_t* reset_first, const uint32_t* reset_off, uint32_t reset_interval,
+                            const uint32_t* write_stream, const uint64_t* write_begin, const uint32_t* write_len, const uint8_t* src,
+                            const uint64_t* src_off, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len,
+                            int8_t* status, uint32_t* new_reset_off, size_t n_streams, size_t n_writes, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!conf || !in_off || !in_len || !reset_first || !out_off || !out_cap || !out_len || !status) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_writes && (!write_stream || !write_begin || !write_len || !src || !src_off)) return TAMP_AMD_BAD_ARGUMENT;
+    if (((!in || !out) && n_streams) || !reset_interval) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || n_writes > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (!conf_valid(conf) || conf->lazy_matching > 1 || !conf->dictionary_reset || conf->use_custom_dictionary) return TAMP_AMD_BAD_ARGUMENT;
+    // (a table row's capacity is 32 bits wide: an interval whose worst case does not fit one is not taken)
+    if (reset_segment_bound(reset_interval, conf->literal, true) > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams == 0) return TAMP_OK;  // (nothing is done)
+    const WriteCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
+                           (uint32_t)header_byte(conf, true), conf->literal, write_stream, write_begin, write_len, src, src_off, n_writes};
+    return batch_write_ranges(conf, c, max_window_bits, {out, out_off, out_cap, out_len, status, new_reset_off}, mem, device, stream);
 }
 
 int tamp_batch_index_resets(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,

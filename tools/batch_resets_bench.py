@@ -32,6 +32,15 @@ input's on every row.  Written to profiles/batch_reset_decode_bench.txt.
 Written to profiles/index_resets_bench.txt.
 
     python tools/batch_resets_bench.py --index [--before-root ../parent-checkout]
+
+`--write`: 1,000 random 4 KiB writes into the same batch, compressed once per process with its index ("Writing ranges"):
+  write, device / host   tamp_batch_write_ranges: only the touched segments are decoded, patched and compressed again
+  today, device / host   what a caller does without it: tamp_batch_decompress_resets of the whole batch, the patch (one indexed store
+                         in torch on the device, in numpy on the host), tamp_batch_compress_resets_index of the whole batch
+Median of the last ten of twelve calls in a fresh process, `--rounds` alternating runs; both ways must give the same streams and the
+same index (SHA-256).
+
+    python tools/batch_resets_bench.py --write
 """
 import argparse
 import hashlib
@@ -389,6 +398,144 @@ def index_main(args):
             f.write("\n".join(lines) + "\n")
 
 
+WRITES, WRITE_BYTES = 1000, 4096
+
+
+def write_child(which, reps):
+    """One row of --write: `write-device`, `write-host`, `today-device`, `today-host`."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from tamp_amd import _lib
+
+    lib = _lib.load()
+    kind, route = which.split("-")
+    flat, in_off, in_len = workload()
+    n, total = len(in_len), int(flat.size)
+    conf = _lib.TampAmdConf(10, 8, 0, 1, 1, 0)
+    cap = np.array([lib.tamp_amd_compress_resets_bound(int(x), INTERVAL, 8) for x in in_len], dtype=np.uint32)
+    c_off = np.zeros(n, dtype=np.uint64)
+    c_off[1:] = np.cumsum(cap.astype(np.uint64))[:-1]
+    entries = int(((np.maximum(in_len.astype(np.uint64), 1) - 1) // INTERVAL).sum())
+    room = np.minimum(in_len.astype(np.uint64) + 1, 0xFFFFFFFF).astype(np.uint32)
+    d_off = np.zeros(n, dtype=np.uint64)
+    d_off[1:] = np.cumsum(room.astype(np.uint64))[:-1]
+    # the writes: disjoint, sorted by (stream, begin); the same ones in every process
+    rng = np.random.default_rng(SEED + 1)
+    taken, rows = {}, []
+    while len(rows) < WRITES:
+        i = int(rng.integers(n))
+        if in_len[i] < WRITE_BYTES:
+            continue
+        b = int(rng.integers(int(in_len[i]) - WRITE_BYTES + 1))
+        if any(abs(b - o) < WRITE_BYTES for o in taken.get(i, ())):
+            continue
+        taken.setdefault(i, []).append(b)
+        rows.append((i, b))
+    rows.sort()
+    w_stream = np.array([r[0] for r in rows], dtype=np.uint32)
+    w_begin = np.array([r[1] for r in rows], dtype=np.uint64)
+    w_len = np.full(WRITES, WRITE_BYTES, dtype=np.uint32)
+    src = rng.integers(32, 127, WRITES * WRITE_BYTES, dtype=np.uint8)
+    src_off = np.arange(WRITES, dtype=np.uint64) * WRITE_BYTES
+    touched = len({(i, k) for i, b in rows for k in range(b // INTERVAL, (b + WRITE_BYTES - 1) // INTERVAL + 1)})
+    # where every source byte goes in the decoded batch (the patch of `today`)
+    where = (d_off[w_stream] + w_begin)[:, None] + np.arange(WRITE_BYTES, dtype=np.uint64)[None, :]
+    dev = torch.device("cuda:0")
+    host = route == "host"
+    mem = _lib.MEM_HOST if host else _lib.MEM_DEVICE
+    comp_room = int(cap.astype(np.uint64).sum()) + 1
+    arrays = dict(flat=flat, in_off=in_off.view(np.int64), in_len=in_len.view(np.int32), comp=np.zeros(comp_room, np.uint8),
+                  c_off=c_off.view(np.int64), cap=cap.view(np.int32), c_len=np.zeros(n, np.int32), c_status=np.full(n, 99, np.int8),
+                  first=np.zeros(n + 1, np.int64), off=np.zeros(max(entries, 1), np.int32), w_stream=w_stream.view(np.int32),
+                  w_begin=w_begin.view(np.int64), w_len=w_len.view(np.int32), src=src, src_off=src_off.view(np.int64),
+                  comp2=np.zeros(comp_room, np.uint8), c2_len=np.zeros(n, np.int32), c2_status=np.full(n, 99, np.int8),
+                  first2=np.zeros(n + 1, np.int64), off2=np.zeros(max(entries, 1), np.int32), where=where.reshape(-1).view(np.int64))
+    if kind == "today":
+        arrays.update(out=np.zeros(int(room.astype(np.uint64).sum()) + 1, np.uint8), d_off=d_off.view(np.int64), room=room.view(np.int32),
+                      d_len=np.zeros(n, np.int32), d_status=np.full(n, 99, np.int8), used=np.zeros(n, np.int32))
+    held = arrays if host else {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+    p = {k: C.c_void_p(v.ctypes.data if host else v.data_ptr()) for k, v in held.items()}
+    rc = lib.tamp_batch_compress_resets_index(C.byref(conf), p["flat"], p["in_off"], p["in_len"], INTERVAL, p["comp"], p["c_off"], p["cap"],
+                                              p["c_len"], p["c_status"], n, LONGEST, mem, 0, None, p["first"], p["off"], entries)
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    ms, wall = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        if kind == "write":
+            rc = lib.tamp_batch_write_ranges(C.byref(conf), 15, p["comp"], p["c_off"], p["c_len"], p["first"], p["off"], INTERVAL, p["w_stream"],
+                                             p["w_begin"], p["w_len"], p["src"], p["src_off"], p["comp2"], p["c_off"], p["cap"], p["c2_len"],
+                                             p["c2_status"], p["off2"], n, WRITES, mem, 0, None)
+        else:
+            rc = lib.tamp_batch_decompress_resets(15, p["comp"], p["c_off"], p["c_len"], p["first"], p["off"], p["out"], p["d_off"], p["room"],
+                                                  p["d_len"], p["d_status"], p["used"], n, mem, 0, None)
+            assert rc == 0, rc
+            held["out"][held["where"]] = held["src"]
+            rc = lib.tamp_batch_compress_resets_index(C.byref(conf), p["out"], p["d_off"], p["in_len"], INTERVAL, p["comp2"], p["c_off"], p["cap"],
+                                                      p["c2_len"], p["c2_status"], n, LONGEST, mem, 0, None, p["first2"], p["off2"], entries)
+        e1.record()
+        e1.synchronize()
+        torch.cuda.synchronize()
+        assert rc == 0, rc
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(e0.elapsed_time(e1))
+    back = held if host else {k: held[k].cpu().numpy() for k in ("comp2", "c2_len", "c2_status", "off2")}
+    assert (back["c2_status"] == 0).all(), back["c2_status"][back["c2_status"] != 0][:8]
+    digest = hashlib.sha256()
+    for i in range(n):
+        digest.update(back["comp2"][int(c_off[i]) : int(c_off[i]) + int(back["c2_len"][i])].tobytes())
+    digest.update(back["off2"][:entries].tobytes())
+    kept, kept_wall = sorted(ms[2:]), sorted(wall[2:])
+    med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2  # noqa: E731
+    print(json.dumps(dict(which=which, streams=n, bytes=total, median_ms=med(kept), min_ms=kept[0], max_ms=kept[-1], wall_ms=med(kept_wall),
+                          calls=reps, touched=touched, segments=entries + n, comp_len=int(back["c2_len"].astype(np.uint64).sum()),
+                          sha256=digest.hexdigest(), lib=_lib.LIB_PATH)))
+
+
+def write_main(args):
+    me = os.path.abspath(__file__)
+
+    def run(which):
+        p = subprocess.run([sys.executable, me, "--write-child", which, str(REPS)], capture_output=True, text=True, timeout=1100)
+        if p.returncode != 0:
+            raise SystemExit(f"{which}: exit {p.returncode}\n{p.stderr[-2000:]}")
+        return json.loads([ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")][-1])
+
+    lines = [f"# tools/batch_resets_bench.py --write: prose corpus tiled into {STREAMS:,} streams, lengths log-uniform in {SHORTEST:,} .. {LONGEST:,} bytes",
+             f"# (seed {SEED}), window 10, literal 8, extended, a reset every 65,536 bytes, compressed once per process with its index; then",
+             f"# {WRITES:,} random disjoint writes of {WRITE_BYTES:,} bytes.  write = tamp_batch_write_ranges; today = tamp_batch_decompress_resets of the",
+             "# whole batch, the patch as ONE indexed store (torch on the device, numpy on the host), tamp_batch_compress_resets_index of the",
+             "# whole batch.  hipEvents around each pass, wall clock around the same span, the device drained at both ends; median of the last ten",
+             "# of twelve passes in a fresh process (min .. max in brackets).  Streams and index of both ways are the same bytes (SHA-256,",
+             "# asserted).  ratio = today / write on the same route.", ""]
+    fmt = lambda r: f"{r['median_ms']:10.2f} ms [{r['min_ms']:.2f} .. {r['max_ms']:.2f}]  wall {r['wall_ms']:10.2f} ms"  # noqa: E731
+    spread = {}
+    for rnd in range(args.rounds):
+        got = {w: run(w) for w in ("write-device", "today-device", "write-host", "today-host")}
+        assert len({r["sha256"] for r in got.values()}) == 1, got
+        first = got["write-device"]
+        lines.append(f"{first['streams']:,} streams, {first['bytes']:,} bytes in {first['segments']:,} segments, {first['touched']:,} of them touched  run {rnd + 1}")
+        for route in ("device", "host"):
+            w, t = got[f"write-{route}"], got[f"today-{route}"]
+            spread.setdefault(route, []).append((w["median_ms"], t["median_ms"]))
+            lines += [f"    write, {route:<7} {fmt(w)}   ratio {t['median_ms'] / w['median_ms']:7.2f}", f"    today, {route:<7} {fmt(t)}"]
+        print("\n".join(lines[-5:]), flush=True)
+        tail = [""]
+        for route in ("device", "host"):
+            ws, ts = [s[0] for s in spread[route]], [s[1] for s in spread[route]]
+            tail.append(f"{route}: write medians {min(ws):.2f} .. {max(ws):.2f} ms, today medians {min(ts):.2f} .. {max(ts):.2f} ms over the runs; "
+                        f"smallest today / write ratio {min(t / w for w, t in spread[route]):.2f}")
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:  # (after every run: a session that is cut short keeps what it measured)
+            f.write("\n".join(lines + tail) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_resets_bench.txt"))
@@ -400,6 +547,8 @@ def main():
     ap.add_argument("--decode-child", nargs=2, default=None)
     ap.add_argument("--index", action="store_true")
     ap.add_argument("--index-child", nargs=2, default=None)
+    ap.add_argument("--write", action="store_true")
+    ap.add_argument("--write-child", nargs=2, default=None)
     args = ap.parse_args()
     if args.child:
         return child(args.child[0], int(args.child[1]))
@@ -407,6 +556,12 @@ def main():
         return decode_child(args.decode_child[0], int(args.decode_child[1]))
     if args.index_child:
         return index_child(args.index_child[0], int(args.index_child[1]))
+    if args.write_child:
+        return write_child(args.write_child[0], int(args.write_child[1]))
+    if args.write:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "write_ranges_bench.txt")
+        return write_main(args)
     if args.index:
         if args.out == ap.get_default("out"):
             args.out = os.path.join(ROOT, "profiles", "index_resets_bench.txt")

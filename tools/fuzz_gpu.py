@@ -1,7 +1,9 @@
 """Randomised differential run on the GPU box: compress (all modes) and decompress (both decoders) against the oracle.
    usage: python tools/fuzz_gpu.py [seconds]   -- prints a summary line; exits 1 on the first mismatch.
           python tools/fuzz_gpu.py [seconds] index   -- random token streams with resets through tamp_amd.index_resets against the
-                                                        CPU token reader (tests/long_stream_writer.py) instead."""
+                                                        CPU token reader (tests/long_stream_writer.py) instead.
+          python tools/fuzz_gpu.py [seconds] write   -- random batches compressed with resets, random disjoint writes through
+                                                        tamp_amd.write_ranges against a fresh compress of the patched data."""
 import os, random, sys, time
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
 import numpy as np
@@ -64,8 +66,80 @@ def index_mode():
     sys.exit(0)
 
 
+def write_mode():
+    """Random batches (every window, literal width and format, lazy or not, any interval), random disjoint writes in random order,
+    host and device memory -> streams, index and status of write_ranges against compress_batch of the patched data."""
+    global rounds, streams
+    import torch
+
+    while time.time() - t0 < budget:
+        window, literal, ext, lazy = rng.randrange(8, 16), rng.randrange(5, 9), rng.random() < 0.5, rng.random() < 0.3
+        N = rng.choice([1, 7, 16, 100, 256, 1000, 4096])
+        n = rng.choice([1, 5, 70, 300])
+        top = (1 << literal) - 1
+        datas = []
+        for _ in range(n):
+            L = rng.choice([0, 1, N, N + 1, 3 * N, rng.randrange(0, 6000)])
+            style = rng.randrange(3)
+            if style == 0:
+                datas.append(bytes(rng.randrange(top + 1) for _ in range(L)))
+            elif style == 1:
+                datas.append(bytes((wl.synth_text(1, max(L, 1), first_index=rng.randrange(1000))[0][:L]) & top))
+            else:
+                datas.append((bytes([rng.randrange(top + 1)]) * rng.randrange(1, 300) * (L // 2 + 1))[:L])
+        kw = dict(window=window, literal=literal, extended=ext, lazy_matching=lazy)
+        base = tamp_amd.compress_batch(datas, dictionary_reset=True, reset_interval=N, reset_index=True, **kw)
+        if (base.status != 0).any():  # (random bytes of a narrow literal width can outgrow the default slab: not this call's business)
+            continue
+        writes, patched = [], [bytearray(d) for d in datas]
+        for i, d in enumerate(datas):
+            pos = 0
+            while rng.random() < 0.7:
+                pos += rng.randrange(0, 4 * N + 2)
+                ln = rng.randrange(0, 3 * N + 2)
+                if pos + ln > len(d):
+                    break
+                src = bytes(rng.randrange(top + 1) for _ in range(ln))
+                writes.append((i, pos, src))
+                patched[i][pos : pos + ln] = src
+                pos += ln
+        rng.shuffle(writes)
+        want = tamp_amd.compress_batch([bytes(b) for b in patched], dictionary_reset=True, reset_interval=N, reset_index=True, **kw)
+        tables = dict(reset_index=base.reset_index, stream_index=[w[0] for w in writes], begin=[w[1] for w in writes], source=[w[2] for w in writes],
+                      lazy_matching=lazy)
+        host = rng.random() < 0.5
+        if host:
+            res = tamp_amd.write_ranges(base.streams(), **tables)
+        else:
+            dev = torch.device('cuda:0')
+            flat, off, ln = tamp_amd.pack_streams(base.streams())
+            t = lambda a, dt: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev).to(dt)
+            res = tamp_amd.write_ranges(torch.from_numpy(np.concatenate([flat, np.zeros(1, np.uint8)])).to(dev), t(off, torch.int64), t(ln, torch.int32),
+                                        window=window, literal=literal, extended=ext, **tables)
+            torch.cuda.synchronize()
+        status = np.asarray(res.status.cpu() if hasattr(res.status, 'cpu') else res.status)
+        got_off = np.asarray(res.reset_index.off.cpu() if hasattr(res.reset_index.off, 'cpu') else res.reset_index.off).astype(np.uint32)
+        # (a patched segment that outgrows its slab fails both ways alike: the status is compared, not asked to be 0)
+        ok = np.asarray(want.status) == 0
+        firsts = np.asarray(want.reset_index.first).astype(np.int64)
+        same_index = all((got_off[firsts[i] : firsts[i + 1]] == want.reset_index.off[firsts[i] : firsts[i + 1]]).all() for i in np.flatnonzero(ok))
+        if (status != want.status).any() or res.streams() != want.streams() or not same_index:
+            bad = [i for i in range(n) if status[i] != want.status[i] or res.stream(i) != want.stream(i)] or ['index']
+            print('WRITE MISMATCH', 'host' if host else 'device', window, literal, ext, lazy, N, n, len(writes), bad[:8], [int(status[i]) for i in bad[:8]])
+            for i in bad[:3]:  # per stream: decoded bytes, old and wanted compressed bytes, its room, its writes
+                print('  stream', i, len(datas[i]), len(base.stream(i)), len(want.stream(i)), int(want.status[i]), int(res._keep[-1][i]) if not host else '-',
+                      sorted((w[1], len(w[2])) for w in writes if w[0] == i))
+            sys.exit(1)
+        rounds += 1
+        streams += n
+    print(f"write fuzz ok: {rounds} rounds, {streams} streams, {time.time() - t0:.0f} s")
+    sys.exit(0)
+
+
 if len(sys.argv) > 2 and sys.argv[2] == 'index':
     index_mode()
+if len(sys.argv) > 2 and sys.argv[2] == 'write':
+    write_mode()
 gens = [lambda n, L, k: wl.synth_text(n, L, first_index=k), lambda n, L, k: wl.lcg_runs(n, L, first_index=k),
         lambda n, L, k: wl.stress(n, L, first_index=k), lambda n, L, k: wl.telemetry(n, L, first_index=k),
         lambda n, L, k: np.random.default_rng(k).integers(0, 256, (n, L), dtype=np.uint8),
