@@ -653,6 +653,78 @@ int tamp_batch_write_ranges(const TampAmdConf *conf, uint8_t max_window_bits,
                             size_t n_streams, size_t n_writes, int mem, int device, void *stream);
 
 /*
+ * APPENDING to such a batch so that it stays seekable.  A stream's size never changes under tamp_batch_write_ranges; this call makes
+ * streams grow, and it KEEPS THE GRID: the closed segments of the new stream hold exactly reset_interval decoded bytes each, so that
+ * tamp_batch_read_ranges and tamp_batch_write_ranges go on addressing byte b at segment b / reset_interval.  (The reference's own
+ * append mode opens with a reset wherever the stream happened to end and loses that.)
+ * Stream i has E index entries and an open segment of m decoded bytes, 0 <= m <= N = reset_interval, and receives L = src_len[i] bytes:
+ *   - the old stream's bytes in front of its open segment (the header, the E closed segments with their resets) keep their place and
+ *     value; they are copied and not looked at
+ *   - the open segment's m bytes followed by the L source bytes are cut at every N bytes into U = max(1, ceil((m + L) / N)) segments;
+ *     all but the last are closed, and each is what tamp_batch_compress_resets writes for those bytes under `conf`
+ *   - the new index holds the old E entries and U - 1 new ones
+ * Hence, for streams tamp_batch_compress_resets_index made under the same conf and reset_interval, the new streams and the new index
+ * are byte for byte what that call returns for old data + appended data; and the new streams decode, with any decoder, to that.
+ *   conf, max_window_bits, in .. reset_interval   as for tamp_batch_write_ranges
+ *   src, src_off, src_len   ONE ROW PER STREAM: stream i receives src[src_off[i] .. + src_len[i]); src_len[i] == 0: nothing.  Any
+ *                   alignment.  Every byte must fit conf->literal bits
+ *   out, out_off, out_cap, out_len, status   the new streams, as for tamp_batch_write_ranges
+ *   new_reset_first n_streams + 1 entries, always written: the running sum of E_i + U_i - 1.  A failing stream keeps E_i rows, which
+ *                   are zeroed, so that the table stays a running sum (a stream whose rows of reset_first do not hold keeps none)
+ *   WHEN A STREAM'S ROWS OF reset_first HOLD: they are in order and inside the table (reset_first[i] <= reset_first[i + 1] <=
+ *                   reset_first[n_streams], reset_first[0] == 0), AND they start at or behind the end of every such pair in front
+ *                   of them -- two pairs that are each in order may still claim the same entries ({0, 5, 3, 8}: streams 0 and 2; here
+ *                   stream 0 holds, streams 1 and 2 do not) -- and reset_off is not NULL unless the stream has no entries.  The
+ *                   entries of streams that hold are disjoint, so the bound below suffices whatever the table holds.  A stream whose
+ *                   rows do not hold and that receives nothing is copied, without entries
+ *   new_reset_off, new_reset_cap   the new entries.  U_i - 1 <= ceil(L_i / N) because m <= N, so reset_first[n_streams] + the sum of
+ *                   ceil(src_len[i] / N) entries ALWAYS suffice, whatever the open segments hold; a smaller new_reset_cap is refused
+ *                   with TAMP_AMD_BAD_ARGUMENT before anything is written (host tables: before a device is looked for)
+ *   status[i]       the first rule that applies:
+ *       (src_len[i] == 0: the stream is copied in one piece whatever it holds, its entries with it: TAMP_OK, or TAMP_OUTPUT_FULL)
+ *       the stream's units alone (ceil(L / N) + 1 rows) outgrow the scratch budget TAMP_AMD_BAD_ARGUMENT
+ *       the header is not what conf makes (tamp_batch_write_ranges' rule) ....... TAMP_INVALID_CONF
+ *       the stream's rows of reset_first do not hold (above) ................... TAMP_AMD_BAD_INDEX
+ *       an entry of the stream out of range or order ........................... TAMP_AMD_BAD_INDEX
+ *       an offset of the open segment out of the window ....................... TAMP_OOB
+ *       the open segment does not parse from the last entry, or decodes to more
+ *       than reset_interval bytes .............................................. TAMP_AMD_BAD_INDEX
+ *       the open segment did not decode to what the walk found (a defect of the
+ *       library) ............................................................... TAMP_ERROR
+ *       a source byte that does not fit conf->literal bits .................... TAMP_EXCESS_BITS
+ *       whatever the compress kernel says of a unit
+ *       the new stream longer than out_cap[i], or than 32 bits hold ........... TAMP_OUTPUT_FULL
+ *     A failing stream has out_len[i] = 0 and unspecified bytes in its slab; nothing is ever written outside [out_off[i], out_off[i] +
+ *     out_cap[i]), and no other stream is affected.
+ * WHAT THE INDEX IS TRUSTED FOR.  Position, as in tamp_batch_read_ranges, and only the stream's LAST entry: the open segment alone is
+ * walked and decoded.  The entries in front of it are checked for range and order and nothing else, so a stream with irregular closed
+ * segments (one tamp_batch_index_resets found in a reference-made file) can be appended to; only the open segment is brought onto the
+ * grid.  A stream that ends with a reset has an empty open segment (m = 0): nothing is decoded, its new segments follow its bytes.
+ *   mem, device, stream   TAMP_AMD_ALL_DEVICES is not taken.  A device-memory call WAITS for one 40-byte record (its rows, which are
+ *                   sized from src_len alone: ceil(L / N) closed rows and one open row per appending stream, so that nothing waits for
+ *                   m; reset_first[n_streams] and the bound of new_reset_off with them) and, where an open segment is decoded, once per
+ *                   slice inside the decode step, which is tamp_batch_read_ranges'.  A host-memory call is synchronous and moves ONLY
+ *                   the open segments, the tables and the sources of the streams that are appended to (packed: nothing that lies
+ *                   between them in `src`) up and the new tails back; the closed segments never cross the link.
+ * SCRATCH is kept per HIP stream (tamp_amd_trim releases it): 35 bytes per stream of the batch, 4 per entry of the new index, and per
+ * row a staging row of reset_interval bytes, a slab and 80 bytes of tables, within the budget of tamp_batch_read_ranges
+ * (TAMP_AMD_RANGES_SCRATCH_MB); a call whose rows outgrow it runs in slices of whole streams (it then reads two tables of n_streams + 1
+ * entries back to cut them).  With TAMP_AMD_RESETS_DEBUG set the call writes one line to stderr:
+ * "[tamp_amd resets] append: <a> appends, <u> units, <s> slices, <b> bytes staged" (u: the rows, b: the bytes of the units).
+ * Returns TAMP_OK (n_streams == 0: at once, nothing is done); TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null conf,
+ * in_off, in_len, reset_first, src_off, src_len, out_off, out_cap, out_len, status or new_reset_first, a null `in`, `src` or `out` with
+ * n_streams > 0, a null new_reset_off with new_reset_cap > 0, reset_interval == 0 or one whose worst-case segment does not fit 32 bits,
+ * a conf that tamp_batch_compress_resets refuses, a bad memory kind, TAMP_AMD_ALL_DEVICES, n_streams >= 2^32; TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_append(const TampAmdConf *conf, uint8_t max_window_bits,
+                      const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                      const uint64_t *reset_first, const uint32_t *reset_off, uint32_t reset_interval,
+                      const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
+                      uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int8_t *status,
+                      uint64_t *new_reset_first, uint32_t *new_reset_off, uint64_t new_reset_cap,
+                      size_t n_streams, int mem, int device, void *stream);
+
+/*
  * FINDING the resets of streams that came without an index: a blob of tamp_amd_compress_resets, a file, a batch whose index was not
  * kept, anything a reference Compressor(dictionary_reset=True) wrote with reset_dictionary() calls of its own or in append mode.
  * The call returns the table tamp_batch_compress_resets_index writes, found on the device: the compressed bits of every stream are
@@ -898,7 +970,7 @@ float tamp_amd_last_kernel_ms(void);
 /* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
  * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
  * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
- * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the tables, staging rows and slabs of tamp_batch_write_ranges, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
+ * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the tables, staging rows and slabs of tamp_batch_write_ranges, the tables, staged entries, staging rows and slabs of tamp_batch_append, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
  * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.

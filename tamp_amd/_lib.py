@@ -49,6 +49,7 @@ SYMBOLS = (
     "tamp_amd_decompress_resets",
     "tamp_batch_read_ranges",
     "tamp_batch_write_ranges",
+    "tamp_batch_append",
     "tamp_batch_index_resets",
     "tamp_batch_pack",
     "tamp_amd_decoder_state_size",
@@ -212,6 +213,9 @@ def load() -> C.CDLL:
     lib.tamp_batch_write_ranges.argtypes = [C.POINTER(TampAmdConf), u8, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz,
                                             i32, i32, vp]
     lib.tamp_batch_write_ranges.restype = i32
+    lib.tamp_batch_append.argtypes = [C.POINTER(TampAmdConf), u8, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, sz, i32,
+                                      i32, vp]
+    lib.tamp_batch_append.restype = i32
     lib.tamp_batch_index_resets.argtypes = [u8, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, sz, i32, i32, vp]
     lib.tamp_batch_index_resets.restype = i32
     lib.tamp_batch_pack.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, sz, u32, i32, vp]

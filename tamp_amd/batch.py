@@ -1045,6 +1045,190 @@ def write_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, b
     return BatchResult(out, out_off, out_len, status, None, ms, reset_index=ResetIndex(first, new_off, interval))
 
 
+def _append_tables(source, source_off, length, stream_index, n_streams, on_device):
+    """Not part of the package's surface: the per-stream source tables of ``append_batch`` from what the caller gave.
+    -> (source, source_off, length): a flat uint8 buffer and one row per STREAM; host arrays (uint64, uint32) unless all three came
+    as CUDA tensors with no ``stream_index``, which are passed as they are.  ValueError on anything that does not fit."""
+    pieces = not _is_torch(source) and not isinstance(source, np.ndarray)
+    if pieces:
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            raise ValueError("source: a sequence of bytes-likes, one per stream, or a flat uint8 buffer with source_off and length")
+        if source_off is not None or length is not None:
+            raise ValueError("source_off and length are derived from a sequence of sources")
+        parts = [_np_u8(b"" if x is None else x) for x in source]
+        length = np.array([p.size for p in parts], dtype=np.uint64)
+        source_off = np.cumsum(length) - length if len(parts) else np.zeros(0, np.uint64)
+        source = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    elif source_off is None or length is None:
+        raise ValueError("a flat source needs source_off and length")
+    if on_device != _is_torch(source) and not (on_device and pieces):
+        raise ValueError("source: where the data is (a CUDA tensor with CUDA data)")
+    rows = n_streams if stream_index is None else len(stream_index)
+    if not len(source_off) == len(length) == rows:
+        raise ValueError("the sources: one per stream, or one per entry of stream_index")
+    if stream_index is None and on_device and _is_torch(source_off) and _is_torch(length):
+        return source, source_off, length  # (CUDA tables of a CUDA call: nobody looks at them, no sync)
+
+    def table(t, what, most, dt):  # (a sequence goes through Python integers: 2^64 - 1 is one)
+        a = t.cpu().numpy() if _is_torch(t) else (t if isinstance(t, np.ndarray) else np.array([int(x) for x in t] or [0], dtype=object)[: len(t)])
+        if a.dtype.kind not in "iuO":
+            raise ValueError(what + ": integers expected")
+        if len(a) and int(a.min()) < 0:
+            raise ValueError(what + ": negative")
+        if len(a) and int(a.max()) > most:
+            raise ValueError(what + ": does not fit %d bits" % most.bit_length())
+        return np.ascontiguousarray(a.astype(dt))
+
+    h_off, h_len = table(source_off, "source_off", (1 << 64) - 1, np.uint64), table(length, "length", 0xFFFFFFFF, np.uint32)
+    if stream_index is None:
+        return source, h_off, h_len
+    idx = table(stream_index, "stream_index", 0xFFFFFFFF, np.uint32).astype(np.int64)
+    if len(idx) and int(idx.max()) >= n_streams:
+        raise ValueError("stream_index: out of range")
+    if len(np.unique(idx)) != len(idx):
+        raise ValueError("stream_index: a stream is named twice")
+    full_off, full_len = np.zeros(n_streams, np.uint64), np.zeros(n_streams, np.uint32)
+    full_off[idx], full_len[idx] = h_off, h_len
+    return source, full_off, full_len
+
+
+def append_batch(data, in_off=None, in_len=None, *, reset_index, source, source_off=None, length=None, stream_index=None,
+                 reset_interval=None, lazy_matching: bool = False, out_cap=None, max_window_bits: int = 15, device: int = 0, stream=None,
+                 timing: bool = False, window=None, literal=None, extended=None) -> BatchResult:
+    """Append bytes to reset-segmented streams so that they stay seekable (``tamp_batch_append``; not in the reference,
+    whose append mode opens with a reset wherever the stream ended).  ``data``, ``reset_index`` and ``reset_interval`` as for
+    ``read_ranges``.  ``source``: one bytes-like per stream, ``b""`` or ``None`` for none -- with ``stream_index=[...]`` one per named
+    stream (a stream named twice or out of range raises ``ValueError``) -- or one flat uint8 buffer (numpy array or CUDA tensor) with
+    per-stream ``source_off`` and ``length``.  Only a stream's open segment is decoded; its bytes and the new ones are cut at every
+    ``reset_interval`` bytes and compressed, and every byte in front of the open segment keeps its place.  For streams
+    ``compress_batch(..., reset_interval=N, reset_index=True)`` made, streams and index are byte for byte what that call makes of
+    old data + appended.  ``window``, ``literal``, ``extended``: the streams' own -- read from the first stream's header for host
+    data, required with CUDA tensors.  ``out_cap=None``: a stream's length plus ``ceil(L / N) + 1`` full closed segments.  The result's
+    ``reset_index`` is the new index; with CUDA tensors its ``off`` is sized by the bound ``entries + sum(ceil(L / N))`` and may have
+    spare entries behind ``first[n]``: every call that takes an index takes it as it stands."""
+    if not isinstance(reset_index, ResetIndex):  # (all decided before the library is looked for)
+        raise ValueError("reset_index: a ResetIndex expected")
+    on_device = _is_torch(data)
+    n_streams = len(data) if in_off is None and not on_device else len(in_len)
+    if len(reset_index.first) != n_streams + 1:
+        raise ValueError("reset_index.first: one entry per stream and one more expected")
+    interval = reset_interval if reset_interval is not None else reset_index.interval
+    if interval is None:
+        raise ValueError("reset_interval: not given and not in the index")
+    if not _is_int(interval) or not 1 <= int(interval) <= 0xFFFFFFFF:
+        raise ValueError("reset_interval: a positive integer that fits 32 bits expected")
+    interval = int(interval)
+    source, source_off, length = _append_tables(source, source_off, length, stream_index, n_streams, on_device)
+    if on_device and (window is None or literal is None or extended is None):
+        raise ValueError("window, literal and extended are required with CUDA tensors")
+    for name, v, lo, hi in (("window", window, 8, 15), ("literal", literal, 5, 8)):
+        if v is not None and (not _is_int(v) or not lo <= int(v) <= hi):
+            raise ValueError(f"{name} must be in {lo}..{hi}, not {v!r}")
+    if out_cap is not None and not _is_int(out_cap) and len(out_cap) != n_streams:
+        raise ValueError("out_cap: one entry per stream expected")
+    if _is_int(out_cap) and not 0 <= int(out_cap) <= 0xFFFFFFFF:
+        raise ValueError("out_cap: does not fit 32 bits")
+    if stream is not None and on_device:
+        import torch  # (tables and output on the launch stream: see compress_batch)
+
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return append_batch(data, in_off, in_len, reset_index=reset_index,
+                                source=source if _is_torch(source) else torch.from_numpy(source).to(data.device), source_off=source_off,
+                                length=length, reset_interval=interval, lazy_matching=lazy_matching, out_cap=out_cap,
+                                max_window_bits=max_window_bits, device=device, stream=None, timing=timing, window=window, literal=literal,
+                                extended=extended)
+    if on_device:
+        import torch
+
+        dev = data.device
+        as_t = lambda x, dt: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.uint64).view(np.int64))).to(device=dev, dtype=dt)  # noqa: E731
+        conf = _conf(int(window), int(literal), extended, None, True, lazy_matching)
+        first_t, off_t = as_t(reset_index.first, torch.int64), as_t(reset_index.off, torch.int32)
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        src_off_t, src_len_t = as_t(source_off, torch.int64), as_t(length, torch.int32)
+        src_t = source if _is_torch(source) else torch.from_numpy(source).to(dev)
+        if not src_t.numel():
+            src_t = torch.zeros(1, dtype=torch.uint8, device=dev)
+        more = ((src_len_t.to(torch.int64) & 0xFFFFFFFF) + (interval - 1)) // interval  # (lengths are uint32 values, whatever the storage)
+        if out_cap is None:
+            cap64 = (in_len_t.to(torch.int64) & 0xFFFFFFFF) + (more + 1) * _append_closed_bound(interval, int(literal))
+        elif _is_int(out_cap):
+            cap64 = torch.full((n_streams,), int(out_cap), dtype=torch.int64, device=dev)
+        else:
+            cap64 = as_t(out_cap, torch.int64) & 0xFFFFFFFF
+        # (one look at the device for what sizes the buffers: the slabs' total, their largest, the bound of the new entries)
+        total, most, fresh = (int(v) for v in torch.stack([cap64.sum(), cap64.max(), more.sum()]).tolist()) if n_streams else (0, 0, 0)
+        if out_cap is None and most > 0xFFFFFFFF:
+            raise ValueError("a stream's bound does not fit 32 bits: pass out_cap")
+        out_cap_t = cap64.to(torch.int32)  # (the low 32 bits: what the library reads as uint32)
+        out_off_t = torch.cumsum(cap64, 0) - cap64
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        out_len_t = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+        status_t = torch.zeros(n_streams, dtype=torch.int8, device=dev)
+        new_cap = int(off_t.numel()) + fresh  # (reset_first[n] <= the entries the old table has room for)
+        new_first_t = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+        new_off_t = torch.zeros(max(new_cap, 1), dtype=torch.int32, device=dev)[:new_cap]
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        lib = _lib.load()
+        lib.tamp_amd_set_timing(1 if timing else 0)
+        _lib.check_launch(lib.tamp_batch_append(
+            C.byref(conf), max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(first_t), _ptr(off_t) if off_t.numel() else None,
+            interval, _ptr(src_t), _ptr(src_off_t), _ptr(src_len_t), _ptr(out), _ptr(out_off_t), _ptr(out_cap_t), _ptr(out_len_t),
+            _ptr(status_t), _ptr(new_first_t), _ptr(new_off_t) if new_cap else None, new_cap, n_streams, _lib.MEM_DEVICE, dev.index or 0,
+            C.c_void_p(st)))
+        ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+        return BatchResult(out, out_off_t, out_len_t, status_t, None, ms,
+                           (data, in_off_t, in_len_t, first_t, off_t, src_t, src_off_t, src_len_t, out_cap_t),
+                           reset_index=ResetIndex(new_first_t, new_off_t, interval))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    if n_streams and int(in_len[0]) and (window is None or literal is None or extended is None):
+        h0 = int(flat[int(in_off[0])])  # (the first stream's header: what every stream that is appended to must have)
+        window = (h0 >> 5) + 8 if window is None else window
+        literal = ((h0 >> 3) & 3) + 5 if literal is None else literal
+        extended = bool((h0 >> 1) & 1) if extended is None else extended
+    conf = _conf(int(window) if window is not None else 10, int(literal) if literal is not None else 8,
+                 True if extended is None else extended, None, True, lazy_matching)
+    to_np = lambda x, dt: np.ascontiguousarray((x.cpu().numpy() if _is_torch(x) else np.asarray(x)).astype(dt))  # noqa: E731
+    first, off = to_np(reset_index.first, np.uint64), to_np(reset_index.off, np.uint32)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    src = _np_u8(source)
+    if not src.size:
+        src = np.zeros(1, np.uint8)
+    more = (length.astype(np.uint64) + np.uint64(interval - 1)) // np.uint64(interval)
+    if out_cap is None:
+        out_cap = in_len.astype(np.uint64) + (more + np.uint64(1)) * np.uint64(_append_closed_bound(interval, int(conf.literal)))
+        if n_streams and int(out_cap.max()) > 0xFFFFFFFF:
+            raise ValueError("a stream's bound does not fit 32 bits: pass out_cap")
+    elif _is_int(out_cap):
+        out_cap = np.full(n_streams, int(out_cap), dtype=np.uint32)
+    out_cap = np.ascontiguousarray(out_cap, dtype=np.uint32)
+    out_off, total = _slab_offsets(out_cap)
+    out = np.zeros(total + 1, dtype=np.uint8)
+    out_len, status = np.zeros(n_streams, dtype=np.uint32), np.zeros(n_streams, dtype=np.int8)
+    new_cap = (int(first[n_streams]) if n_streams else 0) + int(more.sum())
+    new_first, new_off = np.zeros(n_streams + 1, dtype=np.uint64), np.zeros(max(new_cap, 1), dtype=np.uint32)
+    lib = _lib.load()
+    lib.tamp_amd_set_timing(1 if timing else 0)
+    _lib.check_launch(lib.tamp_batch_append(
+        C.byref(conf), max_window_bits, _ptr(flat), _ptr(in_off), _ptr(in_len), _ptr(first), _ptr(off) if off.size else None, interval,
+        _ptr(src), _ptr(source_off), _ptr(length), _ptr(out), _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(status), _ptr(new_first),
+        _ptr(new_off) if new_cap else None, new_cap, n_streams, _lib.MEM_HOST, device, C.c_void_p(stream) if stream else None))
+    ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
+    return BatchResult(out, out_off, out_len, status, None, ms,
+                       reset_index=ResetIndex(new_first, new_off[: int(new_first[n_streams])].copy(), interval))
+
+
+def _append_closed_bound(interval: int, literal: int) -> int:
+    """Bytes a closed segment of ``interval`` bytes can take at most (reset_segment_bound with the FLUSH token)."""
+    return 2 + (interval * (literal + 1) + 16) // 8
+
+
 @dataclass
 class ResetScan:
     """What ``index_resets`` found: the batch's ``ResetIndex`` and, from the token grammar alone, the decoded sizes."""

@@ -1,4 +1,4 @@
-"""Command line of the package: ``python -m tamp_amd compress|decompress|index|build-dictionary`` with the options of the reference's CLI.
+"""Command line of the package: ``python -m tamp_amd compress|decompress|index|append|build-dictionary`` with the options of the reference's CLI.
 
 Mirrors ``tamp/cli/main.py:115-232`` (``tamp compress`` / ``tamp decompress``: ``--input/-i``, ``--output/-o``,
 ``--window/-w``, ``--literal/-l``, ``--dictionary/-d``, ``--lazy-matching``, ``--extended`` / ``--no-extended``; stdin /
@@ -80,6 +80,13 @@ def build_parser() -> argparse.ArgumentParser:
                                 "segments between resets are compressed in parallel, at some cost in ratio")
     x = sub.add_parser("index", help="Find the dictionary resets of compressed files: entries, interval, decoded size.")
     x.add_argument("files", nargs="+", metavar="FILE")
+    a = sub.add_parser("append", help="Append a file's bytes to a stream compressed with --reset-interval; its segments stay N bytes long.")
+    a.add_argument("stream", metavar="STREAM", help="the compressed file")
+    a.add_argument("input", metavar="INPUT", help="the bytes to append")
+    a.add_argument("--output", "-o", default=None, help="the new stream (default: STREAM is rewritten, through a temporary file and a rename)")
+    a.add_argument("--reset-interval", type=int, default=None, metavar="N",
+                   help="the interval the stream was compressed with (needed only while it has no closed segment to tell it by)")
+    a.add_argument("--lazy-matching", action=argparse.BooleanOptionalAction, default=False)
     b = sub.add_parser("build-dictionary", help="Build a custom dictionary from a corpus of messages.")
     b.add_argument("input", metavar="INPUT", help="directory of sample files, or one file cut at --delimiter")
     b.add_argument("--output", "-o", default="dictionary.bin", help="binary dictionary file (effective bytes only)")
@@ -92,6 +99,42 @@ def build_parser() -> argparse.ArgumentParser:
     b.add_argument("--target-fill", "-f", type=float, default=None, help="fraction of the window to fill (default: the knee)")
     b.add_argument("--quiet", "-q", action="store_true")
     return ap
+
+
+def _append(tamp_amd, args) -> int:
+    """``append STREAM INPUT``: the index comes from ``index_resets``, the interval from it or from ``--reset-interval``."""
+    import os
+
+    try:
+        blob, more = Path(args.stream).read_bytes(), Path(args.input).read_bytes()
+        scan = tamp_amd.index_resets([blob])
+        if int(scan.status[0]) not in (0, 2):
+            raise ValueError(f"{args.stream}: not a stream whose resets can be found (status {int(scan.status[0])})")
+        interval = scan.index.interval if int(scan.index.first[1]) else None
+        if interval is None:
+            interval = args.reset_interval
+        elif args.reset_interval is not None and args.reset_interval != interval:
+            raise ValueError(f"{args.stream}: its segments hold {interval} bytes, not {args.reset_interval}")
+        if interval is None:
+            raise ValueError(f"{args.stream}: no closed segment of a regular size yet: pass --reset-interval")
+        res = tamp_amd.append_batch([blob], reset_index=scan.index, reset_interval=interval, source=[more], lazy_matching=args.lazy_matching)
+        if int(res.status[0]) != 0:
+            raise ValueError(f"{args.stream}: the append failed with status {int(res.status[0])}")
+        if args.output is not None:
+            Path(args.output).write_bytes(res.stream(0))
+            return 0
+        tmp = args.stream + ".tmp%d" % os.getpid()
+        try:
+            Path(tmp).write_bytes(res.stream(0))
+            os.replace(tmp, args.stream)
+        except OSError:
+            if os.path.exists(tmp):
+                os.unlink(tmp)  # (nothing is left next to STREAM)
+            raise
+    except (OSError, ValueError) as e:
+        print(f"tamp_amd: {type(e).__name__}: {e}", file=sys.stderr)
+        return 1
+    return 0
 
 
 def main(argv=None) -> int:
@@ -122,6 +165,8 @@ def main(argv=None) -> int:
                                    scan.status[i:i + 1])
             print(f"{f}: status {int(scan.status[i])}, {b - a} resets, interval {own or 'none'}, {scan.size(i)} bytes decoded")
         return 0
+    if args.command == "append":
+        return _append(tamp_amd, args)
     src = args.input if args.input is not None else args.input_pos
     dst = args.output if args.output is not None else args.output_pos
     try:

@@ -34,6 +34,7 @@
 #include "tamp_reset_segments_kernel.hpp"
 #include "tamp_read_ranges_kernel.hpp"
 #include "tamp_write_ranges_kernel.hpp"
+#include "tamp_append_kernel.hpp"
 #include "tamp_reset_index_kernel.hpp"
 #include "tamp_pack_kernel.hpp"
 
@@ -77,7 +78,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_index_resets and launch_pack and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_append, launch_index_resets and launch_pack and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -96,6 +97,7 @@ struct StreamScratch {
     DeviceBuf pack;        // tamp_batch_pack: the scan's per-workgroup sums (8 KiB, allocated once)
     DeviceBuf ranges;      // tamp_batch_read_ranges: the per-range scans and verdicts (the units, stage and scratch of a slice: `resets`)
     DeviceBuf writes, write_units;  // tamp_batch_write_ranges: its tables per stream and per segment; the rows, staging rows and slabs of a slice's units
+    DeviceBuf appends, append_units;  // tamp_batch_append: its tables per stream; the staged entries of the new index, then the rows, staging rows and slabs of a slice's units
     DeviceBuf index_streams, index_chunks, index_entries;  // tamp_batch_index_resets: its tables per stream, per chunk, per entry
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
@@ -108,7 +110,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &writes, &write_units, &index_streams, &index_chunks, &index_entries}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries}) n += b->release();
         return n;
     }
 };
@@ -2826,6 +2828,301 @@ int batch_write_ranges(const TampAmdConf* conf, const WriteCaller& c, uint8_t ma
     return TAMP_OK;
 }
 
+// Appending to reset-segmented streams (tamp_batch_append; kernels and steps: tamp_append_kernel.hpp, the arithmetic:
+// tamp_append.hpp).  The per-stream tables of the whole call lie in `appends`; `append_units` holds the staged entries of the new
+// index and, behind them, the region of a slice: the units run in SLICES of whole streams, each of which fits the budget with its
+// rows, staging rows and slabs.  The decode of a slice's open segments is launch_read_ranges_locked over one range per appending
+// stream (its own tables: `ranges`, `resets`).
+struct AppendOut {
+    uint8_t* out;
+    const uint64_t* out_off;
+    const uint32_t* out_cap;
+    uint32_t* out_len;
+    int8_t* status;
+    uint64_t* new_first;
+    uint32_t* new_off;  // may be null when new_cap is 0
+    uint64_t new_cap;
+};
+struct AppendSliceSpan { uint64_t i0, i1, c0, C, a0, A; };
+// All pointers: device memory.  The call waits for its 40-byte record (rows, entries, the bound that new_reset_off must hold) and,
+// where an open segment is decoded, once per slice inside the shared read path; a call that does not fit one slice reads two tables
+// more to cut it.  `cap_checked`: the caller has held new_cap against the bound already (host tables).
+int launch_append(DeviceCtx* ctx, const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbits, const AppendOut& o, bool cap_checked,
+                  hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    const uint64_t n = c.n;
+    // the tables: 8-byte ones, bytes
+    const size_t at_fail = 256, at_closed = at_fail + 8 * n, at_app = at_closed + 8 * (n + 1), at_count = at_app + 8 * (n + 1);
+    const size_t at_need = at_count + 8 * n, at_whole = at_need + n, at_hold = at_whole + n, all_bytes = at_hold + n + 64;
+    HIP_OK(rec.appends.need(all_bytes));
+    uint8_t* const base = static_cast<uint8_t*>(rec.appends.p);
+    AppendTables t;
+    t.fail = reinterpret_cast<uint64_t*>(base + at_fail), t.closed_first = reinterpret_cast<uint64_t*>(base + at_closed);
+    t.app_first = reinterpret_cast<uint64_t*>(base + at_app), t.count = reinterpret_cast<uint64_t*>(base + at_count);
+    t.need = base + at_need, t.whole = base + at_whole, t.hold = base + at_hold, t.entries = nullptr, t.entries_cap = 0;
+    const uint32_t N = c.interval, row = write_row_bytes(N), slab = (uint32_t)reset_segment_bound(N, conf->literal, true);
+    const uint64_t budget = read_ranges_budget(rec), max_units = std::max<uint64_t>(budget / append_unit_cost(N, slab), 1);
+    const CallTiming call_timing(st);
+    const AppendOrderArgs order = {c, t};
+    hipLaunchKernelGGL(tamp_append_order_kernel, dim3(1), dim3(kResetScanTile), 0, st, order);
+    const AppendPlanArgs plan = {c, t, max_units};
+    hipLaunchKernelGGL(tamp_append_plan_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, plan);
+    const AppendScanArgs scan = {c, t, reinterpret_cast<AppendRecord*>(base)};
+    hipLaunchKernelGGL(tamp_append_scan_kernel, dim3(1), dim3(kResetScanTile), 0, st, scan);
+    HIP_OK(hipGetLastError());
+    AppendRecord have = {0, 0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(&have, base, sizeof have, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (!cap_checked && (have.entries + have.bound < have.entries || have.entries + have.bound > o.new_cap)) {
+        snprintf(t_last_error, sizeof t_last_error, "append: new_reset_cap %llu, %llu entries may be needed", (unsigned long long)o.new_cap,
+                 (unsigned long long)(have.entries + have.bound));
+        return TAMP_AMD_BAD_ARGUMENT;
+    }
+    const uint64_t rows_all = have.closed + have.appends;
+    if (rows_all >= 0xFFFFFFFFull || have.entries + have.closed < have.entries) {
+        snprintf(t_last_error, sizeof t_last_error, "append: %llu rows, %llu entries", (unsigned long long)rows_all, (unsigned long long)have.entries);
+        return TAMP_AMD_BAD_ARGUMENT;
+    }
+    t.entries_cap = have.entries + have.closed;
+    std::vector<AppendSliceSpan> slices = {{0, n, 0, have.closed, 0, have.appends}};
+    if (rows_all > max_units) {
+        std::vector<uint64_t> firsts(2 * (n + 1));  // (closed_first and app_first lie one behind the other)
+        HIP_OK(hipMemcpyAsync(firsts.data(), t.closed_first, firsts.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        const uint64_t* const cf = firsts.data();
+        const uint64_t* const af = cf + n + 1;
+        slices.clear();
+        for (uint64_t i0 = 0; i0 < n;) {  // as many whole streams as fit, one at least (a stream that alone is too many has no rows)
+            uint64_t i1 = i0 + 1;
+            while (i1 < n && (cf[i1 + 1] - cf[i0]) + (af[i1 + 1] - af[i0]) <= max_units) i1++;
+            slices.push_back({i0, i1, cf[i0], cf[i1] - cf[i0], af[i0], af[i1] - af[i0]});
+            i0 = i1;
+        }
+    }
+    size_t region_bytes = 256;
+    for (const AppendSliceSpan& s : slices) region_bytes = std::max<size_t>(region_bytes, append_region_bytes(s.C + s.A, s.A, row, slab));
+    const size_t entries_bytes = (4 * t.entries_cap + 255) & ~(size_t)255;
+    HIP_OK(rec.append_units.need(entries_bytes + region_bytes + 256));
+    t.entries = static_cast<uint32_t*>(rec.append_units.p);
+    uint8_t* const region = static_cast<uint8_t*>(rec.append_units.p) + entries_bytes;
+    const SegmentSpec with_token = {2, (uint16_t)(0xABu << 7), kSegFlushToken}, without = {2, (uint16_t)(0xABu << 7), 0};
+    const uint32_t wide = (uint32_t)ctx->cu_count * 8;
+    uint64_t staged = 0;
+    for (const AppendSliceSpan& span : slices) {
+        const uint64_t U = span.C + span.A;
+        const AppendSlice s = {span.i0, span.i1, span.c0, span.C, span.a0, span.A, region, row, slab};
+        if (U) {
+            const AppendRows w = append_rows_at(region, U, span.A);
+            HIP_OK(hipMemsetAsync(region, 0, append_rows_bytes(U, span.A), st));
+            const AppendRowsArgs rows = {c, t, s};
+            hipLaunchKernelGGL(tamp_append_rows_kernel, dim3((uint32_t)((U + 255) / 256)), dim3(256), 0, st, rows);
+            HIP_OK(hipGetLastError());
+            if (have.decodes) {
+                const ReadCaller rc = {c.in, c.in_off, c.in_len, c.first, c.off, n, N, c.max_wbits, w.range_stream, w.range_begin, w.range_len, span.A};
+                if (const int r = launch_read_ranges_locked(ctx, rec, rc, max_wbits, region, w.range_out, w.m, w.read_status, false, st)) return r;
+            }
+            const AppendAssembleArgs assemble = {c, t, s};
+            hipLaunchKernelGGL(tamp_append_assemble_kernel, dim3((uint32_t)std::min<uint64_t>(U, wide)), dim3(256), 0, st, assemble);
+            HIP_OK(hipGetLastError());
+            BatchTables seg;
+            seg.in = region, seg.in_off = w.row_off, seg.in_len = w.in_len, seg.out = region, seg.out_off = w.slab_off, seg.out_cap = w.cap;
+            seg.out_len = w.out_len, seg.status = w.status, seg.n = U;
+            if (const int r = launch_compress_locked(ctx, rec, conf, seg.rows(0, span.C), N, st, &with_token, nullptr)) return r;
+            if (const int r = launch_compress_locked(ctx, rec, conf, seg.rows(span.C, span.A), N, st, &without, nullptr)) return r;
+            if (dbg) {
+                std::vector<uint32_t> sizes(U);
+                HIP_OK(hipMemcpyAsync(sizes.data(), w.in_len, 4 * U, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                for (const uint32_t v : sizes) staged += v;
+            }
+        }
+        const AppendSpliceArgs splice = {c, t, s, o.out_cap, o.out_len, o.status};
+        hipLaunchKernelGGL(tamp_append_splice_kernel, dim3((uint32_t)std::min<uint64_t>(span.i1 - span.i0, wide)), dim3(kResetScanTile), 0, st, splice);
+        const AppendGatherArgs gather = {c, t, s, o.out, o.out_off, o.out_cap, o.status, o.out_len};
+        hipLaunchKernelGGL(tamp_append_gather_kernel, dim3((uint32_t)std::min<uint64_t>(U + (span.i1 - span.i0), wide)), dim3(256), 0, st, gather);
+        HIP_OK(hipGetLastError());
+    }
+    const AppendIndexArgs index = {t, n, o.new_first};
+    hipLaunchKernelGGL(tamp_append_index_kernel, dim3(1), dim3(kResetScanTile), 0, st, index);
+    if (o.new_off && o.new_cap) {
+        const AppendEntriesArgs entries = {c, t, o.new_first, o.new_off, o.new_cap};
+        hipLaunchKernelGGL(tamp_append_entries_kernel, dim3((uint32_t)std::min<uint64_t>(n, wide)), dim3(256), 0, st, entries);
+    }
+    HIP_OK(hipGetLastError());
+    if (dbg)
+        fprintf(stderr, "[tamp_amd resets] append: %llu appends, %llu units, %zu slices, %llu bytes staged\n", (unsigned long long)have.appends,
+                (unsigned long long)rows_all, slices.size(), (unsigned long long)staged);
+    return TAMP_OK;
+}
+
+// tamp_batch_append behind its checks.  Host memory, on the host pipeline's kept buffers and first stream (one host-memory call per
+// device at a time): the host makes the checks of the header, of reset_first and of the entries itself and uploads ONLY the open
+// segment of every stream that is appended to, behind a copy of its header as a stream without entries of its own (as
+// tamp_batch_read_ranges stages a unit), with the tables and the sources of those streams, packed.  The device call on those streams gives the new tails and
+// their entries, counted from the open segment's start; they come back and are spliced onto the old bytes, which never cross the link.
+int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbits, const AppendOut& o, int mem, int device, void* stream) {
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_append(ctx, conf, c, max_wbits, o, false, static_cast<hipStream_t>(stream));
+    const uint64_t n = c.n;
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> pipe_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    const uint32_t N = c.interval;
+    // whose rows of reset_first hold, and have a table for their entries (the device call's append_index_ok)
+    std::vector<uint8_t> holds(n);
+    append_rows_hold(c.first, n, holds.data());
+    for (uint64_t i = 0; i < n; i++)
+        if (holds[i] && !c.off && c.first[i + 1] != c.first[i]) holds[i] = 0;
+    const uint64_t unit_bound = reset_segment_bound(N, conf->literal, true);
+    uint64_t max_units = 1;
+    {
+        StreamScratch& rec = ctx->scratch(st);
+        std::lock_guard<std::mutex> call_lock(rec.mu);
+        max_units = std::max<uint64_t>(read_ranges_budget(rec) / append_unit_cost(N, (uint32_t)unit_bound), 1);
+    }
+    enum : uint8_t { kWhole = 0, kRun = 1, kFailed = 2 };
+    std::vector<uint8_t> kind(n, kWhole);
+    std::vector<int8_t> pre(n, 0);
+    std::vector<uint32_t> start(n, 0), h_in_len(n, 0), h_cap(n, 0), h_src_len(n, 0);
+    std::vector<uint64_t> h_in_off(n, 0), h_out_off(n, 0), h_src_off(n, 0);
+    struct Piece { uint64_t from, at, len; };  // of the caller's source buffer: neighbours there stay neighbours and are one copy
+    std::vector<Piece> pieces;
+    uint64_t staged = 0, room = 0, src_all = 0, bound_all = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t L = c.src_len[i];
+        if (!L) continue;
+        const uint64_t B = append_entry_bound(L, N);
+        const uint8_t* const s = c.in + c.in_off[i];
+        kind[i] = kFailed;
+        if (B + 1 > max_units) { pre[i] = (int8_t)TAMP_AMD_BAD_ARGUMENT; continue; }
+        if (c.in_len[i] < kResetHeaderBytes || c.max_wbits > 15 || s[0] != c.header || s[1] != 0 || ((c.header >> 5) & 7u) + 8 > c.max_wbits) {
+            pre[i] = (int8_t)TAMP_INVALID_CONF;
+            continue;
+        }
+        pre[i] = (int8_t)TAMP_AMD_BAD_INDEX;
+        if (!holds[i]) continue;
+        const uint64_t E = c.first[i + 1] - c.first[i];
+        bool ok = true;
+        for (uint64_t k = 0; k <= E && ok; k++) ok = read_segment_cut(c.first, c.off, c.in_len, i, k).ok;
+        if (!ok) continue;
+        kind[i] = kRun, pre[i] = 0;
+        start[i] = read_segment_cut(c.first, c.off, c.in_len, i, E).start;
+        h_in_len[i] = kResetHeaderBytes + (c.in_len[i] - start[i]), h_in_off[i] = staged, staged += h_in_len[i];
+        const uint64_t moved = start[i] - kResetHeaderBytes;  // bytes of the new stream that the tail does not hold
+        const uint64_t tail_room = o.out_cap[i] > moved ? o.out_cap[i] - moved : 0;
+        h_cap[i] = (uint32_t)std::min<uint64_t>(tail_room, std::min<uint64_t>(kResetHeaderBytes + (B + 1) * unit_bound, 0xFFFFFFFFull));
+        h_out_off[i] = room, room += h_cap[i];
+        h_src_len[i] = L, bound_all += B;
+        // the sources of the streams that run, back to back: nothing between them goes up
+        h_src_off[i] = src_all;
+        if (!pieces.empty() && pieces.back().from + pieces.back().len == c.src_off[i]) pieces.back().len += L;
+        else pieces.push_back({c.src_off[i], src_all, L});
+        src_all += L;
+    }
+    // the open segments, each behind its stream's header, in pinned staging
+    HIP_OK(P.stage[0].need(staged + 64));
+    uint8_t* const h_stage = static_cast<uint8_t*>(P.stage[0].p);
+    for (uint64_t i = 0; i < n; i++) {
+        if (kind[i] != kRun) continue;
+        uint8_t* const dst = h_stage + h_in_off[i];
+        dst[0] = c.in[c.in_off[i]], dst[1] = 0;
+        memcpy(dst + kResetHeaderBytes, c.in + c.in_off[i] + start[i], c.in_len[i] - start[i]);
+    }
+    HIP_OK(P.in[0].need(staged + 64));
+    HIP_OK(P.in[1].need(src_all + 64));
+    HIP_OK(P.out[0].need(room + 64));
+    // 8-byte tables, 4-byte tables, bytes
+    const size_t meta = 8 * (n + n + (n + 1) + n + (n + 1)) + 4 * (n + n + n + n + bound_all) + n + 64;
+    HIP_OK(P.meta[0].need(meta));
+    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
+    uint64_t* const d_out_off = d_in_off + n;
+    uint64_t* const d_first = d_out_off + n;
+    uint64_t* const d_src_off = d_first + n + 1;
+    uint64_t* const d_new_first = d_src_off + n;
+    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_new_first + n + 1);
+    uint32_t* const d_cap = d_in_len + n;
+    uint32_t* const d_out_len = d_cap + n;
+    uint32_t* const d_src_len = d_out_len + n;
+    uint32_t* const d_new_off = d_src_len + n;
+    int8_t* const d_status = reinterpret_cast<int8_t*>(d_new_off + bound_all);
+    if (staged) HIP_OK(hipMemcpyAsync(P.in[0].p, h_stage, staged, hipMemcpyHostToDevice, st));
+    for (const Piece& pc : pieces)
+        HIP_OK(hipMemcpyAsync(static_cast<uint8_t*>(P.in[1].p) + pc.at, c.src + pc.from, pc.len, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_first, 0, (n + 1) * 8, st));  // (the staged streams have no entries)
+    HIP_OK(hipMemcpyAsync(d_src_off, h_src_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_len, h_in_len.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_cap, h_cap.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_src_len, h_src_len.data(), n * 4, hipMemcpyHostToDevice, st));
+    AppendCaller d = c;
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = d_in_off, d.in_len = d_in_len, d.first = d_first, d.off = nullptr;
+    d.src = static_cast<const uint8_t*>(P.in[1].p), d.src_off = d_src_off, d.src_len = d_src_len;
+    uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
+    const AppendOut dout = {d_out, d_out_off, d_cap, d_out_len, d_status, d_new_first, bound_all ? d_new_off : nullptr, bound_all};
+    if (const int rc = launch_append(ctx, conf, d, max_wbits, dout, true, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    std::vector<uint64_t> t_first(n + 1);
+    std::vector<uint32_t> t_off(bound_all), t_len(n);
+    std::vector<int8_t> t_status(n);
+    HIP_OK(hipMemcpyAsync(t_len.data(), d_out_len, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(t_status.data(), d_status, n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(t_first.data(), d_new_first, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (bound_all) HIP_OK(hipMemcpyAsync(t_off.data(), d_new_off, bound_all * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t extent = 0;  // of the tails: behind the last produced byte
+    for (uint64_t i = 0; i < n; i++)
+        if (kind[i] == kRun && t_status[i] == 0 && t_len[i]) extent = std::max(extent, h_out_off[i] + t_len[i]);
+    const uint8_t* back = nullptr;
+    if (extent) {
+        HIP_OK(P.stage[1].need(extent));
+        HIP_OK(hipMemcpyAsync(P.stage[1].p, d_out, extent, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        back = static_cast<const uint8_t*>(P.stage[1].p);
+    }
+    // the splice: old bytes and old entries in front, the tail and its entries (counted from the open segment's start) behind them.
+    // Streams that hold have disjoint entries inside the table, so the cursor stays inside new_reset_cap; it is held against it all
+    // the same, and a stream whose entries would overrun keeps none
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t E = holds[i] ? c.first[i + 1] - c.first[i] : 0;
+        const uint64_t f0 = c.first[i];
+        const bool overrun = at + E < at || at + E > o.new_cap;
+        if (overrun) E = 0;
+        o.new_first[i] = at;
+        if (kind[i] == kWhole) {
+            const bool fits = c.in_len[i] <= o.out_cap[i];
+            o.status[i] = fits ? (int8_t)TAMP_OK : (int8_t)TAMP_OUTPUT_FULL, o.out_len[i] = fits ? c.in_len[i] : 0;
+            if (fits && c.in_len[i]) memcpy(o.out + o.out_off[i], c.in + c.in_off[i], c.in_len[i]);
+            for (uint64_t k = 0; k < E; k++) o.new_off[at + k] = c.off[f0 + k];
+            at += E;
+            continue;
+        }
+        const uint64_t tail_entries = kind[i] == kRun && t_first[i + 1] >= t_first[i] && t_first[i + 1] <= bound_all ? t_first[i + 1] - t_first[i] : 0;
+        const bool fits = !overrun && at + E + tail_entries <= o.new_cap;
+        const bool ok = kind[i] == kRun && t_status[i] == 0 && t_len[i] >= kResetHeaderBytes && back && fits;
+        const uint64_t moved = ok ? start[i] - kResetHeaderBytes : 0, fresh = ok ? tail_entries : 0;
+        o.status[i] = kind[i] == kFailed ? pre[i] : (ok ? (int8_t)TAMP_OK : (!fits ? (int8_t)TAMP_AMD_BAD_INDEX : (t_status[i] ? t_status[i] : (int8_t)TAMP_ERROR)));
+        o.out_len[i] = ok ? (uint32_t)(moved + t_len[i]) : 0;
+        for (uint64_t k = 0; k < E; k++) o.new_off[at + k] = ok ? c.off[f0 + k] : 0;
+        at += E;
+        if (!ok) continue;
+        memcpy(o.out + o.out_off[i], c.in + c.in_off[i], start[i]);
+        memcpy(o.out + o.out_off[i] + start[i], back + h_out_off[i] + kResetHeaderBytes, t_len[i] - kResetHeaderBytes);
+        for (uint64_t k = 0; k < fresh; k++) o.new_off[at + k] = (uint32_t)(t_off[t_first[i] + k] + moved);
+        at += fresh;
+    }
+    o.new_first[n] = at;
+    return TAMP_OK;
+}
+
 // The reset index of a batch that came without one (tamp_batch_index_resets; kernels and steps: tamp_reset_index_kernel.hpp, the
 // arithmetic: tamp_reset_index.hpp).  All tables in device memory.  The call waits for the 16 bytes that size the chunk tables, for the
 // 4-byte changed-flag of every round, and for the entry count that decides whether the entries fit.  -> TAMP_OK, 1 (more entries than
@@ -3380,6 +3677,30 @@ int tamp_batch_write_ranges(const TampAmdConf* conf, uint8_t max_window_bits, co
     const WriteCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
                            (uint32_t)header_byte(conf, true), conf->literal, write_stream, write_begin, write_len, src, src_off, n_writes};
     return batch_write_ranges(conf, c, max_window_bits, {out, out_off, out_cap, out_len, status, new_reset_off}, mem, device, stream);
+}
+
+int tamp_batch_append(const TampAmdConf* conf, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                      const uint64_t* reset_first, const uint32_t* reset_off, uint32_t reset_interval, const uint8_t* src,
+                      const uint64_t* src_off, const uint32_t* src_len, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                      uint32_t* out_len, int8_t* status, uint64_t* new_reset_first, uint32_t* new_reset_off, uint64_t new_reset_cap,
+                      size_t n_streams, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!conf || !in_off || !in_len || !reset_first || !src_off || !src_len || !out_off || !out_cap || !out_len || !status || !new_reset_first)
+        return TAMP_AMD_BAD_ARGUMENT;
+    if (((!in || !src || !out) && n_streams) || (!new_reset_off && new_reset_cap) || !reset_interval) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (!conf_valid(conf) || conf->lazy_matching > 1 || !conf->dictionary_reset || conf->use_custom_dictionary) return TAMP_AMD_BAD_ARGUMENT;
+    // (a table row's capacity is 32 bits wide: an interval whose worst case does not fit one is not taken)
+    if (reset_segment_bound(reset_interval, conf->literal, true) > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams == 0) return TAMP_OK;  // (nothing is done)
+    // (host tables: the entries new_reset_off must hold are known here; device tables: from the call's record, before anything is written)
+    if (mem == TAMP_AMD_MEM_HOST && append_reset_bound(reset_first[n_streams], src_len, n_streams, reset_interval) > new_reset_cap)
+        return TAMP_AMD_BAD_ARGUMENT;
+    const AppendCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
+                            (uint32_t)header_byte(conf, true), conf->literal, src, src_off, src_len};
+    return batch_append(conf, c, max_window_bits, {out, out_off, out_cap, out_len, status, new_reset_first, new_reset_off, new_reset_cap}, mem,
+                        device, stream);
 }
 
 int tamp_batch_index_resets(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,

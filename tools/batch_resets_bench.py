@@ -41,6 +41,17 @@ Median of the last ten of twelve calls in a fresh process, `--rounds` alternatin
 same index (SHA-256).
 
     python tools/batch_resets_bench.py --write
+
+`--append`: bytes appended to the same batch, compressed once per process with its index ("Appending"); two workloads:
+`small` -- 1,000 streams chosen at random get 4 KiB each -- and `all` -- every stream gets 64 KiB:
+  append, device / host  tamp_batch_append: only the open segments are decoded; they and the new bytes are compressed, the rest is copied
+  today, device / host   what a caller does without it: tamp_batch_decompress_resets of the whole batch into slots with room for the new
+                         bytes, the new bytes stored behind the old ones (one indexed store in torch on the device, a copy per stream in
+                         numpy on the host), tamp_batch_compress_resets_index of the whole batch
+Median of the last ten of twelve calls in a fresh process, `--rounds` alternating runs (two by default); both ways must give the same
+streams and the same index (SHA-256), and after every row the result is decoded and compared with old + appended (SHA-256).
+
+    python tools/batch_resets_bench.py --append
 """
 import argparse
 import hashlib
@@ -535,6 +546,162 @@ def write_main(args):
         with open(args.out, "w") as f:  # (after every run: a session that is cut short keeps what it measured)
             f.write("\n".join(lines + tail) + "\n")
 
+APPEND_LOADS = {"small": (1000, 4096), "all": (STREAMS, 64 << 10)}
+
+
+def append_child(which, reps):
+    """One row of --append: `append-device-small`, `append-host-all`, `today-device-small`, ..."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from tamp_amd import _lib
+
+    lib = _lib.load()
+    kind, route, load = which.split("-")
+    flat, in_off, in_len = workload()
+    n, total = len(in_len), int(flat.size)
+    conf = _lib.TampAmdConf(10, 8, 0, 1, 1, 0)
+    rng = np.random.default_rng(SEED + 2)
+    count, piece = APPEND_LOADS[load]
+    chosen = np.sort(rng.choice(n, count, replace=False))
+    src_len = np.zeros(n, dtype=np.uint32)
+    src_len[chosen] = piece
+    src_off = np.zeros(n, dtype=np.uint64)
+    src_off[1:] = np.cumsum(src_len.astype(np.uint64))[:-1]
+    src = rng.integers(32, 127, count * piece, dtype=np.uint8)
+    new_len = (in_len.astype(np.uint64) + src_len).astype(np.uint32)
+    bound = lambda lens: np.array([lib.tamp_amd_compress_resets_bound(int(x), INTERVAL, 8) for x in lens], dtype=np.uint32)  # noqa: E731
+    offsets = lambda sizes: np.concatenate([[0], np.cumsum(sizes.astype(np.uint64))[:-1]]).astype(np.uint64)  # noqa: E731
+    cap, cap2 = bound(in_len), bound(new_len)
+    c_off, c2_off = offsets(cap), offsets(cap2)
+    entries = int(((np.maximum(in_len.astype(np.uint64), 1) - 1) // INTERVAL).sum())
+    entries2 = entries + int(((src_len.astype(np.uint64) + INTERVAL - 1) // INTERVAL).sum())  # (the bound tamp_batch_append asks for)
+    room2 = np.minimum(new_len.astype(np.uint64) + 1, 0xFFFFFFFF).astype(np.uint32)  # decoded slots with room for the new bytes
+    d2_off = offsets(room2)
+    where = ((d2_off + in_len)[chosen, None] + np.arange(piece, dtype=np.uint64)[None, :]).reshape(-1)  # (where every new byte goes)
+    dev = torch.device("cuda:0")
+    host = route == "host"
+    mem = _lib.MEM_HOST if host else _lib.MEM_DEVICE
+    arrays = dict(flat=flat, in_off=in_off.view(np.int64), in_len=in_len.view(np.int32), comp=np.zeros(int(cap.astype(np.uint64).sum()) + 1, np.uint8),
+                  c_off=c_off.view(np.int64), cap=cap.view(np.int32), c_len=np.zeros(n, np.int32), c_status=np.full(n, 99, np.int8),
+                  first=np.zeros(n + 1, np.int64), off=np.zeros(max(entries, 1), np.int32), src=src, src_off=src_off.view(np.int64),
+                  src_len=src_len.view(np.int32), new_len=new_len.view(np.int32), comp2=np.zeros(int(cap2.astype(np.uint64).sum()) + 1, np.uint8),
+                  c2_off=c2_off.view(np.int64), cap2=cap2.view(np.int32), c2_len=np.zeros(n, np.int32), c2_status=np.full(n, 99, np.int8),
+                  first2=np.zeros(n + 1, np.int64), off2=np.zeros(max(entries2, 1), np.int32),
+                  out=np.zeros(int(room2.astype(np.uint64).sum()) + 1, np.uint8), d2_off=d2_off.view(np.int64), room2=room2.view(np.int32),
+                  d_len=np.zeros(n, np.int32), d_status=np.full(n, 99, np.int8), used=np.zeros(n, np.int32), where=where.view(np.int64))
+    held = arrays if host else {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+    p = {k: C.c_void_p(v.ctypes.data if host else v.data_ptr()) for k, v in held.items()}
+    rc = lib.tamp_batch_compress_resets_index(C.byref(conf), p["flat"], p["in_off"], p["in_len"], INTERVAL, p["comp"], p["c_off"], p["cap"],
+                                              p["c_len"], p["c_status"], n, LONGEST, mem, 0, None, p["first"], p["off"], entries)
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    longest2 = int(new_len.max())
+
+    def decode_into_slots(comp, off_, len_, first_, idx_):
+        r = lib.tamp_batch_decompress_resets(15, p[comp], p[off_], p[len_], p[first_], p[idx_], p["out"], p["d2_off"], p["room2"], p["d_len"],
+                                             p["d_status"], p["used"], n, mem, 0, None)
+        assert r == 0, r
+
+    ms, wall = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        if kind == "append":
+            rc = lib.tamp_batch_append(C.byref(conf), 15, p["comp"], p["c_off"], p["c_len"], p["first"], p["off"], INTERVAL, p["src"], p["src_off"],
+                                       p["src_len"], p["comp2"], p["c2_off"], p["cap2"], p["c2_len"], p["c2_status"], p["first2"], p["off2"], entries2,
+                                       n, mem, 0, None)
+        else:
+            decode_into_slots("comp", "c_off", "c_len", "first", "off")
+            if host:
+                for i in chosen:
+                    at = int(d2_off[i]) + int(in_len[i])
+                    held["out"][at : at + piece] = src[int(src_off[i]) : int(src_off[i]) + piece]
+            else:
+                held["out"][held["where"]] = held["src"]
+            rc = lib.tamp_batch_compress_resets_index(C.byref(conf), p["out"], p["d2_off"], p["new_len"], INTERVAL, p["comp2"], p["c2_off"], p["cap2"],
+                                                      p["c2_len"], p["c2_status"], n, longest2, mem, 0, None, p["first2"], p["off2"], entries2)
+        e1.record()
+        e1.synchronize()
+        torch.cuda.synchronize()
+        assert rc == 0, rc
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(e0.elapsed_time(e1))
+    # the result, decoded, against old + appended
+    if host:
+        held["out"][:] = 0
+    else:
+        held["out"].zero_()
+    decode_into_slots("comp2", "c2_off", "c2_len", "first2", "off2")
+    torch.cuda.synchronize()
+    back = held if host else {k: held[k].cpu().numpy() for k in ("comp2", "c2_len", "c2_status", "first2", "off2", "out", "d_len", "d_status")}
+    assert (back["c2_status"] == 0).all(), back["c2_status"][back["c2_status"] != 0][:8]
+    assert (back["d_len"].view(np.uint32) == new_len).all()
+    got, want = hashlib.sha256(), hashlib.sha256()
+    for i in range(n):
+        got.update(back["out"][int(d2_off[i]) : int(d2_off[i]) + int(new_len[i])].tobytes())
+        want.update(flat[int(in_off[i]) : int(in_off[i]) + int(in_len[i])].tobytes())
+        want.update(src[int(src_off[i]) : int(src_off[i]) + int(src_len[i])].tobytes())
+    assert got.hexdigest() == want.hexdigest(), "the decoded result is not old + appended"
+    digest = hashlib.sha256()
+    for i in range(n):
+        digest.update(back["comp2"][int(c2_off[i]) : int(c2_off[i]) + int(back["c2_len"][i])].tobytes())
+    new_entries = int(back["first2"][n])
+    digest.update(back["first2"].tobytes())
+    digest.update(back["off2"][:new_entries].tobytes())
+    kept, kept_wall = sorted(ms[2:]), sorted(wall[2:])
+    med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2  # noqa: E731
+    print(json.dumps(dict(which=which, streams=n, bytes=total, appended=int(count) * piece, appends=int(count), median_ms=med(kept), min_ms=kept[0],
+                          max_ms=kept[-1], wall_ms=med(kept_wall), calls=reps, segments=entries + n, new_segments=new_entries + n,
+                          comp_len=int(back["c2_len"].astype(np.uint64).sum()), sha256=digest.hexdigest(), decoded_sha256=got.hexdigest(),
+                          lib=_lib.LIB_PATH)))
+
+
+def append_main(args):
+    me = os.path.abspath(__file__)
+
+    def run(which):
+        p = subprocess.run([sys.executable, me, "--append-child", which, str(REPS)], capture_output=True, text=True, timeout=1100)
+        if p.returncode != 0:
+            raise SystemExit(f"{which}: exit {p.returncode}\n{p.stderr[-2000:]}")
+        return json.loads([ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")][-1])
+
+    lines = [f"# tools/batch_resets_bench.py --append: prose corpus tiled into {STREAMS:,} streams, lengths log-uniform in {SHORTEST:,} .. {LONGEST:,} bytes",
+             f"# (seed {SEED}), window 10, literal 8, extended, a reset every 65,536 bytes, compressed once per process with its index; then",
+             "# small: 1,000 streams chosen at random receive 4,096 bytes each; all: every stream receives 65,536 bytes.",
+             "# append = tamp_batch_append; today = tamp_batch_decompress_resets of the whole batch into slots with room for the new bytes, the new",
+             "# bytes stored behind the old ones (ONE indexed store in torch on the device, a copy per stream in numpy on the host),",
+             "# tamp_batch_compress_resets_index of the whole batch.  hipEvents around each pass, wall clock around the same span, the device drained",
+             "# at both ends; median of the last ten of twelve passes in a fresh process (min .. max in brackets).  Streams and index of both ways",
+             "# are the same bytes (SHA-256, asserted), and every row's result decodes to old + appended (SHA-256, asserted in the process).",
+             "# ratio = today / append on the same route.", ""]
+    fmt = lambda r: f"{r['median_ms']:10.2f} ms [{r['min_ms']:.2f} .. {r['max_ms']:.2f}]  wall {r['wall_ms']:10.2f} ms"  # noqa: E731
+    spread = {}
+    for rnd in range(args.rounds):
+        for load in ("small", "all"):
+            got = {w: run(f"{w}-{load}") for w in ("append-device", "today-device", "append-host", "today-host")}
+            assert len({r["sha256"] for r in got.values()}) == 1, got
+            first = got["append-device"]
+            lines.append(f"{load}: {first['appends']:,} appends of {first['appended'] // first['appends']:,} bytes to {first['streams']:,} streams, "
+                         f"{first['bytes']:,} bytes in {first['segments']:,} segments ({first['new_segments']:,} afterwards)  run {rnd + 1}")
+            for route in ("device", "host"):
+                a, t = got[f"append-{route}"], got[f"today-{route}"]
+                spread.setdefault((load, route), []).append((a["median_ms"], t["median_ms"]))
+                lines += [f"    append, {route:<7} {fmt(a)}   ratio {t['median_ms'] / a['median_ms']:7.2f}", f"    today,  {route:<7} {fmt(t)}"]
+            print("\n".join(lines[-5:]), flush=True)
+            tail = [""]
+            for (ld, route), rows in spread.items():
+                aps, ts = [r[0] for r in rows], [r[1] for r in rows]
+                tail.append(f"{ld}, {route}: append medians {min(aps):.2f} .. {max(aps):.2f} ms, today medians {min(ts):.2f} .. {max(ts):.2f} ms over the runs; "
+                            f"smallest today / append ratio {min(t / a for a, t in rows):.2f}")
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:  # (after every row group: a session that is cut short keeps what it measured)
+                f.write("\n".join(lines + tail) + "\n")
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -549,6 +716,8 @@ def main():
     ap.add_argument("--index-child", nargs=2, default=None)
     ap.add_argument("--write", action="store_true")
     ap.add_argument("--write-child", nargs=2, default=None)
+    ap.add_argument("--append", action="store_true")
+    ap.add_argument("--append-child", nargs=2, default=None)
     args = ap.parse_args()
     if args.child:
         return child(args.child[0], int(args.child[1]))
@@ -558,6 +727,14 @@ def main():
         return index_child(args.index_child[0], int(args.index_child[1]))
     if args.write_child:
         return write_child(args.write_child[0], int(args.write_child[1]))
+    if args.append_child:
+        return append_child(args.append_child[0], int(args.append_child[1]))
+    if args.append:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "append_bench.txt")
+        if args.rounds == ap.get_default("rounds"):
+            args.rounds = 2
+        return append_main(args)
     if args.write:
         if args.out == ap.get_default("out"):
             args.out = os.path.join(ROOT, "profiles", "write_ranges_bench.txt")

@@ -3,7 +3,9 @@
           python tools/fuzz_gpu.py [seconds] index   -- random token streams with resets through tamp_amd.index_resets against the
                                                         CPU token reader (tests/long_stream_writer.py) instead.
           python tools/fuzz_gpu.py [seconds] write   -- random batches compressed with resets, random disjoint writes through
-                                                        tamp_amd.write_ranges against a fresh compress of the patched data."""
+                                                        tamp_amd.write_ranges against a fresh compress of the patched data.
+          python tools/fuzz_gpu.py [seconds] append  -- random batches compressed with resets, random chains of appends through
+                                                        tamp_amd.append_batch against a fresh compress of old + appended."""
 import os, random, sys, time
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
 import numpy as np
@@ -136,8 +138,79 @@ def write_mode():
     sys.exit(0)
 
 
+def append_mode():
+    """Random batches (every window, literal width and format, lazy or not, any interval), chains of one to four appends of random
+    lengths around the open segment's room, host memory or device memory (there each call on the previous result's slabs and index as
+    they stand) -> streams, index and status of append_batch after every link against compress_batch of old + appended."""
+    global rounds, streams
+    import torch
+
+    def piece(L, top):
+        style = rng.randrange(3)
+        if style == 0:
+            return bytes(rng.randrange(top + 1) for _ in range(L))
+        if style == 1:
+            return bytes((wl.synth_text(1, max(L, 1), first_index=rng.randrange(1000))[0][:L]) & top)
+        return (bytes([rng.randrange(top + 1)]) * rng.randrange(1, 300) * (L // 2 + 1))[:L]
+
+    links = 0
+    while time.time() - t0 < budget:
+        window, literal, ext, lazy = rng.randrange(8, 16), rng.randrange(5, 9), rng.random() < 0.5, rng.random() < 0.3
+        N = rng.choice([1, 7, 16, 100, 256, 1000, 4096])
+        n = rng.choice([1, 5, 70, 300])
+        top = (1 << literal) - 1
+        datas = [piece(rng.choice([0, 1, N, N + 1, 3 * N, rng.randrange(0, 6000)]), top) for _ in range(n)]
+        kw = dict(window=window, literal=literal, extended=ext, lazy_matching=lazy)
+        base = tamp_amd.compress_batch(datas, dictionary_reset=True, reset_interval=N, reset_index=True, **kw)
+        if (base.status != 0).any():  # (random bytes of a narrow literal width can outgrow the default slab: not this call's business)
+            continue
+        host = rng.random() < 0.5
+        index = base.reset_index
+        if host:
+            args = (base.streams(),)
+        else:
+            dev = torch.device('cuda:0')
+            flat, off, ln = tamp_amd.pack_streams(base.streams())
+            t = lambda a, dt: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev).to(dt)
+            args = (torch.from_numpy(np.concatenate([flat, np.zeros(1, np.uint8)])).to(dev), t(off, torch.int64), t(ln, torch.int32))
+        for _ in range(rng.randrange(1, 5)):
+            srcs = []
+            for d in datas:
+                m = len(d) - (max(1, -(-len(d) // N)) - 1) * N
+                L = rng.choice([0, 0, 1, max(N - m - 1, 0), N - m, N - m + 1, N, 3 * N + 1, rng.randrange(0, 3 * N + 2)])
+                srcs.append(piece(L, top) if rng.random() < 0.8 else None)
+            datas = [d + (s or b'') for d, s in zip(datas, srcs)]
+            want = tamp_amd.compress_batch(datas, dictionary_reset=True, reset_interval=N, reset_index=True, **kw)
+            if (want.status != 0).any():
+                break
+            if host:
+                res = tamp_amd.append_batch(*args, reset_index=index, source=srcs, lazy_matching=lazy)
+                args, index = (res.streams(),), res.reset_index
+            else:
+                res = tamp_amd.append_batch(*args, reset_index=index, source=srcs, **kw)
+                torch.cuda.synchronize()
+                args, index = (res.out, res.out_off, res.out_len), res.reset_index
+            as_np = lambda x: np.asarray(x.cpu() if hasattr(x, 'cpu') else x)
+            status, got_first = as_np(res.status), as_np(index.first).astype(np.uint64)
+            entries = int(want.reset_index.first[-1])
+            got_off = as_np(index.off).view(np.uint32)[:entries]
+            if (status != 0).any() or res.streams() != want.streams() or (got_first != want.reset_index.first).any() or (got_off != want.reset_index.off).any():
+                bad = [i for i in range(n) if status[i] != 0 or res.stream(i) != want.stream(i)] or ['index']
+                print('APPEND MISMATCH', 'host' if host else 'device', window, literal, ext, lazy, N, n, bad[:8], [int(status[i]) for i in bad[:8] if i != 'index'])
+                for i in [b for b in bad[:3] if b != 'index']:
+                    print('  stream', i, 'old + new bytes', len(datas[i]), 'appended', len(srcs[i] or b''), 'got', len(res.stream(i)), 'want', len(want.stream(i)))
+                sys.exit(1)
+            links += 1
+        rounds += 1
+        streams += n
+    print(f"append fuzz ok: {rounds} rounds, {links} appends, {streams} streams, {time.time() - t0:.0f} s")
+    sys.exit(0)
+
+
 if len(sys.argv) > 2 and sys.argv[2] == 'index':
     index_mode()
+if len(sys.argv) > 2 and sys.argv[2] == 'append':
+    append_mode()
 if len(sys.argv) > 2 and sys.argv[2] == 'write':
     write_mode()
 gens = [lambda n, L, k: wl.synth_text(n, L, first_index=k), lambda n, L, k: wl.lcg_runs(n, L, first_index=k),
