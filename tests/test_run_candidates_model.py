@@ -23,10 +23,10 @@ def key_of(buf, c, qpos, W, wp_e, cap_len):
     return (min(ln, cap_len, lim_i) << 16) | lim_i
 
 
-def test_four_candidates_per_run_suffice():
-    rng = random.Random(5)
-    checked = 0
-    for it in range(300):
+def run_heavy_buffers(rng, count=300):
+    """Random run-heavy epoch buffers -> (it, W, blk, buf, wp_e, runs); `runs` as the kernel lists them.  (The caller may draw from
+    `rng` between two buffers; tests/test_run_list_input.py walks the same buffers.)"""
+    for it in range(count):
         W = rng.choice([64, 128, 256])
         blk = rng.choice([64, 128])
         n = W + blk + 48
@@ -48,6 +48,13 @@ def test_four_candidates_per_run_suffice():
             if e - c >= 8:
                 runs.append((c, e))
             c = e
+        yield it, W, blk, buf, wp_e, runs
+
+
+def test_four_candidates_per_run_suffice():
+    rng = random.Random(5)
+    checked = 0
+    for it, W, blk, buf, wp_e, runs in run_heavy_buffers(rng):
         for q in range(blk):
             qpos = W + q
             x = buf[qpos]
