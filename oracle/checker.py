@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -21,6 +22,14 @@ REF_SO = os.path.join(_HERE, "_ref", "libtamp_ref.so")
 
 OK, OUTPUT_FULL, INPUT_EXHAUSTED = 0, 1, 2
 ERROR, EXCESS_BITS, INVALID_CONF, OOB = -1, -2, -3, -4
+
+
+#: oracle/tamp_oracle.h ORACLE_LAZY_*: the outcome of one lazy-matching decision, and where its match came from
+LAZY_EVENTS = ("no_probe_len", "no_probe_ring", "tie_or_shorter", "overlap", "defer", "dropped_by_rle", "dropped_by_ext",
+               "cached_to_ext", "cached_over_rle")
+LAZY_ORIGINS = ("fresh", "cached", "rle")
+LazyEvent = namedtuple("LazyEvent", "event pos origin len idx nlen nidx wp ring")
+_LAZY_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint)
 
 
 class _OracleConf(C.Structure):
@@ -143,6 +152,22 @@ class Oracle(_Base):
         r = self.lib.oracle_compress(C.byref(conf), _p(d) if d is not None else None, _p(a), len(a), _p(out), cap,
                                      C.byref(n))
         return r, out[: n.value].tobytes()
+
+    def lazy_events(self, data, **kw):
+        """``compress(data, lazy_matching=True, **kw)`` with the decision hook installed (oracle_set_lazy_cb,
+        oracle/tamp_oracle.h) -> (status, bytes, [LazyEvent]) in the order the decisions were taken."""
+        events = []
+        cb = _LAZY_CB(lambda user, event, pos, origin, ln, idx, nlen, nidx, wp, ring: events.append(
+            LazyEvent(LAZY_EVENTS[event], int(pos), LAZY_ORIGINS[origin], int(ln), int(idx), int(nlen), int(nidx), int(wp),
+                      int(ring))))
+        self.lib.oracle_set_lazy_cb.argtypes = [_LAZY_CB, C.c_void_p]
+        self.lib.oracle_set_lazy_cb.restype = None
+        self.lib.oracle_set_lazy_cb(cb, None)
+        try:
+            rc, out = self.compress(data, lazy_matching=True, **kw)
+        finally:
+            self.lib.oracle_set_lazy_cb(C.cast(None, _LAZY_CB), None)
+        return rc, out, events
 
     def stream_script(self, ops, *, window=10, literal=8, extended=True, dictionary=None, dictionary_reset=False,
                       append=False, lazy_matching=False):

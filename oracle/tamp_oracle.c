@@ -30,6 +30,19 @@ void oracle_set_token_cb(oracle_token_cb cb, void *user) {
     g_cb = cb;
     g_cb_user = user;
 }
+static oracle_lazy_cb g_lazy_cb;
+static void *g_lazy_user;
+void oracle_set_lazy_cb(oracle_lazy_cb cb, void *user) {
+    g_lazy_cb = cb;
+    g_lazy_user = user;
+}
+/* One lazy-matching decision (or what became of a cached match); never touches the stream. */
+#define LAZY(event, pos, origin, len, idx, nlen, nidx, wp, R)                                              \
+    do {                                                                                                   \
+        if (g_lazy_cb)                                                                                     \
+            g_lazy_cb(g_lazy_user, (event), (pos), (origin), (unsigned)(len), (unsigned)(idx), (unsigned)(nlen), \
+                      (unsigned)(nidx), (unsigned)(wp), (unsigned)(R));                                    \
+    } while (0)
 #define TRACE(kind, pos, len, idx)                                        \
     do {                                                                  \
         if (g_cb) g_cb(g_cb_user, (kind), (pos), (unsigned)(len), (unsigned)(idx)); \
@@ -225,6 +238,8 @@ static int enc_step(Enc *e, unsigned R) {
 
     if (e->extended) { /* poll_extended_handling (compressor.c:437-525) */
         if (e->ext_count) {
+            if (e->lazy_idx >= 0)
+                LAZY(ORACLE_LAZY_DROPPED_BY_EXT, e->p, ORACLE_LAZY_CACHED, e->lazy_len, e->lazy_idx, 0, 0, e->wp, R);
             const unsigned max_ext = e->minp + 11 + EXT_EXTRA_MAX;
             while (R > 0) {
                 if (e->ext_pos + e->ext_count >= e->W || e->ext_count >= max_ext) {
@@ -251,6 +266,7 @@ static int enc_step(Enc *e, unsigned R) {
         }
 
         const uint8_t last = last_window_byte(e);
+        const size_t p_in = e->p;
         unsigned avail = 0;
         while (avail < R && e->rle_count + avail < RLE_MAX && e->in[e->p + avail] == last) avail++;
         const unsigned total = e->rle_count + avail;
@@ -285,16 +301,22 @@ static int enc_step(Enc *e, unsigned R) {
             handled = 1;
         }
         if (handled) {
+            if (e->lazy_idx >= 0)
+                LAZY(ORACLE_LAZY_DROPPED_BY_RLE, p_in, ORACLE_LAZY_CACHED, e->lazy_len, e->lazy_idx, 0, 0, e->wp, R);
             e->lazy_idx = -1;
             return ORACLE_OK;
         }
     }
 
     if (e->lazy) { /* compressor.c:576-619 */
+        int origin = len ? ORACLE_LAZY_FROM_RLE : ORACLE_LAZY_FRESH;
         if (e->lazy_idx >= 0) {
+            if (len) /* the RLE arbitration found (idx, len) on the window as it is now: the cached match still rules */
+                LAZY(ORACLE_LAZY_CACHED_OVER_RLE, e->p, ORACLE_LAZY_CACHED, e->lazy_len, e->lazy_idx, len, idx, e->wp, R);
             idx = (unsigned)e->lazy_idx;
             len = e->lazy_len;
             e->lazy_idx = -1;
+            origin = ORACLE_LAZY_CACHED;
         } else if (len == 0) {
             best_match(e, e->p, R, &idx, &len);
         }
@@ -303,15 +325,22 @@ static int enc_step(Enc *e, unsigned R) {
             best_match(e, e->p + 1, R - 1, &nidx, &nlen);
             /* validate_no_match_overlap (compressor.c:185-188) */
             if (nlen > len && (e->wp < nidx || e->wp >= nidx + nlen)) {
+                LAZY(ORACLE_LAZY_DEFER, e->p, origin, len, idx, nlen, nidx, e->wp, R);
                 e->lazy_idx = (int)nidx;
                 e->lazy_len = nlen;
                 len = 0;
             } else {
+                LAZY(nlen > len ? ORACLE_LAZY_OVERLAP : ORACLE_LAZY_TIE_OR_SHORTER, e->p, origin, len, idx, nlen, nidx,
+                     e->wp, R);
                 e->lazy_idx = -1;
             }
         } else {
+            LAZY(len >= e->minp && len <= 8 ? ORACLE_LAZY_NO_PROBE_RING : ORACLE_LAZY_NO_PROBE_LEN, e->p, origin, len, idx,
+                 0, 0, e->wp, R);
             e->lazy_idx = -1;
         }
+        if (origin == ORACLE_LAZY_CACHED && e->extended && len > e->minp + 11)
+            LAZY(ORACLE_LAZY_CACHED_TO_EXT, e->p, origin, len, idx, 0, 0, e->wp, R);
     } else if (len == 0) {
         best_match(e, e->p, R, &idx, &len);
     }

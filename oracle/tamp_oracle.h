@@ -115,6 +115,28 @@ int oracle_decoder_call(OracleDecoder *d, uint8_t *window, const uint8_t *in, si
 typedef void (*oracle_token_cb)(void *user, int kind, size_t in_pos, unsigned len, unsigned index);
 void oracle_set_token_cb(oracle_token_cb cb, void *user);
 
+/* Per-decision hook for lazy matching (compressor.c:576-619), apart from the token hook: one call for every poll that
+ * reaches the lazy block, saying where its match came from (`origin`), the match (len, idx), the probe of the next
+ * position (nlen, nidx; 0 when none was made), window_pos and the ring fill R, and what was decided (`event`).  Two
+ * more events report a cached match that the RLE / extended handler dropped before the lazy block was reached, and
+ * one a cached match that became the start of an extended match (it follows that poll's decision event), one a cached
+ * match used in place of the match the RLE arbitration handed over (it precedes that poll's decision event). */
+enum {
+    ORACLE_LAZY_NO_PROBE_LEN = 0,   /* len < min_pattern or len > 8 */
+    ORACLE_LAZY_NO_PROBE_RING = 1,  /* R <= len + 2 */
+    ORACLE_LAZY_TIE_OR_SHORTER = 2, /* nlen <= len */
+    ORACLE_LAZY_OVERLAP = 3,        /* nlen > len, but the probe's source covers window_pos */
+    ORACLE_LAZY_DEFER = 4,          /* literal now, (nidx, nlen) cached */
+    ORACLE_LAZY_DROPPED_BY_RLE = 5,
+    ORACLE_LAZY_DROPPED_BY_EXT = 6,
+    ORACLE_LAZY_CACHED_TO_EXT = 7,
+    ORACLE_LAZY_CACHED_OVER_RLE = 8, /* (len, idx) cached, (nlen, nidx) what the RLE arbitration had just found */
+};
+enum { ORACLE_LAZY_FRESH = 0, ORACLE_LAZY_CACHED = 1, ORACLE_LAZY_FROM_RLE = 2 };
+typedef void (*oracle_lazy_cb)(void *user, int event, size_t in_pos, int origin, unsigned len, unsigned idx, unsigned nlen,
+                               unsigned nidx, unsigned window_pos, unsigned ring);
+void oracle_set_lazy_cb(oracle_lazy_cb cb, void *user);
+
 #ifdef __cplusplus
 }
 #endif
