@@ -111,6 +111,21 @@ __device__ __forceinline__ uint32_t lds_u32_unaligned(const uint8_t* base, uint3
     return __builtin_amdgcn_alignbyte(w[1], w[0], off & 3u);
 }
 
+// 4 * N consecutive bytes at an arbitrary LDS byte offset, as N dwords: P[j] = lds_u32_unaligned(base, off + 4 * j), from ONE
+// aligned base -- N + 1 aligned dwords at immediate offsets and N funnel shifts by the one byte phase, where N separate calls
+// compute N addresses and fetch 2 * N dwords (neighbouring pairs overlap).  Reads up to base + (off & ~3) + 4 * N + 3, like
+// the last of those calls.
+template <int N>
+__device__ __forceinline__ void lds_bytes_unaligned(const uint8_t* base, uint32_t off, uint32_t (&P)[N]) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(base + (off & ~3u));
+    const uint32_t sh = off & 3u;
+    uint32_t d[N + 1];
+#pragma unroll
+    for (int j = 0; j <= N; j++) d[j] = w[j];
+#pragma unroll
+    for (int j = 0; j < N; j++) P[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], sh);
+}
+
 // Inclusive scans over the 64 lanes with DPP row shifts and row broadcasts (six data-parallel-primitive moves instead of
 // six ds_bpermute round trips through the LDS pipe with their lane-index arithmetic: __shfl_up compiles to the latter).
 // row_shr:n keeps `old` (the identity) where the source lane lies outside the 16-lane row; row_bcast:15 / :31 hand the

@@ -869,6 +869,11 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     // lengths are counted inside the scatter (kFoldSort, see there), and the 16-byte compare's tail is three ORs (kOrTail,
     // prefix_len16).  Each was judged alone against the build without it: profiles/static_lds_ab.txt.
     constexpr bool kFoldSort = FX, kOrTail = FX;
+    // ... and three more in the code around the bucket scan, each again judged alone (profiles/query_setup_ab.txt): patterns are
+    // loaded from one aligned base (kPat16, lds_bytes_unaligned), the histogram pass treats full quads apart from the one partial
+    // quad a range can end with and stores a block quad's four bucket numbers at once (kQuadHist), and the loops whose trip count
+    // the constant geometry fixes are straight-line stores (kConstLoops).
+    constexpr bool kPat16 = FX, kQuadHist = FX, kConstLoops = FX;
     static_assert(!FX || (PACKED && !LAZY && RUNS && WSCAN == (1u << kFixWbits) && HB == kHb1024 && LOOP && !BLOCKM),
                   "fixed geometry: the run-aware persistent build of the 2^10 window");
     // HB: bucket bits of the bigram index (2,048 buckets; 512 for the short-message build, whose blocks hold a few hundred
@@ -1070,6 +1075,13 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         // bits, rest zero
         const uint32_t nlead = FX ? 1u : a.nlead;  // (fixed builds: the header byte)
         const uint32_t word0 = (BLOCKM && s != 0) ? 0u : (nlead ? (uint32_t)a.lead << 16 : (c_nbits ? c_bits & (0xFFFFFFFFu << (32 - c_nbits)) : 0u));
+        if constexpr (kConstLoops) {
+            // (constant geometry: 516 words are one 8-byte store per thread and a tail of two)
+            static_assert(kLdsFixed.obuf_words % 2 == 0 && kLdsFixed.obuf_words / 2 >= kFixThreads && kLdsFixed.obuf_words / 2 <= 2 * kFixThreads, "pairs of words: one per thread and a guarded tail");
+            uint2* const obuf2 = reinterpret_cast<uint2*>(obuf);
+            obuf2[tid] = make_uint2(tid == 0 ? __builtin_bswap32(word0) : 0u, 0u);
+            if (tid < kLdsFixed.obuf_words / 2 - kFixThreads) obuf2[kFixThreads + tid] = make_uint2(0u, 0u);
+        } else
         for (uint32_t k = tid; k < L.obuf_words; k += nt) obuf[k] = k == 0 ? __builtin_bswap32(word0) : 0;
 
         Walk wk;
@@ -1144,6 +1156,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     }
                     for (uint32_t k = (nw << 2) + tid; k < nfill; k += nt) ebuf[W + k] = k < nload ? src[k] : 0;
                 }
+                if constexpr (kConstLoops) {
+                    static_assert(!kConstLoops || kBuckets / 2 == 2 * kFixThreads, "the cursor words: one pair per thread");
+                    reinterpret_cast<uint2*>(cntw)[tid] = make_uint2(0u, 0u);
+                } else
                 for (uint32_t k = tid; k < kBuckets / 2; k += nt) cntw[k] = 0;
                 if (tid == 0) ctl[cCut] = 0xFFFFFFFFu;
                 __syncthreads();
@@ -1194,6 +1210,19 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             if (all) atomicMin((uint32_t*)&ctl[cCut], c4);
                         }
                     }
+                    // kQuadHist (the fixed-geometry builds): NE0 is uniform, so only the last quad of the range can be partial.  A
+                    // full quad counts its four positions without a test each, and a block quad's four bucket numbers are four
+                    // consecutive u16 slots of `qstart` (c4 - W is a multiple of 4, the table 16-byte aligned): one 8-byte store.
+                    if (kQuadHist && c4 + 4 <= NE0) {
+                        uint32_t hq[4];
+                        hq[0] = mix16<HB>(d0 & 0xFFFFu) >> kRem;
+#pragma unroll
+                        for (uint32_t j = 1; j < 4; j++) hq[j] = mix16<HB>(__builtin_amdgcn_alignbyte(d1, d0, j) & 0xFFFFu) >> kRem;
+#pragma unroll
+                        for (uint32_t j = 0; j < 4; j++) atomicAdd(&cntw[hq[j] >> 1], 1u << ((hq[j] & 1) * 16));
+                        if (c4 >= W) *reinterpret_cast<uint2*>(qstart + (c4 - W)) = make_uint2(hq[0] | (hq[1] << 16), hq[2] | (hq[3] << 16));
+                        continue;
+                    }
 #pragma unroll
                     for (uint32_t j = 0; j < 4; j++) {
                         if (c4 + j < NE0) {
@@ -1211,7 +1240,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     if (cutc < NE0) nvalid = cutc - W + 4, nv = LAZY ? 2 * nvalid : nvalid;
                 }
                 const uint32_t NE = nvalid ? W + nvalid : 0;  // positions the index lists (the counts above are upper bounds)
-                for (uint32_t k = nvalid + tid; k < nvalid + 128 && k < a_blk + 128; k += nt) blen[k] = 0x80;  // sentinels
+                // sentinels (constant geometry: nvalid <= the block, so the second bound never binds and 128 threads store one each)
+                if constexpr (kConstLoops) {
+                    static_assert(kFixThreads >= 128, "one sentinel per thread");
+                    if (tid < 128) blen[nvalid + tid] = 0x80;
+                } else
+                for (uint32_t k = nvalid + tid; k < nvalid + 128 && k < a_blk + 128; k += nt) blen[k] = 0x80;
                 uint32_t nruns = 0;  // listed runs of this epoch (RUNS builds)
                 if constexpr (RUNS) {
                     if (Walk::uni(ctl[cQuad])) {
@@ -1222,6 +1256,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         // them); the match phase derives, per run, the few interior positions that can hold the best
                         // match (see there).  Heads scan their own run; ends are capped a little past the indexed
                         // range (any run remainder > 16 acts the same).
+                        if constexpr (kConstLoops) {
+                            static_assert(((1u << kFixWbits) + kFixBlk + 96) / 32 <= kFixThreads, "the bitmap: a word per thread at most");
+                            if (tid < ((1u << kFixWbits) + kFixBlk + 96) / 32) rbits[tid] = 0;
+                        } else
                         for (uint32_t k = tid; k < (W + a_blk + 96) / 32; k += nt) rbits[k] = 0;
                         if (tid == 0) ctl[cNruns] = 0;
                         if (tid < 8) rxset[tid] = 0;
@@ -1381,8 +1419,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         cap_lenB = Rb >= minp ? (Rb < maxp ? Rb : maxp) : 0;
                     }
                     uint32_t P[4];
+                    if constexpr (kPat16) {
+                        lds_bytes_unaligned(ebuf, W + q, P);  // (one base, five dwords, one byte phase)
+                    } else {
 #pragma unroll
-                    for (int jj = 0; jj < 4; jj++) P[jj] = lds_u32_unaligned(ebuf, W + q + 4 * jj);
+                        for (int jj = 0; jj < 4; jj++) P[jj] = lds_u32_unaligned(ebuf, W + q + 4 * jj);
+                    }
                     // Inside a run of one byte the extended state machine never asks for a match: with the previous
                     // byte repeated 7+ times ahead, or up to the end of the ring, the RLE path owns the position
                     // (compressor.c:470-503 only consults find_best_match for runs of 2..6 that END inside the ring).
@@ -1636,8 +1678,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             const uint32_t R = leftq < kRing ? leftq : kRing;
                             if (R < minp) continue;
                             uint32_t P[4];
+                            if constexpr (kPat16) {
+                                lds_bytes_unaligned(ebuf, W + q, P);  // (P[0] is b01: the same base and phase)
+                            } else {
 #pragma unroll
-                            for (int jj = 0; jj < 4; jj++) P[jj] = lds_u32_unaligned(ebuf, W + q + 4 * jj);
+                                for (int jj = 0; jj < 4; jj++) P[jj] = lds_u32_unaligned(ebuf, W + q + 4 * jj);
+                            }
                             const uint32_t rep = x * 0x01010101u;
                             uint32_t rq = 16;
 #pragma unroll
@@ -1762,13 +1808,18 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                             const uint32_t leftq = n - (e_p0 + q);
                             if (partial && leftq < kRing) continue;  // (the call ends in front of this position)
                             const uint32_t wpq = (e_wp + q) & mask;  // window_pos when the walk arrives here clean
-                            const uint32_t b4 = lds_u32_unaligned(ebuf, W + q - 1);  // previous byte, then the next three
+                            // (kPat16: the twelve bytes from the previous one on, from one aligned base; the two dwords of the run
+                            // test below start three bytes into them)
+                            uint32_t A[3] = {0, 0, 0};
+                            if constexpr (kPat16) lds_bytes_unaligned(ebuf, W + q - 1, A);
+                            const uint32_t b4 = kPat16 ? A[0] : lds_u32_unaligned(ebuf, W + q - 1);  // previous byte, then the next three
                             const uint32_t prev = b4 & 0xFFu, b0 = (b4 >> 8) & 0xFFu, b1 = (b4 >> 16) & 0xFFu;
                             if (prev == b0) {
                                 if (b1 != b0 || leftq < 2) continue;  // (a single byte at the very end of the input)
                                 // run length from q, looked at up to 9 bytes
                                 const uint32_t rep = b0 * 0x01010101u;
-                                const uint32_t x0 = lds_u32_unaligned(ebuf, W + q + 2) ^ rep, x1 = lds_u32_unaligned(ebuf, W + q + 6) ^ rep;
+                                const uint32_t x0 = (kPat16 ? __builtin_amdgcn_alignbyte(A[1], A[0], 3) : lds_u32_unaligned(ebuf, W + q + 2)) ^ rep;
+                                const uint32_t x1 = (kPat16 ? __builtin_amdgcn_alignbyte(A[2], A[1], 3) : lds_u32_unaligned(ebuf, W + q + 6)) ^ rep;
                                 const uint32_t r = 2u + (x0 ? (uint32_t)__builtin_ctz(x0) >> 3 : 4u + (x1 ? (uint32_t)__builtin_ctz(x1) >> 3 : 4u));
                                 if (r > kRleWindowMax || r >= leftq || wpq + r > W) continue;
                                 if (r <= 6 && len > r) {  // the pattern wins: an ordinary match step (or an extended match: slow)
@@ -1803,7 +1854,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     __syncthreads();
                 }
                 }  // (!have_tables)
-                for (uint32_t k = 4 + tid; k < 4 + a_blk / 2 && k < L.obuf_words; k += nt) obuf[k] = 0;  // scan starts out
+                // scan starts out (constant geometry: words 4..515, a pair per thread)
+                if constexpr (kConstLoops) {
+                    static_assert(kFixBlk / 2 == 2 * kFixThreads && 4 + kFixBlk / 2 <= kLdsFixed.obuf_words, "the scan starts: one pair of words per thread");
+                    reinterpret_cast<uint2*>(obuf + 4)[tid] = make_uint2(0u, 0u);
+                } else
+                for (uint32_t k = 4 + tid; k < 4 + a_blk / 2 && k < L.obuf_words; k += nt) obuf[k] = 0;
                 // Jump tables for the walk (the index is dead now, its space is reused).  Within each 64-position
                 // block, lane = position: six rounds of pointer doubling over ds_bpermute give, for every position, where
                 // the chain of plain steps starting there leaves the block (or the "slow" position it stops at) and how
