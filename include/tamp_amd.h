@@ -935,8 +935,10 @@ tamp_res tamp_amd_compress_segment(const TampAmdConf *conf, int emit_header, int
  * bytes (16 when the last poll took none).  The next piece continues from it (resume = 1).  finish = 1 ends the segment like tamp_amd_compress_segment
  * (tamp_compressor_flush with write_token = flush_token) and clears the carry.  This is what bounded-memory writers are
  * built from: tamp_amd.Compressor.write() sends a piece whenever it has gathered enough and returns the bytes written,
- * as tamp/_c_compressor.pyx:74-118 does.  Not offered with conf->lazy_matching (the cached match of compressor.c:576-619
- * is not carried): TAMP_AMD_BAD_ARGUMENT.  Give a piece tamp_amd_compress_bound(input_size + 271, ...) bytes of room;
+ * as tamp/_c_compressor.pyx:74-118 does.  With conf->lazy_matching an unfinished piece also leaves a cached match behind
+ * (compressor.c:576-619), for which TampAmdCarry has no field: this call answers finish = 0 of a lazy configuration with
+ * TAMP_AMD_BAD_ARGUMENT, and tamp_amd_compress_piece_lazy below takes every configuration.
+ * Give a piece tamp_amd_compress_bound(input_size + 271, ...) bytes of room;
  * TAMP_OUTPUT_FULL leaves window_state / *window_pos / *carry byte-identical to what they were, and a piece with finish = 0
  * then delivers nothing (*output_written_size = 0: offered again it emits all its bytes); exact room is enough.
  */
@@ -956,6 +958,29 @@ tamp_res tamp_amd_compress_piece(const TampAmdConf *conf, int emit_header, int a
                                  int flush_token, unsigned char *window_state, uint16_t *window_pos, TampAmdCarry *carry,
                                  unsigned char *output, size_t output_size, size_t *output_written_size,
                                  const unsigned char *input, size_t input_size, int *token_written, int device);
+
+/*
+ * tamp_amd_compress_piece for every configuration, lazy matching included: the same parameters and the same contract, with
+ * a carry that also holds the reference object's cached_match_index / cached_match_size (compressor.c:603-608) -- the match
+ * the call's last poll found one position ahead when it put a literal in front of it.  The next piece's first poll starts
+ * from it.  With a configuration without lazy matching the two fields stay 0 and the bytes are those of
+ * tamp_amd_compress_piece.  finish = 1 clears them with the rest of the carry; TAMP_OUTPUT_FULL of an unfinished piece
+ * leaves all 32 bytes as they came.  A cached match that comes in (cached_len != 0) goes with resume = 1 and a lazy
+ * configuration, excludes a pending run or extended match (poll_extended_handling clears the cache whenever it consumes),
+ * lies inside the window (cached_pos + cached_len <= 1 << window) and is no longer than the tail, whose leading bytes it
+ * matches (the probe saw ring bytes only): anything else is TAMP_AMD_BAD_ARGUMENT, and nothing is written.
+ */
+typedef struct TampAmdLazyCarry {
+    TampAmdCarry carry;  /* as for tamp_amd_compress_piece */
+    uint16_t cached_pos; /* window index of the match cached by the last poll's probe ... */
+    uint8_t cached_len;  /* ... and its length; 0: none (a zero-filled struct is a fresh object) */
+    uint8_t reserved2;
+} TampAmdLazyCarry;      /* 32 bytes */
+tamp_res tamp_amd_compress_piece_lazy(const TampAmdConf *conf, int emit_header, int append_marker, int resume, int finish,
+                                      int flush_token, unsigned char *window_state, uint16_t *window_pos,
+                                      TampAmdLazyCarry *carry, unsigned char *output, size_t output_size,
+                                      size_t *output_written_size, const unsigned char *input, size_t input_size,
+                                      int *token_written, int device);
 
 /* Replaces tamp_decompressor_read_header (decompressor.h:67, decompressor.c:276-297): host-side header parse. */
 tamp_res tamp_amd_read_header(TampAmdConf *conf, const unsigned char *input, size_t input_size,

@@ -62,6 +62,7 @@ SYMBOLS = (
     "tamp_amd_decompress",
     "tamp_amd_compress_segment",
     "tamp_amd_compress_piece",
+    "tamp_amd_compress_piece_lazy",
     "tamp_amd_read_header",
     "tamp_amd_set_timing",
     "tamp_amd_last_kernel_ms",
@@ -116,6 +117,16 @@ class TampAmdCarry(C.Structure):
         ("reserved", C.c_uint16),
         ("bits", C.c_uint32),
         ("tail", C.c_uint8 * 16),
+    ]
+
+
+class TampAmdLazyCarry(C.Structure):
+    """include/tamp_amd.h TampAmdLazyCarry: a TampAmdCarry and the match lazy matching cached for the next position."""
+    _fields_ = [
+        ("carry", TampAmdCarry),
+        ("cached_pos", C.c_uint16),
+        ("cached_len", C.c_uint8),  # 0: none
+        ("reserved2", C.c_uint8),
     ]
 
 
@@ -242,6 +253,9 @@ def load() -> C.CDLL:
     lib.tamp_amd_compress_piece.argtypes = [C.POINTER(TampAmdConf), i32, i32, i32, i32, i32, vp, C.POINTER(C.c_uint16),
                                             C.POINTER(TampAmdCarry), vp, sz, C.POINTER(sz), vp, sz, C.POINTER(i32), i32]
     lib.tamp_amd_compress_piece.restype = C.c_int8
+    lib.tamp_amd_compress_piece_lazy.argtypes = [C.POINTER(TampAmdConf), i32, i32, i32, i32, i32, vp, C.POINTER(C.c_uint16),
+                                                 C.POINTER(TampAmdLazyCarry), vp, sz, C.POINTER(sz), vp, sz, C.POINTER(i32), i32]
+    lib.tamp_amd_compress_piece_lazy.restype = C.c_int8
     lib.tamp_amd_read_header.argtypes = [C.POINTER(TampAmdConf), vp, sz, C.POINTER(sz)]
     lib.tamp_amd_read_header.restype = C.c_int8
     lib.tamp_amd_set_timing.argtypes = [i32]

@@ -49,13 +49,13 @@ class Compressor:
     """``tamp.Compressor`` (tamp/_c_compressor.pyx:13-186) over the piece / segment calls of the engine.
 
     ``write()`` gathers bytes and, whenever ``PIECE_MIN`` of them are waiting, hands them to the GPU as one PIECE
-    (``tamp_amd_compress_piece``, finish = 0): the piece ends as a ``tamp_compressor_compress`` call ends -- no FLUSH token,
+    (``tamp_amd_compress_piece_lazy``, finish = 0): the piece ends as a ``tamp_compressor_compress`` call ends -- no FLUSH token,
     no drain -- and the object keeps what the reference's object keeps (window, window position, a run / extended match
-    that is still growing, < 8 output bits, the unparsed bytes of the 16-byte ring).  ``write()`` returns the bytes that reached ``f``
+    that is still growing, < 8 output bits, the unparsed bytes of the 16-byte ring and, with ``lazy_matching``, the match
+    cached for the next position, compressor.c:576-619).  ``write()`` returns the bytes that reached ``f``
     during the call, like the reference (tamp/_c_compressor.pyx:74-118), and memory stays bounded by ``PIECE_MAX``.
     ``flush()`` / ``reset_dictionary()`` / ``close()`` end the segment on the GPU (FLUSH tokens, ``dictionary_reset``,
-    ``append`` are produced by the kernel, not emulated on the host).  With ``lazy_matching`` the cached match of
-    compressor.c:576-619 is not carried between pieces: such a stream is gathered until the next flush point.
+    ``append`` are produced by the kernel, not emulated on the host).
     """
 
     PIECE_MIN = 64 << 10  # bytes gathered before a piece is worth a launch
@@ -83,14 +83,13 @@ class Compressor:
         if dictionary is not None:
             self._window[:] = bytes(dictionary)
         self._window_pos = C.c_uint16(0)
-        self._carry = _lib.TampAmdCarry()
+        self._carry = _lib.TampAmdLazyCarry()
         self._pending = bytearray()
         self._opened = False    # header / append marker already sent
         self._resume = False    # _window holds a carried window (else: fresh stream)
         self._dirty = False     # data was handed over since the last flush point (compressor.c:548)
         self._last_was_flush = self._append  # compressor.c:234
         self._device = device
-        self._streaming = not lazy_matching
         _lib.load()  # fail loudly now if the native library is missing
 
     def _call(self, data: bytes, finish: bool, want_token: bool):
@@ -103,7 +102,7 @@ class Compressor:
         token = C.c_int(0)
         src = (C.c_ubyte * max(n, 1)).from_buffer_copy(data if n else b"\0")
         first = not self._opened
-        res = lib.tamp_amd_compress_piece(
+        res = lib.tamp_amd_compress_piece_lazy(
             C.byref(self._conf), int(first and not self._append), int(first and self._append), int(self._resume),
             int(finish), int(want_token), self._window, C.byref(self._window_pos), C.byref(self._carry), out, cap,
             C.byref(written), src, n, C.byref(token), self._device)
@@ -118,7 +117,7 @@ class Compressor:
 
     def write(self, data) -> int:
         self._pending += bytes(data)
-        if not self._streaming or len(self._pending) < self.PIECE_MIN:
+        if len(self._pending) < self.PIECE_MIN:
             return 0
         total = 0
         while len(self._pending) >= self.PIECE_MIN:  # bounded pieces, no flush token in between
@@ -135,41 +134,18 @@ class Compressor:
         want_token = bool(flush_token) and not self._last_was_flush  # compressor.c:784
         if n == 0 and not self._dirty and self._opened and not (want_token and self._dictionary_reset):
             return 0  # byte aligned, nothing buffered: the reference's flush writes nothing either
-        if self._streaming:
-            total = 0
-            while len(self._pending) > self.PIECE_MAX:  # (a flush after a very large gathered write: still bounded pieces)
-                piece = bytes(self._pending[: self.PIECE_MAX])
-                del self._pending[: len(piece)]
-                total += self._call(piece, finish=False, want_token=False)[0]
-            written, token = self._call(bytes(self._pending), finish=True, want_token=want_token)
-            total += written
-        else:
-            total, token = self._segment_gathered(want_token)
+        total = 0
+        while len(self._pending) > self.PIECE_MAX:  # (a flush after a very large gathered write: still bounded pieces)
+            piece = bytes(self._pending[: self.PIECE_MAX])
+            del self._pending[: len(piece)]
+            total += self._call(piece, finish=False, want_token=False)[0]
+        written, token = self._call(bytes(self._pending), finish=True, want_token=want_token)
+        total += written
         self._pending.clear()
         self._dirty = False
         if token:
             self._last_was_flush = True
         return total
-
-    def _segment_gathered(self, want_token: bool):
-        """lazy_matching: everything since the last flush point as ONE segment (tamp_amd_compress_segment)."""
-        lib = _lib.load()
-        n = len(self._pending)
-        cap = lib.tamp_amd_compress_bound(n, self._conf.literal, 0) + 4
-        out = (C.c_ubyte * cap)()
-        written = C.c_size_t(0)
-        token = C.c_int(0)
-        src = (C.c_ubyte * max(n, 1)).from_buffer_copy(bytes(self._pending) if n else b"\0")
-        res = lib.tamp_amd_compress_segment(
-            C.byref(self._conf), int(not self._opened and not self._append), int(not self._opened and self._append),
-            int(self._resume), int(want_token), self._window, C.byref(self._window_pos), out, cap,
-            C.byref(written), src, n, C.byref(token), self._device)
-        if res < 0:
-            _raise_for(res)
-        self._opened = self._resume = True
-        if written.value:
-            self.f.write(bytes(out[: written.value]))
-        return written.value, bool(token.value)
 
     def flush(self, write_token: bool = True) -> int:
         n = self._segment(write_token)
@@ -185,7 +161,7 @@ class Compressor:
             self._last_was_flush = False
             total += self._segment(True)
         self._resume = False  # next segment starts from the seed dictionary again (never the custom one)
-        self._carry = _lib.TampAmdCarry()
+        self._carry = _lib.TampAmdLazyCarry()
         self._conf.use_custom_dictionary = 0
         self._window_pos = C.c_uint16(0)
         self._last_was_flush = self._append

@@ -3930,14 +3930,19 @@ tamp_res compat_segment(TampCompressor* compressor, unsigned char* output, size_
 
 namespace {
 // tamp_compressor_compress on an object, large input, ample output room: ONE piece for the batch kernel
-// (tamp_amd_compress_piece, finish = 0) instead of token-by-token parsing by one wavefront -- the same stream and the
+// (tamp_amd_compress_piece_lazy, finish = 0) instead of token-by-token parsing by one wavefront -- the same stream and the
 // same object state as far as any later call can tell, except that every whole output byte leaves now (the reference
 // would hold the last token's bits back until the next poll: `written` may run up to four bytes ahead of it).
 constexpr size_t kCompatPieceMin = 64 << 10;
 bool compat_piece_applies(const TampAmdEncoderState* s, size_t input_size, size_t output_size) {
     if (input_size < kCompatPieceMin || input_size > 0xFFFFFF00ull) return false;
-    if ((s->flags >> 4) & 1) return false;  // lazy matching: the cached match is not carried
-    if (s->cached_match_index >= 0 || s->input_size > 16 || s->bit_buffer_pos > 31) return false;
+    if (s->input_size > 16 || s->bit_buffer_pos > 31) return false;
+    // lazy matching: a cached match goes along (TampAmdLazyCarry) in the shape every poll leaves it in -- nothing else pending,
+    // its bytes in the ring; any other object state stays with the token-level kernel
+    if (s->cached_match_index >= 0 &&
+        (!((s->flags >> 4) & 1) || s->rle_count || s->extended_match_count || s->cached_match_size == 0 ||
+         s->cached_match_size > s->input_size || (size_t)s->cached_match_index + s->cached_match_size > ((size_t)1 << s->window)))
+        return false;
     return output_size >= tamp_amd_compress_bound(input_size + 300, s->literal, 0) + 8;
 }
 
@@ -3947,9 +3952,12 @@ tamp_res compat_piece(TampCompressor* compressor, unsigned char* output, size_t 
     TampAmdConf c;
     std::memset(&c, 0, sizeof c);
     c.window = s->window, c.literal = s->literal, c.extended = (s->flags >> 1) & 1;
-    c.use_custom_dictionary = s->flags & 1, c.dictionary_reset = (s->flags >> 2) & 1;
-    TampAmdCarry carry;
-    std::memset(&carry, 0, sizeof carry);
+    c.use_custom_dictionary = s->flags & 1, c.dictionary_reset = (s->flags >> 2) & 1, c.lazy_matching = (s->flags >> 4) & 1;
+    TampAmdLazyCarry lz;
+    std::memset(&lz, 0, sizeof lz);
+    TampAmdCarry& carry = lz.carry;
+    // (cached_match_index / _size: -1 means none, a length of 0 on this side)
+    if (s->cached_match_index >= 0) lz.cached_pos = (uint16_t)s->cached_match_index, lz.cached_len = s->cached_match_size;
     carry.rle_count = s->rle_count, carry.ext_count = s->extended_match_count, carry.ext_pos = s->extended_match_position;
     carry.bit_count = s->bit_buffer_pos, carry.bits = s->bit_buffer;
     carry.tail_len = s->input_size;
@@ -3957,10 +3965,12 @@ tamp_res compat_piece(TampCompressor* compressor, unsigned char* output, size_t 
     uint16_t wp = s->window_pos;
     int token = 0;
     // (resume = 1: the object's window buffer IS the state -- seeded or custom at init, carried since)
-    tamp_res r = tamp_amd_compress_piece(&c, 0, 0, 1, 0, 0, compressor->window, &wp, &carry, output, output_size, written,
-                                         input, input_size, &token, compat_device());
+    tamp_res r = tamp_amd_compress_piece_lazy(&c, 0, 0, 1, 0, 0, compressor->window, &wp, &lz, output, output_size, written,
+                                              input, input_size, &token, compat_device());
     if (r != TAMP_OK) return r;
     s->window_pos = wp;
+    s->cached_match_index = lz.cached_len ? (int16_t)lz.cached_pos : (int16_t)-1;
+    s->cached_match_size = lz.cached_len;  // (the token-level kernel reads it only behind an index >= 0)
     s->rle_count = carry.rle_count, s->extended_match_count = carry.ext_count, s->extended_match_position = carry.ext_pos;
     s->bit_buffer_pos = carry.bit_count, s->bit_buffer = carry.bit_count ? carry.bits : 0u;
     s->input_pos = 0, s->input_size = carry.tail_len;
@@ -4355,14 +4365,23 @@ namespace {
 // SEGMENT; finish = 0: it ends the way tamp_compressor_compress ends a call (compressor.c:681-722) and `carry` takes what
 // the reference's object would still hold.  A carry that comes in is continued from (its run / extended match bytes and
 // its unparsed tail are put back in front of the input: tamp_compress_kernel.hpp, kSegStateExtra).
+// `cached_pos` / `cached_len` (both or neither): the cached match of lazy matching beside the carry (kSlotLazyPos / kSlotLazyLen).
+// Without them an unfinished piece of a lazy configuration is refused: the match would be lost.
 tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marker, int resume, int finish, int flush_token,
                       unsigned char* window_state, uint16_t* window_pos, TampAmdCarry* carry, unsigned char* output,
                       size_t output_size, size_t* output_written_size, const unsigned char* input, size_t input_size,
-                      int* token_written, int device) {
+                      int* token_written, int device, uint16_t* cached_pos = nullptr, uint8_t* cached_len = nullptr) {
     if (output_written_size) *output_written_size = 0;
     if (token_written) *token_written = 0;
     if (!conf_valid(conf) || conf->lazy_matching > 1 || !window_state || !window_pos) return TAMP_INVALID_CONF;
-    if (!finish && (!carry || conf->lazy_matching)) return TAMP_AMD_BAD_ARGUMENT;  // (lazy: the cached match is not carried)
+    if (!finish && (!carry || (conf->lazy_matching && !cached_len))) return TAMP_AMD_BAD_ARGUMENT;  // (lazy: nowhere to leave the cached match)
+    if (cached_len && *cached_len) {
+        // a cached match belongs to a lazy object in the middle of its input, with no run or extended match pending
+        // (compressor.c:563-570), and its bytes are ring bytes: the probe saw nothing else (:588-596)
+        if (!carry || !resume || !conf->lazy_matching || carry->rle_count || carry->ext_count ||
+            (size_t)*cached_pos + *cached_len > ((size_t)1 << conf->window) || *cached_len > carry->tail_len)
+            return TAMP_AMD_BAD_ARGUMENT;
+    }
     if (input_size > 0xFFFFFF00ull) return TAMP_AMD_BAD_ARGUMENT;
     DeviceCtx* ctx = nullptr;
     int rc = get_ctx(device, &ctx);
@@ -4402,6 +4421,7 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         prefix.insert(prefix.end(), carry->tail, carry->tail + carry->tail_len);
         put(kSlotRle, carry->rle_count, 1), put(kSlotExtCount, carry->ext_count, 1), put(kSlotNbits, carry->bit_count, 1);
         put(kSlotExtPos, carry->ext_pos, 2), put(kSlotBits, carry->bits, 4);
+        if (cached_len && *cached_len) put(kSlotLazyLen, *cached_len, 1), put(kSlotLazyPos, *cached_pos, 2);
     }
     if (!finish && resume && input_size == 0 && !seg.nlead) {
         // tamp_compressor_compress without input: nothing is sunk and nothing polled, even on a full ring
@@ -4461,9 +4481,11 @@ tamp_res segment_core(const TampAmdConf* conf, int emit_header, int append_marke
         std::memcpy(window_state, stbuf.data(), W);
         *window_pos = (uint16_t)get(kSlotWindowPos, 2);
         if (token_written) *token_written = (int)get(kSlotToken, 1);
+        if (cached_len) *cached_pos = 0, *cached_len = 0;
         if (carry) {
             std::memset(carry, 0, sizeof *carry);
             if (!finish) {
+                if (cached_len) *cached_len = (uint8_t)get(kSlotLazyLen, 1), *cached_pos = (uint16_t)(*cached_len ? get(kSlotLazyPos, 2) : 0);
                 carry->rle_count = (uint8_t)get(kSlotRle, 1), carry->ext_count = (uint8_t)get(kSlotExtCount, 1);
                 carry->bit_count = (uint8_t)get(kSlotNbits, 1), carry->ext_pos = (uint16_t)get(kSlotExtPos, 2);
                 carry->bits = get(kSlotBits, 4);
@@ -4502,6 +4524,18 @@ tamp_res tamp_amd_compress_piece(const TampAmdConf* conf, int emit_header, int a
     if (!carry) return TAMP_AMD_BAD_ARGUMENT;
     return segment_core(conf, emit_header, append_marker, resume, finish, flush_token, window_state, window_pos, carry, output,
                         output_size, output_written_size, input, input_size, token_written, device);
+}
+
+tamp_res tamp_amd_compress_piece_lazy(const TampAmdConf* conf, int emit_header, int append_marker, int resume, int finish,
+                                      int flush_token, unsigned char* window_state, uint16_t* window_pos, TampAmdLazyCarry* carry,
+                                      unsigned char* output, size_t output_size, size_t* output_written_size,
+                                      const unsigned char* input, size_t input_size, int* token_written, int device) {
+    if (output_written_size) *output_written_size = 0;
+    if (token_written) *token_written = 0;
+    if (!carry) return TAMP_AMD_BAD_ARGUMENT;
+    return segment_core(conf, emit_header, append_marker, resume, finish, flush_token, window_state, window_pos, &carry->carry,
+                        output, output_size, output_written_size, input, input_size, token_written, device, &carry->cached_pos,
+                        &carry->cached_len);
 }
 
 }  // extern "C"

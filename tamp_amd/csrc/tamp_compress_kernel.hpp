@@ -740,7 +740,9 @@ enum : uint32_t {
     kSlotExtCount = 4,   // u8 extended-match count
     kSlotNbits = 5,      // u8 pending output bits (in: 0..31, a reference object may sit on a whole token; out: 0..7)
     kSlotExtPos = 6,     // u16 extended-match window position
+    kSlotLazyLen = 8,    // u8 lazy builds: length of the match cached by the last poll's probe (cached_match_size), 0 = none
     kSlotParsed = 9,     // u32 input bytes parsed (out)
+    kSlotLazyPos = 13,   // u16 lazy builds: that match's window index in ring coordinates (cached_match_index)
     kSlotBits = 16,      // u32 the pending bits, left aligned (first bit in bit 31)
 };
 // The fields behind the token flag are what a TampCompressor carries between two calls that are NOT separated by a
@@ -748,6 +750,11 @@ enum : uint32_t {
 // the way tamp_compressor_compress_cb ends a call (compressor.c:681-722): parse steps only while 16 bytes of look-ahead
 // are there, no drain.  The bytes a pending run / extended match has consumed, and the unparsed tail of the previous
 // call, come back IN FRONT of the next call's input (the host shim puts them there).
+// The lazy builds carry cached_match_index / cached_match_size as well (kSlotLazyPos / kSlotLazyLen): the match the
+// call's last poll found at position + 1 when it deferred (compressor.c:603-608).  It excludes a pending run or extended
+// match (poll_extended_handling clears the cache whenever it consumes, :563-570), its bytes lie in the unparsed tail,
+// and the next call's first poll starts from it.  A zero-filled slot carries none; the other builds neither read nor
+// write the two fields.
 constexpr uint32_t kSegStateExtra = 24;
 // ctl words
 enum : uint32_t { cAct = 0, cShift = 1, cP0 = 2, cPending = 3, cWp = 4, cNtok = 5, cExcess = 6, cBlk = 7, cWave = 8, cNruns = 12, cQuad = 13, cNext = 14, cCut = 15, cCutThr = 16 };
@@ -1093,6 +1100,16 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
         wk.ext_resolved = false, wk.ntok = 0, wk.ns = 0, wk.lane = lane;
         wk.ctlw = (Walk::CtlWord*)ctl, wk.coop = nt == 256;
         wk.lazy = lazy, wk.lazy_valid = false, wk.lazy_idx = 0, wk.lazy_len = 0, wk.blen2 = blen2, wk.bidx2 = bidx2;
+        if constexpr (LAZY) {
+            // the match the previous call's last poll cached (kSlotLazyLen / kSlotLazyPos): this call's first poll starts from it,
+            // whether the call ends like tamp_compressor_compress or drains.  No run and no extended match is pending beside it,
+            // so that poll is the step at position e_pending = 0, which the walk hands to the state machine.
+            if (st_io && (seg_flags & kSegResume)) {
+                wk.lazy_len = Walk::uni(st_io[W + kSlotLazyLen]);
+                wk.lazy_idx = Walk::uni((uint32_t)st_io[W + kSlotLazyPos] | ((uint32_t)st_io[W + kSlotLazyPos + 1] << 8));
+                wk.lazy_valid = wk.lazy_len != 0;
+            }
+        }
         if (tid_k == 0) ctl[cCutThr] = (FIX == kFixV1) ? 0u : a.cut_run;  // (read after the load phase's barrier)
         // (the byte behind the 15 prefix codes: every control word has a second use during the walk; read by the same thread, behind the stream)
         if (DICTS && !BLOCKM && tid_k == 0) codetab[kDictBadByte] = dict_ok ? 0 : 1;
@@ -2133,6 +2150,13 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                 st_io[W + kSlotRle] = (uint8_t)wk.rle_count, st_io[W + kSlotExtCount] = (uint8_t)wk.ext_count;
                                 st_io[W + kSlotExtPos] = (uint8_t)wk.ext_pos, st_io[W + kSlotExtPos + 1] = (uint8_t)(wk.ext_pos >> 8);
                                 for (uint32_t k = 0; k < 4; k++) st_io[W + kSlotParsed + k] = (uint8_t)(p >> (8 * k));
+                                if constexpr (LAZY) {
+                                    // the match the call's last poll cached when it deferred; a drain leaves none
+                                    const bool cached = partial && wk.lazy_valid;
+                                    st_io[W + kSlotLazyLen] = cached ? (uint8_t)wk.lazy_len : 0;
+                                    st_io[W + kSlotLazyPos] = cached ? (uint8_t)wk.lazy_idx : 0;
+                                    st_io[W + kSlotLazyPos + 1] = cached ? (uint8_t)(wk.lazy_idx >> 8) : 0;
+                                }
                             }
                         }
                         act = kActDone;

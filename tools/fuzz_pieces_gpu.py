@@ -2,7 +2,9 @@
 live reference object (oracle/_ref): the stream must be the reference's at every flush point and at the end, the running
 byte count at most eight bytes ahead of it in between (the reference's object holds back the bits of its last token, <= 4 bytes,
 and in the extended format a run / extended match it has not closed yet, <= 35 bits more; 5 was seen once in 5,000 scripts).
-usage: python tools/fuzz_pieces_gpu.py [seconds]   (GPU box)"""
+Lazy mode (a second argument `lazy`, or PIECES_LAZY=1): the same scripts with lazy_matching=True on both sides -- the cached match
+of compressor.c:576-619 then travels from piece to piece (tamp_amd_compress_piece_lazy).
+usage: python tools/fuzz_pieces_gpu.py [seconds] [lazy]   (GPU box)"""
 import io, os, random, sys, time
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
 import numpy as np
@@ -16,6 +18,7 @@ rng = random.Random(int(os.environ.get('FUZZ_SEED', '9')))
 tamp_amd.Compressor.PIECE_MIN = 1
 # PIECES_FOCUS=1: only the class of the one mismatch seen in round 6 (70,000 bytes, window 2^10, v1 format, no dictionary reset)
 FOCUS = os.environ.get('PIECES_FOCUS', '') not in ('', '0')
+LAZY = 'lazy' in sys.argv[2:] or os.environ.get('PIECES_LAZY', '') not in ('', '0')
 def long_repeats(L, k):
     r = np.random.default_rng(k)
     buf = bytearray(r.integers(97, 97 + int(r.integers(2, 20)), 64, dtype=np.uint8).tobytes())
@@ -56,10 +59,10 @@ while time.time() - t0 < budget:
         if dreset and rng.random() < 0.03: ops.append(("reset",))
     ops.append(("close",))
     want_counts = []
-    rc, want = ref.stream_script(ops, window=window, literal=literal, extended=ext, dictionary_reset=dreset, counts=want_counts)
+    rc, want = ref.stream_script(ops, window=window, literal=literal, extended=ext, dictionary_reset=dreset, lazy_matching=LAZY, counts=want_counts)
     assert rc == 0, rc
     f = io.BytesIO()
-    c = tamp_amd.Compressor(f, window=window, literal=literal, extended=ext, dictionary_reset=dreset)
+    c = tamp_amd.Compressor(f, window=window, literal=literal, extended=ext, dictionary_reset=dreset, lazy_matching=LAZY)
     got_counts = []
     for op in ops:
         if op[0] == "write": got_counts.append(c.write(op[1]))
@@ -70,13 +73,13 @@ while time.time() - t0 < budget:
     if f.getvalue() != want:
         got = f.getvalue()
         first = next((i for i in range(min(len(got), len(want))) if got[i] != want[i]), min(len(got), len(want)))
-        print("STREAM MISMATCH", scripts, window, literal, ext, dreset, "sizes", len(got), len(want), "first differing byte", first,
+        print("STREAM MISMATCH", scripts, window, literal, ext, dreset, "lazy" if LAZY else "default parse", "sizes", len(got), len(want), "first differing byte", first,
               "bytes out before each op", list(np.cumsum(got_counts))[:60],
               [(o[0], len(o[1]) if o[0] == 'write' else o[1:]) for o in ops][:60], flush=True)
         again = 0  # the same script three more times: a wrong answer that comes back is an algorithm bug, one that does not is a race
         for _ in range(3):
             f2 = io.BytesIO()
-            c2 = tamp_amd.Compressor(f2, window=window, literal=literal, extended=ext, dictionary_reset=dreset)
+            c2 = tamp_amd.Compressor(f2, window=window, literal=literal, extended=ext, dictionary_reset=dreset, lazy_matching=LAZY)
             for op in ops:
                 if op[0] == "write": c2.write(op[1])
                 elif op[0] == "flush": c2.flush(op[1])
@@ -97,4 +100,4 @@ while time.time() - t0 < budget:
         if (op[0] == "write" and not 0 <= d <= 8) or (op[0] != "write" and d != 0):
             print("COUNT MISMATCH", scripts, i, op[0], d); sys.exit(1)
     scripts += 1
-print(f"fuzz_pieces ok: {scripts} scripts, {calls} calls, all equal to the reference object ({time.time()-t0:.0f} s)")
+print(f"fuzz_pieces ok ({'lazy matching' if LAZY else 'default parse'}, seed {os.environ.get('FUZZ_SEED', '9')}): {scripts} scripts, {calls} calls, all equal to the reference object ({time.time()-t0:.0f} s)")
