@@ -91,6 +91,42 @@ __host__ __device__ __forceinline__ void token_words(uint32_t v, uint32_t nb, ui
     *w_lo = __builtin_bswap32((uint32_t)x);
 }
 
+// The bucket scan's candidate lengths in BIT units (the fixed-geometry compress builds, kBitLen): a candidate's common prefix
+// with the pattern is kept as the bit offset of the first difference, 16..128, and becomes a byte count by one shift.
+// A candidate that passed the scan's window test has y = distance << LB | (its bytes 2, 3 ^ the pattern's, LB bits): the XOR of
+// byte 2 in bits 0..7 and of the low LB - 8 bits of byte 3 above them.  The first set bit of y therefore classifies it:
+//   below LB      a shallow candidate, and that bit | 16 is its first difference counted from the pattern's first bit (bytes 0 and 1
+//                 agree: the same bucket and rest): 16..23 -> 2 bytes, 24..16 + LB - 1 -> 3;
+//   LB or above   (the distance's bits; all ones for y == 0, the oldest window byte) a deep candidate: the 16-byte compare decides.
+// first_set_or_ones is v_ffbl_b32 as the hardware defines it: all ones for a zero operand.
+__host__ __device__ __forceinline__ uint32_t first_set_or_ones(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+#else
+    return x ? (uint32_t)__builtin_ctz(x) : 0xFFFFFFFFu;
+#endif
+}
+constexpr uint32_t kScanBitsCap = 128;  // a 16-byte hit
+template <uint32_t LB>
+__host__ __device__ __forceinline__ bool scan_is_deep(uint32_t first_bit_of_y) { return first_bit_of_y > LB - 1; }
+__host__ __device__ __forceinline__ uint32_t scan_shallow_bits(uint32_t first_bit_of_y) { return first_bit_of_y | 16u; }
+// The 16-byte compare's four difference dwords (candidate ^ pattern, little-endian, in byte order) to the capped bit offset of the
+// first difference: 0..128.  `| 32` (64, 96) is exact for 0..31 and keeps all ones; the cap rides in the second three-way minimum.
+// (`cap`: kScanBitsCap, which the kernel hands over in a register of its choice -- 128 is no inline constant of the three-operand
+// encoding, and left to itself the compiler keeps it in one more scalar register of a kernel that spills those)
+__host__ __device__ __forceinline__ uint32_t scan_deep_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3,
+                                                            uint32_t cap = kScanBitsCap) {
+    const uint32_t t0 = first_set_or_ones(x0), t1 = first_set_or_ones(x1) | 32u, t2 = first_set_or_ones(x2) | 64u,
+                   t3 = first_set_or_ones(x3) | 96u;
+    const uint32_t m = t0 < t1 ? (t0 < t2 ? t0 : t2) : (t1 < t2 ? t1 : t2);
+    const uint32_t m2 = m < t3 ? m : t3;
+    return m2 < cap ? m2 : cap;
+}
+__host__ __device__ __forceinline__ uint32_t scan_bits_len(uint32_t bits) { return bits >> 3; }    // bytes: 2..16 (deep: 0..16)
+__host__ __device__ __forceinline__ uint32_t scan_bits_hit16(uint32_t bits) { return bits >> 7; }  // 1 for a 16-byte hit
+
 // Dictionary tables (the *_dicts calls): stream i's dictionary is the W bytes at `off` = dict_off[i] of a buffer of `len`
 // bytes.  Offsets are multiples of 16: the decoders seed their windows with 16-byte loads, the compress kernel with dwords.
 constexpr uint32_t kDictOffAlign = 16;

@@ -206,6 +206,13 @@ __device__ __forceinline__ uint32_t prefix_len16(const uint8_t* ebuf, uint32_t c
     const uint32_t t3 = OR_TAIL ? ffbl_or_ones(x3) | 96u : __builtin_elementwise_add_sat(ffbl_or_ones(x3), 96u);
     return min(min(min(t0, t1), min(t2, t3)) >> 3, 16u);
 }
+// The same compare with its result left in bits (kBitLen, the fixed-geometry builds' bucket scan): the bit offset of the first
+// difference, capped at 128 inside the minimum chain -- two v_min3 where the byte form spends a v_min, a v_min3, a shift and a
+// second v_min; the scan's one shift by 3 sits behind the merge with the shallow candidates (scan_deep_bits, tamp_common.hpp).
+__device__ __forceinline__ uint32_t prefix_bits16(const uint8_t* ebuf, uint32_t c, const uint32_t (&P)[4], uint32_t cap) {
+    const LdsU128 v = *reinterpret_cast<const LdsU128*>(ebuf + c);
+    return scan_deep_bits(v.x ^ P[0], v.y ^ P[1], v.z ^ P[2], v.w ^ P[3], cap);
+}
 
 // Candidate whose bytes run past the newest window byte: the ring continues with the OLDEST window byte, i.e.
 // candidate byte k is ebuf[c + k] for k < t and ebuf[c - W + k] for k >= t, with t = q + W - c in 1..15 -- or 16: the
@@ -881,6 +888,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     // quad a range can end with and stores a block quad's four bucket numbers at once (kQuadHist), and the loops whose trip count
     // the constant geometry fixes are straight-line stores (kConstLoops).
     constexpr bool kPat16 = FX, kQuadHist = FX, kConstLoops = FX;
+    // ... and one inside the bucket scan's loop body (profiles/bucket_bits_ab.txt): a candidate's class is read off the first set
+    // bit of `y`, and its length stays in bit units until one shared shift (kBitLen; scan_shallow_bits, prefix_bits16).
+    constexpr bool kBitLen = FX;
     static_assert(!FX || (PACKED && !LAZY && RUNS && WSCAN == (1u << kFixWbits) && HB == kHb1024 && LOOP && !BLOCKM),
                   "fixed geometry: the run-aware persistent build of the 2^10 window");
     // HB: bucket bits of the bigram index (2,048 buckets; 512 for the short-message build, whose blocks hold a few hundred
@@ -1419,6 +1429,10 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 asm volatile("" : "+v"(tid));
                 lane = (int)(tid & (kWave - 1)), wave = tid >> 6, wk.lane = lane;  // (re-derived: see above)
                 const uint32_t nq = nvalid - e_pending;
+                // kBitLen: the compare's cap of 128 bits in a vector register (scan_deep_bits; the one the zero of the byte
+                // form's sub-dword compare held)
+                uint32_t bits_cap = kScanBitsCap;
+                if constexpr (kBitLen) asm("" : "+v"(bits_cap));
                 TAMP_PROF_ONLY(unsigned long long f0 = 0, f1 = 0, f2 = 0, f3 = 0, niter = 0, fc = __builtin_readcyclecounter();)
                 for (uint32_t j = tid; j < nq; j += nt) {
                     const uint32_t q = sorted[j];
@@ -1488,14 +1502,31 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                 const uint32_t y = (e ^ pkx) - qs;
                                 if (y < ((Ws - 1) << kLB)) {  // in the window and the same bigram
                                     const uint32_t d = y >> kLB;  // Ws - d bytes before the candidate reaches the newest byte
-                                    const uint32_t low = y & ((1u << kLB) - 1);
-                                    uint32_t len = (low & 0xFFu) ? 2u : 3u;
-                                    if (low == 0) {  // the next two bytes agree too (the entry's bits of the second)
-                                        len = prefix_len16<kOrTail>(ebuf, q + d, P);
-                                        if (TAMP_DBG(0x1000000u)) {  // (the compare once more -- same result -- for its exact count)
-                                            asm volatile("" ::: "memory");
-                                            len = max(len, prefix_len16<kOrTail>(ebuf, q + d, P));
+                                    uint32_t len, hit16;
+                                    if constexpr (kBitLen) {
+                                        // the first set bit of y: below kLB a byte of the entry differs (2 or 3 bytes, as bits
+                                        // 16..29); at or above it -- d's bits, all ones for d = 0 -- the entry agrees
+                                        const uint32_t fb = first_set_or_ones(y);
+                                        uint32_t bits = scan_shallow_bits(fb);
+                                        if (scan_is_deep<kLB>(fb)) {
+                                            bits = prefix_bits16(ebuf, q + d, P, bits_cap);
+                                            if (TAMP_DBG(0x1000000u)) {  // (the compare once more -- same result -- for its exact count)
+                                                asm volatile("" ::: "memory");
+                                                bits = max(bits, prefix_bits16(ebuf, q + d, P, bits_cap));
+                                            }
                                         }
+                                        len = scan_bits_len(bits), hit16 = scan_bits_hit16(bits);
+                                    } else {
+                                        const uint32_t low = y & ((1u << kLB) - 1);
+                                        len = (low & 0xFFu) ? 2u : 3u;
+                                        if (low == 0) {  // the next two bytes agree too (the entry's bits of the second)
+                                            len = prefix_len16<kOrTail>(ebuf, q + d, P);
+                                            if (TAMP_DBG(0x1000000u)) {  // (as above)
+                                                asm volatile("" ::: "memory");
+                                                len = max(len, prefix_len16<kOrTail>(ebuf, q + d, P));
+                                            }
+                                        }
+                                        hit16 = len >> 4;
                                     }
                                     // (the wrap zone and the key: as in the generic loop below.  One test: the compare reaches the
                                     // newest byte iff d + len >= Ws; a 16-byte hit exactly 16 bytes in front of it -- exact as it
@@ -1503,7 +1534,7 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                                     if (d + len >= Ws) {
                                         wrapmask |= 1u << (Ws - d);
                                     } else {
-                                        if constexpr (RUNS) n16 += len >> 4;
+                                        if constexpr (RUNS) n16 += hit16;
                                         const uint32_t lim_i = ((nb - d) & (Ws - 1)) + 1;
                                         key = max(key, (min(len, min(cap_len, lim_i)) << 16) | lim_i);
                                     }
