@@ -982,6 +982,79 @@ tamp_res tamp_amd_compress_piece_lazy(const TampAmdConf *conf, int emit_header, 
                                       size_t *output_written_size, const unsigned char *input, size_t input_size,
                                       int *token_written, int device);
 
+/*
+ * Batch piece calls: MANY streaming compressors, each handed one bounded piece, advanced together by the batch compress
+ * kernel -- tamp_amd_compress_piece_lazy for every object of an array at once.  For a server with thousands of open
+ * streams: message k of a stream matches against its messages 0..k-1, and a write costs no launch of its own.
+ *
+ * An object is 48 bytes followed by its window (1 << conf->window bytes, ring order), `object_stride` bytes apart
+ * (a multiple of 16, >= tamp_amd_piece_object_size(conf->window); device memory: `objects` itself 16-byte aligned).  A
+ * zero-filled object is a fresh one.  With conf->use_custom_dictionary a fresh object's window bytes are the dictionary.
+ *
+ * ops[i] says what object i's piece is: TAMP_AMD_PIECE_HEADER / _APPEND_MARKER (emit_header / append_marker: what leads the
+ * output), _RESUME (the object carries on; without it the object is fresh and its carry is ignored), _FINISH (the piece
+ * ends with a flush; without it, the way tamp_compressor_compress ends a call), _FLUSH_TOKEN (with _FINISH: flush_token),
+ * _SKIP (the object takes no part: neither it, its slab nor its result rows are written, and its input and slab are not
+ * read; device memory: the object and its table rows are not read either, whereas the host-memory call copies the whole
+ * object array and whole tables to the device, so they must be readable there).
+ *
+ * THE CONTRACT.  For every object whose op is not _SKIP, status[i], out_len[i], the bytes out[out_off[i] .. + out_len[i])
+ * and the object afterwards -- window, window_pos, all 32 carry bytes, token_written -- are exactly what
+ * tamp_amd_compress_piece_lazy gives for that object alone with the five flags taken from ops[i] (only the block-mode
+ * shortcut of a whole fresh v1 stream is not taken; it produces the same bytes).  One field is tidier here: carry.ext_pos
+ * is 0 whenever carry.ext_count is 0 -- the single call leaves a position of no meaning there that depends on how its launch
+ * was laid out, and here nothing about an object may depend on the other objects of the call.  So: a piece without input on a resumed
+ * object polls nothing and releases the whole bytes among its pending bits; TAMP_OUTPUT_FULL and TAMP_EXCESS_BITS leave the
+ * object byte for byte as it came, an unfinished piece then delivers out_len[i] = 0 and a finishing one keeps
+ * tamp_batch_compress's room rule; give a piece tamp_amd_compress_bound(in_len[i] + 271, ...) of room.  Per object
+ * TAMP_AMD_BAD_ARGUMENT (out_len[i] = 0, object untouched): a carry that breaks the rules of tamp_amd_compress_piece(_lazy),
+ * unknown op bits, _HEADER | _APPEND_MARKER together, in_len[i] > 0xFFFFFF00 (no byte of such an object's input or slab is
+ * touched, whatever its offsets say; host memory: likewise an input or slab that would end beyond 2^64).  An unfinished piece under lazy matching is
+ * accepted: the object has the cached-match fields.  Nothing is written outside [out_off[i], out_off[i] + out_cap[i]), no
+ * object is affected by another's failure, and with host memory nothing behind out_len[i] is written.  Slabs must not overlap.
+ *
+ * The call returns TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for: a bad memory kind, TAMP_AMD_ALL_DEVICES
+ * (objects stay on one device), n_objects >= 2^32; and with n_objects > 0 for a null conf, objects, ops, in_off, in_len,
+ * out_off, out_cap, out_len or status, a stride below the object size or not a multiple of 16, device-memory objects that
+ * are not 16-byte aligned.  An invalid conf: TAMP_INVALID_CONF.  n_objects == 0: TAMP_OK, nothing is done.
+ * `max_in_len` is a hint that may be 0; the call measures its pieces itself.
+ *
+ * HOW IT RUNS.  The objects are sorted by (what leads, how the piece ends) -- at most nine classes, ONE in the steady state
+ * where every stream is mid-stream with the same kind of write -- and each class that occurs is one launch of the compress
+ * kernel over staged rows.  Per object and call the window is copied once each way and the input once.  THE CALL WAITS
+ * ONCE, early, for an 88-byte record of class counts (as tamp_batch_compress_resets and tamp_batch_read_ranges do);
+ * everything behind that wait is asynchronous on `stream`, so results are valid once `stream` is.  The staging rows are
+ * per-stream scratch (tamp_amd_trim releases them).  Host memory: objects, tables and input travel to the device and back
+ * inside the call, which returns complete.
+ */
+typedef struct TampAmdPieceObject { /* 48 bytes; the window (1 << conf->window bytes, ring order) follows */
+    TampAmdLazyCarry carry;         /* as for tamp_amd_compress_piece_lazy */
+    uint16_t window_pos;
+    uint8_t token_written;          /* out: this call's finishing flush wrote a FLUSH token */
+    uint8_t reserved[13];
+} TampAmdPieceObject;
+size_t tamp_amd_piece_object_size(uint8_t window_bits); /* 48 + (1 << window_bits), host only */
+
+enum {
+    TAMP_AMD_PIECE_HEADER = 1,
+    TAMP_AMD_PIECE_APPEND_MARKER = 2,
+    TAMP_AMD_PIECE_RESUME = 4,
+    TAMP_AMD_PIECE_FINISH = 8,
+    TAMP_AMD_PIECE_FLUSH_TOKEN = 16,
+    TAMP_AMD_PIECE_SKIP = 128
+};
+
+int tamp_batch_compress_pieces(const TampAmdConf *conf, void *objects, size_t object_stride, const uint8_t *ops,
+                               const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                               const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int8_t *status,
+                               size_t n_objects, uint32_t max_in_len, int mem, int device, void *stream);
+/* Where the time of the calling thread's most recent device-memory tamp_batch_compress_pieces call went, in milliseconds
+ * (hipEvents on its stream, recorded while tamp_amd_set_timing(1) is on): out4[0] classify kernel and the wait,
+ * [1] stage kernel, [2] the compress launches, [3] unstage kernel; -1 each where nothing was recorded (timing off, or the
+ * call launched no compress kernel).  tamp_amd_last_kernel_ms() is the whole call.  Returns TAMP_OK, or
+ * TAMP_AMD_BAD_ARGUMENT for a null pointer. */
+int tamp_amd_pieces_phase_ms(float *out4);
+
 /* Replaces tamp_decompressor_read_header (decompressor.h:67, decompressor.c:276-297): host-side header parse. */
 tamp_res tamp_amd_read_header(TampAmdConf *conf, const unsigned char *input, size_t input_size,
                               size_t *input_consumed_size);
@@ -995,7 +1068,7 @@ float tamp_amd_last_kernel_ms(void);
 /* Releases the device scratch the library keeps between calls on `device`, one set per HIP stream that a call ever ran on:
  * the global-window decoder's slab (4 GiB at most), the split decoder's token records (up to a quarter of the free device
  * memory, 8 GiB at most), the block-mode tables of one long v1 stream (up to 3 bytes per input byte), the gathered tables of
- * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the tables, staging rows and slabs of tamp_batch_write_ranges, the tables, staged entries, staging rows and slabs of tamp_batch_append, the 8 KiB of tamp_batch_pack's scan and the long-stream decoder's chunk tables, tail maps and
+ * the expensive-first ordering (37 bytes per stream of the batch), the slabs of tamp_amd_compress_resets, the tables, stage and scratch of tamp_batch_read_ranges, the tables, staging rows and slabs of tamp_batch_write_ranges, the tables, staged entries, staging rows and slabs of tamp_batch_append, the 8 KiB of tamp_batch_pack's scan, the tables, state rows and input rows of tamp_batch_compress_pieces and the long-stream decoder's chunk tables, tail maps and
  * lag lists -- and the staging buffers of the host-memory calls (pinned host memory sized by the largest
  * output extent ever staged, device chunk buffers, the object calls' state rows: the batch, resume, segment and piece calls
  * and the reference-named objects share them).  Synchronises those streams first.  Returns the bytes released or a negative TAMP_AMD_* code.

@@ -21,6 +21,8 @@ WINDOW_BITS_EXACT = 0x80  # include/tamp_amd.h: TAMP_AMD_WINDOW_BITS_EXACT
 MEM_HOST, MEM_DEVICE = 0, 1
 RESETS_SCAN_TILE = 1024  # include/tamp_amd.h TAMP_AMD_RESETS_SCAN_TILE
 INDEX_RESETS_CHUNK_BITS = 1024  # include/tamp_amd.h TAMP_AMD_INDEX_RESETS_CHUNK_BITS
+# include/tamp_amd.h TAMP_AMD_PIECE_*: the op bits of tamp_batch_compress_pieces
+PIECE_HEADER, PIECE_APPEND_MARKER, PIECE_RESUME, PIECE_FINISH, PIECE_FLUSH_TOKEN, PIECE_SKIP = 1, 2, 4, 8, 16, 128
 
 # every symbol include/tamp_amd.h declares (tests/test_capi_symbols.py checks header <-> library <-> this list)
 SYMBOLS = (
@@ -63,6 +65,9 @@ SYMBOLS = (
     "tamp_amd_compress_segment",
     "tamp_amd_compress_piece",
     "tamp_amd_compress_piece_lazy",
+    "tamp_amd_piece_object_size",
+    "tamp_batch_compress_pieces",
+    "tamp_amd_pieces_phase_ms",
     "tamp_amd_read_header",
     "tamp_amd_set_timing",
     "tamp_amd_last_kernel_ms",
@@ -127,6 +132,16 @@ class TampAmdLazyCarry(C.Structure):
         ("cached_pos", C.c_uint16),
         ("cached_len", C.c_uint8),  # 0: none
         ("reserved2", C.c_uint8),
+    ]
+
+
+class TampAmdPieceObject(C.Structure):
+    """include/tamp_amd.h TampAmdPieceObject: the 48 bytes in front of an object's window (tamp_batch_compress_pieces)."""
+    _fields_ = [
+        ("carry", TampAmdLazyCarry),
+        ("window_pos", C.c_uint16),
+        ("token_written", C.c_uint8),
+        ("reserved", C.c_uint8 * 13),
     ]
 
 
@@ -256,6 +271,12 @@ def load() -> C.CDLL:
     lib.tamp_amd_compress_piece_lazy.argtypes = [C.POINTER(TampAmdConf), i32, i32, i32, i32, i32, vp, C.POINTER(C.c_uint16),
                                                  C.POINTER(TampAmdLazyCarry), vp, sz, C.POINTER(sz), vp, sz, C.POINTER(i32), i32]
     lib.tamp_amd_compress_piece_lazy.restype = C.c_int8
+    lib.tamp_amd_piece_object_size.argtypes = [u8]
+    lib.tamp_amd_piece_object_size.restype = sz
+    lib.tamp_batch_compress_pieces.argtypes = [C.POINTER(TampAmdConf), vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, u32, i32, i32, vp]
+    lib.tamp_batch_compress_pieces.restype = i32
+    lib.tamp_amd_pieces_phase_ms.argtypes = [C.POINTER(C.c_float * 4)]
+    lib.tamp_amd_pieces_phase_ms.restype = i32
     lib.tamp_amd_read_header.argtypes = [C.POINTER(TampAmdConf), vp, sz, C.POINTER(sz)]
     lib.tamp_amd_read_header.restype = C.c_int8
     lib.tamp_amd_set_timing.argtypes = [i32]

@@ -1572,3 +1572,256 @@ class EncoderBatch:
 
     def full(self):
         return self.states[:, 7] == 16
+
+
+class CompressorBatch:
+    """``n`` streaming compressors on the device, advanced together: ``tamp_amd.Compressor`` for thousands of open streams.
+
+    Stream ``i`` is ONE reference ``Compressor`` with the same keywords: the concatenation of everything the calls below have
+    returned for it is, byte for byte, what that object writes for the same sequence of ``write`` / ``flush`` /
+    ``reset_dictionary`` / ``close`` calls (per call the boundaries may differ by the up to 31 bits the reference's object holds
+    back).  Message ``k`` of a stream therefore matches against its messages ``0..k-1``, which independent streams
+    (``compress_batch``) cannot.  Every call is ONE ``tamp_batch_compress_pieces`` launch sequence over all streams
+    (include/tamp_amd.h): there is no gather threshold, a ``write`` sends every non-empty chunk as an unfinished piece at once.
+
+    The objects (48 bytes + window each) live in one CUDA uint8 tensor ``objects`` of shape ``(n, stride)`` and never leave the
+    device; the per-stream bookkeeping of ``codec.Compressor`` (header sent, window carried, data since the last flush point,
+    last token was a FLUSH) is numpy arrays on the host.  Each method returns a ``BatchResult`` whose slabs are sized with
+    ``compress_bound(len + 271, ...)``; streams that took no part have ``out_len == 0`` and ``status == 0``.  With ``literal``
+    below 8 a stream can fail with ``TAMP_EXCESS_BITS``: its object and bookkeeping stay as the failed piece found them, and
+    whatever else the call held for that stream (the rest of a ``write`` above ``PIECE_MAX``) is not sent; the statuses are then
+    read back after every library call, one sync each.
+    """
+
+    def __init__(self, n: int, *, window: int = 10, literal: int = 8, extended: bool = True, dictionary=None,
+                 lazy_matching: bool = False, dictionary_reset: bool = False, append: bool = False, device: int = 0, stream=None):
+        if dictionary is not None and len(dictionary) != (1 << window):
+            raise ValueError("Dictionary-window size mismatch.")
+        if not (8 <= window <= 15 and 5 <= literal <= 8):
+            raise ValueError("window must be in 8..15 and literal in 5..8")
+        if append and (not dictionary_reset or dictionary is not None):
+            raise ValueError("append needs dictionary_reset=True and no dictionary")  # compressor.c:209
+        if isinstance(n, bool) or not _is_int(n) or n < 0:
+            raise ValueError("n must be a non-negative integer")
+        from .codec import Compressor
+
+        self.n, self.window_bits, self.literal = int(n), window, literal
+        self._lit_seed = literal if extended else 8  # compressor.c:224-225
+        self._conf = _conf(window, literal, extended, dictionary, dictionary_reset, lazy_matching)
+        self._dictionary = None if dictionary is None else _np_u8(dictionary).copy()
+        self._dictionary_reset, self._append = bool(dictionary_reset), bool(append)
+        self._piece_max = Compressor.PIECE_MAX
+        self._stream, self._device = stream, device
+        self.stride = 48 + (1 << window)
+        self._objects = self._nothing_t = self._dev_t = None  # (made by the first call: constructing needs neither library nor device)
+        self._seed_t = None
+        self._opened = np.zeros(self.n, dtype=bool)           # header / append marker already sent
+        self._resume = np.zeros(self.n, dtype=bool)           # the object holds a carried window (else: fresh stream)
+        self._dirty = np.zeros(self.n, dtype=bool)            # data was handed over since the last flush point (compressor.c:548)
+        self._last_was_flush = np.full(self.n, self._append)  # compressor.c:234
+
+    @property
+    def _dev(self):
+        if self._dev_t is None:
+            import torch
+
+            self._dev_t = torch.device("cuda", self._device)
+        return self._dev_t
+
+    @property
+    def objects(self):
+        """The objects: a CUDA uint8 tensor of shape ``(n, stride)``, each row 48 bytes of ``TampAmdPieceObject`` and the window."""
+        if self._objects is None:
+            import torch
+
+            _lib.load()  # fail loudly if the native library is missing
+            with self._on_stream():
+                self._objects = torch.zeros((self.n, self.stride), dtype=torch.uint8, device=self._dev)
+                if self._dictionary is not None:
+                    self._objects[:, 48:] = torch.from_numpy(self._dictionary).to(self._dev)
+        return self._objects
+
+    @property
+    def _nothing(self):
+        if self._nothing_t is None:
+            import torch
+
+            with self._on_stream():
+                self._nothing_t = torch.zeros(16, dtype=torch.uint8, device=self._dev)
+        return self._nothing_t
+
+    def _on_stream(self):
+        import contextlib
+
+        import torch
+
+        if self._stream is None:
+            return contextlib.nullcontext()
+        return torch.cuda.stream(torch.cuda.ExternalStream(int(self._stream), device=self._dev))
+
+    def _which(self, which) -> np.ndarray:
+        mask = np.zeros(self.n, dtype=bool)
+        if which is None:
+            mask[:] = True
+            return mask
+        idx = [int(i) for i in which]
+        if any(i < 0 or i >= self.n for i in idx):
+            raise ValueError(f"which: stream indices must be in 0..{self.n - 1}")
+        mask[idx] = True
+        return mask
+
+    def _leads(self, live: np.ndarray) -> np.ndarray:
+        """The op bits that say how the piece opens, for the streams of ``live``; the others get SKIP."""
+        lead = np.where(self._opened, 0, _lib.PIECE_APPEND_MARKER if self._append else _lib.PIECE_HEADER)
+        ops = lead | np.where(self._resume, _lib.PIECE_RESUME, 0)
+        return np.where(live, ops, _lib.PIECE_SKIP).astype(np.uint8)
+
+    def _run(self, rounds, data, in_off):
+        """``rounds``: a list of (ops uint8[n], in_len uint32[n], input shift) on the host.  One library call per round, every
+        round's bytes behind the previous round's in the stream's slab.  A stream whose piece fails (``TAMP_EXCESS_BITS``, which
+        needs ``literal`` below 8: only then are the statuses read back, one sync per round) takes no part in the later rounds:
+        its object stays where the failed piece found it, and its status is that failure.
+        -> (BatchResult, streams that completed a piece, streams that failed one)"""
+        import torch
+
+        lib = _lib.load()
+        n, dev = self.n, self._dev
+        caps = [np.where(ops & _lib.PIECE_SKIP, 0, compress_bound(ln.astype(np.int64) + 271, self.literal, self._dictionary_reset))
+                for ops, ln, _ in rounds]
+        advanced, failed = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+        cap = np.sum(caps, axis=0, dtype=np.int64) if rounds else np.zeros(n, dtype=np.int64)
+        off = np.cumsum(cap) - cap
+        with self._on_stream():
+            st = self._stream if self._stream is not None else torch.cuda.current_stream(dev).cuda_stream
+            out = torch.empty(max(int(cap.sum()), 1), dtype=torch.uint8, device=dev)
+            out_off = torch.from_numpy(off).to(dev)
+            out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            status = torch.zeros(n, dtype=torch.int8, device=dev)
+            keep = [data, in_off]
+            for k, (ops, ln, shift) in enumerate(rounds):
+                ops = np.where(failed, _lib.PIECE_SKIP, ops).astype(np.uint8)
+                live = (ops & _lib.PIECE_SKIP) == 0
+                ops_t = torch.from_numpy(ops).to(dev)
+                len_t = torch.from_numpy(ln.astype(np.int32)).to(dev)
+                cap_t = torch.from_numpy(caps[k].astype(np.int32)).to(dev)
+                off_t = in_off + shift if shift else in_off
+                first = k == 0
+                o_off = out_off if first else out_off + out_len.to(torch.int64)
+                o_len = out_len if first else torch.zeros(n, dtype=torch.int32, device=dev)
+                o_status = status if first else torch.zeros(n, dtype=torch.int8, device=dev)
+                rc = lib.tamp_batch_compress_pieces(C.byref(self._conf), _ptr(self.objects), self.stride, _ptr(ops_t), _ptr(data),
+                                                    _ptr(off_t), _ptr(len_t), _ptr(out), _ptr(o_off), _ptr(cap_t), _ptr(o_len),
+                                                    _ptr(o_status), n, int(ln.max()) if n else 0, _lib.MEM_DEVICE, dev.index or 0,
+                                                    C.c_void_p(st))
+                _lib.check_launch(rc)
+                if not first:
+                    out_len += o_len
+                    status = torch.where(status == 0, o_status, status)
+                keep += [ops_t, len_t, cap_t, off_t, o_off, o_len, o_status]
+                # (at literal 8 a piece with room for its worst case cannot fail: no read-back)
+                bad = live & (o_status.cpu().numpy() != _lib.OK) if self.literal < 8 and n else np.zeros(n, dtype=bool)
+                advanced |= live & ~bad
+                failed |= bad
+        return BatchResult(out, out_off, out_len, status, None, -1.0, tuple(keep)), advanced, failed
+
+    def write(self, chunks, in_off=None, in_len=None):
+        """One bytes-like or ``None`` per stream, or a flat CUDA uint8 tensor with CUDA ``in_off`` / ``in_len`` tables (the
+        lengths are read back: the bookkeeping is the host's).  Every non-empty chunk goes to its stream as an unfinished
+        piece, cut at ``Compressor.PIECE_MAX``."""
+        import torch
+
+        if _is_torch(chunks):
+            if in_off is None or in_len is None or int(in_len.numel()) != self.n or int(in_off.numel()) != self.n:
+                raise ValueError(f"write: in_off and in_len need {self.n} entries")
+            lens = in_len.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+            with self._on_stream():
+                data, off_t = chunks, in_off.to(torch.int64)
+        else:
+            chunks = list(chunks)
+            if len(chunks) != self.n:
+                raise ValueError(f"write: {len(chunks)} chunks for {self.n} streams")
+            flat, offs, lens32 = pack_streams([b"" if c is None else c for c in chunks])
+            lens = lens32.astype(np.int64)
+            with self._on_stream():
+                data = torch.from_numpy(flat.copy()).to(self._dev) if flat.size else self._nothing
+                off_t = torch.from_numpy(offs.astype(np.int64)).to(self._dev)
+        rounds = []
+        shift = 0
+        while True:
+            ln = np.clip(lens - shift, 0, self._piece_max)
+            live = ln > 0
+            if not live.any():
+                break
+            # (a stream's second piece of one write: its first has opened it)
+            ops = self._leads(live) if not shift else np.where(live, _lib.PIECE_RESUME, _lib.PIECE_SKIP).astype(np.uint8)
+            rounds.append((ops, ln.astype(np.uint32), shift))
+            shift += self._piece_max
+        res, done, _ = self._run(rounds, data, off_t)
+        self._opened |= done
+        self._resume |= done
+        self._dirty |= done
+        return res
+
+    def flush(self, write_token: bool = True, which=None):
+        """``Compressor.flush`` on the streams of ``which`` (all of them by default)."""
+        return self._flush(self._which(which), bool(write_token))
+
+    def _flush(self, sel: np.ndarray, write_token: bool):
+        self._last_was_flush &= ~(sel & self._dirty)  # compressor.c:548
+        want = sel & write_token & ~self._last_was_flush  # compressor.c:784
+        # byte aligned, nothing handed over: the reference's flush writes nothing either
+        live = sel & (self._dirty | ~self._opened | (want & self._dictionary_reset))
+        ops = self._leads(live) | np.where(live, _lib.PIECE_FINISH, 0).astype(np.uint8) \
+            | np.where(live & want, _lib.PIECE_FLUSH_TOKEN, 0).astype(np.uint8)
+        with self._on_stream():
+            import torch
+
+            zeros = torch.zeros(self.n, dtype=torch.int64, device=self._dev)
+        res, done, _ = self._run([(ops, np.zeros(self.n, dtype=np.uint32), 0)] if live.any() else [], self._nothing, zeros)
+        self._opened |= done
+        self._resume |= done
+        self._dirty &= ~done
+        asked = done & want
+        if asked.any():
+            # compressor.c:784-794: the token is written when bits are pending or the stream allows dictionary resets
+            token = asked if self._dictionary_reset else asked & (self.objects[:, 34].cpu().numpy() != 0)
+            self._last_was_flush |= token
+        return res
+
+    def reset_dictionary(self, which=None):
+        """``tamp_compressor_reset_dictionary`` (compressor.c:845-881) on the streams of ``which``: the double FLUSH, then a fresh
+        seeded window."""
+        if not self._dictionary_reset:
+            raise ValueError("reset_dictionary needs dictionary_reset=True")  # TAMP_INVALID_CONF
+        import torch
+
+        sel = self._which(which)
+        # both flushes write their token (the stream allows resets), so both rounds are known now
+        first = self._leads(sel) | np.where(sel, _lib.PIECE_FINISH | _lib.PIECE_FLUSH_TOKEN, 0).astype(np.uint8)
+        second = np.where(sel, _lib.PIECE_RESUME | _lib.PIECE_FINISH | _lib.PIECE_FLUSH_TOKEN, _lib.PIECE_SKIP).astype(np.uint8)
+        none = np.zeros(self.n, dtype=np.uint32)
+        with self._on_stream():
+            zeros = torch.zeros(self.n, dtype=torch.int64, device=self._dev)
+        res, advanced, failed = self._run([(first, none, 0), (second, none, 0)] if sel.any() else [], self._nothing, zeros)
+        done = advanced & ~failed
+        self._resume |= advanced & failed  # (the first flush went through, the second did not: opened, and no reset)
+        self._opened |= advanced
+        if done.any():
+            with self._on_stream():
+                idx = torch.from_numpy(np.flatnonzero(done)).to(self._dev)
+                self.objects[idx, :48] = 0  # a fresh object; the next segment starts from the seeded window, never the custom one
+                if self._conf.use_custom_dictionary:
+                    if self._seed_t is None:
+                        seed = np.zeros(1 << self.window_bits, dtype=np.uint8)
+                        _lib.load().tamp_initialize_dictionary(_ptr(seed), seed.size, self._lit_seed)
+                        self._seed_t = torch.from_numpy(seed).to(self._dev)
+                    self.objects[idx, 48:] = self._seed_t
+        self._opened |= done
+        self._resume &= ~done
+        self._dirty &= ~done
+        self._last_was_flush = np.where(done, self._append, self._last_was_flush)
+        return res
+
+    def close(self):
+        """``Compressor.close``: the final flush of every stream (with a FLUSH token where the stream allows resets)."""
+        return self._flush(np.ones(self.n, dtype=bool), self._dictionary_reset)

@@ -37,6 +37,7 @@
 #include "tamp_append_kernel.hpp"
 #include "tamp_reset_index_kernel.hpp"
 #include "tamp_pack_kernel.hpp"
+#include "tamp_pieces_kernel.hpp"
 
 using namespace tamp_amd;
 
@@ -78,7 +79,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_append, launch_index_resets and launch_pack and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_append, launch_index_resets, launch_pack and launch_pieces and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -99,6 +100,7 @@ struct StreamScratch {
     DeviceBuf writes, write_units;  // tamp_batch_write_ranges: its tables per stream and per segment; the rows, staging rows and slabs of a slice's units
     DeviceBuf appends, append_units;  // tamp_batch_append: its tables per stream; the staged entries of the new index, then the rows, staging rows and slabs of a slice's units
     DeviceBuf index_streams, index_chunks, index_entries;  // tamp_batch_index_resets: its tables per stream, per chunk, per entry
+    DeviceBuf pieces, piece_rows;  // tamp_batch_compress_pieces: its record and tables per object and per row; the state rows and input rows
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -110,7 +112,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries, &pieces, &piece_rows}) n += b->release();
         return n;
     }
 };
@@ -550,7 +552,7 @@ int launch_compress_blocks(DeviceCtx* ctx, StreamScratch& rec, CompressArgs a0, 
 }
 
 // `t`: device memory.  `seg` / `d_state`: a piece of one stream (segment_core), its state row.
-// `rec`: the stream's scratch record, locked by the caller (launch_compress; launch_compress_resets and launch_compress_batch_resets, which hold it over their slices).
+// `rec`: the stream's scratch record, locked by the caller (launch_compress; launch_compress_resets and launch_compress_batch_resets, which hold it over their slices; launch_pieces, over its classes).
 int launch_compress_locked(DeviceCtx* ctx, StreamScratch& rec, const TampAmdConf* conf, const BatchTables& t, uint32_t max_in_len,
                            hipStream_t st, const SegmentSpec* seg, uint8_t* d_state) {
     const size_t n_streams = t.n;
@@ -3393,6 +3395,8 @@ struct OneRow {
 
 }  // namespace
 
+#include "tamp_pieces.hpp"
+
 extern "C" {
 
 void tamp_initialize_dictionary(unsigned char* buffer, size_t size, uint8_t literal) {
@@ -3781,6 +3785,28 @@ int tamp_batch_decompress_resume(void* states, size_t state_stride, uint8_t wind
                                  size_t n_streams, int mem, int device, void* stream) {
     return batch_decompress_resume({in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, nullptr, nullptr, 0, n_streams},
                                    states, state_stride, window_bits_max, mem, device, stream);
+}
+
+size_t tamp_amd_piece_object_size(uint8_t window_bits) {
+    return sizeof(TampAmdPieceObject) + ((size_t)1 << window_bits);
+}
+
+int tamp_batch_compress_pieces(const TampAmdConf* conf, void* objects, size_t object_stride, const uint8_t* ops, const uint8_t* in,
+                               const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                               const uint32_t* out_cap, uint32_t* out_len, int8_t* status, size_t n_objects, uint32_t max_in_len, int mem,
+                               int device, void* stream) {
+    (void)max_in_len;  // (the call measures its pieces itself: the classify kernel's record)
+    return batch_compress_pieces(conf, {objects, object_stride, ops, {in, in_off, in_len, out, out_off, out_cap, out_len, status, nullptr, nullptr, nullptr, 0, n_objects}},
+                                 mem, device, stream);
+}
+
+int tamp_amd_pieces_phase_ms(float* out4) {
+    if (!out4) return TAMP_AMD_BAD_ARGUMENT;
+    for (int k = 0; k < 4; k++) out4[k] = -1.0f;
+    if (!t_piece_ev_valid || hipEventSynchronize(t_piece_ev[4]) != hipSuccess) return TAMP_OK;
+    for (int k = 0; k < 4; k++)
+        if (hipEventElapsedTime(&out4[k], t_piece_ev[k], t_piece_ev[k + 1]) != hipSuccess) out4[k] = -1.0f;
+    return TAMP_OK;
 }
 
 size_t tamp_amd_encoder_state_size(uint8_t window_bits_max) {
