@@ -765,6 +765,9 @@ enum : uint32_t {
 constexpr uint32_t kSegStateExtra = 24;
 // ctl words
 enum : uint32_t { cAct = 0, cShift = 1, cP0 = 2, cPending = 3, cWp = 4, cNtok = 5, cExcess = 6, cBlk = 7, cWave = 8, cNruns = 12, cQuad = 13, cNext = 14, cCut = 15, cCutThr = 16 };
+// (17: the walk's Walk::kCoopCmd.)  18: the match phase's group counter (kClaim) -- the walk's kCoopE outside that phase, which every
+// request writes before the helpers read it
+enum : uint32_t { cClaim = 18 };
 
 // Instrumented builds (-DTAMP_PROF; tools/prof_phases.py, tools/solo_phases.py, tools/phase_valu5.sh).  Everything they add to
 // the kernel goes through these macros, and in a product build every one of them expands to nothing (TAMP_DBG: to `false`):
@@ -891,6 +894,11 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
     // ... and one inside the bucket scan's loop body (profiles/bucket_bits_ab.txt): a candidate's class is read off the first set
     // bit of `y`, and its length stays in bit units until one shared shift (kBitLen; scan_shallow_bits, prefix_bits16).
     constexpr bool kBitLen = FX;
+    // ... and one in how the match phase hands the sorted queries to the wavefronts (profiles/match_claim_ab.txt): a wavefront
+    // takes the next group of 64 from a counter in LDS whenever it is done with one (kClaim, see the match phase), where the
+    // strided loop always gave wavefront 0 the longest group of every four and wavefront 3 the shortest.
+    // Judged against the strided loop and against a static "snake" order (odd rows of four groups reversed), which got half of it.
+    constexpr bool kClaim = FX;
     static_assert(!FX || (PACKED && !LAZY && RUNS && WSCAN == (1u << kFixWbits) && HB == kHb1024 && LOOP && !BLOCKM),
                   "fixed geometry: the run-aware persistent build of the 2^10 window");
     // HB: bucket bits of the bigram index (2,048 buckets; 512 for the short-message build, whose blocks hold a few hundred
@@ -1247,7 +1255,12 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                         for (uint32_t j = 1; j < 4; j++) hq[j] = mix16<HB>(__builtin_amdgcn_alignbyte(d1, d0, j) & 0xFFFFu) >> kRem;
 #pragma unroll
                         for (uint32_t j = 0; j < 4; j++) atomicAdd(&cntw[hq[j] >> 1], 1u << ((hq[j] & 1) * 16));
-                        if (c4 >= W) *reinterpret_cast<uint2*>(qstart + (c4 - W)) = make_uint2(hq[0] | (hq[1] << 16), hq[2] | (hq[3] << 16));
+                        // (the four numbers as values of their own -- a bit-field extract each -- so that a pair is one shift-and-OR:
+                        // left to itself the compiler masks the shifted products into half-words, eleven instructions for these seven)
+                        if (c4 >= W) {
+                            asm("" : "+v"(hq[0]), "+v"(hq[1]), "+v"(hq[2]), "+v"(hq[3]));
+                            *reinterpret_cast<uint2*>(qstart + (c4 - W)) = make_uint2(hq[0] | (hq[1] << 16), hq[2] | (hq[3] << 16));
+                        }
                         continue;
                     }
 #pragma unroll
@@ -1395,6 +1408,9 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 // (kFoldSort: the lengths were counted by the scatter, and its last barrier is behind us)
                 if (!kFoldSort && tid < 64) bins[tid] = 0;
                 if (tid == 0) ctl[cCut] = nvalid;  // (everybody has read the cut position: several barriers back)
+                // kClaim: the match phase's group counter starts at zero.  (Its last claims were the previous epoch's, in front of
+                // the barrier that ends its match phase; the first ones come behind the two barriers of the sort below.)
+                if (kClaim && tid == 0) ctl[cClaim] = 0;
                 if constexpr (!kFoldSort) {
                     __syncthreads();
                     for (uint32_t q = e_pending + tid; q < nvalid; q += nt) {
@@ -1434,7 +1450,28 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                 uint32_t bits_cap = kScanBitsCap;
                 if constexpr (kBitLen) asm("" : "+v"(bits_cap));
                 TAMP_PROF_ONLY(unsigned long long f0 = 0, f1 = 0, f2 = 0, f3 = 0, niter = 0, fc = __builtin_readcyclecounter();)
-                for (uint32_t j = tid; j < nq; j += nt) {
+                // kClaim (the fixed-geometry builds): `sorted` lists the queries longest bracket first, and with j = tid, tid + nt, ...
+                // wavefront w runs groups w, w + 4, w + 8, ... of 64: wavefront 0 the longest of every four, wavefront 3 the
+                // shortest, and the workgroup waits at the barrier behind the phase for wavefront 0 (replayed: 50.4 / 39.1 / 27.1 /
+                // 20.8 lock-step iterations per epoch, tools/wave_balance.py).  Instead a wavefront takes the next group whenever
+                // it is done with one: lane 0 counts a control word up and the wavefront goes on with the group of that number (35.9
+                // for the longest; one LDS atomic of one lane per group -- 64 lanes adding 1 to the same word would be 64 serial
+                // updates in the LDS unit, twenty times per epoch).  Nobody waits for anybody: a wavefront that finds the counter
+                // at the end of the list or past it leaves for the barrier.  What a query computes and stores does not depend on
+                // who runs it.
+                auto claim_group = [&]() {
+                    // (counted in groups with the wrapping increment, whose limit is never reached: an add of a uniform 64 is
+                    // rewritten by the compiler into a count of the active lanes, ten instructions for the one that is active)
+                    uint32_t b = 0;
+                    if (lane == 0) b = __builtin_amdgcn_atomic_inc32((uint32_t*)&ctl[cClaim], 0xFFFFFFFFu, __ATOMIC_RELAXED, "workgroup");
+                    return Walk::uni(b) << 6;
+                };
+                // (the claim sits in the loop's condition, so that it is in the code once; the other builds' loop is `j = tid; j < nq; j += nt`)
+                for (uint32_t j = kClaim ? 0u : tid; kClaim ? (j = claim_group()) < nq : j < nq; j = kClaim ? j : j + nt) {
+                    if constexpr (kClaim) {  // (j: the group's first index, uniform -- the loop ends on the scalar unit; the last group may be partial)
+                        if ((uint32_t)lane >= nq - j) continue;
+                        j += (uint32_t)lane;
+                    }
                     const uint32_t q = sorted[j];
                     const uint32_t leftq = n - (e_p0 + q);
                     const uint32_t R = leftq < kRing ? leftq : kRing;
@@ -1710,10 +1747,14 @@ __device__ __forceinline__ void compress_streams(CompressArgs a_k) {
                     // window index" and the limit W - index, the best interior candidate of the run inside the window
                     // is one of: the first one, the one at window index 0, b - rq, b - rq + 1.  Those (at most) four
                     // are compared like any index entry and merged into the result of the first pass (each thread
-                    // revisits its own queries).  Interior positions within 15 bytes of the newest window byte run into
+                    // revisits its own queries; kClaim: whichever wavefront took their group in the first pass, so a workgroup
+                    // barrier stands between the passes -- nruns is uniform, and most epochs have none.  This pass keeps the
+                    // strided loop: the sort does not order what it costs, and claiming here measured no gain on any corpus).
+                    // Interior positions within 15 bytes of the newest window byte run into
                     // the oldest ones like their indexed neighbours (prefix_len_wrapped16).
                     if (nruns)
                     TAMP_REPEAT(0x2000000u) {  // (the second time it finds its own results)
+                        if constexpr (kClaim) __syncthreads();
                         for (uint32_t j = tid; j < nq; j += nt) {
                             const uint32_t q = sorted[j];
                             const uint32_t b01 = lds_u32_unaligned(ebuf, W + q);
