@@ -834,6 +834,40 @@ int tamp_batch_decompress_resume(void *states, size_t state_stride, uint8_t wind
                                  const uint32_t *out_cap, uint32_t *out_len, int8_t *status, uint32_t *in_consumed,
                                  size_t n_streams, int mem, int device, void *stream);
 
+/*
+ * Objects that stay on the device, advanced a selection at a time: the receiving side of tamp_batch_compress_pieces.
+ *
+ * tamp_batch_decompress_pieces is tamp_batch_decompress_resume on device memory with row r of every table acting on object
+ * object_index[r] (NULL: on object r): in[in_off[r] .. +in_len[r]) and out_cap[r] bytes of room at out + out_off[r] go to that
+ * object, and out_len[r], status[r], in_consumed[r] are its call's results.  An object no row names is neither read nor
+ * written, state or window -- a round in which few connections received anything costs what those few cost.  NAMING ONE OBJECT
+ * IN TWO ROWS OF ONE CALL IS THE CALLER'S ERROR: the rows run concurrently and the object is left undefined.
+ *
+ * tamp_batch_decoded_size_pieces answers, for row r, what tamp_batch_decompress_pieces would report for object object_index[r]
+ * given the same input and out_cap = limit[r] (NULL: no limit below 2^32 - 1): decoded_size = out_len, status, in_consumed.  It
+ * starts from whatever the object's last call left -- bits in the bit buffer, a header not yet complete, a token cut short --
+ * reads the object's 16 state bytes and the input, never the window, and writes nothing to `states`, so any number of rows may
+ * name the same object.  One kernel, one lane per row; nothing is allocated and nothing read back.
+ *
+ * Both: all pointers are device memory on `device`, the call is asynchronous on `stream` (NULL: the default stream) and waits
+ * for nothing.  in_consumed may be NULL.  Returns TAMP_OK when the kernel was launched (n_rows == 0: nothing is); before a device
+ * is looked for, TAMP_AMD_BAD_ARGUMENT for a null table with n_rows > 0 (in_off, in_len, the size / out_len table, status; the
+ * decode call: out_off and out_cap as well), null states with n_rows > 0, n_rows >= 2^32, window_bits_max outside 8..15, a
+ * state_stride that is not a multiple of 16 or below tamp_amd_decoder_state_size(window_bits_max), TAMP_AMD_ALL_DEVICES;
+ * TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_decompress_pieces(void *states, size_t state_stride, uint8_t window_bits_max,
+                                 const uint32_t *object_index /* may be NULL */, const uint8_t *in, const uint64_t *in_off,
+                                 const uint32_t *in_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                                 uint32_t *out_len, int8_t *status, uint32_t *in_consumed, size_t n_rows, int device,
+                                 void *stream);
+
+int tamp_batch_decoded_size_pieces(const void *states, size_t state_stride, uint8_t window_bits_max,
+                                   const uint32_t *object_index /* may be NULL: row r -> object r */, const uint8_t *in,
+                                   const uint64_t *in_off, const uint32_t *in_len,
+                                   const uint32_t *limit /* may be NULL: none below 2^32-1 */, uint32_t *decoded_size,
+                                   int8_t *status, uint32_t *in_consumed, size_t n_rows, int device, void *stream);
+
 /* ---- compressor objects below flush granularity -----------------------------------------------
  *
  * What TampCompressor is in the reference (compressor.h:13-66): a 16-byte input ring that is parsed only while it is

@@ -23,7 +23,7 @@ class ExcessBitsError(Exception):
 
 from ._lib import NativeLibraryError  # noqa: E402
 from .batch import (  # noqa: E402
-    BatchResult, DecodedSizes, DecoderBatch, DictionaryTable, EncoderBatch, CompressorBatch, compress_batch, compress_bound, decoded_size_batch, decompress_batch,
+    BatchResult, DecodedSizes, DecoderBatch, DictionaryTable, EncoderBatch, CompressorBatch, DecompressorBatch, compress_batch, compress_bound, decoded_size_batch, decompress_batch,
     pack_streams, trim, ResetIndex, PackedBatch, pack_batch, read_ranges, RangeResult, index_resets, ResetScan,
     write_ranges, append_batch,
 )
@@ -41,7 +41,7 @@ from .sharding import partition_streams, shard_for_rank  # noqa: E402
 
 __all__ = [
     "ExcessBitsError", "NativeLibraryError", "BatchResult", "compress", "decompress", "compress_batch",
-    "decompress_batch", "decoded_size_batch", "DecodedSizes", "DictionaryTable", "ResetIndex", "PackedBatch", "pack_batch", "read_ranges", "write_ranges", "append_batch", "RangeResult", "index_resets", "ResetScan", "compress_bound", "pack_streams", "trim", "DecoderBatch", "EncoderBatch", "CompressorBatch", "Compressor", "Decompressor", "TextCompressor",
+    "decompress_batch", "decoded_size_batch", "DecodedSizes", "DictionaryTable", "ResetIndex", "PackedBatch", "pack_batch", "read_ranges", "write_ranges", "append_batch", "RangeResult", "index_resets", "ResetScan", "compress_bound", "pack_streams", "trim", "DecoderBatch", "EncoderBatch", "CompressorBatch", "DecompressorBatch", "Compressor", "Decompressor", "TextCompressor",
     "TextDecompressor", "open", "initialize_dictionary", "compute_min_pattern_size", "bit_size",
     "partition_streams", "shard_for_rank",
 ]

@@ -57,6 +57,8 @@ SYMBOLS = (
     "tamp_amd_decoder_state_size",
     "tamp_amd_decoder_state_init",
     "tamp_batch_decompress_resume",
+    "tamp_batch_decompress_pieces",
+    "tamp_batch_decoded_size_pieces",
     "tamp_amd_encoder_state_size",
     "tamp_amd_encoder_state_init",
     "tamp_batch_compress_resume",
@@ -252,6 +254,10 @@ def load() -> C.CDLL:
     lib.tamp_amd_decoder_state_init.restype = C.c_int8
     lib.tamp_batch_decompress_resume.argtypes = [vp, sz, u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, vp]
     lib.tamp_batch_decompress_resume.restype = i32
+    lib.tamp_batch_decompress_pieces.argtypes = [vp, sz, u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
+    lib.tamp_batch_decompress_pieces.restype = i32
+    lib.tamp_batch_decoded_size_pieces.argtypes = [vp, sz, u8, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
+    lib.tamp_batch_decoded_size_pieces.restype = i32
     lib.tamp_amd_encoder_state_size.argtypes = [u8]
     lib.tamp_amd_encoder_state_size.restype = sz
     lib.tamp_amd_encoder_state_init.argtypes = [vp, C.POINTER(TampAmdConf), i32, u8]

@@ -1825,3 +1825,192 @@ class CompressorBatch:
     def close(self):
         """``Compressor.close``: the final flush of every stream (with a FLUSH token where the stream allows resets)."""
         return self._flush(np.ones(self.n, dtype=bool), self._dictionary_reset)
+
+
+def _read_participants(chunks, which_mask: np.ndarray) -> np.ndarray:
+    """Which streams take part in a ``DecompressorBatch.read`` of host chunks: every chunk that is not ``None`` -- ``b""`` takes part
+    with no input, which drains a token an earlier ``TAMP_OUTPUT_FULL`` cut short -- and every stream ``which`` names."""
+    return np.fromiter((c is not None for c in chunks), dtype=bool, count=len(chunks)) | which_mask
+
+
+def _read_which(which, n: int) -> np.ndarray:
+    """``which`` of ``DecompressorBatch.read`` as a mask; an index out of range or named twice is refused (two rows advancing one
+    object in the same launch would leave it undefined)."""
+    mask = np.zeros(n, dtype=bool)
+    if which is None:
+        return mask
+    idx = [int(i) for i in which]
+    if any(i < 0 or i >= n for i in idx):
+        raise ValueError(f"which: stream indices must be in 0..{n - 1}")
+    if len(set(idx)) != len(idx):
+        raise ValueError("which: a stream is named twice")
+    mask[idx] = True
+    return mask
+
+
+def _read_slabs(size, max_out: int):
+    """The slabs of a ``read`` whose sizes the query found: stream ``i`` gets ``min(size[i] + 1, max_out)`` bytes of room at the running
+    sum of the rooms in front of it (``decompress_batch`` sizes its slabs the same way; the spare byte lets a piece that ends in
+    bits too short for a token report ``TAMP_INPUT_EXHAUSTED``, not ``TAMP_OUTPUT_FULL``).  ``size``: uint32 values as a numpy array or
+    a torch tensor (int32 storage included) -> (cap, off) in 64 bits, the same kind."""
+    if _is_torch(size):
+        import torch
+
+        cap = torch.clamp((size.to(torch.int64) & 0xFFFFFFFF) + 1, max=int(max_out))
+        return cap, torch.cumsum(cap, 0) - cap
+    cap = np.minimum((np.asarray(size).astype(np.int64) & 0xFFFFFFFF) + 1, int(max_out))
+    return cap, np.cumsum(cap) - cap
+
+
+class DecompressorBatch:
+    """``n`` streaming decoders on the device, advanced together: the receiving side of ``CompressorBatch``.
+
+    Stream ``i`` is one reference ``TampDecompressor`` (tamp/_c_src/tamp/decompressor.h:13-57), as with ``DecoderBatch`` and with
+    the same arguments -- ``conf=None`` reads each stream's header, a ``dictionary`` sits in every object's window -- but the
+    objects (16 bytes of state + the window each) live in one CUDA uint8 tensor ``objects`` of shape ``(n, stride)`` and never
+    leave the device, input and output are CUDA tensors, and a round touches only the objects of the streams that take part.
+
+    ``read(chunks)`` offers stream ``i`` the bytes ``chunks[i]`` and returns a ``BatchResult`` of ``n`` rows: the decoded bytes, the
+    reference's status (2 input exhausted, 1 output full, negative = error) and ``in_consumed`` per stream.  What was not consumed
+    must be offered again.
+    """
+
+    def __init__(self, n: int, *, window_bits: int = 15, conf: Optional[TampAmdConf] = None, dictionary=None, device: int = 0,
+                 stream=None):
+        if isinstance(n, bool) or not _is_int(n) or n < 0:
+            raise ValueError("n must be a non-negative integer")
+        if not 8 <= window_bits <= 15:
+            raise ValueError("window_bits must be in 8..15")
+        if conf is not None and conf.use_custom_dictionary and dictionary is None:
+            raise ValueError("custom dictionary expected")
+        if conf is not None and dictionary is not None and not conf.use_custom_dictionary:
+            raise ValueError("a dictionary needs conf.use_custom_dictionary")
+        self.n, self.window_bits = int(n), window_bits
+        self.stride = (16 + (1 << window_bits) + 15) & ~15  # tamp_amd_decoder_state_size, in whole 16 bytes
+        self._conf = conf
+        self._dictionary = None if dictionary is None else _np_u8(dictionary)[: 1 << window_bits].copy()
+        self._stream, self._device = stream, device
+        self._objects = self._dev_t = None  # (made by the first call: constructing needs neither library nor device)
+
+    _dev = CompressorBatch._dev
+    _on_stream = CompressorBatch._on_stream
+
+    @property
+    def objects(self):
+        """The objects: a CUDA uint8 tensor of shape ``(n, stride)``, each row a ``TampAmdDecoderState`` and the window."""
+        if self._objects is None:
+            import torch
+
+            lib = _lib.load()
+            one = np.zeros(self.stride, dtype=np.uint8)
+            if self._dictionary is not None:  # the window buffer holds the dictionary, as with the reference's object
+                one[16 : 16 + len(self._dictionary)] = self._dictionary
+            res = lib.tamp_amd_decoder_state_init(_ptr(one), C.byref(self._conf) if self._conf is not None else None, self.window_bits)
+            if res != _lib.OK:
+                raise ValueError(f"tamp_amd_decoder_state_init -> {res}")
+            with self._on_stream():
+                self._objects = torch.from_numpy(one).to(self._dev).unsqueeze(0).repeat(self.n, 1)
+        return self._objects
+
+    def read(self, chunks, in_off=None, in_len=None, *, out_cap=None, max_out=None, which=None) -> BatchResult:
+        """One bytes-like or ``None`` per stream, or a flat CUDA uint8 tensor with CUDA ``in_off`` / ``in_len`` tables -- ``out``,
+        ``out_off``, ``out_len`` of a ``CompressorBatch`` result go in as they are.
+
+        A ``None`` chunk (tensors: ``in_len == 0``) means the stream takes no part: its object is untouched and its rows of the result
+        are 0.  ``b""`` (tensors: a stream named in ``which``) takes part with no input, which drains a token an earlier
+        ``TAMP_OUTPUT_FULL`` cut short.
+
+        ``out_cap=None``: ``tamp_batch_decoded_size_pieces`` finds what each piece decodes to from where its object stands, and stream
+        ``i`` is decoded into ``min(size + 1, max_out)`` bytes at the running sum (one device-to-host sync for the total).  A stream
+        above ``max_out`` comes back with ``TAMP_OUTPUT_FULL``, ``max_out`` bytes and its ``in_consumed``, and a later ``read``
+        continues it; a stream whose piece is in error is decoded all the same and reports that error.
+        ``out_cap`` = an int or one value per stream: one decode launch into that much room, no query."""
+        import torch
+
+        n = self.n
+        max_out = 0xFFFFFFFF if max_out is None else int(max_out)
+        if not 0 <= max_out <= 0xFFFFFFFF:
+            raise ValueError("max_out must fit 32 bits")
+        which_mask = _read_which(which, n)
+        on_device = _is_torch(chunks)
+        if on_device:
+            if in_off is None or in_len is None or int(in_len.numel()) != n or int(in_off.numel()) != n:
+                raise ValueError(f"read: in_off and in_len need {n} entries")
+        else:
+            chunks = list(chunks)
+            if len(chunks) != n:
+                raise ValueError(f"read: {len(chunks)} chunks for {n} streams")
+        cap_all = None
+        if out_cap is not None:
+            if _is_int(out_cap):
+                cap_all = np.full(n, int(out_cap), dtype=np.int64)
+            else:
+                cap_all = np.asarray(out_cap.cpu() if _is_torch(out_cap) else out_cap).astype(np.int64).reshape(-1)
+                if cap_all.size != n:
+                    raise ValueError(f"read: out_cap needs {n} entries")
+            if n and (cap_all.min() < 0 or cap_all.max() > 0xFFFFFFFF):
+                raise ValueError("out_cap must fit 32 bits")
+
+        lib = _lib.load()
+        dev = self._dev
+        with self._on_stream():
+            st = self._stream if self._stream is not None else torch.cuda.current_stream(dev).cuda_stream
+            # ---- the rows: one per stream that takes part, in stream order ----
+            if on_device:
+                data = chunks
+                part = (in_len != 0) | torch.from_numpy(which_mask).to(dev) if which_mask.any() else in_len != 0
+                idx = torch.nonzero(part).flatten()  # (reads the count back: the rows are sized on the host)
+                m = int(idx.numel())
+                off_t, len_t = in_off.to(torch.int64), in_len.to(torch.int32)
+                if m != n:
+                    off_t, len_t = off_t[idx], len_t[idx]
+            else:
+                idx_np = np.flatnonzero(_read_participants(chunks, which_mask))
+                m = int(idx_np.size)
+                flat, offs, lens = pack_streams([chunks[i] if chunks[i] is not None else b"" for i in idx_np])
+                data = torch.from_numpy(flat.copy()).to(dev) if flat.size else torch.zeros(16, dtype=torch.uint8, device=dev)
+                off_t = torch.from_numpy(offs.astype(np.int64)).to(dev)
+                len_t = torch.from_numpy(lens.astype(np.int32)).to(dev)
+                idx = torch.from_numpy(idx_np).to(dev)
+            if m == 0:
+                zeros = torch.zeros(n, dtype=torch.int32, device=dev)
+                return BatchResult(torch.zeros(1, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.int64, device=dev), zeros,
+                                   torch.zeros(n, dtype=torch.int8, device=dev), zeros.clone())
+            obj_t = idx.to(torch.int32) if m != n else None  # (every stream, in order: the identity needs no table)
+            objects = self.objects
+            out_len = torch.empty(m, dtype=torch.int32, device=dev)
+            status = torch.empty(m, dtype=torch.int8, device=dev)
+            consumed = torch.empty(m, dtype=torch.int32, device=dev)
+            keep = [data, off_t, len_t, obj_t]
+            # ---- room ----
+            if cap_all is None:
+                limit_t = None  # (no limit below 2^32 - 1: no table)
+                if max_out != 0xFFFFFFFF:
+                    limit_t = torch.full((m,), max_out - (1 << 32) if max_out >= 1 << 31 else max_out, dtype=torch.int32, device=dev)
+                rc = lib.tamp_batch_decoded_size_pieces(_ptr(objects), self.stride, self.window_bits, _ptr(obj_t), _ptr(data), _ptr(off_t),
+                                                        _ptr(len_t), _ptr(limit_t), _ptr(out_len), _ptr(status), _ptr(consumed), m,
+                                                        dev.index or 0, C.c_void_p(st))
+                _lib.check_launch(rc)
+                cap64, o_off = _read_slabs(out_len, max_out)
+                total = int(cap64.sum().item())  # (the one value read back: it sizes the output tensor)
+                keep.append(limit_t)
+            else:
+                sel = cap_all if m == n else cap_all[idx.cpu().numpy()]
+                total = int(sel.sum())
+                cap64 = torch.from_numpy(sel).to(dev)
+                o_off = torch.cumsum(cap64, 0) - cap64
+            cap_t = cap64.to(torch.int32)  # (the low 32 bits: what the library reads as uint32)
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            rc = lib.tamp_batch_decompress_pieces(_ptr(objects), self.stride, self.window_bits, _ptr(obj_t), _ptr(data), _ptr(off_t),
+                                                  _ptr(len_t), _ptr(out), _ptr(o_off), _ptr(cap_t), _ptr(out_len), _ptr(status),
+                                                  _ptr(consumed), m, dev.index or 0, C.c_void_p(st))
+            _lib.check_launch(rc)
+            keep += [cap_t, o_off, out_len, status, consumed]
+            if m != n:  # the rows back to their streams; the others are 0
+                def spread(rows, dtype):
+                    full = torch.zeros(n, dtype=dtype, device=dev)
+                    full[idx] = rows
+                    return full
+                o_off, out_len = spread(o_off, torch.int64), spread(out_len, torch.int32)
+                status, consumed = spread(status, torch.int8), spread(consumed, torch.int32)
+        return BatchResult(out, o_off, out_len, status, consumed, -1.0, tuple(keep))

@@ -30,6 +30,7 @@
 #include "tamp_decompress_wave_kernel.hpp"
 #include "tamp_decompress_plan.hpp"
 #include "tamp_decompress_resume_kernel.hpp"
+#include "tamp_decoded_size_pieces_kernel.hpp"
 #include "tamp_compress_resume_kernel.hpp"
 #include "tamp_reset_segments_kernel.hpp"
 #include "tamp_read_ranges_kernel.hpp"
@@ -1258,7 +1259,9 @@ int launch_decoded_size(DeviceCtx* ctx, const BatchTables& t, uint8_t max_wbits,
 }
 
 // Resumable decoding: one wavefront per decoder object (tamp_decompress_resume_kernel.hpp).
-int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uint8_t bits_max, const BatchTables& t, hipStream_t st) {
+// `object_index` (tamp_batch_decompress_pieces, device memory): row r of the tables acts on object object_index[r]; null: on object r.
+int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, uint8_t bits_max, const BatchTables& t, hipStream_t st,
+                             const uint32_t* object_index = nullptr) {
     const size_t n_streams = t.n;
     if (n_streams == 0) return TAMP_OK;
     ResumeArgs ra;
@@ -1266,12 +1269,31 @@ int launch_decompress_resume(DeviceCtx* ctx, uint8_t* d_states, size_t stride, u
     a = decompress_args(ctx, t);
     a.dict = nullptr, a.dict_len = 0, a.dict_off = nullptr;  // a custom dictionary is the initial content of the object's window
     a.max_wbits = bits_max;
-    ra.states = d_states, ra.state_stride = stride;
+    ra.states = d_states, ra.state_stride = stride, ra.object_index = object_index;
     const WaveGeometry g = wave_geometry(bits_max, n_streams, ctx->cu_count);
     timing_begin(st);
     const int rc = launch_waves(tamp_decompress_resume_kernel, ra, g, decode_wave_lds(bits_max, g.waves), st);
     timing_end(st);
     if (rc != TAMP_OK) return rc;
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
+// The size query for decoder objects: one lane per row, one launch, nothing allocated and nothing read back
+// (tamp_decoded_size_pieces_kernel.hpp).  `t`: device tables -- out_cap holds the limits (may be null), out_len takes the sizes.
+int launch_decoded_size_pieces(DeviceCtx* ctx, const uint8_t* d_states, size_t stride, uint8_t bits_max, const uint32_t* object_index,
+                               const BatchTables& t, hipStream_t st) {
+    if (t.n == 0) return TAMP_OK;
+    SizePiecesArgs a;
+    a.states = d_states, a.state_stride = stride, a.object_index = object_index;
+    a.in = t.in, a.in_off = t.in_off, a.in_len = t.in_len, a.limit = t.out_cap;
+    a.out_len = t.out_len, a.status = t.status, a.in_consumed = t.in_consumed;
+    a.n_rows = (uint32_t)t.n, a.max_wbits = bits_max;
+    const SizeGeometry g = size_pieces_geometry(t.n, (uint32_t)ctx->cu_count);
+    a.spw = g.spw;
+    timing_begin(st);
+    hipLaunchKernelGGL(tamp_decoded_size_pieces_kernel, dim3(g.grid), dim3(256), g.lds, st, a);
+    timing_end(st);
     HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
@@ -3314,15 +3336,19 @@ int batch_decoded_size(BatchTables t, uint8_t max_window_bits, int mem, int devi
     });
 }
 
+// What an array of objects is refused for, whatever the call does with it (the object calls below, the size query for decoder objects).
+bool object_array_refused(size_t n, const void* states, size_t state_stride, size_t state_size, uint8_t window_bits_max) {
+    return (n && !states) || window_bits_max < 8 || window_bits_max > 15 || (state_stride & 15) || state_stride < state_size ||
+           (reinterpret_cast<uintptr_t>(states) & 3);
+}
+
 // The two object calls behind their entry points (the reference-named objects of include/tamp_compat.h call them with a one-row
 // record): what the call alone checks, then device memory or the host pipeline with the state rows travelling with the chunks.
 template <class Launch>  // Launch(ctx, d_states, device tables, stream)
 int run_object_batch(const BatchTables& t, void* states, size_t state_stride, size_t state_size, uint8_t window_bits_max, int mem,
                      int device, void* stream, const Launch& launch) {
     if (const int rc = batch_refused(t, true, mem, device)) return rc;
-    if ((t.n && !states) || window_bits_max < 8 || window_bits_max > 15 || (state_stride & 15) || state_stride < state_size ||
-        (reinterpret_cast<uintptr_t>(states) & 3))
-        return TAMP_AMD_BAD_ARGUMENT;
+    if (object_array_refused(t.n, states, state_stride, state_size, window_bits_max)) return TAMP_AMD_BAD_ARGUMENT;
     DeviceCtx* ctx = nullptr;  // (objects stay on one device: TAMP_AMD_ALL_DEVICES is no device)
     if (const int rc = get_ctx(device, &ctx)) return rc;
     if (mem == TAMP_AMD_MEM_DEVICE) return launch(ctx, static_cast<uint8_t*>(states), t, static_cast<hipStream_t>(stream));
@@ -3785,6 +3811,31 @@ int tamp_batch_decompress_resume(void* states, size_t state_stride, uint8_t wind
                                  size_t n_streams, int mem, int device, void* stream) {
     return batch_decompress_resume({in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, nullptr, nullptr, 0, n_streams},
                                    states, state_stride, window_bits_max, mem, device, stream);
+}
+
+int tamp_batch_decompress_pieces(void* states, size_t state_stride, uint8_t window_bits_max, const uint32_t* object_index,
+                                 const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                                 const uint32_t* out_cap, uint32_t* out_len, int8_t* status, uint32_t* in_consumed, size_t n_rows,
+                                 int device, void* stream) {
+    const BatchTables t = {in, in_off, in_len, out, out_off, out_cap, out_len, status, in_consumed, nullptr, nullptr, 0, n_rows};
+    return run_object_batch(t, states, state_stride, tamp_amd_decoder_state_size(window_bits_max), window_bits_max, TAMP_AMD_MEM_DEVICE,
+                            device, stream, [&](DeviceCtx* ctx, uint8_t* d_states, const BatchTables& d, hipStream_t st) {
+        return launch_decompress_resume(ctx, d_states, state_stride, window_bits_max, d, st, object_index);
+    });
+}
+
+int tamp_batch_decoded_size_pieces(const void* states, size_t state_stride, uint8_t window_bits_max, const uint32_t* object_index,
+                                   const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* limit,
+                                   uint32_t* decoded_size, int8_t* status, uint32_t* in_consumed, size_t n_rows, int device, void* stream) {
+    // (no slab: out = out_off = null, the limits travel as the out_cap table -- which run_object_batch's check would insist on)
+    const BatchTables t = {in, in_off, in_len, nullptr, nullptr, limit, decoded_size, status, in_consumed, nullptr, nullptr, 0, n_rows};
+    if (const int rc = batch_refused(t, false, TAMP_AMD_MEM_DEVICE, device)) return rc;
+    if (object_array_refused(n_rows, states, state_stride, tamp_amd_decoder_state_size(window_bits_max), window_bits_max))
+        return TAMP_AMD_BAD_ARGUMENT;
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    return launch_decoded_size_pieces(ctx, static_cast<const uint8_t*>(states), state_stride, window_bits_max, object_index, t,
+                                      static_cast<hipStream_t>(stream));
 }
 
 size_t tamp_amd_piece_object_size(uint8_t window_bits) {

@@ -199,4 +199,43 @@ __device__ __forceinline__ ExactTok exact_token(RefReader& r, const StreamHeader
     return {kExMatch, match_len, off};
 }
 
+// The payload of an RLE / extended-match symbol whose bits are committed (decode_rle / decode_extended_match with the loop's
+// refill-and-retry, decompressor.c:114-273,447-456).  `got` = 0: nothing of it read yet; 1: an extended match whose size
+// `match_len` is known and whose offset is still to come (TOKEN_EXT_MATCH parked by an earlier call).  For a decoder that picks a token
+// up where an earlier call left it (tamp_decoded_size_pieces_kernel.hpp).  exact_token above keeps these rules inline: called from
+// there, this function cost the size-only parse two more spilled SGPRs, and its instruction stream is not to change.
+__device__ __forceinline__ ExactTok exact_payload(RefReader& r, const StreamHeader& h, const bool rle, int got, uint32_t match_len) {
+    const uint32_t W = 1u << h.wbits;
+    const uint32_t trailing = rle ? 4u : 3u;
+    uint32_t value = 0, off = 0;
+    for (;;) {
+        if (got == 0) {
+            uint32_t u3 = 0;
+            int hsym = (r.nb >= 1 + trailing) ? read_symbol(r.bb, r.nb, u3) : -1;
+            if (hsym >= 0 && r.nb - u3 < trailing) hsym = -1;
+            if (hsym >= 0) {
+                uint32_t b3 = r.bb << u3;
+                value = ((uint32_t)hsym << trailing) + (b3 >> (32 - trailing));
+                r.bb = b3 << trailing;
+                r.nb -= u3 + trailing;
+                got = rle ? 2 : 1;
+                if (!rle) match_len = value + h.minp + 12;
+            }
+        }
+        if (got == 1 && r.nb >= h.wbits) {
+            off = r.bb >> (32 - h.wbits);
+            r.bb <<= h.wbits;
+            r.nb -= h.wbits;
+            got = 2;
+        }
+        if (got == 2) break;
+        const uint32_t before = r.nb;
+        r.refill();
+        if (r.nb == before && r.ip == r.n) return {kExShort, 0, 0};  // starved
+    }
+    if (rle) return {kExRle, value + 2, 0};  // decompressor.c:140-173
+    if (off >= W || off + match_len > W) return {kExOob, 0, 0};  // decompressor.c:229-236
+    return {kExExt, match_len, off};
+}
+
 }  // namespace tamp_amd

@@ -138,6 +138,14 @@ static inline SizeGeometry size_geometry(size_t n_streams, uint32_t cu_count) {
     return {spw, (uint32_t)std::max<size_t>(1, std::min((waves + 3) / 4, (size_t)cu_count * 8)), split_size_lds(256)};
 }
 
+// The size query for decoder objects (tamp_batch_decoded_size_pieces, tamp_decoded_size_pieces_kernel.hpp): a lane per row by the
+// same rule -- rows per wavefront from parse_spw, one grid of 256-thread workgroups in strides beyond eight per CU -- and no LDS: the
+// kernel runs the exact loop alone.
+static inline SizeGeometry size_pieces_geometry(size_t n_rows, uint32_t cu_count) {
+    const SizeGeometry g = size_geometry(n_rows, cu_count);
+    return {g.spw, g.grid, 0u};
+}
+
 // Lane per stream, windows in LDS: one 64-lane workgroup per 64 streams, one padded row per lane; the bulk build (streams of 512
 // compressed bytes and more) adds per-lane staging.  The ONE definition: the capacity estimate and the launch both read it.
 struct LaneLdsGeometry { uint32_t lds_row, lds, per_cu, grid; };

@@ -24,6 +24,8 @@ struct ResumeArgs {
     DecompressArgs d;       // per-call input / output tables; d.max_wbits = window capacity of every object
     uint8_t* states;        // object i at states + i * state_stride: 16-byte state, then (1 << max_wbits) window bytes
     uint64_t state_stride;
+    const uint32_t* object_index;  // row s of d's tables acts on object object_index[s] (tamp_batch_decompress_pieces); null: on object s.
+                                   // An object no row names is neither read nor written; two rows naming one object is the caller's error
 };
 
 // decompressor.c:39-42
@@ -45,7 +47,15 @@ __global__ void __launch_bounds__(256) tamp_decompress_resume_kernel(ResumeArgs 
 
     const uint32_t gw = blockIdx.x * nwaves + wave, tw = gridDim.x * nwaves;
     for (uint32_t s = gw; s < a.n_streams; s += tw) {
-        uint8_t* const slot = ra.states + (uint64_t)s * ra.state_stride;
+        // The table's pointer is read from the kernel-argument segment here, once per object (ResumeArgs is the kernel's only
+        // argument: offset 0 of the segment), and not taken from `ra`: the compiler would carry it across the token loop in two more
+        // SGPRs, and the kernel has none to spare (31 spilled SGPRs before the table existed, 34 with `ra.object_index`, 29 this way).
+        typedef const uint32_t* IndexTable;
+        typedef const volatile IndexTable __attribute__((address_space(4)))* IndexTableArg;
+        const IndexTable index = *(IndexTableArg)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                  offsetof(ResumeArgs, object_index));
+        const uint32_t obj = index ? uni32(index[s]) : s;
+        uint8_t* const slot = ra.states + (uint64_t)obj * ra.state_stride;
         uint8_t* const gwin = slot + 16;
         const uint32_t* const sw = reinterpret_cast<const uint32_t*>(slot);
         // state words: [bit_buffer][window_pos | bit_buffer_pos << 16 | token_state << 24]
