@@ -574,6 +574,54 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t *in, const uin
                            size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
 
 /*
+ * The table of SEGMENT ENDS of a batch whose reset segments differ in size: streams a reference Compressor(dictionary_reset) wrote
+ * with reset_dictionary() calls of its own, append-mode logs, streams compressed with different intervals.  From what
+ * tamp_batch_index_resets returns (reset_first, closed_size, open_size) it makes ONE uint64 table with an entry per segment, not per
+ * reset: stream i with E = reset_first[i + 1] - reset_first[i] resets has E + 1 segments, its entries lie at
+ * segment_end[reset_first[i] + i + k] for k = 0 .. E, and the table has reset_first[n_streams] + n_streams entries, which is the
+ * room `segment_end` must have.  Entry k is the decoded size of the stream's segments 0 .. k: non-decreasing, the last one the
+ * stream's decoded size.  Segment k covers the decoded bytes [B(k), B(k + 1)) with B(0) = 0 and B(k) = entry k - 1; segments of no
+ * bytes (two resets in a row, an append marker at an empty file) are legal.  A size of 0xFFFFFFFF ("2^32 - 1 or more") makes its
+ * entry and every later entry of its stream 2^64 - 1.  Rows of reset_first that are no running sum add nothing; nothing is read
+ * or written outside the four tables whatever they hold.
+ *   mem, device, stream   device memory: a per-stream running sum over the rows of the whole batch, a lane per row, in two launches on
+ *                   `stream`; NOTHING is read back and the stream is never waited for, so index -> table -> ranges stays on the
+ *                   device.  Host memory: the same sum on the host; no device is looked for.
+ * Returns TAMP_OK (n_streams == 0: at once); TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null reset_first or
+ * segment_end, a null open_size with n_streams > 0, a null closed_size (host memory: with reset_first[n_streams] != 0; device
+ * memory: with n_streams > 0), a bad memory kind, TAMP_AMD_ALL_DEVICES, n_streams >= 2^32; TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_segment_ends(const uint64_t *reset_first, const uint32_t *closed_size, const uint32_t *open_size,
+                            uint64_t *segment_end, size_t n_streams, int mem, int device, void *stream);
+
+/*
+ * tamp_batch_read_ranges for segments of ANY size: `segment_end` (tamp_batch_segment_ends) in place of reset_interval.  The segment
+ * of a byte is found by a search in the stream's entries where that call divides; everything behind that -- stage, walk, decode,
+ * gather -- the result tables, the scratch budget, the slices, the debug line and the memory-kind rules are that call's.  Per range
+ * with range_len[q] > 0 on an eligible stream (the rules up to the reset_first one are unchanged), `total` the stream's last entry:
+ *       range_begin[q] >= total .............................................. TAMP_INPUT_EXHAUSTED, 0 (from the table alone: no units)
+ *   otherwise end = min(begin + len, total), the sum saturating in 64 bits; k0 = the number of entries <= begin among the stream's
+ *   first E (empty segments are stepped over), k1 = the number <= end - 1.  The units are segments k0 .. k1: every one but the last
+ *   is asked for its whole size, the last for end - B(k1); the scratch is end - B(k0) -- true sizes, the open segment's too -- and
+ *   the range's bytes start begin - B(k0) bytes into it.  end - begin bytes are delivered: TAMP_OK when that is range_len[q], else
+ *   TAMP_INPUT_EXHAUSTED.
+ * WHAT THE TABLE IS TRUSTED FOR.  Position, as the index is: the table says which segment holds a byte, and it is verified on what
+ * a range touches.  Each of these is TAMP_AMD_BAD_INDEX and 0 bytes for the range, and affects no other: B(k0) <= begin < B(k0 + 1)
+ * does not hold behind the search (a table that is not sorted); a touched entry below the one in front of it; a touched segment
+ * whose table size is 2^32 - 1 or more; a touched segment, closed OR open, that does not decode to exactly its table size; and, as
+ * before, a closed segment that does not end at its entry behind FLUSH, FLUSH, and an entry of reset_off out of range or order.  An
+ * offset out of the window stays TAMP_OOB.  The search is memory safe for any contents of the table: its bounds come from
+ * reset_first (segment_end must have reset_first[n_streams] + n_streams entries).  A forged table AND index whose touched segments
+ * happen to parse to the forged sizes can deliver other bytes.
+ * Returns as tamp_batch_read_ranges, with a null segment_end in place of reset_interval == 0.
+ */
+int tamp_batch_read_ranges_grid(uint8_t max_window_bits, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                                const uint64_t *reset_first, const uint32_t *reset_off, const uint64_t *segment_end,
+                                const uint32_t *range_stream, const uint64_t *range_begin, const uint32_t *range_len,
+                                uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int8_t *status,
+                                size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
+
+/*
  * WRITING byte ranges into such streams: the other half of random access.  Write q replaces the decoded bytes
  * [write_begin[q], write_begin[q] + write_len[q]) of stream write_stream[q] with src[src_off[q] .. + write_len[q]).  Only the segments
  * a write touches are decoded (by tamp_batch_read_ranges' own steps), patched and compressed again; every other segment keeps its

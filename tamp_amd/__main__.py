@@ -1,4 +1,4 @@
-"""``python -m tamp_amd compress|decompress|index|append ...`` (tamp_amd/cli.py)."""
+"""``python -m tamp_amd compress|decompress|index|append|read ...`` (tamp_amd/cli.py)."""
 import sys
 
 from .cli import main

@@ -50,6 +50,8 @@ SYMBOLS = (
     "tamp_batch_decompress_resets",
     "tamp_amd_decompress_resets",
     "tamp_batch_read_ranges",
+    "tamp_batch_read_ranges_grid",
+    "tamp_batch_segment_ends",
     "tamp_batch_write_ranges",
     "tamp_batch_append",
     "tamp_batch_index_resets",
@@ -238,6 +240,10 @@ def load() -> C.CDLL:
     lib.tamp_amd_decompress_resets.restype = i32
     lib.tamp_batch_read_ranges.argtypes = [u8, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, vp]
     lib.tamp_batch_read_ranges.restype = i32
+    lib.tamp_batch_read_ranges_grid.argtypes = [u8, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, vp]
+    lib.tamp_batch_read_ranges_grid.restype = i32
+    lib.tamp_batch_segment_ends.argtypes = [vp, vp, vp, vp, sz, i32, i32, vp]
+    lib.tamp_batch_segment_ends.restype = i32
     lib.tamp_batch_write_ranges.argtypes = [C.POINTER(TampAmdConf), u8, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz,
                                             i32, i32, vp]
     lib.tamp_batch_write_ranges.restype = i32

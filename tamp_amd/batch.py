@@ -767,7 +767,7 @@ class RangeResult:
         return [self.range(q) for q in range(len(self.out_len))]
 
 
-def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, begin, length, reset_interval=None,
+def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, begin, length, reset_interval=None, segment_ends=None,
                 max_window_bits: int = 15, device: int = 0, stream=None, timing: bool = False) -> RangeResult:
     """Byte ranges of reset-segmented streams, without decoding the rest (``tamp_batch_read_ranges``; not in the
     reference).  ``data`` as for ``decompress_batch``: the streams of ``compress_batch(..., reset_interval=N, reset_index=True)``,
@@ -775,7 +775,12 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
     segments it touches are staged and decoded.  The three range tables are sequences, numpy arrays or CUDA tensors.  The output is
     the ranges back to back; ``status[q]`` is 0 when all of range ``q`` was delivered, 2 when the stream ended first (``out_len[q]``
     bytes are there), negative otherwise -- -22 when the index does not hold up on the touched segments.  The index is trusted
-    for position: pass the compressor's own.  ``reset_interval`` defaults to ``reset_index.interval``."""
+    for position: pass the compressor's own.  ``reset_interval`` defaults to ``reset_index.interval``.
+
+    ``segment_ends=``: the table of segment ends (``ResetScan.segment_ends()``, ``tamp_batch_read_ranges_grid``) for streams whose
+    segments differ in size -- reference-made streams with resets of their own, append-mode logs, batches compressed with different
+    intervals.  With it no interval is needed, and one that is given is ignored; the table is trusted for position like the index
+    and verified on the segments a range touches (status -22 where it does not hold up).  It lives where ``data`` lives."""
     if not isinstance(reset_index, ResetIndex):  # (all decided before the library is looked for)
         raise ValueError("reset_index: a ResetIndex expected")
     n_streams = len(data) if in_off is None and not _is_torch(data) else len(in_len)
@@ -783,12 +788,34 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
         raise ValueError("reset_index.first: one entry per stream and one more expected")
     if not len(stream_index) == len(begin) == len(length):
         raise ValueError("stream_index, begin and length: one entry per range each")
-    interval = reset_interval if reset_interval is not None else reset_index.interval
-    if interval is None:
-        raise ValueError("reset_interval: not given and not in the index")
-    if not _is_int(interval) or not 1 <= int(interval) <= 0xFFFFFFFF:
-        raise ValueError("reset_interval: a positive integer that fits 32 bits expected")
-    interval = int(interval)
+    if segment_ends is not None:
+        interval = 0
+        if not (_is_torch(segment_ends) or isinstance(segment_ends, np.ndarray)):
+            segment_ends = np.array([int(x) for x in segment_ends] or [0], dtype=object)[: len(segment_ends)]
+        if _is_torch(segment_ends):  # (torch dtypes have no kind: integers are what is neither floating, complex nor bool)
+            dt = segment_ends.dtype
+            kind = "f" if dt.is_floating_point or dt.is_complex or "bool" in str(dt) else "i"
+        else:
+            kind = segment_ends.dtype.kind
+        if segment_ends.ndim != 1 or kind not in "iuO":
+            raise ValueError("segment_ends: a 1-D table of integers expected")
+        if len(segment_ends) != len(reset_index.off) + n_streams:  # (the tables' lengths: nothing is read back)
+            raise ValueError("segment_ends: one entry per segment expected, len(reset_index.off) + the number of streams")
+        if (_is_torch(segment_ends) and segment_ends.is_cuda) != (_is_torch(data) and data.is_cuda):
+            raise ValueError("segment_ends: on another memory kind than the data")
+        if _is_torch(segment_ends) and not segment_ends.is_cuda:  # (int64 storage holds uint64 values, as in the other tables)
+            segment_ends = segment_ends.long().numpy().view(np.uint64)
+        if not _is_torch(segment_ends):
+            if len(segment_ends) and (int(segment_ends.min()) < 0 or int(segment_ends.max()) > (1 << 64) - 1):
+                raise ValueError("segment_ends: does not fit 64 bits")
+            segment_ends = np.ascontiguousarray(segment_ends.astype(np.uint64))
+    else:
+        interval = reset_interval if reset_interval is not None else reset_index.interval
+        if interval is None:
+            raise ValueError("reset_interval: not given and not in the index")
+        if not _is_int(interval) or not 1 <= int(interval) <= 0xFFFFFFFF:
+            raise ValueError("reset_interval: a positive integer that fits 32 bits expected")
+        interval = int(interval)
     n_ranges = len(stream_index)
     on_device = _is_torch(data)
     tables = (stream_index, begin, length)
@@ -813,9 +840,15 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
 
         with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
             return read_ranges(data, in_off, in_len, reset_index=reset_index, stream_index=stream_index, begin=begin, length=length,
-                               reset_interval=interval, max_window_bits=max_window_bits, device=device, stream=None, timing=timing)
+                               reset_interval=interval or None, segment_ends=segment_ends, max_window_bits=max_window_bits, device=device,
+                               stream=None, timing=timing)
     lib = _lib.load()
     lib.tamp_amd_set_timing(1 if timing else 0)
+
+    def call(*a):  # (the two entries differ in ONE argument: the interval, or the table)
+        if segment_ends is None:
+            return lib.tamp_batch_read_ranges(*a)
+        return lib.tamp_batch_read_ranges_grid(*a[:6], _ptr(ends), *a[7:])
     if on_device:
         import torch
 
@@ -831,13 +864,16 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
         out_len_t = torch.empty(n_ranges, dtype=torch.int32, device=dev)
         status_t = torch.empty(n_ranges, dtype=torch.int8, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _lib.check_launch(lib.tamp_batch_read_ranges(
+        # (an empty table still needs an address: the call refuses a null one)
+        ends = None if segment_ends is None else (segment_ends.to(device=dev, dtype=torch.int64).contiguous() if segment_ends.numel()
+                                                  else torch.zeros(1, dtype=torch.int64, device=dev))
+        _lib.check_launch(call(
             max_window_bits, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), _ptr(first_t), _ptr(off_t) if off_t.numel() else None, interval,
             _ptr(stream_t), _ptr(begin_t), _ptr(length_t), _ptr(out), _ptr(out_off_t), _ptr(out_len_t), _ptr(status_t), n_streams,
             n_ranges, _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st)))
         ms = lib.tamp_amd_last_kernel_ms() if timing else -1.0
         return RangeResult(out, out_off_t, out_len_t, status_t, ms,
-                           (data, in_off_t, in_len_t, first_t, off_t, stream_t, begin_t, length_t))
+                           (data, in_off_t, in_len_t, first_t, off_t, stream_t, begin_t, length_t, ends))
     if in_off is None:
         flat, in_off, in_len = pack_streams(data)
     else:
@@ -852,7 +888,8 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
     out_off, total = _slab_offsets(range_len)
     out = np.zeros(total + 1, dtype=np.uint8)
     out_len, status = np.zeros(n_ranges, dtype=np.uint32), np.zeros(n_ranges, dtype=np.int8)
-    _lib.check_launch(lib.tamp_batch_read_ranges(
+    ends = None if segment_ends is None else (segment_ends if segment_ends.size else np.zeros(1, np.uint64))
+    _lib.check_launch(call(
         max_window_bits, _ptr(flat), _ptr(in_off), _ptr(in_len), _ptr(first), _ptr(off) if off.size else None, interval, _ptr(range_stream),
         _ptr(range_begin), _ptr(range_len), _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(status), n_streams, n_ranges, _lib.MEM_HOST,
         device, C.c_void_p(stream) if stream else None))
@@ -1245,6 +1282,54 @@ class ResetScan:
         closed = self.closed_size[a:b]
         closed = closed.cpu().numpy() if _is_torch(closed) else np.asarray(closed)
         return int((closed.astype(np.int64) & 0xFFFFFFFF).sum()) + (int(self.open_size[i]) & 0xFFFFFFFF)
+
+    def segment_ends(self, *, device: int = 0, stream=None):
+        """The table of segment ends of the scanned batch, for ``read_ranges(..., segment_ends=)``: see ``segment_ends``.  Made once,
+        where the scan's tables live, and kept on the object."""
+        if self._segment_ends is None:
+            self._segment_ends = segment_ends(self.index.first, self.closed_size, self.open_size, device=device, stream=stream)
+        return self._segment_ends
+
+    _segment_ends = None  # (a class attribute until the first call: no field, so the dataclass is what it was)
+
+
+def segment_ends(first, closed_size, open_size, *, device: int = 0, stream=None):
+    """The table of segment ends (``tamp_batch_segment_ends``; not in the reference) from an index's ``first`` and the
+    sizes ``index_resets`` found: one uint64 entry per SEGMENT, stream ``i``'s at ``[first[i] + i, first[i + 1] + i + 1)``, entry ``k``
+    the decoded size of its segments ``0 .. k`` -- the last one the stream's decoded size.  numpy tables give a numpy table, computed
+    on the host; CUDA tensors give an int64 tensor, computed on the device with no read-back and no wait."""
+    n = len(first) - 1
+    if n < 0 or len(open_size) != n:
+        raise ValueError("first: one entry per stream and one more expected, open_size: one per stream")
+    on_device = _is_torch(first) and first.is_cuda
+    if any((_is_torch(t) and t.is_cuda) != on_device for t in (closed_size, open_size)):
+        raise ValueError("first, closed_size and open_size: on one memory kind expected")
+    lib = _lib.load()
+    if on_device:
+        import torch
+
+        dev = first.device
+        first_t, open_t = first.to(torch.int64).contiguous(), open_size.to(torch.int32).contiguous()
+        closed_t = closed_size.to(torch.int32).contiguous() if closed_size.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+        if stream is not None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=dev)):
+                ends = torch.empty(max(len(closed_size) + n, 1), dtype=torch.int64, device=dev)
+        else:
+            ends = torch.empty(max(len(closed_size) + n, 1), dtype=torch.int64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check_launch(lib.tamp_batch_segment_ends(_ptr(first_t), _ptr(closed_t), _ptr(open_t), _ptr(ends), n, _lib.MEM_DEVICE,
+                                                      dev.index or 0, C.c_void_p(st)))
+        ends = ends[: len(closed_size) + n]
+        ends._tamp_keep = (first_t, closed_t, open_t)  # (the asynchronous launch still reads them)
+        return ends
+    to_np = lambda x, dt: np.ascontiguousarray((x.numpy() if _is_torch(x) else np.asarray(x)).astype(dt))  # noqa: E731
+    first, closed, open_size = to_np(first, np.uint64), to_np(closed_size, np.uint32), to_np(open_size, np.uint32)
+    if int(first[n]) != len(closed):
+        raise ValueError("closed_size: first[-1] entries expected")
+    ends = np.zeros(max(len(closed) + n, 1), dtype=np.uint64)
+    _lib.check_launch(lib.tamp_batch_segment_ends(_ptr(first), _ptr(closed) if closed.size else None, _ptr(open_size), _ptr(ends), n,
+                                                  _lib.MEM_HOST, device, None))
+    return ends[: len(closed) + n]
 
 
 def _detect_interval(first, closed, open_size, status):

@@ -1,4 +1,4 @@
-"""Command line of the package: ``python -m tamp_amd compress|decompress|index|append|build-dictionary`` with the options of the reference's CLI.
+"""Command line of the package: ``python -m tamp_amd compress|decompress|index|append|read|build-dictionary`` with the options of the reference's CLI.
 
 Mirrors ``tamp/cli/main.py:115-232`` (``tamp compress`` / ``tamp decompress``: ``--input/-i``, ``--output/-o``,
 ``--window/-w``, ``--literal/-l``, ``--dictionary/-d``, ``--lazy-matching``, ``--extended`` / ``--no-extended``; stdin /
@@ -87,6 +87,11 @@ def build_parser() -> argparse.ArgumentParser:
     a.add_argument("--reset-interval", type=int, default=None, metavar="N",
                    help="the interval the stream was compressed with (needed only while it has no closed segment to tell it by)")
     a.add_argument("--lazy-matching", action=argparse.BooleanOptionalAction, default=False)
+    r = sub.add_parser("read", help="Read a byte range of a compressed file with dictionary resets, decoding only the segments it touches.")
+    r.add_argument("file", metavar="FILE", help="the compressed file; its segments may be of any size")
+    r.add_argument("--begin", "-b", type=_bits(0, (1 << 64) - 1), required=True, metavar="B", help="the range's first decoded byte")
+    r.add_argument("--length", "-n", type=_bits(0, 0xFFFFFFFF), required=True, metavar="L", help="decoded bytes to read")
+    r.add_argument("--output", "-o", default=None, help="output file (default: stdout)")
     b = sub.add_parser("build-dictionary", help="Build a custom dictionary from a corpus of messages.")
     b.add_argument("input", metavar="INPUT", help="directory of sample files, or one file cut at --delimiter")
     b.add_argument("--output", "-o", default="dictionary.bin", help="binary dictionary file (effective bytes only)")
@@ -137,6 +142,26 @@ def _append(tamp_amd, args) -> int:
     return 0
 
 
+def _read(tamp_amd, args) -> int:
+    """``read FILE --begin B --length L``: the index comes from ``index_resets``, the grid from its table of segment ends."""
+    try:
+        blob = Path(args.file).read_bytes()
+        if len(blob) < 1 or not blob[0] & 1:
+            raise ValueError(f"{args.file}: the stream has no dictionary resets (its header's reset bit is not set): decompress it instead")
+        scan = tamp_amd.index_resets([blob])
+        if int(scan.status[0]) != 0:
+            raise ValueError(f"{args.file}: not a stream whose resets can be found (status {int(scan.status[0])})")
+        res = tamp_amd.read_ranges([blob], reset_index=scan.index, segment_ends=scan.segment_ends(), stream_index=[0],
+                                   begin=[args.begin], length=[args.length])
+        if int(res.status[0]) not in (0, 2):
+            raise ValueError(f"{args.file}: the read failed with status {int(res.status[0])}")
+    except (OSError, ValueError) as e:
+        print(f"tamp_amd: {type(e).__name__}: {e}", file=sys.stderr)
+        return 1
+    _deliver(args.output, res.range(0))
+    return 0
+
+
 def main(argv=None) -> int:
     import tamp_amd
 
@@ -167,6 +192,8 @@ def main(argv=None) -> int:
         return 0
     if args.command == "append":
         return _append(tamp_amd, args)
+    if args.command == "read":
+        return _read(tamp_amd, args)
     src = args.input if args.input is not None else args.input_pos
     dst = args.output if args.output is not None else args.output_pos
     try:

@@ -34,6 +34,7 @@
 #include "tamp_compress_resume_kernel.hpp"
 #include "tamp_reset_segments_kernel.hpp"
 #include "tamp_read_ranges_kernel.hpp"
+#include "tamp_segment_ends_kernel.hpp"
 #include "tamp_write_ranges_kernel.hpp"
 #include "tamp_append_kernel.hpp"
 #include "tamp_reset_index_kernel.hpp"
@@ -80,7 +81,7 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_append, launch_index_resets, launch_pack and launch_pieces and held to the call's last launch: one library call at a time enqueues on a
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_append, launch_index_resets, launch_segment_ends, launch_pack and launch_pieces and held to the call's last launch: one library call at a time enqueues on a
 // stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
 // lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
@@ -98,6 +99,7 @@ struct StreamScratch {
     DeviceBuf resets;      // dictionary-reset segments: the slice's table rows and output slabs (launch_compress_resets), a batch's per-stream words in front (launch_compress_batch_resets)
     DeviceBuf pack;        // tamp_batch_pack: the scan's per-workgroup sums (8 KiB, allocated once)
     DeviceBuf ranges;      // tamp_batch_read_ranges: the per-range scans and verdicts (the units, stage and scratch of a slice: `resets`)
+    DeviceBuf ends;        // tamp_batch_segment_ends: the scan's per-workgroup sums (16 KiB, allocated once)
     DeviceBuf writes, write_units;  // tamp_batch_write_ranges: its tables per stream and per segment; the rows, staging rows and slabs of a slice's units
     DeviceBuf appends, append_units;  // tamp_batch_append: its tables per stream; the staged entries of the new index, then the rows, staging rows and slabs of a slice's units
     DeviceBuf index_streams, index_chunks, index_entries;  // tamp_batch_index_resets: its tables per stream, per chunk, per entry
@@ -113,7 +115,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries, &pieces, &piece_rows}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &ends, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries, &pieces, &piece_rows}) n += b->release();
         return n;
     }
 };
@@ -2398,6 +2400,9 @@ size_t read_ranges_budget(const StreamScratch& rec) {
 }
 constexpr size_t kReadRangesHead = 256;  // the record, in front of the per-range tables
 size_t read_ranges_bytes(uint64_t nr) { return kReadRangesHead + 24 * (nr + 1) + 2 * nr + 64; }
+// (the table form: a skip per range behind them, ReadTable::skip)
+size_t read_ranges_grid_bytes(uint64_t nr) { return ((read_ranges_bytes(nr) + 7) & ~(size_t)7) + 8 * nr; }
+uint64_t* read_ranges_skip_at(uint8_t* base, uint64_t nr) { return reinterpret_cast<uint64_t*>(base + ((read_ranges_bytes(nr) + 7) & ~(size_t)7)); }
 ReadRanges read_ranges_at(uint8_t* base, uint64_t nr) {
     ReadRanges r;
     r.unit_first = reinterpret_cast<uint64_t*>(base + kReadRangesHead), r.scratch_first = r.unit_first + nr + 1;
@@ -2419,12 +2424,17 @@ std::vector<ReadSliceSpan> read_ranges_slices(const uint64_t* cost_first, const 
     return slices;
 }
 // The steps of a slice behind its staged units: the walk, the decode of the unit rows by the existing launch path, the gather.
-// `c`: what the gather reads of the caller's tables (interval, range_begin, range_len).
+// `c`: what the gather reads of the caller's tables (interval, range_begin, range_len).  `g`: the table form (its skips), or null.
 int launch_read_tail(DeviceCtx* ctx, StreamScratch& rec, const ReadCaller& c, const ReadRanges& r, const ReadSlice& s, uint8_t max_wbits,
-                     uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int8_t* status, hipStream_t st) {
+                     uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int8_t* status, hipStream_t st, const ReadTable* g = nullptr) {
     if (s.U) {
-        const ReadWalkArgs walk = {s, r.failed, c.interval};
-        hipLaunchKernelGGL(tamp_read_walk_kernel, dim3((uint32_t)((s.U + 63) / 64)), dim3(64), 0, st, walk);
+        if (g) {
+            const ReadWalkGridArgs walk = {s, r.failed};
+            hipLaunchKernelGGL(tamp_read_walk_kernel<ReadWalkGridArgs>, dim3((uint32_t)((s.U + 63) / 64)), dim3(64), 0, st, walk);
+        } else {
+            const ReadWalkArgs walk = {s, r.failed, c.interval};
+            hipLaunchKernelGGL(tamp_read_walk_kernel<ReadWalkArgs>, dim3((uint32_t)((s.U + 63) / 64)), dim3(64), 0, st, walk);
+        }
         HIP_OK(hipGetLastError());
         const ReadUnits u = read_units_at(s.region, s.U);
         BatchTables ut;
@@ -2432,8 +2442,14 @@ int launch_read_tail(DeviceCtx* ctx, StreamScratch& rec, const ReadCaller& c, co
         ut.out_len = u.out_len, ut.status = u.status, ut.n = s.U;
         if (const int rc = launch_decompress_locked(ctx, rec, ut, max_wbits, st)) return rc;
     }
-    const ReadGatherArgs gather = {c, r, s, out, out_off, out_len, status};
-    hipLaunchKernelGGL(tamp_read_gather_kernel, dim3((uint32_t)std::min<uint64_t>(s.q1 - s.q0, (uint64_t)ctx->cu_count * 8)), dim3(256), 0, st, gather);
+    const dim3 gather_grid((uint32_t)std::min<uint64_t>(s.q1 - s.q0, (uint64_t)ctx->cu_count * 8));
+    if (g) {
+        const ReadGatherGridArgs gather = {c, r, s, out, out_off, out_len, status, *g};
+        hipLaunchKernelGGL(tamp_read_gather_kernel<ReadGatherGridArgs>, gather_grid, dim3(256), 0, st, gather);
+    } else {
+        const ReadGatherArgs gather = {c, r, s, out, out_off, out_len, status};
+        hipLaunchKernelGGL(tamp_read_gather_kernel<ReadGatherArgs>, gather_grid, dim3(256), 0, st, gather);
+    }
     HIP_OK(hipGetLastError());
     return TAMP_OK;
 }
@@ -2446,14 +2462,22 @@ void read_ranges_debug(uint64_t ranges, uint64_t units, size_t slices, uint64_t 
 // region -- and, only when the call does not fit ONE slice, for the three scans that say where to cut it.
 // `rec`: the stream's scratch record, locked by the caller (launch_read_ranges; launch_write_ranges, whose touched segments are read
 // as ranges of their own), who also holds the call's event pair.
+// `segment_end`: the table form (tamp_batch_read_ranges_grid; c.interval is not read), or null.
 int launch_read_ranges_locked(DeviceCtx* ctx, StreamScratch& rec, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off,
-                              uint32_t* out_len, int8_t* status, bool dbg, hipStream_t st) {
+                              uint32_t* out_len, int8_t* status, bool dbg, hipStream_t st, const uint64_t* segment_end = nullptr) {
     const uint64_t nr = c.n_ranges, budget = read_ranges_budget(rec);
-    HIP_OK(rec.ranges.need(read_ranges_bytes(nr)));
+    HIP_OK(rec.ranges.need(segment_end ? read_ranges_grid_bytes(nr) : read_ranges_bytes(nr)));
     uint8_t* const tabs = static_cast<uint8_t*>(rec.ranges.p);
     const ReadRanges r = read_ranges_at(tabs, nr);
-    const ReadCountArgs count = {c, budget, r, reinterpret_cast<ReadRecord*>(tabs)};
-    hipLaunchKernelGGL(tamp_read_count_kernel, dim3(1), dim3(kResetScanTile), 0, st, count);
+    const ReadTable table = {segment_end, read_ranges_skip_at(tabs, nr)};
+    const ReadTable* const g = segment_end ? &table : nullptr;
+    if (g) {
+        const ReadCountGridArgs count = {c, budget, r, reinterpret_cast<ReadRecord*>(tabs), table};
+        hipLaunchKernelGGL(tamp_read_count_kernel<ReadCountGridArgs>, dim3(1), dim3(kResetScanTile), 0, st, count);
+    } else {
+        const ReadCountArgs count = {c, budget, r, reinterpret_cast<ReadRecord*>(tabs)};
+        hipLaunchKernelGGL(tamp_read_count_kernel<ReadCountArgs>, dim3(1), dim3(kResetScanTile), 0, st, count);
+    }
     HIP_OK(hipGetLastError());
     ReadRecord have = {0, 0};
     HIP_OK(hipMemcpyAsync(&have, tabs, sizeof have, hipMemcpyDeviceToHost, st));
@@ -2478,13 +2502,18 @@ int launch_read_ranges_locked(DeviceCtx* ctx, StreamScratch& rec, const ReadCall
     for (const ReadSliceSpan& span : slices) {
         const ReadSlice s = {span.q0, span.q1, units_of(span), static_cast<uint8_t*>(rec.resets.p)};
         if (s.U) {
-            const ReadUnitsArgs units = {c, budget, r, s};
-            hipLaunchKernelGGL(tamp_read_units_kernel, dim3((uint32_t)((s.U + 255) / 256)), dim3(256), 0, st, units);
+            if (g) {
+                const ReadUnitsGridArgs units = {c, budget, r, s, table};
+                hipLaunchKernelGGL(tamp_read_units_kernel<ReadUnitsGridArgs>, dim3((uint32_t)((s.U + 255) / 256)), dim3(256), 0, st, units);
+            } else {
+                const ReadUnitsArgs units = {c, budget, r, s};
+                hipLaunchKernelGGL(tamp_read_units_kernel<ReadUnitsArgs>, dim3((uint32_t)((s.U + 255) / 256)), dim3(256), 0, st, units);
+            }
             const ReadStageArgs stage = {c, s};
             hipLaunchKernelGGL(tamp_read_stage_kernel, dim3((uint32_t)std::min<uint64_t>(s.U, (uint64_t)ctx->cu_count * 8)), dim3(256), 0, st, stage);
             HIP_OK(hipGetLastError());
         }
-        if (const int rc = launch_read_tail(ctx, rec, c, r, s, max_wbits, out, out_off, out_len, status, st)) return rc;
+        if (const int rc = launch_read_tail(ctx, rec, c, r, s, max_wbits, out, out_off, out_len, status, st, g)) return rc;
     }
     if (dbg) {  // (the line waits for the count's last entry; a call without the variable does not)
         uint64_t staged = 0;
@@ -2495,18 +2524,19 @@ int launch_read_ranges_locked(DeviceCtx* ctx, StreamScratch& rec, const ReadCall
     return TAMP_OK;
 }
 int launch_read_ranges(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
-                       int8_t* status, hipStream_t st) {
+                       int8_t* status, hipStream_t st, const uint64_t* segment_end) {
     StreamScratch& rec = ctx->scratch(st);
     std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
     const CallTiming call_timing(st);
-    return launch_read_ranges_locked(ctx, rec, c, max_wbits, out, out_off, out_len, status, getenv("TAMP_AMD_RESETS_DEBUG") != nullptr, st);
+    return launch_read_ranges_locked(ctx, rec, c, max_wbits, out, out_off, out_len, status, getenv("TAMP_AMD_RESETS_DEBUG") != nullptr, st, segment_end);
 }
 
 // Host memory, on the host pipeline's first stream (one host-memory call per device at a time): the host counts and cuts with the
 // functions the kernels use and copies ONLY the touched segments, a header in front of each, into pinned staging; per slice the
 // units' rows and that stage go up, the result tables and the packed ranges come back, and the delivered bytes are placed.
+// `segment_end`: the table form (the caller's table, in host memory), or null.
 int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
-                     int8_t* status) {
+                     int8_t* status, const uint64_t* segment_end) {
     using Pipe = DeviceCtx::HostPipe;
     Pipe& P = ctx->pipe;
     std::lock_guard<std::mutex> pipe_lock(P.mu);
@@ -2518,13 +2548,22 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
     const uint64_t nr = c.n_ranges, budget = read_ranges_budget(rec);
     // the count, on the host
     std::vector<ReadPlan> plan(nr);
+    std::vector<ReadGridPlan> grid_plan(segment_end ? nr : 0);  // (the table form: plan[q] is grid_plan[q].p)
+    std::vector<uint64_t> skip(segment_end ? nr : 0);
+    std::vector<uint32_t> unit_size;  // (the table form: the units' table sizes of a slice)
     std::vector<uint64_t> unit_first(nr + 1), cost_first(nr + 1), packed_off(nr);
     std::vector<int8_t> verdict(nr);
     std::vector<uint8_t> failed(nr, 0);
     uint64_t units_all = 0, cost_all = 0, staged_all = 0;
     for (uint64_t q = 0; q < nr; q++) {
-        plan[q] = read_range_plan(c.in, c.in_off, c.in_len, c.first, c.off, c.n, c.interval, c.max_wbits, budget, c.range_stream[q],
-                                  c.range_begin[q], c.range_len[q]);
+        if (segment_end) {
+            grid_plan[q] = read_grid_plan(c.in, c.in_off, c.in_len, c.first, c.off, segment_end, c.n, c.max_wbits, budget, c.range_stream[q],
+                                          c.range_begin[q], c.range_len[q]);
+            plan[q] = grid_plan[q].p, skip[q] = grid_plan[q].skip;
+        } else {
+            plan[q] = read_range_plan(c.in, c.in_off, c.in_len, c.first, c.off, c.n, c.interval, c.max_wbits, budget, c.range_stream[q],
+                                      c.range_begin[q], c.range_len[q]);
+        }
         unit_first[q] = units_all, cost_first[q] = cost_all, verdict[q] = (int8_t)plan[q].verdict;
         units_all += plan[q].units, cost_all += plan[q].units ? read_plan_cost(plan[q]) : 0;
     }
@@ -2532,8 +2571,10 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
     const std::vector<ReadSliceSpan> slices = read_ranges_slices(cost_first.data(), unit_first.data(), nr, budget);
     // the per-range tables of the device steps: unit_first and the verdicts in `ranges` (the walk's `failed` follows per slice), what
     // the gather reads of the caller's tables and the results in the pipeline's meta buffer
-    HIP_OK(rec.ranges.need(read_ranges_bytes(nr)));
+    HIP_OK(rec.ranges.need(segment_end ? read_ranges_grid_bytes(nr) : read_ranges_bytes(nr)));
     const ReadRanges r = read_ranges_at(static_cast<uint8_t*>(rec.ranges.p), nr);
+    const ReadTable table = {nullptr, read_ranges_skip_at(static_cast<uint8_t*>(rec.ranges.p), nr)};  // (the device steps read the skips alone)
+    const ReadTable* const g = segment_end ? &table : nullptr;
     HIP_OK(P.meta[0].need(nr * (8 + 8 + 4 + 4 + 1) + 64));
     uint64_t* const d_begin = static_cast<uint64_t*>(P.meta[0].p);
     uint64_t* const d_out_off = d_begin + nr;
@@ -2547,6 +2588,7 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
     HIP_OK(hipMemcpyAsync(r.verdict, verdict.data(), nr, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_begin, c.range_begin, nr * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_len, c.range_len, nr * 4, hipMemcpyHostToDevice, st));
+    if (g && nr) HIP_OK(hipMemcpyAsync(table.skip, skip.data(), nr * 8, hipMemcpyHostToDevice, st));
     for (const ReadSliceSpan& span : slices) {
         const uint64_t U = unit_first[span.q1] - unit_first[span.q0];
         uint64_t staged = 0, scratch = 0, packed = 0;
@@ -2563,11 +2605,18 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
             uint8_t* const h = static_cast<uint8_t*>(P.stage[0].p);
             uint8_t* const h_stage = h + rows_bytes;
             const ReadUnits u = read_units_at(h, U);  // (the uploaded rows alone)
+            if (g) unit_size.assign(U, 0);
             uint64_t x = 0, stage_at = 0, scratch_at = 0;
             for (uint64_t q = span.q0; q < span.q1; q++) {
                 const uint64_t i = c.range_stream[q];
                 for (uint64_t j = 0; j < plan[q].units; j++, x++) {
-                    const ReadUnit w = read_range_unit(c.first, c.off, c.in_len, c.interval, i, plan[q], j);
+                    ReadUnit w;
+                    if (g) {
+                        const ReadGridUnit gw = read_grid_unit(c.first, c.off, c.in_len, segment_end, i, grid_plan[q], j);
+                        w = gw.u, unit_size[x] = gw.size;
+                    } else {
+                        w = read_range_unit(c.first, c.off, c.in_len, c.interval, i, plan[q], j);
+                    }
                     u.in_off[x] = read_stage_at(U) + stage_at + w.place, u.out_off[x] = read_scratch_at(U, staged) + scratch_at + w.room;
                     u.in_len[x] = w.in_len, u.need[x] = w.need, u.owner[x] = (uint32_t)(q - span.q0);
                     u.flags[x] = (uint8_t)((w.cut.closed ? kReadUnitClosed : 0) | (plan[q].k0 + j ? kReadUnitBehindReset : 0));
@@ -2582,13 +2631,16 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
             }
             HIP_OK(hipMemcpyAsync(s.region, h, rows_bytes, hipMemcpyHostToDevice, st));
             if (staged) HIP_OK(hipMemcpyAsync(s.region + read_stage_at(U), h_stage, staged, hipMemcpyHostToDevice, st));
+            // (the table form: what the walk holds each unit to, into the row the units kernel of a device-memory call fills;
+            // pageable memory: the copy has left `unit_size` when the call returns)
+            if (g) HIP_OK(hipMemcpyAsync(read_units_at(s.region, U).size, unit_size.data(), U * 4, hipMemcpyHostToDevice, st));
         }
         const uint64_t nq = span.q1 - span.q0;
         HIP_OK(hipMemcpyAsync(r.failed + span.q0, failed.data() + span.q0, nq, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_out_off + span.q0, packed_off.data() + span.q0, nq * 8, hipMemcpyHostToDevice, st));
         HIP_OK(P.out[0].need(packed + 1));
         uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
-        if (const int rc = launch_read_tail(ctx, rec, d, r, s, max_wbits, d_out, d_out_off, d_out_len, d_status, st)) {
+        if (const int rc = launch_read_tail(ctx, rec, d, r, s, max_wbits, d_out, d_out_off, d_out_len, d_status, st, g)) {
             (void)hipStreamSynchronize(st);
             return rc;
         }
@@ -2611,12 +2663,29 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
 }
 
 int batch_read_ranges(const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int8_t* status,
-                      int mem, int device, void* stream) {
+                      int mem, int device, void* stream, const uint64_t* segment_end = nullptr) {
     DeviceCtx* ctx = nullptr;
     if (const int rc = get_ctx(device, &ctx)) return rc;
-    if (mem == TAMP_AMD_MEM_DEVICE) return launch_read_ranges(ctx, c, max_wbits, out, out_off, out_len, status, static_cast<hipStream_t>(stream));
+    if (mem == TAMP_AMD_MEM_DEVICE)
+        return launch_read_ranges(ctx, c, max_wbits, out, out_off, out_len, status, static_cast<hipStream_t>(stream), segment_end);
     if (!c.off && c.n && c.first[c.n] != 0) return TAMP_AMD_BAD_ARGUMENT;  // (entries and no table to hold them)
-    return read_ranges_host(ctx, c, max_wbits, out, out_off, out_len, status);
+    return read_ranges_host(ctx, c, max_wbits, out, out_off, out_len, status, segment_end);
+}
+
+// The table of segment ends (tamp_batch_segment_ends; kernels: tamp_segment_ends_kernel.hpp).  Device memory: two launches on the
+// call's stream, nothing read back, the stream never waited for -- the row count is read on the device, the grid comes from the CU
+// count.  Host memory: the same running sum, with the same functions, on the host; no device is looked for.
+int launch_segment_ends(DeviceCtx* ctx, const uint64_t* first, const uint32_t* closed_size, const uint32_t* open_size, uint64_t* segment_end,
+                        uint64_t n, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    HIP_OK(rec.ends.need(kSegmentEndsMaxGrid * sizeof(SegmentEndSum), false));
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->cu_count * 4, kSegmentEndsMaxGrid));
+    const SegmentEndsArgs a = {first, closed_size, open_size, n, static_cast<SegmentEndSum*>(rec.ends.p), segment_end};
+    if (grid > 1) hipLaunchKernelGGL(tamp_segment_ends_sums_kernel, dim3(grid), dim3(kResetScanTile), 0, st, a);
+    hipLaunchKernelGGL(tamp_segment_ends_apply_kernel, dim3(grid), dim3(kResetScanTile), 0, st, a);
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
 }
 
 // Writing byte ranges into reset-segmented streams (tamp_batch_write_ranges; kernels and steps: tamp_write_ranges_kernel.hpp, the
@@ -3687,6 +3756,41 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t* in, const uin
     const ReadCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
                           range_stream, range_begin, range_len, n_ranges};
     return batch_read_ranges(c, max_window_bits, out, out_off, out_len, status, mem, device, stream);
+}
+
+int tamp_batch_read_ranges_grid(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                const uint64_t* reset_first, const uint32_t* reset_off, const uint64_t* segment_end,
+                                const uint32_t* range_stream, const uint64_t* range_begin, const uint32_t* range_len, uint8_t* out,
+                                const uint64_t* out_off, uint32_t* out_len, int8_t* status, size_t n_streams, size_t n_ranges, int mem,
+                                int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!in_off || !in_len || !reset_first || !range_stream || !range_begin || !range_len || !out_off || !out_len || !status)
+        return TAMP_AMD_BAD_ARGUMENT;
+    if ((!in && n_streams) || (!out && n_ranges) || !segment_end) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || n_ranges > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_ranges == 0) return TAMP_OK;  // (nothing is touched)
+    const ReadCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, 0, (uint32_t)(max_window_bits & 0x7F),
+                          range_stream, range_begin, range_len, n_ranges};
+    return batch_read_ranges(c, max_window_bits, out, out_off, out_len, status, mem, device, stream, segment_end);
+}
+
+int tamp_batch_segment_ends(const uint64_t* reset_first, const uint32_t* closed_size, const uint32_t* open_size, uint64_t* segment_end,
+                            size_t n_streams, int mem, int device, void* stream) {
+    // (refused before a device is looked for; closed_size may be null only where there is no entry to read through it, which a
+    // host-memory call can tell)
+    if (!reset_first || !segment_end || (!open_size && n_streams)) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull) return TAMP_AMD_BAD_ARGUMENT;
+    if (!closed_size && (mem == TAMP_AMD_MEM_DEVICE ? n_streams != 0 : reset_first[n_streams] != 0)) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams == 0) return TAMP_OK;  // (no rows)
+    if (mem == TAMP_AMD_MEM_HOST) {
+        segment_ends_fill(reset_first, closed_size, open_size, segment_end, n_streams);
+        return TAMP_OK;
+    }
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    return launch_segment_ends(ctx, reset_first, closed_size, open_size, segment_end, n_streams, static_cast<hipStream_t>(stream));
 }
 
 int tamp_batch_write_ranges(const TampAmdConf* conf, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,

@@ -15,6 +15,11 @@
 //   (the decode: launch_decompress_locked over the unit rows)
 //   tamp_read_gather_kernel  a workgroup per range: its status and length, its bytes from the scratch to the caller's buffer
 // A host-memory call makes the first three steps on the host, with the same functions, and uploads the units' rows and the stage.
+//
+// THE GRID is a policy of the count, units, walk and gather steps: every closed segment N bytes (tamp_batch_read_ranges: the
+// ...Args structs, whose instantiations are the code the kernels were before there was a choice), or the table of segment ends
+// (tamp_batch_read_ranges_grid: the ...GridArgs structs, which carry a ReadTable behind the same members).  With the table a unit's
+// size is its table size, which the walk holds the closed AND the open segment to, and the gather's skip comes from the plan.
 #pragma once
 #include "tamp_common.hpp"
 #include "tamp_reset_segments.hpp"
@@ -53,6 +58,13 @@ struct ReadRanges {
     uint8_t* failed;
 };
 struct ReadRecord { uint64_t units, cost; };  // what a device-memory call reads back: all units, all bytes of scratch they ask for
+// The table form's own: the caller's table (null where a step does not read it) and, in the stream's scratch behind the per-range
+// tables, where each range's bytes start in its scratch (<- the count).  A unit's table size lies in its `size` row (<- the units
+// step), where the walk finds it and leaves what it counted.
+struct ReadTable {
+    const uint64_t* segment_end;
+    uint64_t* skip;
+};
 
 // The units' rows of a slice [q0, q1) of the ranges: U = unit_first[q1] - unit_first[q0] rows.  Offsets count from the slice's
 // region, which holds the rows, the stage and the scratch, in this order.
@@ -92,17 +104,34 @@ __host__ __device__ constexpr uint64_t read_scratch_at(uint64_t U, uint64_t stag
 __host__ __device__ constexpr uint64_t read_region_bytes(uint64_t U, uint64_t staged, uint64_t scratch) { return read_scratch_at(U, staged) + scratch + 64; }
 
 struct ReadCountArgs {
+    static constexpr bool kTable = false;
     ReadCaller c;
     uint64_t budget;
     ReadRanges r;
     ReadRecord* rec;
 };
-__global__ void __launch_bounds__(kResetScanTile) tamp_read_count_kernel(ReadCountArgs a) {
+struct ReadCountGridArgs {
+    static constexpr bool kTable = true;
+    ReadCaller c;
+    uint64_t budget;
+    ReadRanges r;
+    ReadRecord* rec;
+    ReadTable g;
+};
+template <class A>
+__global__ void __launch_bounds__(kResetScanTile) tamp_read_count_kernel(A a) {
     __shared__ uint64_t wave_sum[kResetScanTile / kWave];
     // what every range comes to, into the tables (each lane reads back only what it wrote itself) ...
     for (uint64_t q = threadIdx.x; q < a.c.n_ranges; q += kResetScanTile) {
-        const ReadPlan p = read_range_plan(a.c.in, a.c.in_off, a.c.in_len, a.c.first, a.c.off, a.c.n, a.c.interval, a.c.max_wbits, a.budget,
-                                           a.c.range_stream[q], a.c.range_begin[q], a.c.range_len[q]);
+        ReadPlan p;
+        if constexpr (A::kTable) {  // (the table form leaves the range's skip for the gather)
+            const ReadGridPlan g = read_grid_plan(a.c.in, a.c.in_off, a.c.in_len, a.c.first, a.c.off, a.g.segment_end, a.c.n, a.c.max_wbits,
+                                                  a.budget, a.c.range_stream[q], a.c.range_begin[q], a.c.range_len[q]);
+            p = g.p, a.g.skip[q] = g.skip;
+        } else {
+            p = read_range_plan(a.c.in, a.c.in_off, a.c.in_len, a.c.first, a.c.off, a.c.n, a.c.interval, a.c.max_wbits, a.budget,
+                                a.c.range_stream[q], a.c.range_begin[q], a.c.range_len[q]);
+        }
         a.r.unit_first[q] = p.units, a.r.scratch_first[q] = p.scratch, a.r.stage_first[q] = p.staged;
         a.r.verdict[q] = (int8_t)p.verdict, a.r.failed[q] = 0;
     }
@@ -134,12 +163,22 @@ struct ReadSlice {
 };
 
 struct ReadUnitsArgs {
+    static constexpr bool kTable = false;
     ReadCaller c;
     uint64_t budget;
     ReadRanges r;
     ReadSlice s;
 };
-__global__ void __launch_bounds__(256) tamp_read_units_kernel(ReadUnitsArgs a) {
+struct ReadUnitsGridArgs {
+    static constexpr bool kTable = true;
+    ReadCaller c;
+    uint64_t budget;
+    ReadRanges r;
+    ReadSlice s;
+    ReadTable g;
+};
+template <class A>
+__global__ void __launch_bounds__(256) tamp_read_units_kernel(A a) {
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= a.s.U) return;
     const ReadUnits u = read_units_at(a.s.region, a.s.U);
@@ -153,12 +192,29 @@ __global__ void __launch_bounds__(256) tamp_read_units_kernel(ReadUnitsArgs a) {
     const uint64_t q = lo, j = g - a.r.unit_first[q];
     const uint32_t i = a.c.range_stream[q];
     // (the plan again: the range has units, so the stream and its rows of the index held up)
-    const ReadPlan p = read_range_plan(a.c.in, a.c.in_off, a.c.in_len, a.c.first, a.c.off, a.c.n, a.c.interval, a.c.max_wbits, a.budget, i,
-                                       a.c.range_begin[q], a.c.range_len[q]);
+    ReadPlan p;
+    [[maybe_unused]] ReadGridPlan gp;
+    if constexpr (A::kTable) {
+        gp = read_grid_plan(a.c.in, a.c.in_off, a.c.in_len, a.c.first, a.c.off, a.g.segment_end, a.c.n, a.c.max_wbits, a.budget, i,
+                            a.c.range_begin[q], a.c.range_len[q]);
+        p = gp.p;
+    } else {
+        p = read_range_plan(a.c.in, a.c.in_off, a.c.in_len, a.c.first, a.c.off, a.c.n, a.c.interval, a.c.max_wbits, a.budget, i,
+                            a.c.range_begin[q], a.c.range_len[q]);
+    }
     const uint64_t staged = a.r.stage_first[a.s.q1] - a.r.stage_first[a.s.q0];
     ReadUnit w = {{0, 0, false, false}, 0, 0, 0, 0};  // (stays so only if the tables changed behind the count kernel: nothing is read through them then)
     const bool counted = p.verdict == kReadGo && j < p.units;
-    if (counted) w = read_range_unit(a.c.first, a.c.off, a.c.in_len, a.c.interval, i, p, j);
+    if constexpr (A::kTable) {
+        uint32_t size = 0;
+        if (counted) {
+            const ReadGridUnit gw = read_grid_unit(a.c.first, a.c.off, a.c.in_len, a.g.segment_end, i, gp, j);
+            w = gw.u, size = gw.size;
+        }
+        u.size[x] = size;  // (what the walk holds the unit to)
+    } else {
+        if (counted) w = read_range_unit(a.c.first, a.c.off, a.c.in_len, a.c.interval, i, p, j);
+    }
     u.in_off[x] = read_stage_at(a.s.U) + (a.r.stage_first[q] - a.r.stage_first[a.s.q0]) + w.place;
     u.out_off[x] = read_scratch_at(a.s.U, staged) + (a.r.scratch_first[q] - a.r.scratch_first[a.s.q0]) + w.room;
     u.in_len[x] = w.in_len, u.need[x] = w.need, u.owner[x] = (uint32_t)(q - a.s.q0);
@@ -186,18 +242,28 @@ __global__ void __launch_bounds__(256) tamp_read_stage_kernel(ReadStageArgs a) {
 }
 
 struct ReadWalkArgs {
+    static constexpr bool kTable = false;
     ReadSlice s;
     const uint8_t* failed;  // per range of the call
     uint32_t interval;
 };
-__global__ void __launch_bounds__(64) tamp_read_walk_kernel(ReadWalkArgs a) {
+struct ReadWalkGridArgs {
+    static constexpr bool kTable = true;
+    ReadSlice s;
+    const uint8_t* failed;
+};
+template <class A>
+__global__ void __launch_bounds__(64) tamp_read_walk_kernel(A a) {
     __shared__ uint8_t lut[128];
     build_prefix_lut(lut);
     __syncthreads();
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= a.s.U) return;
     const ReadUnits u = read_units_at(a.s.region, a.s.U);
-    const uint32_t n = u.in_len[x], N = a.interval;
+    uint32_t grid_n;  // fixed grid: the interval; the table: the unit's table size
+    if constexpr (A::kTable) grid_n = u.size[x];
+    else grid_n = a.interval;
+    const uint32_t n = u.in_len[x], N = grid_n;
     uint64_t bytes = 0;
     uint8_t verdict = u.verdict[x];
     if (n && verdict == kReadWalkOk) {
@@ -218,8 +284,8 @@ __global__ void __launch_bounds__(64) tamp_read_walk_kernel(ReadWalkArgs a) {
             if (!last) bytes += (rec >> 2) & 0xFFu;
         }
         // a closed segment ends exactly at its boundary behind FLUSH, FLUSH and holds exactly N bytes, which is what makes k * N an
-        // address; the open one ends as a stream ends, out of tokens, with N bytes at most
-        const bool ok = closed ? (t == end && last && before && bytes == N) : bytes <= N;
+        // address; the open one ends as a stream ends, out of tokens, with N bytes at most -- or, with the table, its table size too
+        const bool ok = closed ? (t == end && last && before && bytes == N) : (A::kTable ? bytes == N : bytes <= N);
         verdict = bad ? kReadWalkOob : (ok ? kReadWalkOk : kReadWalkBad);
     }
     const bool decode = n && verdict == kReadWalkOk && !a.failed[a.s.q0 + u.owner[x]];
@@ -230,6 +296,7 @@ __global__ void __launch_bounds__(64) tamp_read_walk_kernel(ReadWalkArgs a) {
 }
 
 struct ReadGatherArgs {
+    static constexpr bool kTable = false;
     ReadCaller c;
     ReadRanges r;
     ReadSlice s;
@@ -238,7 +305,19 @@ struct ReadGatherArgs {
     uint32_t* out_len;
     int8_t* status;
 };
-__global__ void __launch_bounds__(256) tamp_read_gather_kernel(ReadGatherArgs a) {
+struct ReadGatherGridArgs {
+    static constexpr bool kTable = true;
+    ReadCaller c;
+    ReadRanges r;
+    ReadSlice s;
+    uint8_t* out;
+    const uint64_t* out_off;
+    uint32_t* out_len;
+    int8_t* status;
+    ReadTable g;
+};
+template <class A>
+__global__ void __launch_bounds__(256) tamp_read_gather_kernel(A a) {
     __shared__ unsigned long long total_s;
     __shared__ uint32_t seen_s;
     const ReadUnits u = read_units_at(a.s.region, a.s.U);
@@ -272,7 +351,9 @@ __global__ void __launch_bounds__(256) tamp_read_gather_kernel(ReadGatherArgs a)
         else if (seen & 2u) status = (int8_t)kReadBadIndex;
         else if (seen & 4u) status = (int8_t)kError;
         else {
-            const uint64_t skip = read_range_skip(a.c.range_begin[q], a.c.range_begin[q] / a.c.interval, a.c.interval);
+            uint64_t skip;
+            if constexpr (A::kTable) skip = a.g.skip[q];
+            else skip = read_range_skip(a.c.range_begin[q], a.c.range_begin[q] / a.c.interval, a.c.interval);
             delivered = read_range_delivered(total, skip, len);
             status = delivered == len ? (int8_t)kOk : (int8_t)kInputExhausted;
             // the range's units decoded back to back from its first scratch byte: one contiguous copy

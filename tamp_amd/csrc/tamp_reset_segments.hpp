@@ -2,9 +2,11 @@
 // is cut into segments, what a segment's slab holds, what the whole stream can take -- and, for a batch of such buffers
 // (tamp_batch_compress_resets), which stream and cut a row of its two segment tables stands for, and the same for the rows a reset
 // index claims on the way back (tamp_batch_decompress_resets), and what a byte range of such a stream touches
-// (tamp_batch_read_ranges).  Arithmetic only, for the host and the device: no HIP type, so that tests/test_reset_segments_host.py,
-// tests/test_batch_resets_host.py, tests/test_batch_reset_index_host.py and tests/test_read_ranges_host.py compile it into
-// stand-alone host programs.  The kernels that use it: tamp_reset_segments_kernel.hpp, tamp_read_ranges_kernel.hpp.
+// (tamp_batch_read_ranges; with segments of any size: tamp_batch_segment_ends, tamp_batch_read_ranges_grid).  Arithmetic only, for the
+// host and the device: no HIP type, so that tests/test_reset_segments_host.py, tests/test_batch_resets_host.py,
+// tests/test_batch_reset_index_host.py, tests/test_read_ranges_host.py and tests/test_read_ranges_grid_host.py compile it into
+// stand-alone host programs.  The kernels that use it: tamp_reset_segments_kernel.hpp, tamp_read_ranges_kernel.hpp,
+// tamp_segment_ends_kernel.hpp.
 #pragma once
 #include <stdint.h>
 
@@ -254,6 +256,145 @@ TAMP_HD inline ReadUnit read_range_unit(const uint64_t* first, const uint32_t* o
 TAMP_HD constexpr uint64_t read_range_skip(uint64_t begin, uint64_t k0, uint32_t N) { return begin - k0 * N; }
 TAMP_HD constexpr uint32_t read_range_delivered(uint64_t total, uint64_t skip, uint32_t len) {
     return total > skip ? (total - skip < len ? (uint32_t)(total - skip) : len) : 0;
+}
+
+// ---- the same for segments of ANY size: the table of segment ends (tamp_batch_segment_ends, tamp_batch_read_ranges_grid) ----
+// One uint64 entry per SEGMENT of the batch: stream i with E entries in the index has E + 1, at segment_end[first[i] + i + k] for
+// k = 0 .. E, entry k the decoded size of its segments 0 .. k (non-decreasing; the last one the stream's decoded size).  Segment k
+// covers decoded bytes [B(k), B(k + 1)) with B(0) = 0 and B(k) = entry k - 1; segments of no bytes are legal.  The segment of a byte
+// is found by a search where the fixed form divides; everything behind that is the fixed form's.  The table is TRUSTED for position
+// and checked on what a range touches; the search reads inside the stream's rows whatever they hold (its bounds come from first).
+constexpr uint64_t kSegmentEndSaturated = ~0ull;  // an entry behind a segment of "2^32 - 1 or more" bytes
+constexpr uint32_t kSegmentSizeSaturated = 0xFFFFFFFFu;
+
+// Where stream i's rows of the table start (the stream's rows of `first` hold up: read_index_usable).
+TAMP_HD inline uint64_t segment_end_row(const uint64_t* first, uint64_t i) { return first[i] + i; }
+// Owner of table row p < first[n] + n: the last stream whose first row is not behind p (batch_reset_owner with the key first[i] + i,
+// which grows with every stream: no stream is stepped over).
+TAMP_HD inline uint64_t segment_end_owner(const uint64_t* first, uint64_t n, uint64_t p) {
+    uint64_t lo = 0, hi = n;  // row(lo) <= p < row(hi)
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (segment_end_row(first, mid) <= p) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// The running sum the table is made of (tamp_batch_segment_ends), as the operator of a SEGMENTED scan: `head` says that a stream's
+// first row lies in the span the value stands for, and then the value counts from that row.  A saturated size makes its entry and
+// every later one of its stream kSegmentEndSaturated (true sums stay far below: fewer than 2^32 entries of less than 2^32 each).
+struct SegmentEndSum {
+    uint64_t v;
+    uint32_t head;
+};
+TAMP_HD constexpr SegmentEndSum segment_end_identity() { return {0, 0}; }
+TAMP_HD constexpr uint64_t segment_end_add(uint64_t a, uint64_t b) {
+    return a == kSegmentEndSaturated || b == kSegmentEndSaturated ? kSegmentEndSaturated : a + b;
+}
+TAMP_HD constexpr SegmentEndSum segment_end_combine(const SegmentEndSum& a, const SegmentEndSum& b) {  // (a in front of b)
+    return b.head ? b : SegmentEndSum{segment_end_add(a.v, b.v), a.head};
+}
+// What row p of the table adds: the size of its segment, and whether it is its stream's first.  Reads inside the three tables
+// whatever `first` holds (rows that make no sense add nothing).
+TAMP_HD inline SegmentEndSum segment_end_term(const uint64_t* first, const uint32_t* closed_size, const uint32_t* open_size, uint64_t n,
+                                              uint64_t p) {
+    const uint64_t i = segment_end_owner(first, n, p), row = segment_end_row(first, i);
+    if (p < row) return segment_end_identity();  // (first[0] != 0)
+    const uint64_t k = p - row, E = reset_index_entries(first, n, i);
+    uint32_t size = 0;
+    if (k < E) size = closed_size[first[i] + k];
+    else if (k == E) size = open_size[i];
+    return {size == kSegmentSizeSaturated ? kSegmentEndSaturated : size, k == 0 ? 1u : 0u};
+}
+// The whole table, row by row: what a host-memory call does, and what the kernels' scan comes to.
+inline void segment_ends_fill(const uint64_t* first, const uint32_t* closed_size, const uint32_t* open_size, uint64_t* segment_end,
+                              uint64_t n) {
+    const uint64_t rows = n ? first[n] + n : 0;
+    SegmentEndSum sum = segment_end_identity();
+    for (uint64_t p = 0; p < rows; p++) {
+        sum = segment_end_combine(sum, segment_end_term(first, closed_size, open_size, n, p));
+        segment_end[p] = sum.v;
+    }
+}
+
+// A range of the table form before anything is decoded: ReadPlan with the table's own figures.  `base` = B(k0), `skip` = begin -
+// base: where the range's bytes start in its scratch.  The last unit is asked for end - B(k1) bytes, every other one for its whole
+// size, and the scratch is end - B(k0): true sizes, the open segment's too.
+struct ReadGridPlan {
+    ReadPlan p;
+    uint64_t base, skip;
+};
+// Entries k < E of a stream's rows T that are <= b (an upper bound; any contents: the result is in 0 .. E).
+TAMP_HD inline uint64_t segment_end_search(const uint64_t* T, uint64_t E, uint64_t b) {
+    uint64_t lo = 0, hi = E;  // rows in front of lo are <= b, rows from hi on are not (of a sorted table)
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (T[mid] <= b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+TAMP_HD inline ReadGridPlan read_grid_plan(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint64_t* first,
+                                           const uint32_t* off, const uint64_t* segment_end, uint64_t n, uint32_t max_wbits,
+                                           uint64_t budget, uint32_t stream, uint64_t begin, uint32_t len) {
+    ReadGridPlan g = {{kReadBadArgument, 0, 0, 0, 0, 0, 0}, 0, 0};
+    ReadPlan& p = g.p;
+    if (stream >= n) return g;
+    p.verdict = kReadOk;
+    if (len == 0) return g;  // (the stream is not looked at)
+    const uint64_t i = stream;
+    p.verdict = kReadInvalidConf;
+    if (!read_header_eligible(in + in_off[i], in_len[i], max_wbits)) return g;
+    p.verdict = kReadBadIndex;
+    if (!read_index_usable(first, n, i) || (!off && first[i + 1] != first[i])) return g;  // (entries and no table to hold them)
+    const uint64_t E = first[i + 1] - first[i];
+    const uint64_t* const T = segment_end + segment_end_row(first, i);
+    const uint64_t total = T[E];
+    p.verdict = kReadInputExhausted;
+    if (begin >= total) return g;  // (at or behind the stream's end: answered from the table alone)
+    const uint64_t sum = read_sat_add(begin, len), end = sum < total ? sum : total;
+    const uint64_t k0 = segment_end_search(T, E, begin), k1 = segment_end_search(T, E, end - 1);
+    p.k0 = k0;
+    // what the search promises of a sorted table, looked at: both ends lie in the segment found for them.  (The units kernel
+    // checks every entry between them against the one in front of it, which makes B(k0) <= ... <= T[k1] a chain.)
+    const uint64_t b0 = k0 ? T[k0 - 1] : 0, b1 = k1 ? T[k1 - 1] : 0;
+    p.verdict = kReadBadIndex;
+    if (!(b0 <= begin && begin < T[k0]) || k1 < k0 || !(b1 <= end - 1 && end - 1 < T[k1])) return g;
+    if (T[k0] - b0 >= kSegmentSizeSaturated || T[k1] - b1 >= kSegmentSizeSaturated) return g;  // (a segment of 2^32 - 1 bytes or more)
+    const uint64_t units = k1 - k0 + 1;
+    const ReadCut a = read_segment_cut(first, off, in_len, i, k0), b = read_segment_cut(first, off, in_len, i, k1);
+    if (!a.ok || !b.ok || b.end < a.start) return g;
+    const uint32_t last_need = (uint32_t)(end - b1);
+    const uint64_t scratch = end - b0, staged = (uint64_t)(b.end - a.start) + kResetHeaderBytes * units;
+    p.verdict = kReadBadArgument;  // the range alone outgrows what the call may take
+    if (units > budget / kReadUnitRow || read_sat_add(read_sat_add(scratch, staged), units * kReadUnitRow) > budget) return g;
+    p.verdict = kReadGo, p.units = units, p.scratch = scratch, p.staged = staged, p.last_need = last_need, p.span_start = a.start;
+    g.base = b0, g.skip = begin - b0;
+    return g;
+}
+// Unit j < units of such a range: segment k0 + j, read_range_unit with the table's sizes.  `size`: what the table says the segment
+// decodes to, which the walk holds it to; a touched entry below the one in front of it, or a size of 2^32 - 1 or more, is no unit.
+struct ReadGridUnit {
+    ReadUnit u;
+    uint32_t size;
+};
+TAMP_HD inline ReadGridUnit read_grid_unit(const uint64_t* first, const uint32_t* off, const uint32_t* in_len, const uint64_t* segment_end,
+                                           uint64_t i, const ReadGridPlan& g, uint64_t j) {
+    const ReadPlan& p = g.p;
+    const uint64_t* const T = segment_end + segment_end_row(first, i);
+    const uint64_t k = p.k0 + j, b = k ? T[k - 1] : 0, e = T[k];
+    ReadGridUnit w;
+    ReadUnit& u = w.u;
+    u.cut = read_segment_cut(first, off, in_len, i, k);
+    const uint64_t span = p.staged - kResetHeaderBytes * p.units;  // span_start .. span_start + span
+    if (u.cut.ok && (u.cut.start < p.span_start || (uint64_t)u.cut.end - p.span_start > span)) u.cut.ok = false;
+    if (e < b || e - b >= kSegmentSizeSaturated || b < g.base) u.cut.ok = false;
+    w.size = u.cut.ok ? (uint32_t)(e - b) : 0;
+    u.need = !u.cut.ok ? 0 : (j + 1 == p.units ? p.last_need : w.size);
+    u.in_len = u.cut.ok ? u.cut.end - u.cut.start + kResetHeaderBytes : 0;
+    u.place = u.cut.ok ? (uint64_t)(u.cut.start - p.span_start) + kResetHeaderBytes * j : 0;
+    u.room = u.cut.ok ? b - g.base : 0;
+    return w;
 }
 
 }  // namespace tamp_amd
