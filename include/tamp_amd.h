@@ -622,6 +622,89 @@ int tamp_batch_read_ranges_grid(uint8_t max_window_bits, const uint8_t *in, cons
                                 size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
 
 /*
+ * A SEEK INDEX: byte ranges of streams that have NO dictionary resets -- the output of tamp_batch_compress without a reset
+ * interval, of a connection of compressor objects, of a reference Compressor.  The stream is decoded once and a CHECKPOINT of the
+ * decoder is kept every `interval` decoded bytes; a later read starts at the nearest one (what zran does for deflate).
+ * A checkpoint is a decoder object as tamp_batch_decompress_resume carries it between calls: checkpoint k (k >= 1) is the
+ * reference's object, initialised without a configuration, after k calls of tamp_decompressor_decompress that were each offered
+ * all input not yet consumed and exactly `interval` bytes of room (each returns TAMP_OUTPUT_FULL with `interval` bytes), and next
+ * to it in_pos, the sum of their consumed counts.  Its decoded position is exactly k * interval -- inside an RLE run (token_state
+ * 1), an extended match (3) or a plain match (token_state 0, skip_bytes > 0) if that is where the room ran out.  A stream that
+ * decodes to S bytes (what tamp_batch_decompress delivers: the bytes in front of the first error) has C = 0 checkpoints for
+ * S == 0 and (S - 1) / interval otherwise: one for every k >= 1 with k * interval < S.  The state in front of the first byte is not
+ * stored.
+ *   dictionary, dictionary_len, max_window_bits, in, in_off, in_len   as for tamp_batch_decompress (one custom dictionary for the
+ *                   call; TAMP_AMD_WINDOW_BITS_EXACT is not taken)
+ *   interval        decoded bytes between checkpoints, > 0
+ *   ckpt_first      n_streams + 1 entries, only read: the running sum of how many rows each stream has ROOM for (from a size
+ *                   query: tamp_batch_decoded_size); row r of stream i is row ckpt_first[i] + r of the two tables below
+ *   ckpt_in         uint32 per row: in_pos
+ *   ckpt_state      rows of state_stride bytes, 16-byte aligned: TampAmdDecoderState (window_bits_max = max_window_bits), then
+ *                   the window; state_stride >= tamp_amd_decoder_state_size(max_window_bits), a multiple of 16.  A stream with a
+ *                   smaller window uses the first 1 << w window bytes of its rows
+ *   decoded_size[i], status[i]   S as 64 bits, and what tamp_batch_decompress reports for the stream with unlimited room
+ *                   (TAMP_INPUT_EXHAUSTED for one that ends normally); TAMP_AMD_BAD_ARGUMENT for a stream of 2^29 - 512 compressed
+ *                   bytes or more
+ * Stream i writes its first min(C, room) rows and never a row outside its own; when decoded_size[i] says that more exist than it
+ * had room for, call again with more.  (A stream with the dictionary-reset bit whose decoded size is an exact multiple of the
+ * interval and that ends in a reset may write the row behind its last one where it has room for it.)
+ * A device-memory call is one asynchronous launch on `stream`: nothing is allocated, nothing read back.  A host-memory call is
+ * synchronous and copies back the two result tables and exactly the rows written.
+ * Returns TAMP_OK; TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null in_off, in_len, ckpt_first, decoded_size or
+ * status, a null `in` with n_streams > 0, interval == 0, max_window_bits outside 8..15, a state_stride or ckpt_state that is not as
+ * above, a bad memory kind, TAMP_AMD_ALL_DEVICES, n_streams >= 2^32, (host memory) a ckpt_first that is no running sum or null row
+ * tables where it has room; TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_seek_index(const uint8_t *dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t *in,
+                          const uint64_t *in_off, const uint32_t *in_len, uint32_t interval, const uint64_t *ckpt_first,
+                          uint32_t *ckpt_in, void *ckpt_state, size_t state_stride, uint64_t *decoded_size, int8_t *status,
+                          size_t n_streams, int mem, int device, void *stream);
+
+/*
+ * Reading byte ranges through such an index.  The range tables, the output and the result tables are tamp_batch_read_ranges's;
+ * the index tables are tamp_batch_seek_index's, with the stream's ROWS in ckpt_first (R rows of stream i: checkpoints 1 .. R) and
+ * ckpt_first[n_streams] rows in each table.  A range is cut at the checkpoints it crosses and every piece is a UNIT of its own,
+ * one wavefront: unit (q, k), k = min(begin / interval, R) .. min((begin + len - 1) / interval, R), loads row k (k == 0: a fresh
+ * object and the stream's header), picks up the token the checkpoint lies in, drops the bytes in front of max(begin, k * interval),
+ * and decodes the bytes up to min(end, (k + 1) * interval) -- the last unit: up to end -- straight to their place in
+ * out + out_off[q].  With fewer rows than checkpoints (R < C) the last row serves everything behind it.
+ *   out_len[q], status[q]   per range, the first rule that applies:
+ *       range_stream[q] >= n_streams, or a stream of 2^29 - 512 compressed bytes or more ... TAMP_AMD_BAD_ARGUMENT, 0
+ *       range_len[q] == 0 ............................................................. TAMP_OK, 0 (the stream is not looked at)
+ *       in_len == 0, or less than the header .......................................... TAMP_INPUT_EXHAUSTED, 0
+ *       a non-zero second header byte, a window above max_window_bits, the custom bit
+ *       without a dictionary of 1 << w bytes ........................................... TAMP_INVALID_CONF, 0
+ *       the stream's rows of ckpt_first are no running sum inside ckpt_first[n_streams] . TAMP_AMD_BAD_INDEX, 0
+ *       a row a unit starts at does not hold up: its conf byte is not the stream's header
+ *       byte, the configured flag is missing, token_state is not 0, 1 or 3, window_pos or
+ *       a pending token lies outside the window, in_pos lies inside the header, beyond
+ *       in_len[i] or below the row's in front of it ..................................... TAMP_AMD_BAD_INDEX, 0
+ *       an offset out of the window on the way ........................................ TAMP_OOB and the bytes in front of it
+ *       otherwise: TAMP_OK and range_len[q] when all bytes were delivered, TAMP_INPUT_EXHAUSTED and the bytes delivered when
+ *       the stream ended first
+ *   Exactly out_len[q] bytes are written at out + out_off[q] and nothing else of `out`; a range with a bad row writes nothing, and
+ *   none affects another.  The index is only read: any number of units may start at the same row.
+ * The index is TRUSTED FOR POSITION, as tamp_batch_read_ranges trusts its own: a forged row that passes the checks delivers other
+ * bytes.  Memory safety holds for any contents of every table (ckpt_in and ckpt_state must have ckpt_first[n_streams] rows).
+ *   mem, device, stream   TAMP_AMD_ALL_DEVICES is not taken.  A device-memory call WAITS once, early, for one 8-byte record (how
+ *                   many units the ranges come to); everything behind that is asynchronous on `stream`.  A host-memory call is
+ *                   synchronous: it plans on the host and copies ONLY the touched rows (each once) and the touched units'
+ *                   compressed spans [ckpt_in[k], ckpt_in[k + 1]) -- the last one to in_len -- to the device, never the whole
+ *                   streams, and writes exactly the delivered bytes and the two result tables.
+ * The per-range tables and the unit table (40 bytes a unit) live in scratch kept per HIP stream (tamp_amd_trim releases it).
+ * Returns TAMP_OK (n_ranges == 0: at once); TAMP_AMD_BAD_ARGUMENT, before a device is looked for, for a null in_off, in_len,
+ * ckpt_first, range_stream, range_begin, range_len, out_off, out_len or status, a null `in` with n_streams > 0, a null `out` with
+ * n_ranges > 0, interval == 0, max_window_bits outside 8..15, a state_stride or ckpt_state that is not as above, a bad memory kind,
+ * TAMP_AMD_ALL_DEVICES, n_streams or n_ranges >= 2^32; TAMP_AMD_NO_DEVICE.
+ */
+int tamp_batch_read_ranges_seek(const uint8_t *dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t *in,
+                                const uint64_t *in_off, const uint32_t *in_len, uint32_t interval, const uint64_t *ckpt_first,
+                                const uint32_t *ckpt_in, const void *ckpt_state, size_t state_stride,
+                                const uint32_t *range_stream, const uint64_t *range_begin, const uint32_t *range_len,
+                                uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int8_t *status,
+                                size_t n_streams, size_t n_ranges, int mem, int device, void *stream);
+
+/*
  * WRITING byte ranges into such streams: the other half of random access.  Write q replaces the decoded bytes
  * [write_begin[q], write_begin[q] + write_len[q]) of stream write_stream[q] with src[src_off[q] .. + write_len[q]).  Only the segments
  * a write touches are decoded (by tamp_batch_read_ranges' own steps), patched and compressed again; every other segment keeps its

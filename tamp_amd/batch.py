@@ -897,6 +897,272 @@ def read_ranges(data, in_off=None, in_len=None, *, reset_index, stream_index, be
     return RangeResult(out, out_off, out_len, status, ms)
 
 
+def _aligned_rows(rows: int, stride: int) -> np.ndarray:
+    """uint8 [rows, stride] on a 16-byte boundary (the row stores are 16 bytes wide)."""
+    raw = np.zeros(rows * stride + 16, dtype=np.uint8)
+    at = (-raw.ctypes.data) & 15
+    return raw[at : at + rows * stride].reshape(rows, stride)
+
+
+@dataclass
+class SeekIndex:
+    """Checkpoints of a batch's streams every ``interval`` decoded bytes (``build_seek_index`` makes one, ``read_ranges_seek`` reads
+    through it; ``tamp_batch_seek_index`` of the C ABI says what a checkpoint is).  Stream ``i``'s rows are
+    ``first[i]:first[i + 1]`` of ``in_pos`` (input bytes consumed) and ``state`` (16 bytes of decoder state, then the window; rows
+    sized for ``window_bits``); row ``r`` of a stream is its decoder after ``(r + 1) * interval`` decoded bytes.  ``size`` and
+    ``status`` per stream: what it decodes to, and what decoding it reports.  numpy arrays (uint64, uint32, uint8, uint64, int8) or
+    CUDA tensors (int64, int32, uint8, int64, int8), like the other tables."""
+    first: object
+    in_pos: object
+    state: object
+    interval: int
+    window_bits: int
+    size: object
+    status: object
+    _keep: object = None  # device tensors the asynchronous launch still reads
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes the index occupies."""
+        return sum(int(t.numel()) * t.element_size() if _is_torch(t) else int(t.nbytes)
+                   for t in (self.first, self.in_pos, self.state, self.size, self.status))
+
+    def to(self, device) -> "SeekIndex":
+        """The index in host memory (``"cpu"``: numpy arrays) or on a CUDA device (tensors)."""
+        if str(device) == "cpu":
+            host = lambda t, dt: np.ascontiguousarray(t.cpu().numpy().view(dt) if _is_torch(t) else np.asarray(t, dtype=dt))  # noqa: E731
+            state = host(self.state, np.uint8)
+            rows = _aligned_rows(*state.shape) if state.ndim == 2 else state
+            rows[...] = state
+            return SeekIndex(host(self.first, np.uint64), host(self.in_pos, np.uint32), rows, self.interval, self.window_bits,
+                             host(self.size, np.uint64), host(self.status, np.int8))
+        import torch
+
+        dev = lambda t, dt, st: (t if _is_torch(t) else torch.from_numpy(np.ascontiguousarray(t).view(dt))).to(device=device, dtype=st)  # noqa: E731
+        return SeekIndex(dev(self.first, np.int64, torch.int64), dev(self.in_pos, np.int32, torch.int32),
+                         dev(self.state, np.uint8, torch.uint8).contiguous(), self.interval, self.window_bits,
+                         dev(self.size, np.int64, torch.int64), dev(self.status, np.int8, torch.int8))
+
+    def save(self, path) -> None:
+        """One ``.npz`` file at exactly ``path``, with host arrays."""
+        h = self.to("cpu")
+        with open(path, "wb") as f:
+            np.savez(f, first=h.first, in_pos=h.in_pos, state=h.state, interval=np.uint64(h.interval),
+                     window_bits=np.uint64(h.window_bits), size=h.size, status=h.status)
+
+    @staticmethod
+    def load(path) -> "SeekIndex":
+        with np.load(path) as z:
+            state = z["state"]
+            rows = _aligned_rows(*state.shape)
+            rows[...] = state
+            return SeekIndex(z["first"].astype(np.uint64), z["in_pos"].astype(np.uint32), rows, int(z["interval"]),
+                             int(z["window_bits"]), z["size"].astype(np.uint64), z["status"].astype(np.int8))
+
+
+def _seek_interval(interval, window_bits: int) -> int:
+    if interval is None:
+        return 16 << window_bits
+    if not _is_int(interval) or not 1 <= int(interval) <= 0xFFFFFFFF:
+        raise ValueError("interval: a positive integer that fits 32 bits expected")
+    return int(interval)
+
+
+def build_seek_index(data, in_off=None, in_len=None, *, interval=None, dictionary=None, max_window_bits: int = 15, device: int = 0,
+                     stream=None) -> SeekIndex:
+    """Checkpoints for reading byte ranges of streams that have NO dictionary resets (``tamp_batch_seek_index``, DESIGN.md 3.13;
+    not in the reference): the streams of plain ``compress`` / ``compress_batch``, of a ``CompressorBatch``, of a reference
+    ``Compressor``.  ``data`` as for ``decompress_batch``.  Every stream is decoded once, without its bytes being written anywhere,
+    and its decoder is kept every ``interval`` decoded bytes (default ``16 << max_window_bits``: an index of about 1/16 of the
+    decoded size).  The rows are sized by ``decoded_size_batch`` first; for host data ``max_window_bits`` becomes the largest
+    window a header of the batch asks for (``max_window_bits`` at most)."""
+    if not _is_int(max_window_bits) or not 8 <= int(max_window_bits) <= 15:
+        raise ValueError("max_window_bits: 8 .. 15 expected")
+    if interval is not None:
+        _seek_interval(interval, 8)
+    if _is_torch(data):
+        if in_off is None or in_len is None or not (_is_torch(in_off) and _is_torch(in_len)):
+            raise ValueError("in_off, in_len: CUDA tensors expected with CUDA data")
+        import torch
+
+        w = int(max_window_bits)
+        N = _seek_interval(interval, w)
+        if stream is not None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+                return build_seek_index(data, in_off, in_len, interval=N, dictionary=dictionary, max_window_bits=w, device=device)
+        lib = _lib.load()
+        dev = data.device
+        n = int(in_len.numel())
+        sizes = decoded_size_batch(data, in_off, in_len, dictionary=dictionary, max_window_bits=w)
+        S = sizes.size.to(torch.int64) & 0xFFFFFFFF
+        rows = torch.clamp(S - 1, min=0) // N
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)
+        dict_t = None if dictionary is None else (dictionary if _is_torch(dictionary) else torch.from_numpy(_np_u8(dictionary).copy())).to(dev)
+        stride = 16 + (1 << w)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for _ in range(2):  # (a stream of 2^32 bytes or more: the size query stops there, the index says the rest)
+            first_t = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            first_t[1:] = torch.cumsum(rows, 0)
+            total = int(first_t[-1].item())
+            in_pos_t = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+            state_t = torch.zeros((max(total, 1), stride), dtype=torch.uint8, device=dev)
+            size_t = torch.zeros(n, dtype=torch.int64, device=dev)
+            status_t = torch.zeros(n, dtype=torch.int8, device=dev)
+            _lib.check_launch(lib.tamp_batch_seek_index(
+                _ptr(dict_t), 0 if dict_t is None else int(dict_t.numel()), w, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), N, _ptr(first_t),
+                _ptr(in_pos_t), _ptr(state_t), stride, _ptr(size_t), _ptr(status_t), n, _lib.MEM_DEVICE, dev.index or 0, C.c_void_p(st)))
+            if not bool((S >= 0xFFFFFFFF).any().item()):
+                break
+            S, rows = size_t, torch.clamp(size_t - 1, min=0) // N
+        return SeekIndex(first_t, in_pos_t[:total], state_t[:total], N, w, size_t, status_t,
+                         (data, in_off_t, in_len_t, dict_t, in_pos_t, state_t))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    n = len(in_len)
+    live = in_len > 0
+    if live.any() and int((in_off[live].astype(np.uint64) + in_len[live]).max()) > flat.size:
+        raise ValueError("in_off, in_len: a stream lies outside the data")
+    heads = flat[in_off[live].astype(np.int64)] if live.any() else np.zeros(0, np.uint8)
+    w = min(int(max_window_bits), int(((heads >> 5) & 7).max()) + 8 if len(heads) else 8)
+    N = _seek_interval(interval, w)
+    lib = _lib.load()
+    sizes = decoded_size_batch(flat, in_off, in_len, dictionary=dictionary, max_window_bits=w, device=device)
+    S = sizes.size.astype(np.uint64)
+    dict_a = None if dictionary is None else _np_u8(dictionary)
+    stride = 16 + (1 << w)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    for _ in range(2):  # (as above)
+        rows = np.where(S > 0, (np.maximum(S, np.uint64(1)) - np.uint64(1)) // np.uint64(N), np.uint64(0)).astype(np.uint64)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        first[1:] = np.cumsum(rows)
+        total = int(first[-1])
+        in_pos = np.zeros(max(total, 1), dtype=np.uint32)
+        state = _aligned_rows(max(total, 1), stride)
+        size = np.zeros(n, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.int8)
+        _lib.check_launch(lib.tamp_batch_seek_index(
+            _ptr(dict_a), 0 if dict_a is None else len(dict_a), w, _ptr(flat), _ptr(in_off), _ptr(in_len), N, _ptr(first), _ptr(in_pos),
+            _ptr(state), stride, _ptr(size), _ptr(status), n, _lib.MEM_HOST, device, None))
+        if not (S >= 0xFFFFFFFF).any():
+            break
+        S = size
+    return SeekIndex(first, in_pos[:total], state[:total], N, w, size, status)
+
+
+def read_ranges_seek(data, in_off=None, in_len=None, *, seek_index, stream_index, begin, length, dictionary=None, device: int = 0,
+                     stream=None) -> RangeResult:
+    """Byte ranges of streams WITHOUT dictionary resets, through a ``SeekIndex`` (``tamp_batch_read_ranges_seek``, DESIGN.md 3.13;
+    not in the reference).  Range ``q`` is ``decompress(stream stream_index[q])[begin[q] : begin[q] + length[q]]``: decoding starts
+    at the checkpoint in front of ``begin[q]``, a range that crosses checkpoints is decoded by one wavefront per interval, and the
+    bytes go straight to their place in the output.  Tables, output and statuses as for ``read_ranges`` (-22: a row of the index
+    does not hold up; -4 comes with the bytes in front of the offending token).  The index is trusted for position and lives where
+    ``data`` lives (``SeekIndex.to``)."""
+    if not isinstance(seek_index, SeekIndex):  # (all decided before the library is looked for)
+        raise ValueError("seek_index: a SeekIndex expected")
+    on_device = _is_torch(data)
+    if on_device and (in_off is None or in_len is None):
+        raise ValueError("in_off, in_len: expected with CUDA data")
+    n_streams = len(data) if in_off is None and not on_device else len(in_len)
+    if len(seek_index.first) != n_streams + 1:
+        raise ValueError("seek_index.first: one entry per stream and one more expected")
+    N = _seek_interval(seek_index.interval, 8)
+    w = seek_index.window_bits
+    if not _is_int(w) or not 8 <= int(w) <= 15:
+        raise ValueError("seek_index.window_bits: 8 .. 15 expected")
+    w = int(w)
+    for t in (seek_index.first, seek_index.in_pos, seek_index.state):
+        if _is_torch(t) != on_device or (on_device and not t.is_cuda):
+            raise ValueError("seek_index: on another memory kind than the data (SeekIndex.to)")
+    stride = 16 + (1 << w)
+    if len(seek_index.state.shape) != 2 or int(seek_index.state.shape[1]) != stride or len(seek_index.state) != len(seek_index.in_pos):
+        raise ValueError("seek_index.state: one row of 16 + (1 << window_bits) bytes per entry of in_pos expected")
+    if not len(stream_index) == len(begin) == len(length):
+        raise ValueError("stream_index, begin and length: one entry per range each")
+    n_ranges = len(stream_index)
+    tables = (stream_index, begin, length)
+    if not (on_device and all(_is_torch(t) for t in tables)):  # (CUDA tables of a CUDA call are checked by nobody: no sync)
+        def host_table(t, what, most, dt):  # -> numpy array of dt; a sequence goes through Python integers (2^64 - 1 is one)
+            a = t.cpu().numpy() if _is_torch(t) else (t if isinstance(t, np.ndarray) else np.array([int(x) for x in t] or [0], dtype=object)[: len(t)])
+            if a.dtype.kind not in "iuO":
+                raise ValueError(what + ": integers expected")
+            if len(a) and int(a.min()) < 0 and what == "begin":
+                raise ValueError(what + ": negative")
+            if len(a) and (int(a.min()) < 0 or int(a.max()) > most):
+                raise ValueError(what + ": does not fit %d bits" % most.bit_length())
+            return np.ascontiguousarray(a.astype(dt))
+
+        h_stream = host_table(stream_index, "stream_index", 0xFFFFFFFF, np.uint32)
+        h_begin = host_table(begin, "begin", (1 << 64) - 1, np.uint64)
+        h_length = host_table(length, "length", 0xFFFFFFFF, np.uint32)
+        if on_device:
+            stream_index, begin, length = h_stream, h_begin, h_length
+    if not on_device:
+        first = np.ascontiguousarray(seek_index.first, dtype=np.uint64)
+        if len(first) and (int(first[0]) != 0 or (np.diff(first.astype(np.int64)) < 0).any() or int(first[-1]) != len(seek_index.in_pos)):
+            raise ValueError("seek_index.first: a running sum from 0 to the number of rows expected")
+    if stream is not None and on_device:
+        import torch  # (tables and output on the launch stream: see compress_batch)
+
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+            return read_ranges_seek(data, in_off, in_len, seek_index=seek_index, stream_index=stream_index, begin=begin, length=length,
+                                    dictionary=dictionary, device=device, stream=None)
+    lib = _lib.load()
+    if on_device:
+        import torch
+
+        dev = data.device
+        as_t = lambda x, dt: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.uint64).view(np.int64))).to(device=dev, dtype=dt)  # noqa: E731
+        first_t, in_pos_t = seek_index.first.to(device=dev, dtype=torch.int64), seek_index.in_pos.to(device=dev, dtype=torch.int32).contiguous()
+        state_t = seek_index.state.to(device=dev).contiguous()
+        if state_t.numel() and state_t.data_ptr() & 15:
+            state_t = torch.cat([state_t.reshape(-1), torch.zeros(16, dtype=torch.uint8, device=dev)])[: state_t.numel()].reshape(state_t.shape)
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)  # kept alive on the result (async launch)
+        stream_t, begin_t, length_t = as_t(stream_index, torch.int32), as_t(begin, torch.int64), as_t(length, torch.int32)
+        len64 = length_t.to(torch.int64) & 0xFFFFFFFF  # (lengths are uint32 values, whatever the storage)
+        out_off_t = torch.cumsum(len64, 0) - len64
+        total = int(len64.sum().item()) if n_ranges else 0
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        out_len_t = torch.empty(n_ranges, dtype=torch.int32, device=dev)
+        status_t = torch.empty(n_ranges, dtype=torch.int8, device=dev)
+        dict_t = None if dictionary is None else (dictionary if _is_torch(dictionary) else torch.from_numpy(_np_u8(dictionary).copy())).to(dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check_launch(lib.tamp_batch_read_ranges_seek(
+            _ptr(dict_t), 0 if dict_t is None else int(dict_t.numel()), w, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), N, _ptr(first_t),
+            _ptr(in_pos_t) if in_pos_t.numel() else None, _ptr(state_t) if state_t.numel() else None, stride, _ptr(stream_t), _ptr(begin_t),
+            _ptr(length_t), _ptr(out), _ptr(out_off_t), _ptr(out_len_t), _ptr(status_t), n_streams, n_ranges, _lib.MEM_DEVICE,
+            dev.index or 0, C.c_void_p(st)))
+        return RangeResult(out, out_off_t, out_len_t, status_t, -1.0,
+                           (data, in_off_t, in_len_t, first_t, in_pos_t, state_t, stream_t, begin_t, length_t, dict_t, seek_index))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    in_pos = np.ascontiguousarray(seek_index.in_pos, dtype=np.uint32)
+    state = np.ascontiguousarray(seek_index.state, dtype=np.uint8)
+    if state.size and state.ctypes.data & 15:
+        rows = _aligned_rows(*state.shape)
+        rows[...] = state
+        state = rows
+    dict_a = None if dictionary is None else _np_u8(dictionary)
+    out_off, total = _slab_offsets(h_length)
+    out = np.zeros(total + 1, dtype=np.uint8)
+    out_len, status = np.zeros(n_ranges, dtype=np.uint32), np.zeros(n_ranges, dtype=np.int8)
+    _lib.check_launch(lib.tamp_batch_read_ranges_seek(
+        _ptr(dict_a), 0 if dict_a is None else len(dict_a), w, _ptr(flat), _ptr(in_off), _ptr(in_len), N, _ptr(first),
+        _ptr(in_pos) if in_pos.size else None, _ptr(state) if state.size else None, stride, _ptr(h_stream), _ptr(h_begin), _ptr(h_length),
+        _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(status), n_streams, n_ranges, _lib.MEM_HOST, device, None))
+    return RangeResult(out, out_off, out_len, status)
+
+
 def _write_tables(stream_index, begin, length, source_off, n_streams):
     """Not part of the package's surface: the host tables of ``write_ranges`` as the C call takes them -- checked, then sorted stably
     by (stream, begin), writes of no bytes first among equals.  -> (stream uint32, begin uint64, length uint32, source_off uint64); ValueError on negative values, values

@@ -40,6 +40,7 @@
 #include "tamp_reset_index_kernel.hpp"
 #include "tamp_pack_kernel.hpp"
 #include "tamp_pieces_kernel.hpp"
+#include "tamp_seek_kernel.hpp"
 
 using namespace tamp_amd;
 
@@ -104,6 +105,7 @@ struct StreamScratch {
     DeviceBuf appends, append_units;  // tamp_batch_append: its tables per stream; the staged entries of the new index, then the rows, staging rows and slabs of a slice's units
     DeviceBuf index_streams, index_chunks, index_entries;  // tamp_batch_index_resets: its tables per stream, per chunk, per entry
     DeviceBuf pieces, piece_rows;  // tamp_batch_compress_pieces: its record and tables per object and per row; the state rows and input rows
+    DeviceBuf seek, seek_units;  // tamp_batch_read_ranges_seek: the per-range scan, byte counts, flags and verdicts; the unit table
     // In front of slab.need / split.need: kernels of earlier calls on the stream may still use a buffer that this call has
     // outgrown, so the stream is drained before it is freed.  (The tables of the other members are freed by need() alone:
     // hipFree waits for the device.)
@@ -115,7 +117,7 @@ struct StreamScratch {
     }
     size_t release() {  // -> the bytes freed (tamp_amd_trim, under `mu`, the stream drained)
         size_t n = 0;
-        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &ends, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries, &pieces, &piece_rows}) n += b->release();
+        for (DeviceBuf* b : {&slab, &split, &blk, &lpt, &long_tab, &long_tails, &long_lags, &resets, &pack, &ranges, &ends, &writes, &write_units, &appends, &append_units, &index_streams, &index_chunks, &index_entries, &pieces, &piece_rows, &seek, &seek_units}) n += b->release();
         return n;
     }
 };
@@ -3491,6 +3493,7 @@ struct OneRow {
 }  // namespace
 
 #include "tamp_pieces.hpp"
+#include "tamp_seek.hpp"
 
 extern "C" {
 
@@ -3756,6 +3759,49 @@ int tamp_batch_read_ranges(uint8_t max_window_bits, const uint8_t* in, const uin
     const ReadCaller c = {in, in_off, in_len, reset_first, reset_off, n_streams, reset_interval, (uint32_t)(max_window_bits & 0x7F),
                           range_stream, range_begin, range_len, n_ranges};
     return batch_read_ranges(c, max_window_bits, out, out_off, out_len, status, mem, device, stream);
+}
+
+int tamp_batch_seek_index(const uint8_t* dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off,
+                          const uint32_t* in_len, uint32_t interval, const uint64_t* ckpt_first, uint32_t* ckpt_in, void* ckpt_state,
+                          size_t state_stride, uint64_t* decoded_size, int8_t* status, size_t n_streams, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!in_off || !in_len || !ckpt_first || !decoded_size || !status || (!in && n_streams) || !interval) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || max_window_bits < 8 || max_window_bits > 15) return TAMP_AMD_BAD_ARGUMENT;
+    if ((state_stride & 15) || state_stride < tamp_amd_decoder_state_size(max_window_bits) || (reinterpret_cast<uintptr_t>(ckpt_state) & 15))
+        return TAMP_AMD_BAD_ARGUMENT;
+    if (mem == TAMP_AMD_MEM_HOST && n_streams && ckpt_first[n_streams] > ckpt_first[0] && (!ckpt_in || !ckpt_state)) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams == 0) return TAMP_OK;
+    const SeekIndexCall c = {dictionary, dictionary_len, max_window_bits, in, in_off, in_len, interval, ckpt_first, ckpt_in,
+                             static_cast<uint8_t*>(ckpt_state), state_stride, decoded_size, status, n_streams};
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_seek_index(ctx, c, static_cast<hipStream_t>(stream));
+    return seek_index_host(ctx, c);
+}
+
+int tamp_batch_read_ranges_seek(const uint8_t* dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in,
+                                const uint64_t* in_off, const uint32_t* in_len, uint32_t interval, const uint64_t* ckpt_first,
+                                const uint32_t* ckpt_in, const void* ckpt_state, size_t state_stride, const uint32_t* range_stream,
+                                const uint64_t* range_begin, const uint32_t* range_len, uint8_t* out, const uint64_t* out_off,
+                                uint32_t* out_len, int8_t* status, size_t n_streams, size_t n_ranges, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!in_off || !in_len || !ckpt_first || !range_stream || !range_begin || !range_len || !out_off || !out_len || !status)
+        return TAMP_AMD_BAD_ARGUMENT;
+    if ((!in && n_streams) || (!out && n_ranges) || !interval) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || n_ranges > 0xFFFFFFFFull || max_window_bits < 8 || max_window_bits > 15) return TAMP_AMD_BAD_ARGUMENT;
+    if ((state_stride & 15) || state_stride < tamp_amd_decoder_state_size(max_window_bits) || (reinterpret_cast<uintptr_t>(ckpt_state) & 15))
+        return TAMP_AMD_BAD_ARGUMENT;
+    if (n_ranges == 0) return TAMP_OK;  // (nothing is touched)
+    const SeekCaller c = {in, in_off, in_len, n_streams, dictionary ? dictionary_len : 0, ckpt_first, ckpt_in,
+                          static_cast<const uint8_t*>(ckpt_state), state_stride, interval, max_window_bits, range_stream, range_begin,
+                          range_len, n_ranges};
+    const SeekReadOut o = {out, out_off, out_len, status};
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_read_seek(ctx, c, dictionary, o, static_cast<hipStream_t>(stream));
+    return read_seek_host(ctx, c, dictionary, o);
 }
 
 int tamp_batch_read_ranges_grid(uint8_t max_window_bits, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,

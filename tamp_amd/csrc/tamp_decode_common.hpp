@@ -204,7 +204,10 @@ __device__ __forceinline__ ExactTok exact_token(RefReader& r, const StreamHeader
 // `match_len` is known and whose offset is still to come (TOKEN_EXT_MATCH parked by an earlier call).  For a decoder that picks a token
 // up where an earlier call left it (tamp_decoded_size_pieces_kernel.hpp).  exact_token above keeps these rules inline: called from
 // there, this function cost the size-only parse two more spilled SGPRs, and its instruction stream is not to change.
-__device__ __forceinline__ ExactTok exact_payload(RefReader& r, const StreamHeader& h, const bool rle, int got, uint32_t match_len) {
+// `parked` (may be null; the decoders that keep the object's state pass it): set where the reference parks the size of an extended
+// match because its offset is not in the buffer yet (pending_match_size, decompressor.c:215-222), whatever becomes of the token.
+__device__ __forceinline__ ExactTok exact_payload(RefReader& r, const StreamHeader& h, const bool rle, int got, uint32_t match_len,
+                                                  uint32_t* parked = nullptr) {
     const uint32_t W = 1u << h.wbits;
     const uint32_t trailing = rle ? 4u : 3u;
     uint32_t value = 0, off = 0;
@@ -227,6 +230,8 @@ __device__ __forceinline__ ExactTok exact_payload(RefReader& r, const StreamHead
             r.bb <<= h.wbits;
             r.nb -= h.wbits;
             got = 2;
+        } else if (got == 1 && parked) {
+            *parked = match_len;
         }
         if (got == 2) break;
         const uint32_t before = r.nb;
@@ -236,6 +241,43 @@ __device__ __forceinline__ ExactTok exact_payload(RefReader& r, const StreamHead
     if (rle) return {kExRle, value + 2, 0};  // decompressor.c:140-173
     if (off >= W || off + match_len > W) return {kExOob, 0, 0};  // decompressor.c:229-236
     return {kExExt, match_len, off};
+}
+
+// exact_token for a decoder that keeps the object's state (tamp_seek_kernel.hpp): the same token of the reference's loop from a
+// buffer refilled at its top, with the payload of an RLE / extended symbol read by exact_payload, so that `parked` tells what the
+// reference left in pending_match_size on the way.  A plain match is consumed here; the reference keeps such a token in its buffer
+// until it is delivered, so a caller that needs the buffer of that moment copies bb / nb in front of the call.
+__device__ __forceinline__ ExactTok exact_token_state(RefReader& r, const StreamHeader& h, uint32_t* parked) {
+    const uint32_t W = 1u << h.wbits;
+    if (r.bb >> 31) {  // literal, decompressor.c:466-482
+        if (r.nb < 1 + h.lbits) return {kExShort, 0, 0};
+        const uint32_t c = (r.bb << 1) >> (32 - h.lbits);
+        r.bb <<= 1 + h.lbits;
+        r.nb -= 1 + h.lbits;
+        return {kExLit, 1, c};
+    }
+    uint32_t b2 = r.bb << 1, n2 = r.nb - 1, used = 0;
+    const int sym = read_symbol(b2, n2, used);
+    if (sym < 0) return {kExShort, 0, 0};
+    b2 <<= used;
+    n2 -= used;
+    if (sym == kSymFlush) {  // decompressor.c:501-514
+        r.bb = b2 << (n2 & 7);
+        r.nb = n2 & ~7u;
+        return {kExFlush, 0, 0};
+    }
+    if (h.extended && sym >= kSymRle) {  // symbol bits are committed before the payload is read (decompressor.c:521-526)
+        r.bb = b2;
+        r.nb = n2;
+        return exact_payload(r, h, sym == kSymRle, 0, 0, parked);
+    }
+    if (n2 < h.wbits) return {kExShort, 0, 0};  // plain match, decompressor.c:529-572
+    const uint32_t match_len = (uint32_t)sym + h.minp;
+    const uint32_t off = b2 >> (32 - h.wbits);
+    if (off >= W || off + match_len > W) return {kExOob, 0, 0};
+    r.bb = b2 << h.wbits;
+    r.nb = n2 - h.wbits;
+    return {kExMatch, match_len, off};
 }
 
 }  // namespace tamp_amd

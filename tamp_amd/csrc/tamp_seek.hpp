@@ -1,0 +1,287 @@
+// tamp_seek.hpp -- tamp_batch_seek_index and tamp_batch_read_ranges_seek behind their entry points (included by tamp_capi.hip,
+// which owns the device context, the per-stream scratch records and the host pipeline).  The kernels: tamp_seek_kernel.hpp.
+//
+// The index, device memory: one launch on the caller's stream, nothing allocated, nothing read back.  Host memory: the streams'
+// extent, the tables and the dictionary go up on the host pipeline's first stream, and the sizes, the statuses and exactly the rows
+// each stream wrote come back.
+// The read, device memory, under the stream's scratch record's launch lock:
+//   count  ->  ONE wait for the 8-byte unit count  ->  units  ->  decode  ->  gather
+// Everything behind the wait is asynchronous.  Host memory: count and units run on the host (the same two functions), and what goes
+// up is the unit table, each touched row once and each unit's compressed span -- never a whole stream unless a unit spans it.
+#pragma once
+#include <unordered_map>
+
+namespace {
+
+struct SeekIndexCall {  // the entry point's arguments
+    const uint8_t* dict;
+    size_t dict_len;
+    uint8_t max_wbits;
+    const uint8_t* in;
+    const uint64_t* in_off;
+    const uint32_t* in_len;
+    uint32_t interval;
+    const uint64_t* first;
+    uint32_t* ckpt_in;
+    uint8_t* states;
+    size_t stride;
+    uint64_t* decoded_size;
+    int8_t* status;
+    size_t n;
+};
+
+int launch_seek_index(DeviceCtx* ctx, const SeekIndexCall& c, hipStream_t st) {
+    if (c.n == 0) return TAMP_OK;
+    SeekIndexArgs a;
+    a.in = c.in, a.in_off = c.in_off, a.in_len = c.in_len;
+    a.dict = c.dict, a.dict_len = c.dict ? c.dict_len : 0, a.seed_dicts = ctx->seed_dicts;
+    a.ckpt_first = c.first, a.ckpt_in = c.ckpt_in, a.ckpt_state = c.states, a.state_stride = c.stride;
+    a.decoded_size = c.decoded_size, a.status = c.status;
+    a.interval = c.interval, a.max_wbits = c.max_wbits, a.n_streams = (uint32_t)c.n;
+    const WaveGeometry g = wave_geometry(c.max_wbits, c.n, ctx->cu_count);
+    timing_begin(st);
+    const int rc = launch_waves(tamp_seek_index_kernel, a, g, seek_wave_lds(c.max_wbits, g.waves), st);
+    timing_end(st);
+    if (rc != TAMP_OK) return rc;
+    HIP_OK(hipGetLastError());
+    return TAMP_OK;
+}
+
+// The extent of a batch's streams on the host and their offsets counted from its start (an empty stream points at the start).
+struct HostExtent {
+    uint64_t lo = 0, hi = 0;
+    std::vector<uint64_t> off;
+    HostExtent(const uint64_t* in_off, const uint32_t* in_len, size_t n) : off(n) {
+        uint64_t l = ~0ull, h = 0;
+        for (size_t i = 0; i < n; i++)
+            if (in_len[i]) l = std::min(l, in_off[i]), h = std::max(h, in_off[i] + in_len[i]);
+        if (h >= l) lo = l, hi = h;
+        for (size_t i = 0; i < n; i++) off[i] = in_len[i] ? in_off[i] - lo : 0;
+    }
+};
+
+int seek_index_host(DeviceCtx* ctx, const SeekIndexCall& c) {
+    using Pipe = DeviceCtx::HostPipe;
+    Pipe& P = ctx->pipe;
+    std::lock_guard<std::mutex> pipe_lock(P.mu);
+    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+    hipStream_t st = P.s[0];
+    const size_t n = c.n;
+    for (size_t i = 0; i < n; i++)
+        if (c.first[i + 1] < c.first[i]) return TAMP_AMD_BAD_ARGUMENT;  // (no running sum: the rows cannot be placed)
+    const uint64_t rows = c.first[n] - c.first[0];
+    const HostExtent ext(c.in_off, c.in_len, n);
+    const size_t first_at = n * 8, len_at = first_at + (n + 1) * 8;
+    const size_t size_at = (rows * 4 + 7) & ~(size_t)7, status_at = size_at + n * 8;
+    HIP_OK(P.in[0].need(ext.hi - ext.lo + 64));
+    HIP_OK(P.meta[0].need(len_at + n * 4 + 64));
+    HIP_OK(P.out[0].need(status_at + n + 64));
+    HIP_OK(P.state[0].need(rows * c.stride + 64));
+    if (c.dict && c.dict_len) HIP_OK(P.dict.need(std::min(c.dict_len, kSeedTable)));
+    uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
+    uint8_t* const o = static_cast<uint8_t*>(P.out[0].p);
+    std::vector<uint64_t> h_first(n + 1);
+    for (size_t i = 0; i <= n; i++) h_first[i] = c.first[i] - c.first[0];
+    if (ext.hi > ext.lo) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + ext.lo, ext.hi - ext.lo, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m, ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m + first_at, h_first.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m + len_at, c.in_len, n * 4, hipMemcpyHostToDevice, st));
+    if (c.dict && c.dict_len) HIP_OK(hipMemcpyAsync(P.dict.p, c.dict, std::min(c.dict_len, kSeedTable), hipMemcpyHostToDevice, st));
+    SeekIndexCall d = c;
+    d.dict = c.dict && c.dict_len ? static_cast<const uint8_t*>(P.dict.p) : nullptr, d.dict_len = std::min(c.dict_len, kSeedTable);
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = reinterpret_cast<const uint64_t*>(m);
+    d.first = reinterpret_cast<const uint64_t*>(m + first_at), d.in_len = reinterpret_cast<const uint32_t*>(m + len_at);
+    d.ckpt_in = reinterpret_cast<uint32_t*>(o), d.states = static_cast<uint8_t*>(P.state[0].p);
+    d.decoded_size = reinterpret_cast<uint64_t*>(o + size_at), d.status = reinterpret_cast<int8_t*>(o + status_at);
+    const int rc = launch_seek_index(ctx, d, st);
+    if (rc != TAMP_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(c.decoded_size, d.decoded_size, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(c.status, d.status, n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    // the rows each stream wrote, runs of neighbours in one transfer
+    uint64_t run0 = 0, run1 = 0;
+    auto flush = [&]() -> int {
+        if (run1 > run0) {
+            HIP_OK(hipMemcpyAsync(c.states + (c.first[0] + run0) * c.stride, d.states + run0 * c.stride, (run1 - run0) * c.stride, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(c.ckpt_in + c.first[0] + run0, d.ckpt_in + run0, (run1 - run0) * 4, hipMemcpyDeviceToHost, st));
+        }
+        return TAMP_OK;
+    };
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t S = c.decoded_size[i], C = S ? (S - 1) / c.interval : 0;
+        const uint64_t w = std::min(C, h_first[i + 1] - h_first[i]);
+        if (!w) continue;
+        if (h_first[i] != run1) {
+            if (const int frc = flush()) return frc;
+            run0 = h_first[i];
+        }
+        run1 = h_first[i] + w;
+    }
+    if (const int frc = flush()) return frc;
+    HIP_OK(hipStreamSynchronize(st));
+    return TAMP_OK;
+}
+
+struct SeekReadOut {
+    uint8_t* out;
+    const uint64_t* out_off;
+    uint32_t* out_len;
+    int8_t* status;
+};
+
+ReadSeekArgs read_seek_args(const DeviceCtx* ctx, const SeekCaller& c, const uint8_t* dict, const SeekUnit* units, uint64_t U,
+                            const SeekRanges& r, const SeekReadOut& o) {
+    ReadSeekArgs a;
+    a.in = c.in, a.dict = dict, a.dict_len = dict ? c.dict_len : 0, a.seed_dicts = ctx->seed_dicts;
+    a.states = c.states, a.stride = c.stride, a.units = units, a.U = U, a.got = r.got, a.flags = r.flags;
+    a.out = o.out, a.out_off = o.out_off, a.max_wbits = c.max_wbits;
+    return a;
+}
+
+// Units are claimed by stride over a grid of at most cu_count * 64 workgroups, as the wave-per-stream kernels are launched.
+int launch_read_seek_kernel(DeviceCtx* ctx, const ReadSeekArgs& a, hipStream_t st) {
+    const WaveGeometry g = wave_geometry(a.max_wbits, a.U, ctx->cu_count);
+    return launch_waves(tamp_read_seek_kernel, a, g, seek_wave_lds(a.max_wbits, g.waves), st);
+}
+
+int launch_read_seek(DeviceCtx* ctx, const SeekCaller& c, const uint8_t* dict, const SeekReadOut& o, hipStream_t st) {
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);  // (to the last launch of the call: the lock rule above StreamScratch)
+    const uint64_t nr = c.n_ranges;
+    const size_t got_at = (nr + 1) * 8, flags_at = got_at + nr * 4, verdict_at = flags_at + nr * 4;
+    HIP_OK(rec.seek.need(verdict_at + nr + 64));
+    uint8_t* const sb = static_cast<uint8_t*>(rec.seek.p);
+    const SeekRanges r = {reinterpret_cast<uint64_t*>(sb), reinterpret_cast<uint32_t*>(sb + got_at), reinterpret_cast<uint32_t*>(sb + flags_at),
+                          reinterpret_cast<int8_t*>(sb + verdict_at)};
+    const CallTiming call_timing(st);
+    const SeekCountArgs ca = {c, r};
+    hipLaunchKernelGGL(tamp_seek_count_kernel, dim3(1), dim3(kResetScanTile), 0, st, ca);
+    HIP_OK(hipGetLastError());
+    uint64_t U = 0;
+    HIP_OK(hipMemcpyAsync(&U, r.unit_first + nr, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (U > 0xFFFFFFFFull * 255) return TAMP_AMD_BAD_ARGUMENT;  // (the grid of the lane-per-unit step)
+    if (U) {
+        HIP_OK(rec.seek_units.need(U * sizeof(SeekUnit)));
+        SeekUnit* const units = static_cast<SeekUnit*>(rec.seek_units.p);
+        const SeekUnitsArgs ua = {c, r, units, U};
+        hipLaunchKernelGGL(tamp_seek_units_kernel, dim3((uint32_t)((U + 255) / 256)), dim3(256), 0, st, ua);
+        HIP_OK(hipGetLastError());
+        if (const int rc = launch_read_seek_kernel(ctx, read_seek_args(ctx, c, dict, units, U, r, o), st)) return rc;
+        HIP_OK(hipGetLastError());
+    }
+    const SeekGatherArgs ga = {r, c.range_len, nr, o.out_len, o.status};
+    hipLaunchKernelGGL(tamp_seek_gather_kernel, dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, st, ga);
+    HIP_OK(hipGetLastError());
+    if (getenv("TAMP_AMD_RESETS_DEBUG"))
+        fprintf(stderr, "[tamp_amd seek] read ranges: %llu ranges, %llu units\n", (unsigned long long)nr, (unsigned long long)U);
+    return TAMP_OK;
+}
+
+int read_seek_host(DeviceCtx* ctx, const SeekCaller& c, const uint8_t* dict, const SeekReadOut& o) {
+    using Pipe = DeviceCtx::HostPipe;
+    const uint64_t nr = c.n_ranges;
+    // count and units, on the host
+    std::vector<SeekUnit> units;
+    std::vector<uint8_t> spans, rows;
+    std::vector<uint64_t> d_out_off(nr, 0);
+    std::vector<int32_t> verdict(nr);
+    std::unordered_map<uint32_t, uint32_t> row_at;  // a touched row -> its place among the uploaded ones
+    uint64_t out_bytes = 0;
+    for (uint64_t q = 0; q < nr; q++) {
+        const SeekPlan p = seek_range_plan(c, q);
+        verdict[q] = p.verdict;
+        if (p.verdict != kSeekGo) continue;
+        const size_t u0 = units.size();
+        bool ok = true;
+        for (uint64_t j = 0; ok && j < p.units; j++) {
+            SeekUnit u;
+            ok = seek_range_unit(c, q, p, j, u);
+            if (ok) units.push_back(u);
+        }
+        if (!ok) {  // (a range with a bad row has no units and writes nothing)
+            units.resize(u0);
+            verdict[q] = kSeekBadIndex;
+            continue;
+        }
+        d_out_off[q] = out_bytes;
+        out_bytes += (c.range_len[q] + 3ull) & ~3ull;
+    }
+    for (SeekUnit& u : units) {  // the touched rows, once each, and the units' spans
+        if (u.row != kSeekFresh) {
+            const auto it = row_at.find(u.row);
+            if (it != row_at.end()) {
+                u.row = it->second;
+            } else {
+                const uint32_t at = (uint32_t)row_at.size();
+                const uint8_t* const src = c.states + (uint64_t)u.row * c.stride;
+                rows.insert(rows.end(), src, src + c.stride);
+                row_at.emplace(u.row, at);
+                u.row = at;
+            }
+        }
+        const uint64_t at = spans.size();
+        spans.insert(spans.end(), c.in + u.in_at, c.in + u.in_at + u.in_n);
+        spans.resize((spans.size() + 3) & ~(size_t)3);
+        u.in_at = at;
+    }
+    const uint64_t U = units.size();
+    std::vector<uint32_t> got(nr, 0), flags(nr, 0);
+    std::vector<uint8_t> h_out(out_bytes);
+    if (U) {
+        Pipe& P = ctx->pipe;
+        std::lock_guard<std::mutex> pipe_lock(P.mu);
+        if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+        hipStream_t st = P.s[0];
+        const size_t off_at = (U * sizeof(SeekUnit) + 7) & ~(size_t)7;
+        const size_t got_at = (out_bytes + 7) & ~(size_t)7, flags_at = got_at + nr * 4;
+        HIP_OK(P.in[0].need(spans.size() + 64));
+        HIP_OK(P.state[0].need(rows.size() + 64));
+        HIP_OK(P.meta[0].need(off_at + nr * 8 + 64));
+        HIP_OK(P.out[0].need(flags_at + nr * 4 + 64));
+        const size_t dl = dict && c.dict_len ? std::min<size_t>(c.dict_len, kSeedTable) : 0;
+        if (dl) HIP_OK(P.dict.need(dl));
+        uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
+        uint8_t* const ob = static_cast<uint8_t*>(P.out[0].p);
+        if (!spans.empty()) HIP_OK(hipMemcpyAsync(P.in[0].p, spans.data(), spans.size(), hipMemcpyHostToDevice, st));
+        if (!rows.empty()) HIP_OK(hipMemcpyAsync(P.state[0].p, rows.data(), rows.size(), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(m, units.data(), U * sizeof(SeekUnit), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(m + off_at, d_out_off.data(), nr * 8, hipMemcpyHostToDevice, st));
+        if (dl) HIP_OK(hipMemcpyAsync(P.dict.p, dict, dl, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(ob + got_at, 0, nr * 8, st));
+        SeekCaller d = c;
+        d.in = static_cast<const uint8_t*>(P.in[0].p), d.states = static_cast<const uint8_t*>(P.state[0].p), d.dict_len = dl;
+        const SeekRanges r = {nullptr, reinterpret_cast<uint32_t*>(ob + got_at), reinterpret_cast<uint32_t*>(ob + flags_at), nullptr};
+        const SeekReadOut dout = {ob, reinterpret_cast<const uint64_t*>(m + off_at), nullptr, nullptr};
+        const int rc = launch_read_seek_kernel(ctx, read_seek_args(ctx, d, dl ? static_cast<const uint8_t*>(P.dict.p) : nullptr,
+                                                                    reinterpret_cast<const SeekUnit*>(m), U, r, dout), st);
+        if (rc != TAMP_OK) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        HIP_OK(hipGetLastError());
+        if (out_bytes) HIP_OK(hipMemcpyAsync(h_out.data(), ob, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(got.data(), ob + got_at, nr * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(flags.data(), ob + flags_at, nr * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    for (uint64_t q = 0; q < nr; q++) {  // the gather step
+        int32_t status = verdict[q];
+        uint32_t len = 0;
+        if (status == kSeekGo) {
+            len = std::min(got[q], c.range_len[q]);
+            status = (flags[q] & kSeekSawOob) ? (int32_t)kOob : (len == c.range_len[q] ? (int32_t)kOk : (int32_t)kInputExhausted);
+            if (len) memcpy(o.out + o.out_off[q], h_out.data() + d_out_off[q], len);
+        }
+        o.status[q] = (int8_t)status, o.out_len[q] = len;
+    }
+    if (getenv("TAMP_AMD_RESETS_DEBUG"))
+        fprintf(stderr, "[tamp_amd seek] read ranges (host): %llu ranges, %llu units, %llu rows and %llu bytes of spans uploaded\n",
+                (unsigned long long)nr, (unsigned long long)U, (unsigned long long)row_at.size(), (unsigned long long)spans.size());
+    return TAMP_OK;
+}
+
+}  // namespace
