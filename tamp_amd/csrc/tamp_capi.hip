@@ -22,6 +22,7 @@
 
 #include "tamp_amd.h"
 #include "tamp_compat.h"
+#include "tamp_host_stage.hpp"
 #include "tamp_compress_kernel.hpp"
 #include "tamp_compress_plan.hpp"
 #include "tamp_decompress_kernel.hpp"
@@ -82,11 +83,15 @@ using PinnedBuf = GrowBuf<pinned_alloc, hipHostFree>;
 // share its buffers (the next call's kernels find the previous call's done with them), launches on different streams run
 // concurrently and do not.
 // LOCK RULE.  DeviceCtx::scratch(st) holds the map's mutex for the look-up only.  `mu` is taken at the top of
-// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges, launch_write_ranges, launch_append, launch_index_resets, launch_segment_ends, launch_pack and launch_pieces and held to the call's last launch: one library call at a time enqueues on a
-// stream and may touch its record.  Under it the members are used directly -- no second lock, no pointer that outlives the
-// lock -- and the record is passed down (launch_compress_locked, launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
+// launch_compress, launch_compress_resets, launch_compress_batch_resets, launch_decompress, launch_read_ranges,
+// launch_write_ranges, launch_append, launch_index_resets, launch_segment_ends, launch_pack and launch_pieces and held to the
+// call's last launch: one library call at a time enqueues on a stream and may touch its record.  Under it the members are used
+// directly -- no second lock, no pointer that outlives the lock -- and the record is passed down (launch_compress_locked,
+// launch_compress_blocks, launch_decompress_long): `mu` is not recursive.
 // tamp_amd_trim takes `mu` and drains the stream before it frees, so it can neither free what a call is about to launch
 // with nor what a launched kernel still uses.
+// A host-memory call (HostCall below) holds the host pipeline's mutex; where it takes a record's `mu` as well, the pipeline's
+// comes FIRST and the record's second, never the reverse (read_ranges_host, batch_append).
 struct StreamScratch {
     std::mutex mu;
     DeviceBuf slab;        // lane decoder with the windows in global memory: one window slot per resident lane
@@ -168,6 +173,49 @@ unsigned long long* g_prof = nullptr;  // -DTAMP_PROF builds: device buffer of p
             return TAMP_AMD_NO_DEVICE;                                                                    \
         }                                                                                                 \
     } while (0)
+
+// One host-memory call on the pipeline's first stream: it holds P.mu (one such call per device at a time) and, behind open(),
+// P.s[0] exists.  Every way out of the call drains that stream: the call's copies go to and from its own vectors and the
+// caller's arrays, and none of them may still be in flight when those go away -- so a local that an asynchronous copy reads or
+// writes is declared IN FRONT of the HostCall and outlives the drain.  (Behind the last wait of a call that completes: nothing.)
+struct HostCall {
+    DeviceCtx::HostPipe& P;
+    std::lock_guard<std::mutex> pipe_lock;
+    hipStream_t st = nullptr;
+    explicit HostCall(DeviceCtx* ctx) : P(ctx->pipe), pipe_lock(P.mu) {}
+    int open() {  // -> TAMP_OK, or TAMP_AMD_NO_DEVICE with the error text set: the call returns it
+        if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
+        st = P.s[0];
+        return TAMP_OK;
+    }
+    ~HostCall() {
+        if (st && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+    }
+};
+
+// The produced bytes of a host-memory call's slabs, back to the caller: row i's len[i] bytes from d_slab + d_off[i] to
+// out + out_off[i].  Through ONE pinned transfer of the slabs' extent when that is at most 512 MiB (the rows are placed by the
+// host), else -- or with the debugging switch below set, or without the pinned memory -- row by row; nothing when no row
+// produced a byte.  The stream is idle when it returns TAMP_OK.
+int copy_back_slabs(DeviceCtx::HostPipe& P, hipStream_t st, const uint8_t* d_slab, uint64_t extent, const uint64_t* d_off, uint8_t* out,
+                    const uint64_t* out_off, const uint32_t* len, size_t n) {
+    uint64_t produced = 0;
+    for (size_t i = 0; i < n; i++) produced += len[i];
+    if (!produced) return TAMP_OK;
+    if (extent <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(extent) == hipSuccess) {
+        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
+        HIP_OK(hipMemcpyAsync(P.stage[0].p, d_slab, extent, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < n; i++)
+            if (len[i]) memcpy(out + out_off[i], stg + d_off[i], len[i]);
+        return TAMP_OK;
+    }
+    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
+    for (size_t i = 0; i < n; i++)
+        if (len[i]) HIP_OK(hipMemcpyAsync(out + out_off[i], d_slab + d_off[i], len[i], hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return TAMP_OK;
+}
 
 void seed_dictionary_host(unsigned char* buf, size_t size, uint8_t literal) {
     // common.c:18-52: xorshift32 from 3758097560, one draw per 8 bytes, nibble selects from a 16-entry table.
@@ -1815,11 +1863,10 @@ int compress_resets(const TampAmdConf* conf, const uint8_t* in, uint64_t in_len,
     if (const int rc = get_ctx(device, &ctx)) return rc;
     if (mem == TAMP_AMD_MEM_DEVICE)
         return launch_compress_resets(ctx, conf, in, in_len, interval, out, out_cap, out_len, status, reset_off, static_cast<hipStream_t>(stream));
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> call_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
     const uint64_t K = reset_segment_count(in_len, interval);
     const uint64_t room = std::min<uint64_t>(out_cap, tamp_amd_compress_resets_bound(in_len, interval, conf->literal));
     HIP_OK(P.in[0].need(in_len + 64));  // the kernels' vector loads may run past the last byte
@@ -1832,10 +1879,7 @@ int compress_resets(const TampAmdConf* conf, const uint8_t* in, uint64_t in_len,
     uint64_t* const d_reset = d_len + 2;
     if (in_len) HIP_OK(hipMemcpyAsync(d_in, in, in_len, hipMemcpyHostToDevice, st));
     // (`room` instead of out_cap: a total above the bound does not exist, one above out_cap is above `room` as well)
-    if (const int rc = launch_compress_resets(ctx, conf, d_in, in_len, interval, d_out, room, d_len, d_status, reset_off ? d_reset : nullptr, st)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    if (const int rc = launch_compress_resets(ctx, conf, d_in, in_len, interval, d_out, room, d_len, d_status, reset_off ? d_reset : nullptr, st)) return rc;
     HIP_OK(hipMemcpyAsync(out_len, d_len, 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(status, d_status, 1, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -1969,51 +2013,46 @@ int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_
     if (mem == TAMP_AMD_MEM_DEVICE) return launch_compress_batch_resets(ctx, conf, t, interval, max_in_len, nullptr, index, static_cast<hipStream_t>(stream));
     const size_t n = t.n;
     if (n == 0) return TAMP_OK;
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> call_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
-    uint64_t in_lo = ~0ull, in_hi = 0, closed = 0, room = 0;
+    uint64_t closed = 0;
     uint32_t longest = 0;
-    std::vector<uint64_t> h_in_off(n), h_out_off(n);
+    std::vector<uint64_t> h_out_off(n);
     std::vector<uint32_t> h_cap(n);
     for (size_t i = 0; i < n; i++) {
         const uint32_t len = t.in_len[i];
-        if (len) in_lo = std::min(in_lo, t.in_off[i]), in_hi = std::max(in_hi, t.in_off[i] + len);
         longest = std::max(longest, len);
         closed += batch_reset_closed_count(len, interval);
         h_cap[i] = (uint32_t)std::min<uint64_t>(t.out_cap[i], reset_stream_bound(len, interval, conf->literal));
-        h_out_off[i] = room, room += h_cap[i];
     }
     if (index.off && closed > index.cap) return TAMP_AMD_BAD_ARGUMENT;  // (before anything is written, the device path's rule)
-    if (in_hi < in_lo) in_lo = in_hi = 0;
-    for (size_t i = 0; i < n; i++) h_in_off[i] = t.in_len[i] ? t.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
-    HIP_OK(P.in[0].need(in_hi - in_lo + 64));  // the kernels' vector loads may run past the last byte
+    const HostExtent ext(t.in_off, t.in_len, n);
+    const uint64_t room = dense_slabs(h_cap.data(), n, h_out_off.data());
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    HIP_OK(P.in[0].need(ext.bytes() + 64));  // the kernels' vector loads may run past the last byte
     HIP_OK(P.out[0].need(room + 1));
-    const size_t index_at = (n * (8 + 8 + 4 + 4 + 4 + 1) + 3) & ~(size_t)3;  // the reset index, behind the tables
-    HIP_OK(P.meta[0].need(index_at + (index.off ? closed * 4 : 0) + 64));
+    TableCarver m;
+    const auto m_in_off = m.take<uint64_t>(n), m_out_off = m.take<uint64_t>(n);
+    const auto m_in_len = m.take<uint32_t>(n), m_cap = m.take<uint32_t>(n), m_out_len = m.take<uint32_t>(n);
+    const auto m_status = m.take<int8_t>(n);
+    const auto m_reset_off = m.take<uint32_t>(index.off ? closed : 0);  // the reset index, behind the tables
+    HIP_OK(P.meta[0].need(m.bytes()));
+    void* const mp = P.meta[0].p;
     BatchTables d;
-    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
-    uint64_t* const d_out_off = d_in_off + n;
-    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_out_off + n);
-    uint32_t* const d_cap = d_in_len + n;
-    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = d_in_off, d.in_len = d_in_len;
-    d.out = static_cast<uint8_t*>(P.out[0].p), d.out_off = d_out_off, d.out_cap = d_cap;
-    d.out_len = d_cap + n, d.status = reinterpret_cast<int8_t*>(d.out_len + n), d.n = n;
-    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, t.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_in_len, t.in_len, n * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_cap, h_cap.data(), n * 4, hipMemcpyHostToDevice, st));
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = m_in_off.in(mp), d.in_len = m_in_len.in(mp);
+    d.out = static_cast<uint8_t*>(P.out[0].p), d.out_off = m_out_off.in(mp), d.out_cap = m_cap.in(mp);
+    d.out_len = m_out_len.in(mp), d.status = m_status.in(mp), d.n = n;
+    if (ext.bytes()) HIP_OK(hipMemcpyAsync(P.in[0].p, t.in + ext.lo, ext.bytes(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_off.in(mp), ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_out_off.in(mp), h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_len.in(mp), t.in_len, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_cap.in(mp), h_cap.data(), n * 4, hipMemcpyHostToDevice, st));
     (void)max_in_len;  // (the tables are here: the longest stream is known exactly and stands for the caller's hint)
     const BatchResetCounted counted = {closed, longest};
-    uint32_t* const d_reset_off = index.off ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(P.meta[0].p) + index_at) : nullptr;
+    uint32_t* const d_reset_off = index.off ? m_reset_off.in(mp) : nullptr;
     // (the first table is the host's own count below; the entries come back with the results)
-    if (const int rc = launch_compress_batch_resets(ctx, conf, d, interval, std::max(longest, 1u), &counted, {nullptr, d_reset_off, closed}, st)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    if (const int rc = launch_compress_batch_resets(ctx, conf, d, interval, std::max(longest, 1u), &counted, {nullptr, d_reset_off, closed}, st)) return rc;
     HIP_OK(hipMemcpyAsync(t.out_len, d.out_len, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(t.status, d.status, n, hipMemcpyDeviceToHost, st));
     if (index.off && closed) HIP_OK(hipMemcpyAsync(index.off, d_reset_off, closed * 4, hipMemcpyDeviceToHost, st));
@@ -2023,22 +2062,7 @@ int batch_compress_resets(const TampAmdConf* conf, const BatchTables& t, uint32_
         for (size_t i = 0; i < n; i++) index.first[i] = run, run += batch_reset_closed_count(t.in_len[i], interval);
         index.first[n] = run;
     }
-    uint64_t produced = 0;
-    for (size_t i = 0; i < n; i++) produced += t.out_len[i];
-    if (!produced) return TAMP_OK;
-    if (room <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(room) == hipSuccess) {
-        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
-        HIP_OK(hipMemcpyAsync(P.stage[0].p, d.out, room, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < n; i++)
-            if (t.out_len[i]) memcpy(t.out + t.out_off[i], stg + h_out_off[i], t.out_len[i]);
-        return TAMP_OK;
-    }
-    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
-    for (size_t i = 0; i < n; i++)
-        if (t.out_len[i]) HIP_OK(hipMemcpyAsync(t.out + t.out_off[i], d.out + h_out_off[i], t.out_len[i], hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return TAMP_OK;
+    return copy_back_slabs(P, st, d.out, room, h_out_off.data(), t.out, t.out_off, t.out_len, n);
 }
 
 // Reading a stream with dictionary resets back (tamp_amd_decompress_resets): the long-stream decoder's front settles the token
@@ -2189,20 +2213,16 @@ int decompress_resets(uint8_t max_wbits, const uint8_t* in, uint32_t n, uint8_t*
     if (const int rc = get_ctx(device, &ctx)) return rc;
     if (mem == TAMP_AMD_MEM_DEVICE)
         return decompress_resets_device(ctx, in, n, out, cap, max_wbits, static_cast<hipStream_t>(stream), out_len, status, consumed);
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> call_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
     HIP_OK(P.in[0].need((size_t)n + 64));
     if (out) HIP_OK(P.out[0].need((size_t)cap + 1));
     uint8_t* const d_in = static_cast<uint8_t*>(P.in[0].p);
     uint8_t* const d_out = out ? static_cast<uint8_t*>(P.out[0].p) : nullptr;
     if (n) HIP_OK(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, st));
-    if (const int rc = decompress_resets_device(ctx, d_in, n, d_out, cap, max_wbits, st, out_len, status, consumed)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    if (const int rc = decompress_resets_device(ctx, d_in, n, d_out, cap, max_wbits, st, out_len, status, consumed)) return rc;
     if (out && *out_len) {
         HIP_OK(hipMemcpyAsync(out, d_out, *out_len, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -2328,66 +2348,43 @@ int batch_decompress_resets(const BatchTables& t, const uint64_t* first, const u
     }
     const uint64_t C = counted.closed;
     if (C && !off) return TAMP_AMD_BAD_ARGUMENT;
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> call_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
-    uint64_t in_lo = ~0ull, in_hi = 0, room = 0;
-    std::vector<uint64_t> h_in_off(n), h_out_off(n);
-    for (size_t i = 0; i < n; i++) {
-        if (t.in_len[i]) in_lo = std::min(in_lo, t.in_off[i]), in_hi = std::max(in_hi, t.in_off[i] + t.in_len[i]);
-        h_out_off[i] = room, room += t.out ? t.out_cap[i] : 0;
-    }
-    if (in_hi < in_lo) in_lo = in_hi = 0;
-    for (size_t i = 0; i < n; i++) h_in_off[i] = t.in_len[i] ? t.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
-    HIP_OK(P.in[0].need(in_hi - in_lo + 64));  // the kernels' vector loads may run past the last byte
+    const HostExtent ext(t.in_off, t.in_len, n);
+    std::vector<uint64_t> h_out_off(n, 0);
+    const uint64_t room = t.out ? dense_slabs(t.out_cap, n, h_out_off.data()) : 0;
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    HIP_OK(P.in[0].need(ext.bytes() + 64));  // the kernels' vector loads may run past the last byte
     if (t.out) HIP_OK(P.out[0].need(room + 1));
-    const size_t index_at = (n * (8 + 8 + 4 + 4 + 4 + 4) + 7) & ~(size_t)7, status_at = index_at + (n + 1) * 8 + C * 4;
-    HIP_OK(P.meta[0].need(status_at + n + 64));
-    uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
-    uint64_t* const d_in_off = reinterpret_cast<uint64_t*>(m);
-    uint64_t* const d_out_off = d_in_off + n;
-    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_out_off + n);
-    uint32_t* const d_cap = d_in_len + n;
-    uint64_t* const d_first = reinterpret_cast<uint64_t*>(m + index_at);
-    uint32_t* const d_off = reinterpret_cast<uint32_t*>(d_first + n + 1);
+    TableCarver m;
+    const auto m_in_off = m.take<uint64_t>(n), m_out_off = m.take<uint64_t>(n);
+    const auto m_in_len = m.take<uint32_t>(n), m_cap = m.take<uint32_t>(n), m_out_len = m.take<uint32_t>(n), m_consumed = m.take<uint32_t>(n);
+    const auto m_first = m.take<uint64_t>(n + 1);
+    const auto m_off = m.take<uint32_t>(C);
+    const auto m_status = m.take<int8_t>(n);
+    HIP_OK(P.meta[0].need(m.bytes()));
+    void* const mp = P.meta[0].p;
+    uint64_t* const d_first = m_first.in(mp);
+    uint32_t* const d_off = m_off.in(mp);
     BatchTables d;
-    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = d_in_off, d.in_len = d_in_len;
-    d.out = t.out ? static_cast<uint8_t*>(P.out[0].p) : nullptr, d.out_off = t.out ? d_out_off : nullptr, d.out_cap = d_cap;
-    d.out_len = d_cap + n, d.in_consumed = d.out_len + n, d.status = reinterpret_cast<int8_t*>(m + status_at), d.n = n;
-    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, t.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_in_len, t.in_len, n * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_cap, t.out_cap, n * 4, hipMemcpyHostToDevice, st));
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = m_in_off.in(mp), d.in_len = m_in_len.in(mp);
+    d.out = t.out ? static_cast<uint8_t*>(P.out[0].p) : nullptr, d.out_off = t.out ? m_out_off.in(mp) : nullptr, d.out_cap = m_cap.in(mp);
+    d.out_len = m_out_len.in(mp), d.in_consumed = m_consumed.in(mp), d.status = m_status.in(mp), d.n = n;
+    if (ext.bytes()) HIP_OK(hipMemcpyAsync(P.in[0].p, t.in + ext.lo, ext.bytes(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_off.in(mp), ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_out_off.in(mp), h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_len.in(mp), t.in_len, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_cap.in(mp), t.out_cap, n * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_first, first, (n + 1) * 8, hipMemcpyHostToDevice, st));
     if (C) HIP_OK(hipMemcpyAsync(d_off, off, C * 4, hipMemcpyHostToDevice, st));
-    if (const int rc = launch_decompress_batch_resets(ctx, d, d_first, d_off, max_wbits, &counted, st)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    if (const int rc = launch_decompress_batch_resets(ctx, d, d_first, d_off, max_wbits, &counted, st)) return rc;
     HIP_OK(hipMemcpyAsync(t.out_len, d.out_len, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(t.status, d.status, n, hipMemcpyDeviceToHost, st));
     if (t.in_consumed) HIP_OK(hipMemcpyAsync(t.in_consumed, d.in_consumed, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (!t.out) return TAMP_OK;
-    uint64_t produced = 0;
-    for (size_t i = 0; i < n; i++) produced += t.out_len[i];
-    if (!produced) return TAMP_OK;
-    if (room <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(room) == hipSuccess) {
-        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
-        HIP_OK(hipMemcpyAsync(P.stage[0].p, d.out, room, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < n; i++)
-            if (t.out_len[i]) memcpy(t.out + t.out_off[i], stg + h_out_off[i], t.out_len[i]);
-        return TAMP_OK;
-    }
-    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
-    for (size_t i = 0; i < n; i++)
-        if (t.out_len[i]) HIP_OK(hipMemcpyAsync(t.out + t.out_off[i], d.out + h_out_off[i], t.out_len[i], hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return TAMP_OK;
+    return copy_back_slabs(P, st, d.out, room, h_out_off.data(), t.out, t.out_off, t.out_len, n);
 }
 
 // Reading byte ranges of reset-segmented streams (tamp_batch_read_ranges; kernels and steps: tamp_read_ranges_kernel.hpp, the
@@ -2539,16 +2536,7 @@ int launch_read_ranges(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, u
 // `segment_end`: the table form (the caller's table, in host memory), or null.
 int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
                      int8_t* status, const uint64_t* segment_end) {
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> pipe_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
-    StreamScratch& rec = ctx->scratch(st);
-    std::lock_guard<std::mutex> call_lock(rec.mu);
-    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
-    const uint64_t nr = c.n_ranges, budget = read_ranges_budget(rec);
-    // the count, on the host
+    const uint64_t nr = c.n_ranges;
     std::vector<ReadPlan> plan(nr);
     std::vector<ReadGridPlan> grid_plan(segment_end ? nr : 0);  // (the table form: plan[q] is grid_plan[q].p)
     std::vector<uint64_t> skip(segment_end ? nr : 0);
@@ -2556,6 +2544,15 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
     std::vector<uint64_t> unit_first(nr + 1), cost_first(nr + 1), packed_off(nr);
     std::vector<int8_t> verdict(nr);
     std::vector<uint8_t> failed(nr, 0);
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    StreamScratch& rec = ctx->scratch(st);
+    std::lock_guard<std::mutex> call_lock(rec.mu);
+    const bool dbg = getenv("TAMP_AMD_RESETS_DEBUG") != nullptr;
+    const uint64_t budget = read_ranges_budget(rec);
+    // the count, on the host
     uint64_t units_all = 0, cost_all = 0, staged_all = 0;
     for (uint64_t q = 0; q < nr; q++) {
         if (segment_end) {
@@ -2577,12 +2574,15 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
     const ReadRanges r = read_ranges_at(static_cast<uint8_t*>(rec.ranges.p), nr);
     const ReadTable table = {nullptr, read_ranges_skip_at(static_cast<uint8_t*>(rec.ranges.p), nr)};  // (the device steps read the skips alone)
     const ReadTable* const g = segment_end ? &table : nullptr;
-    HIP_OK(P.meta[0].need(nr * (8 + 8 + 4 + 4 + 1) + 64));
-    uint64_t* const d_begin = static_cast<uint64_t*>(P.meta[0].p);
-    uint64_t* const d_out_off = d_begin + nr;
-    uint32_t* const d_len = reinterpret_cast<uint32_t*>(d_out_off + nr);
-    uint32_t* const d_out_len = d_len + nr;
-    int8_t* const d_status = reinterpret_cast<int8_t*>(d_out_len + nr);
+    TableCarver m;
+    const auto m_begin = m.take<uint64_t>(nr), m_out_off = m.take<uint64_t>(nr);
+    const auto m_len = m.take<uint32_t>(nr), m_out_len = m.take<uint32_t>(nr);
+    const auto m_status = m.take<int8_t>(nr);
+    HIP_OK(P.meta[0].need(m.bytes()));
+    void* const mp = P.meta[0].p;
+    uint64_t *const d_begin = m_begin.in(mp), *const d_out_off = m_out_off.in(mp);
+    uint32_t *const d_len = m_len.in(mp), *const d_out_len = m_out_len.in(mp);
+    int8_t* const d_status = m_status.in(mp);
     ReadCaller d = {};
     d.interval = c.interval, d.max_wbits = c.max_wbits, d.range_begin = d_begin, d.range_len = d_len, d.n_ranges = nr;
     const CallTiming call_timing(st);
@@ -2642,10 +2642,7 @@ int read_ranges_host(DeviceCtx* ctx, const ReadCaller& c, uint8_t max_wbits, uin
         HIP_OK(hipMemcpyAsync(d_out_off + span.q0, packed_off.data() + span.q0, nq * 8, hipMemcpyHostToDevice, st));
         HIP_OK(P.out[0].need(packed + 1));
         uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
-        if (const int rc = launch_read_tail(ctx, rec, d, r, s, max_wbits, d_out, d_out_off, d_out_len, d_status, st, g)) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
+        if (const int rc = launch_read_tail(ctx, rec, d, r, s, max_wbits, d_out, d_out_off, d_out_len, d_status, st, g)) return rc;
         HIP_OK(hipMemcpyAsync(out_len + span.q0, d_out_len + span.q0, nq * 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(status + span.q0, d_status + span.q0, nq, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -2832,54 +2829,39 @@ int batch_write_ranges(const TampAmdConf* conf, const WriteCaller& c, uint8_t ma
     const uint64_t n = c.n, nw = c.n_writes, C = c.first[n];
     if (!c.off && C) return TAMP_AMD_BAD_ARGUMENT;  // (entries and no table to hold them)
     if (C + n < C) return TAMP_AMD_BAD_ARGUMENT;
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> pipe_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
     const uint64_t unit_bound = reset_segment_bound(c.interval, conf->literal, true);
-    uint64_t in_lo = ~0ull, in_hi = 0, src_lo = ~0ull, src_hi = 0, room = 0;
-    std::vector<uint64_t> h_in_off(n), h_out_off(n), h_src_off(nw), grow(n, 0);
+    std::vector<uint64_t> h_out_off(n), grow(n, 0);
     std::vector<uint32_t> h_cap(n);
-    for (uint64_t q = 0; q < nw; q++) {
-        const uint32_t i = c.write_stream[q], len = c.write_len[q];
-        if (i >= n || !len) continue;
-        src_lo = std::min(src_lo, c.src_off[q]), src_hi = std::max(src_hi, c.src_off[q] + len);
-        grow[i] += ((uint64_t)len / c.interval + 2) * unit_bound;  // (what its touched segments can take at most)
-    }
-    for (uint64_t i = 0; i < n; i++) {
-        const uint32_t len = c.in_len[i];
-        if (len) in_lo = std::min(in_lo, c.in_off[i]), in_hi = std::max(in_hi, c.in_off[i] + len);
-        // the new stream: its untouched bytes, no more than it has, and its touched segments again
-        h_cap[i] = (uint32_t)std::min<uint64_t>(o.out_cap[i], std::min<uint64_t>((uint64_t)len + kResetHeaderBytes + grow[i], 0xFFFFFFFFull));
-        h_out_off[i] = room, room += h_cap[i];
-    }
-    if (in_hi < in_lo) in_lo = in_hi = 0;
-    if (src_hi < src_lo) src_lo = src_hi = 0;
-    for (uint64_t i = 0; i < n; i++) h_in_off[i] = c.in_len[i] ? c.in_off[i] - in_lo : 0;
-    for (uint64_t q = 0; q < nw; q++) h_src_off[q] = c.write_stream[q] < n && c.write_len[q] ? c.src_off[q] - src_lo : 0;
-    HIP_OK(P.in[0].need(in_hi - in_lo + 64));
-    HIP_OK(P.in[1].need(src_hi - src_lo + 64));
+    const auto lands = [&](size_t q) { return c.write_stream[q] < n; };  // (a write to a stream there is: the others name no source bytes)
+    for (uint64_t q = 0; q < nw; q++)  // (what a stream's touched segments can take at most)
+        if (lands(q) && c.write_len[q]) grow[c.write_stream[q]] += ((uint64_t)c.write_len[q] / c.interval + 2) * unit_bound;
+    for (uint64_t i = 0; i < n; i++)  // the new stream: its untouched bytes, no more than it has, and its touched segments again
+        h_cap[i] = (uint32_t)std::min<uint64_t>(o.out_cap[i], std::min<uint64_t>((uint64_t)c.in_len[i] + kResetHeaderBytes + grow[i], 0xFFFFFFFFull));
+    const HostExtent ext(c.in_off, c.in_len, n), src(c.src_off, c.write_len, nw, lands);
+    const uint64_t room = dense_slabs(h_cap.data(), n, h_out_off.data());
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    HIP_OK(P.in[0].need(ext.bytes() + 64));
+    HIP_OK(P.in[1].need(src.bytes() + 64));
     HIP_OK(P.out[0].need(room + 1));
-    // 8-byte tables, 4-byte tables, bytes
-    const size_t meta = 8 * (n + n + (n + 1) + nw + nw) + 4 * (n + n + n + C + C + nw + nw) + n + 64;
-    HIP_OK(P.meta[0].need(meta));
-    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
-    uint64_t* const d_out_off = d_in_off + n;
-    uint64_t* const d_first = d_out_off + n;
-    uint64_t* const d_begin = d_first + n + 1;
-    uint64_t* const d_src_off = d_begin + nw;
-    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_src_off + nw);
-    uint32_t* const d_cap = d_in_len + n;
-    uint32_t* const d_out_len = d_cap + n;
-    uint32_t* const d_off = d_out_len + n;
-    uint32_t* const d_new_off = d_off + C;
-    uint32_t* const d_wstream = d_new_off + C;
-    uint32_t* const d_wlen = d_wstream + nw;
-    int8_t* const d_status = reinterpret_cast<int8_t*>(d_wlen + nw);
-    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-    if (src_hi > src_lo) HIP_OK(hipMemcpyAsync(P.in[1].p, c.src + src_lo, src_hi - src_lo, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    TableCarver m;
+    const auto m_in_off = m.take<uint64_t>(n), m_out_off = m.take<uint64_t>(n), m_first = m.take<uint64_t>(n + 1);
+    const auto m_begin = m.take<uint64_t>(nw), m_src_off = m.take<uint64_t>(nw);
+    const auto m_in_len = m.take<uint32_t>(n), m_cap = m.take<uint32_t>(n), m_out_len = m.take<uint32_t>(n);
+    const auto m_off = m.take<uint32_t>(C), m_new_off = m.take<uint32_t>(C), m_wstream = m.take<uint32_t>(nw), m_wlen = m.take<uint32_t>(nw);
+    const auto m_status = m.take<int8_t>(n);
+    HIP_OK(P.meta[0].need(m.bytes()));
+    void* const mp = P.meta[0].p;
+    uint64_t *const d_in_off = m_in_off.in(mp), *const d_out_off = m_out_off.in(mp), *const d_first = m_first.in(mp);
+    uint64_t *const d_begin = m_begin.in(mp), *const d_src_off = m_src_off.in(mp);
+    uint32_t *const d_in_len = m_in_len.in(mp), *const d_cap = m_cap.in(mp), *const d_out_len = m_out_len.in(mp);
+    uint32_t *const d_off = m_off.in(mp), *const d_new_off = m_new_off.in(mp), *const d_wstream = m_wstream.in(mp), *const d_wlen = m_wlen.in(mp);
+    int8_t* const d_status = m_status.in(mp);
+    if (ext.bytes()) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + ext.lo, ext.bytes(), hipMemcpyHostToDevice, st));
+    if (src.bytes()) HIP_OK(hipMemcpyAsync(P.in[1].p, c.src + src.lo, src.bytes(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_out_off, h_out_off.data(), n * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_first, c.first, (n + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_in_len, c.in_len, n * 4, hipMemcpyHostToDevice, st));
@@ -2887,7 +2869,7 @@ int batch_write_ranges(const TampAmdConf* conf, const WriteCaller& c, uint8_t ma
     if (C) HIP_OK(hipMemcpyAsync(d_off, c.off, C * 4, hipMemcpyHostToDevice, st));
     if (nw) {
         HIP_OK(hipMemcpyAsync(d_begin, c.write_begin, nw * 8, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_src_off, h_src_off.data(), nw * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_src_off, src.off.data(), nw * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_wstream, c.write_stream, nw * 4, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_wlen, c.write_len, nw * 4, hipMemcpyHostToDevice, st));
     }
@@ -2897,30 +2879,12 @@ int batch_write_ranges(const TampAmdConf* conf, const WriteCaller& c, uint8_t ma
     uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
     const WriteOut dout = {d_out, d_out_off, d_cap, d_out_len, d_status, o.new_reset_off ? d_new_off : nullptr};
     const uint64_t S = C + n;
-    if (const int rc = launch_write_ranges(ctx, conf, d, max_wbits, dout, &S, st)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    if (const int rc = launch_write_ranges(ctx, conf, d, max_wbits, dout, &S, st)) return rc;
     HIP_OK(hipMemcpyAsync(o.out_len, d_out_len, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(o.status, d_status, n, hipMemcpyDeviceToHost, st));
     if (o.new_reset_off && C) HIP_OK(hipMemcpyAsync(o.new_reset_off, d_new_off, C * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    uint64_t produced = 0;
-    for (uint64_t i = 0; i < n; i++) produced += o.out_len[i];
-    if (!produced) return TAMP_OK;
-    if (room <= ((uint64_t)512 << 20) && !getenv("TAMP_AMD_NO_STAGED_COPYBACK") && P.stage[0].need(room) == hipSuccess) {
-        const uint8_t* const stg = static_cast<const uint8_t*>(P.stage[0].p);
-        HIP_OK(hipMemcpyAsync(P.stage[0].p, d_out, room, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        for (uint64_t i = 0; i < n; i++)
-            if (o.out_len[i]) memcpy(o.out + o.out_off[i], stg + h_out_off[i], o.out_len[i]);
-        return TAMP_OK;
-    }
-    (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
-    for (uint64_t i = 0; i < n; i++)
-        if (o.out_len[i]) HIP_OK(hipMemcpyAsync(o.out + o.out_off[i], d_out + h_out_off[i], o.out_len[i], hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return TAMP_OK;
+    return copy_back_slabs(P, st, d_out, room, h_out_off.data(), o.out, o.out_off, o.out_len, n);
 }
 
 // Appending to reset-segmented streams (tamp_batch_append; kernels and steps: tamp_append_kernel.hpp, the arithmetic:
@@ -3062,11 +3026,13 @@ int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbi
     if (const int rc = get_ctx(device, &ctx)) return rc;
     if (mem == TAMP_AMD_MEM_DEVICE) return launch_append(ctx, conf, c, max_wbits, o, false, static_cast<hipStream_t>(stream));
     const uint64_t n = c.n;
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> pipe_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
+    std::vector<uint32_t> start(n, 0), h_in_len(n, 0), h_cap(n, 0), h_src_len(n, 0), t_off, t_len(n);
+    std::vector<uint64_t> h_in_off(n, 0), h_out_off(n, 0), h_src_off(n, 0), t_first(n + 1);
+    std::vector<int8_t> t_status(n);
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
     const uint32_t N = c.interval;
     // whose rows of reset_first hold, and have a table for their entries (the device call's append_index_ok)
     std::vector<uint8_t> holds(n);
@@ -3083,11 +3049,9 @@ int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbi
     enum : uint8_t { kWhole = 0, kRun = 1, kFailed = 2 };
     std::vector<uint8_t> kind(n, kWhole);
     std::vector<int8_t> pre(n, 0);
-    std::vector<uint32_t> start(n, 0), h_in_len(n, 0), h_cap(n, 0), h_src_len(n, 0);
-    std::vector<uint64_t> h_in_off(n, 0), h_out_off(n, 0), h_src_off(n, 0);
     struct Piece { uint64_t from, at, len; };  // of the caller's source buffer: neighbours there stay neighbours and are one copy
     std::vector<Piece> pieces;
-    uint64_t staged = 0, room = 0, src_all = 0, bound_all = 0;
+    uint64_t staged = 0, src_all = 0, bound_all = 0;
     for (uint64_t i = 0; i < n; i++) {
         const uint32_t L = c.src_len[i];
         if (!L) continue;
@@ -3111,7 +3075,6 @@ int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbi
         const uint64_t moved = start[i] - kResetHeaderBytes;  // bytes of the new stream that the tail does not hold
         const uint64_t tail_room = o.out_cap[i] > moved ? o.out_cap[i] - moved : 0;
         h_cap[i] = (uint32_t)std::min<uint64_t>(tail_room, std::min<uint64_t>(kResetHeaderBytes + (B + 1) * unit_bound, 0xFFFFFFFFull));
-        h_out_off[i] = room, room += h_cap[i];
         h_src_len[i] = L, bound_all += B;
         // the sources of the streams that run, back to back: nothing between them goes up
         h_src_off[i] = src_all;
@@ -3119,6 +3082,7 @@ int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbi
         else pieces.push_back({c.src_off[i], src_all, L});
         src_all += L;
     }
+    const uint64_t room = dense_slabs(h_cap.data(), n, h_out_off.data());  // (the tails of the streams that run: the others have no room)
     // the open segments, each behind its stream's header, in pinned staging
     HIP_OK(P.stage[0].need(staged + 64));
     uint8_t* const h_stage = static_cast<uint8_t*>(P.stage[0].p);
@@ -3131,20 +3095,19 @@ int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbi
     HIP_OK(P.in[0].need(staged + 64));
     HIP_OK(P.in[1].need(src_all + 64));
     HIP_OK(P.out[0].need(room + 64));
-    // 8-byte tables, 4-byte tables, bytes
-    const size_t meta = 8 * (n + n + (n + 1) + n + (n + 1)) + 4 * (n + n + n + n + bound_all) + n + 64;
-    HIP_OK(P.meta[0].need(meta));
-    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
-    uint64_t* const d_out_off = d_in_off + n;
-    uint64_t* const d_first = d_out_off + n;
-    uint64_t* const d_src_off = d_first + n + 1;
-    uint64_t* const d_new_first = d_src_off + n;
-    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_new_first + n + 1);
-    uint32_t* const d_cap = d_in_len + n;
-    uint32_t* const d_out_len = d_cap + n;
-    uint32_t* const d_src_len = d_out_len + n;
-    uint32_t* const d_new_off = d_src_len + n;
-    int8_t* const d_status = reinterpret_cast<int8_t*>(d_new_off + bound_all);
+    TableCarver m;
+    const auto m_in_off = m.take<uint64_t>(n), m_out_off = m.take<uint64_t>(n), m_first = m.take<uint64_t>(n + 1);
+    const auto m_src_off = m.take<uint64_t>(n), m_new_first = m.take<uint64_t>(n + 1);
+    const auto m_in_len = m.take<uint32_t>(n), m_cap = m.take<uint32_t>(n), m_out_len = m.take<uint32_t>(n), m_src_len = m.take<uint32_t>(n);
+    const auto m_new_off = m.take<uint32_t>(bound_all);
+    const auto m_status = m.take<int8_t>(n);
+    HIP_OK(P.meta[0].need(m.bytes()));
+    void* const mp = P.meta[0].p;
+    uint64_t *const d_in_off = m_in_off.in(mp), *const d_out_off = m_out_off.in(mp), *const d_first = m_first.in(mp);
+    uint64_t *const d_src_off = m_src_off.in(mp), *const d_new_first = m_new_first.in(mp);
+    uint32_t *const d_in_len = m_in_len.in(mp), *const d_cap = m_cap.in(mp), *const d_out_len = m_out_len.in(mp), *const d_src_len = m_src_len.in(mp);
+    uint32_t* const d_new_off = m_new_off.in(mp);
+    int8_t* const d_status = m_status.in(mp);
     if (staged) HIP_OK(hipMemcpyAsync(P.in[0].p, h_stage, staged, hipMemcpyHostToDevice, st));
     for (const Piece& pc : pieces)
         HIP_OK(hipMemcpyAsync(static_cast<uint8_t*>(P.in[1].p) + pc.at, c.src + pc.from, pc.len, hipMemcpyHostToDevice, st));
@@ -3160,13 +3123,8 @@ int batch_append(const TampAmdConf* conf, const AppendCaller& c, uint8_t max_wbi
     d.src = static_cast<const uint8_t*>(P.in[1].p), d.src_off = d_src_off, d.src_len = d_src_len;
     uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
     const AppendOut dout = {d_out, d_out_off, d_cap, d_out_len, d_status, d_new_first, bound_all ? d_new_off : nullptr, bound_all};
-    if (const int rc = launch_append(ctx, conf, d, max_wbits, dout, true, st)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    std::vector<uint64_t> t_first(n + 1);
-    std::vector<uint32_t> t_off(bound_all), t_len(n);
-    std::vector<int8_t> t_status(n);
+    if (const int rc = launch_append(ctx, conf, d, max_wbits, dout, true, st)) return rc;
+    t_off.resize(bound_all);
     HIP_OK(hipMemcpyAsync(t_len.data(), d_out_len, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(t_status.data(), d_status, n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(t_first.data(), d_new_first, (n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -3318,41 +3276,35 @@ int launch_index_resets(DeviceCtx* ctx, const IndexCaller& c, uint64_t* reset_fi
 // transfer of their extent, and the tables alone come back.
 int index_resets_host(DeviceCtx* ctx, const IndexCaller& c, uint64_t* reset_first, uint32_t* reset_off, uint32_t* closed_size,
                       uint32_t* open_size, uint64_t reset_cap, int8_t* status) {
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> pipe_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
     const size_t n = c.n;
-    uint64_t in_lo = ~0ull, in_hi = 0, total = 0;
-    std::vector<uint64_t> h_in_off(n);
-    for (size_t i = 0; i < n; i++)
-        if (c.in_len[i]) in_lo = std::min(in_lo, c.in_off[i]), in_hi = std::max(in_hi, c.in_off[i] + c.in_len[i]), total += c.in_len[i];
-    if (in_hi < in_lo) in_lo = in_hi = 0;
-    for (size_t i = 0; i < n; i++) h_in_off[i] = c.in_len[i] ? c.in_off[i] - in_lo : 0;  // (an empty stream points at the staging buffer)
+    const HostExtent ext(c.in_off, c.in_len, n);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) total += c.in_len[i];
     const uint64_t cap = std::min<uint64_t>(reset_cap, total);  // (every reset ends on a byte of its own)
-    HIP_OK(P.in[0].need(in_hi - in_lo + 64));
-    HIP_OK(P.meta[0].need(n * (8 + 4) + 64));
-    const size_t off_at = (n + 1) * 8, closed_at = off_at + cap * 4, open_at = closed_at + cap * 4, status_at = open_at + n * 4;
-    HIP_OK(P.out[0].need(status_at + n + 64));
-    uint64_t* const d_in_off = static_cast<uint64_t*>(P.meta[0].p);
-    uint32_t* const d_in_len = reinterpret_cast<uint32_t*>(d_in_off + n);
-    uint8_t* const o = static_cast<uint8_t*>(P.out[0].p);
-    uint64_t* const d_first = reinterpret_cast<uint64_t*>(o);
-    uint32_t* const d_off = reinterpret_cast<uint32_t*>(o + off_at);
-    uint32_t* const d_closed = reinterpret_cast<uint32_t*>(o + closed_at);
-    uint32_t* const d_open = reinterpret_cast<uint32_t*>(o + open_at);
-    int8_t* const d_status = reinterpret_cast<int8_t*>(o + status_at);
-    if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_in_off, h_in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    TableCarver m, o;  // the caller's tables in `meta`, the results in `out`
+    const auto m_in_off = m.take<uint64_t>(n);
+    const auto m_in_len = m.take<uint32_t>(n);
+    const auto o_first = o.take<uint64_t>(n + 1);
+    const auto o_off = o.take<uint32_t>(cap), o_closed = o.take<uint32_t>(cap), o_open = o.take<uint32_t>(n);
+    const auto o_status = o.take<int8_t>(n);
+    HIP_OK(P.in[0].need(ext.bytes() + 64));
+    HIP_OK(P.meta[0].need(m.bytes()));
+    HIP_OK(P.out[0].need(o.bytes()));
+    void *const mp = P.meta[0].p, *const op = P.out[0].p;
+    uint64_t *const d_in_off = m_in_off.in(mp), *const d_first = o_first.in(op);
+    uint32_t *const d_in_len = m_in_len.in(mp), *const d_off = o_off.in(op), *const d_closed = o_closed.in(op), *const d_open = o_open.in(op);
+    int8_t* const d_status = o_status.in(op);
+    if (ext.bytes()) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + ext.lo, ext.bytes(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_in_off, ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_in_len, c.in_len, n * 4, hipMemcpyHostToDevice, st));
     const IndexCaller d = {static_cast<const uint8_t*>(P.in[0].p), d_in_off, d_in_len, c.n, c.max_wbits};
     const int rc = launch_index_resets(ctx, d, d_first, cap ? d_off : nullptr, closed_size && cap ? d_closed : nullptr,
                                        open_size ? d_open : nullptr, cap, d_status, st);
-    if (rc != TAMP_OK && rc != 1) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    if (rc != TAMP_OK && rc != 1) return rc;
     HIP_OK(hipMemcpyAsync(reset_first, d_first, (n + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
     if (open_size) HIP_OK(hipMemcpyAsync(open_size, d_open, n * 4, hipMemcpyDeviceToHost, st));

@@ -119,9 +119,6 @@ int launch_pieces(DeviceCtx* ctx, const TampAmdConf* conf, const PieceCall& c, h
 
 // Host memory: one round trip on the host pipeline's first stream and kept buffers.
 int run_host_pieces(DeviceCtx* ctx, const TampAmdConf* conf, const PieceCall& c) {
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> call_lock(P.mu);
     const BatchTables& h = c.t;
     const size_t n = h.n;
     uint8_t* const objects = static_cast<uint8_t*>(c.objects);
@@ -140,37 +137,35 @@ int run_host_pieces(DeviceCtx* ctx, const TampAmdConf* conf, const PieceCall& c)
     if (in_hi <= in_lo) in_lo = in_hi = 0;
     if (out_hi <= out_lo) out_lo = out_hi = 0;
     if ((in_hi > in_lo && !h.in) || (out_hi > out_lo && !h.out)) return TAMP_AMD_BAD_ARGUMENT;
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
-    std::vector<uint32_t> out_len(n);  // what comes back (declared in front of the drain below: they outlive it)
+    std::vector<uint32_t> out_len(n);  // what comes back
     std::vector<int8_t> status(n);
     std::vector<uint8_t> objs(n * c.stride);
-    // Every way out of the call drains the stream: the copies below go to and from this function's own vectors and the caller's
-    // arrays, and none of them may still be in flight when those go away.  (Behind the last wait of a call that completes: nothing.)
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError(); }
-    } drain{st};
-    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t o_in_off = 0, o_out_off = n * 8, o_in_len = o_out_off + n * 8, o_out_cap = o_in_len + n * 4;
-    const size_t o_out_len = o_out_cap + n * 4, o_status = o_out_len + n * 4, o_ops = o_status + up(n);
-    HIP_OK(P.meta[0].need(o_ops + n));
+    std::vector<uint64_t> slab_at(n, 0);  // where a live object's slab starts on the device
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    TableCarver m;
+    const auto m_in_off = m.take<uint64_t>(n), m_out_off = m.take<uint64_t>(n);
+    const auto m_in_len = m.take<uint32_t>(n), m_out_cap = m.take<uint32_t>(n), m_out_len = m.take<uint32_t>(n);
+    const auto m_status = m.take<int8_t>(n);
+    const auto m_ops = m.take<uint8_t>(n, 16);
+    HIP_OK(P.meta[0].need(m.bytes()));
     HIP_OK(P.state[0].need(n * c.stride));
     HIP_OK(P.in[0].need((size_t)(in_hi - in_lo) + 64));
     HIP_OK(P.out[0].need((size_t)(out_hi - out_lo) + 1));
-    uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
+    void* const mp = P.meta[0].p;
     uint8_t* const d_out = static_cast<uint8_t*>(P.out[0].p);
     PieceCall d = c;
-    d.objects = P.state[0].p, d.ops = m + o_ops;
+    d.objects = P.state[0].p, d.ops = m_ops.in(mp);
     d.t.in = static_cast<const uint8_t*>(P.in[0].p) - in_lo, d.t.out = d_out - out_lo;
-    d.t.in_off = reinterpret_cast<const uint64_t*>(m + o_in_off), d.t.out_off = reinterpret_cast<const uint64_t*>(m + o_out_off);
-    d.t.in_len = reinterpret_cast<const uint32_t*>(m + o_in_len), d.t.out_cap = reinterpret_cast<const uint32_t*>(m + o_out_cap);
-    d.t.out_len = reinterpret_cast<uint32_t*>(m + o_out_len), d.t.status = reinterpret_cast<int8_t*>(m + o_status);
-    HIP_OK(hipMemcpyAsync(m + o_in_off, h.in_off, n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m + o_out_off, h.out_off, n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m + o_in_len, in_len_d.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m + o_out_cap, h.out_cap, n * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m + o_ops, c.ops, n, hipMemcpyHostToDevice, st));
+    d.t.in_off = m_in_off.in(mp), d.t.out_off = m_out_off.in(mp), d.t.in_len = m_in_len.in(mp), d.t.out_cap = m_out_cap.in(mp);
+    d.t.out_len = m_out_len.in(mp), d.t.status = m_status.in(mp);
+    HIP_OK(hipMemcpyAsync(m_in_off.in(mp), h.in_off, n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_out_off.in(mp), h.out_off, n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_len.in(mp), in_len_d.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_out_cap.in(mp), h.out_cap, n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_ops.in(mp), c.ops, n, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(P.state[0].p, objects, n * c.stride, hipMemcpyHostToDevice, st));
     if (in_hi > in_lo) HIP_OK(hipMemcpyAsync(P.in[0].p, h.in + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
     if (const int rc = launch_pieces(ctx, conf, d, st)) return rc;
@@ -178,21 +173,16 @@ int run_host_pieces(DeviceCtx* ctx, const TampAmdConf* conf, const PieceCall& c)
     HIP_OK(hipMemcpyAsync(out_len.data(), d.t.out_len, n * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(status.data(), d.t.status, n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(objs.data(), P.state[0].p, n * c.stride, hipMemcpyDeviceToHost, st));
-    const size_t extent = out_hi - out_lo;
-    const bool staged = extent && extent <= ((size_t)512 << 20) && P.stage[0].need(extent) == hipSuccess;
-    if (extent && !staged) (void)hipGetLastError();  // (a failed pinned allocation must not poison later calls)
-    if (staged) HIP_OK(hipMemcpyAsync(P.stage[0].p, d_out, extent, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     for (size_t i = 0; i < n; i++) {
-        if (c.ops[i] & TAMP_AMD_PIECE_SKIP) continue;
-        h.out_len[i] = out_len[i], h.status[i] = status[i];
+        if (c.ops[i] & TAMP_AMD_PIECE_SKIP) {
+            out_len[i] = 0;  // (a skipped object brings nothing back)
+            continue;
+        }
+        h.out_len[i] = out_len[i], h.status[i] = status[i], slab_at[i] = out_len[i] ? h.out_off[i] - out_lo : 0;
         if (status[i] == TAMP_OK) std::memcpy(objects + i * c.stride, objs.data() + i * c.stride, kPieceObjectHeader + ((size_t)1 << conf->window));
-        if (!out_len[i]) continue;
-        if (staged) std::memcpy(h.out + h.out_off[i], static_cast<const uint8_t*>(P.stage[0].p) + (h.out_off[i] - out_lo), out_len[i]);
-        else HIP_OK(hipMemcpyAsync(h.out + h.out_off[i], d_out + (h.out_off[i] - out_lo), out_len[i], hipMemcpyDeviceToHost, st));
     }
-    if (!staged) HIP_OK(hipStreamSynchronize(st));
-    return TAMP_OK;
+    return copy_back_slabs(P, st, d_out, out_hi - out_lo, slab_at.data(), h.out, h.out_off, out_len.data(), n);
 }
 
 int batch_compress_pieces(const TampAmdConf* conf, const PieceCall& c, int mem, int device, void* stream) {

@@ -47,57 +47,41 @@ int launch_seek_index(DeviceCtx* ctx, const SeekIndexCall& c, hipStream_t st) {
     return TAMP_OK;
 }
 
-// The extent of a batch's streams on the host and their offsets counted from its start (an empty stream points at the start).
-struct HostExtent {
-    uint64_t lo = 0, hi = 0;
-    std::vector<uint64_t> off;
-    HostExtent(const uint64_t* in_off, const uint32_t* in_len, size_t n) : off(n) {
-        uint64_t l = ~0ull, h = 0;
-        for (size_t i = 0; i < n; i++)
-            if (in_len[i]) l = std::min(l, in_off[i]), h = std::max(h, in_off[i] + in_len[i]);
-        if (h >= l) lo = l, hi = h;
-        for (size_t i = 0; i < n; i++) off[i] = in_len[i] ? in_off[i] - lo : 0;
-    }
-};
-
 int seek_index_host(DeviceCtx* ctx, const SeekIndexCall& c) {
-    using Pipe = DeviceCtx::HostPipe;
-    Pipe& P = ctx->pipe;
-    std::lock_guard<std::mutex> pipe_lock(P.mu);
-    if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-    hipStream_t st = P.s[0];
     const size_t n = c.n;
     for (size_t i = 0; i < n; i++)
         if (c.first[i + 1] < c.first[i]) return TAMP_AMD_BAD_ARGUMENT;  // (no running sum: the rows cannot be placed)
     const uint64_t rows = c.first[n] - c.first[0];
     const HostExtent ext(c.in_off, c.in_len, n);
-    const size_t first_at = n * 8, len_at = first_at + (n + 1) * 8;
-    const size_t size_at = (rows * 4 + 7) & ~(size_t)7, status_at = size_at + n * 8;
-    HIP_OK(P.in[0].need(ext.hi - ext.lo + 64));
-    HIP_OK(P.meta[0].need(len_at + n * 4 + 64));
-    HIP_OK(P.out[0].need(status_at + n + 64));
-    HIP_OK(P.state[0].need(rows * c.stride + 64));
-    if (c.dict && c.dict_len) HIP_OK(P.dict.need(std::min(c.dict_len, kSeedTable)));
-    uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
-    uint8_t* const o = static_cast<uint8_t*>(P.out[0].p);
     std::vector<uint64_t> h_first(n + 1);
     for (size_t i = 0; i <= n; i++) h_first[i] = c.first[i] - c.first[0];
-    if (ext.hi > ext.lo) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + ext.lo, ext.hi - ext.lo, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m, ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m + first_at, h_first.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(m + len_at, c.in_len, n * 4, hipMemcpyHostToDevice, st));
-    if (c.dict && c.dict_len) HIP_OK(hipMemcpyAsync(P.dict.p, c.dict, std::min(c.dict_len, kSeedTable), hipMemcpyHostToDevice, st));
+    HostCall host(ctx);
+    if (const int rc = host.open()) return rc;
+    DeviceCtx::HostPipe& P = host.P;
+    const hipStream_t st = host.st;
+    TableCarver m, o;  // the caller's tables in `meta`, the results in `out`
+    const auto m_in_off = m.take<uint64_t>(n), m_first = m.take<uint64_t>(n + 1);
+    const auto m_in_len = m.take<uint32_t>(n);
+    const auto o_ckpt_in = o.take<uint32_t>(rows);
+    const auto o_size = o.take<uint64_t>(n);
+    const auto o_status = o.take<int8_t>(n);
+    HIP_OK(P.in[0].need(ext.bytes() + 64));
+    HIP_OK(P.meta[0].need(m.bytes()));
+    HIP_OK(P.out[0].need(o.bytes()));
+    HIP_OK(P.state[0].need(rows * c.stride + 64));
+    if (c.dict && c.dict_len) HIP_OK(P.dict.need(std::min(c.dict_len, kSeedTable)));
+    void *const mp = P.meta[0].p, *const op = P.out[0].p;
     SeekIndexCall d = c;
     d.dict = c.dict && c.dict_len ? static_cast<const uint8_t*>(P.dict.p) : nullptr, d.dict_len = std::min(c.dict_len, kSeedTable);
-    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = reinterpret_cast<const uint64_t*>(m);
-    d.first = reinterpret_cast<const uint64_t*>(m + first_at), d.in_len = reinterpret_cast<const uint32_t*>(m + len_at);
-    d.ckpt_in = reinterpret_cast<uint32_t*>(o), d.states = static_cast<uint8_t*>(P.state[0].p);
-    d.decoded_size = reinterpret_cast<uint64_t*>(o + size_at), d.status = reinterpret_cast<int8_t*>(o + status_at);
-    const int rc = launch_seek_index(ctx, d, st);
-    if (rc != TAMP_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    d.in = static_cast<const uint8_t*>(P.in[0].p), d.in_off = m_in_off.in(mp), d.first = m_first.in(mp), d.in_len = m_in_len.in(mp);
+    d.ckpt_in = o_ckpt_in.in(op), d.states = static_cast<uint8_t*>(P.state[0].p);
+    d.decoded_size = o_size.in(op), d.status = o_status.in(op);
+    if (ext.bytes()) HIP_OK(hipMemcpyAsync(P.in[0].p, c.in + ext.lo, ext.bytes(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_off.in(mp), ext.off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_first.in(mp), h_first.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(m_in_len.in(mp), c.in_len, n * 4, hipMemcpyHostToDevice, st));
+    if (c.dict && c.dict_len) HIP_OK(hipMemcpyAsync(P.dict.p, c.dict, std::min(c.dict_len, kSeedTable), hipMemcpyHostToDevice, st));
+    if (const int rc = launch_seek_index(ctx, d, st)) return rc;
     HIP_OK(hipMemcpyAsync(c.decoded_size, d.decoded_size, n * 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(c.status, d.status, n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -182,7 +166,6 @@ int launch_read_seek(DeviceCtx* ctx, const SeekCaller& c, const uint8_t* dict, c
 }
 
 int read_seek_host(DeviceCtx* ctx, const SeekCaller& c, const uint8_t* dict, const SeekReadOut& o) {
-    using Pipe = DeviceCtx::HostPipe;
     const uint64_t nr = c.n_ranges;
     // count and units, on the host
     std::vector<SeekUnit> units;
@@ -232,40 +215,39 @@ int read_seek_host(DeviceCtx* ctx, const SeekCaller& c, const uint8_t* dict, con
     std::vector<uint32_t> got(nr, 0), flags(nr, 0);
     std::vector<uint8_t> h_out(out_bytes);
     if (U) {
-        Pipe& P = ctx->pipe;
-        std::lock_guard<std::mutex> pipe_lock(P.mu);
-        if (!P.s[0]) HIP_OK(hipStreamCreateWithFlags(&P.s[0], hipStreamNonBlocking));
-        hipStream_t st = P.s[0];
-        const size_t off_at = (U * sizeof(SeekUnit) + 7) & ~(size_t)7;
-        const size_t got_at = (out_bytes + 7) & ~(size_t)7, flags_at = got_at + nr * 4;
+        HostCall host(ctx);
+        if (const int rc = host.open()) return rc;
+        DeviceCtx::HostPipe& P = host.P;
+        const hipStream_t st = host.st;
+        TableCarver m, o;  // the units and where the ranges land in `meta`; the ranges' bytes, then got and flags as one table, in `out`
+        const auto m_units = m.take<SeekUnit>(U);
+        const auto m_out_off = m.take<uint64_t>(nr);
+        const auto o_out = o.take<uint8_t>(out_bytes);
+        const auto o_got = o.take<uint32_t>(2 * nr, 8);
         HIP_OK(P.in[0].need(spans.size() + 64));
         HIP_OK(P.state[0].need(rows.size() + 64));
-        HIP_OK(P.meta[0].need(off_at + nr * 8 + 64));
-        HIP_OK(P.out[0].need(flags_at + nr * 4 + 64));
+        HIP_OK(P.meta[0].need(m.bytes()));
+        HIP_OK(P.out[0].need(o.bytes()));
         const size_t dl = dict && c.dict_len ? std::min<size_t>(c.dict_len, kSeedTable) : 0;
         if (dl) HIP_OK(P.dict.need(dl));
-        uint8_t* const m = static_cast<uint8_t*>(P.meta[0].p);
-        uint8_t* const ob = static_cast<uint8_t*>(P.out[0].p);
+        void *const mp = P.meta[0].p, *const op = P.out[0].p;
+        uint32_t *const d_got = o_got.in(op), *const d_flags = d_got + nr;
         if (!spans.empty()) HIP_OK(hipMemcpyAsync(P.in[0].p, spans.data(), spans.size(), hipMemcpyHostToDevice, st));
         if (!rows.empty()) HIP_OK(hipMemcpyAsync(P.state[0].p, rows.data(), rows.size(), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(m, units.data(), U * sizeof(SeekUnit), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(m + off_at, d_out_off.data(), nr * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(m_units.in(mp), units.data(), U * sizeof(SeekUnit), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(m_out_off.in(mp), d_out_off.data(), nr * 8, hipMemcpyHostToDevice, st));
         if (dl) HIP_OK(hipMemcpyAsync(P.dict.p, dict, dl, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(ob + got_at, 0, nr * 8, st));
+        HIP_OK(hipMemsetAsync(d_got, 0, nr * 8, st));
         SeekCaller d = c;
         d.in = static_cast<const uint8_t*>(P.in[0].p), d.states = static_cast<const uint8_t*>(P.state[0].p), d.dict_len = dl;
-        const SeekRanges r = {nullptr, reinterpret_cast<uint32_t*>(ob + got_at), reinterpret_cast<uint32_t*>(ob + flags_at), nullptr};
-        const SeekReadOut dout = {ob, reinterpret_cast<const uint64_t*>(m + off_at), nullptr, nullptr};
-        const int rc = launch_read_seek_kernel(ctx, read_seek_args(ctx, d, dl ? static_cast<const uint8_t*>(P.dict.p) : nullptr,
-                                                                    reinterpret_cast<const SeekUnit*>(m), U, r, dout), st);
-        if (rc != TAMP_OK) {
-            (void)hipStreamSynchronize(st);
+        const SeekRanges r = {nullptr, d_got, d_flags, nullptr};
+        const SeekReadOut dout = {o_out.in(op), m_out_off.in(mp), nullptr, nullptr};
+        if (const int rc = launch_read_seek_kernel(ctx, read_seek_args(ctx, d, dl ? static_cast<const uint8_t*>(P.dict.p) : nullptr, m_units.in(mp), U, r, dout), st))
             return rc;
-        }
         HIP_OK(hipGetLastError());
-        if (out_bytes) HIP_OK(hipMemcpyAsync(h_out.data(), ob, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(got.data(), ob + got_at, nr * 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(flags.data(), ob + flags_at, nr * 4, hipMemcpyDeviceToHost, st));
+        if (out_bytes) HIP_OK(hipMemcpyAsync(h_out.data(), o_out.in(op), out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(got.data(), d_got, nr * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(flags.data(), d_flags, nr * 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
     }
     for (uint64_t q = 0; q < nr; q++) {  // the gather step
