@@ -661,6 +661,45 @@ int tamp_batch_seek_index(const uint8_t *dictionary, size_t dictionary_len, uint
                           size_t n_streams, int mem, int device, void *stream);
 
 /*
+ * EXTENDING such an index when its streams have GROWN, without building it again.  Precondition: every stream's old bytes -- the
+ * ones its rows were made from -- are a PREFIX of its bytes now (a connection that wrote another message, a log that was
+ * appended to).  The call does not and cannot check that; an index of other bytes gives rows of no use, within memory safety.
+ * The result is, byte for byte, what tamp_batch_seek_index gives for the grown streams: rows, in_pos, decoded_size and status.
+ *   ckpt_first, ckpt_in, ckpt_state, state_stride, decoded_size, status, and all in front of them: tamp_batch_seek_index's.
+ *                   ckpt_first is the running sum of each stream's ROOM, as there
+ *   ckpt_have       uint32 per stream, only read: how many of stream i's rows already hold its old checkpoints, in their places
+ *                   at the front of its room
+ * Continuing from a stream's last row would be wrong: the calls that made the last rows may have met the old end of the input,
+ * and a refill that the end cut short leaves a smaller bit_buffer, bit_buffer_pos and in_pos than the same call leaves with
+ * more input behind it.  Such rows are exactly those whose in_pos is the old in_len, and several rows can share it.  The old
+ * in_len is not recorded, and the rule does without it:
+ *   The RESTART ROW of a stream that holds `have` rows is the last of them whose in_pos is smaller than the in_pos of row
+ *   have - 1; if there is none the stream restarts from its header with a fresh object.  Rows up to and including the restart
+ *   row are final and only read.  Every row behind it is decoded again and written again.
+ * (Every row in front of the restart row has an in_pos smaller still, so below the old in_len: final.)  Per stream:
+ *   rows 0 .. restart are read; rows restart + 1 .. min(C, room) - 1 are written, and nothing else of the tables
+ *   have == 0 ........ a build, exactly tamp_batch_seek_index
+ *   have == room ..... writes no row it did not have and is the size query: decoded_size says C; call again with more
+ *   have > room, or a restart row that does not hold up -- tamp_batch_read_ranges_seek's checks of a row a unit starts at (its
+ *   conf byte is not the stream's header byte, the configured flag is missing, token_state is not 0, 1 or 3, window_pos or a
+ *   pending token lies outside the window, in_pos lies inside the header, beyond in_len[i] or below the row's in front of it),
+ *   a row between it and the last one whose in_pos lies beyond in_len[i], or a token at the restart row's place that is not
+ *   the one the row names ... TAMP_AMD_BAD_INDEX and decoded_size 0 for that stream; it writes no row and affects no other stream
+ *   The stream's own verdicts (no bytes, a bad header, TAMP_AMD_BAD_ARGUMENT for its length) come first, as the build gives them.
+ * The index is TRUSTED FOR POSITION, as in the read; memory safety holds for any contents of every table (ckpt_in and ckpt_state
+ * must have ckpt_first[n_streams] rows).
+ * A device-memory call is one asynchronous launch on `stream`: nothing is allocated, nothing read back.  A host-memory call is
+ * synchronous: the rule, the header and the restart row's checks run on the host, and per stream it uploads ONLY the restart row
+ * and the compressed bytes from that row's in_pos to in_len (a restart from the header: the stream from byte 0), and copies back
+ * only the rows written and the two result tables.
+ * Returns as tamp_batch_seek_index; a null ckpt_have is a TAMP_AMD_BAD_ARGUMENT too, before a device is looked for.
+ */
+int tamp_batch_seek_index_extend(const uint8_t *dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t *in,
+                                 const uint64_t *in_off, const uint32_t *in_len, uint32_t interval, const uint64_t *ckpt_first,
+                                 const uint32_t *ckpt_have, uint32_t *ckpt_in, void *ckpt_state, size_t state_stride,
+                                 uint64_t *decoded_size, int8_t *status, size_t n_streams, int mem, int device, void *stream);
+
+/*
  * Reading byte ranges through such an index.  The range tables, the output and the result tables are tamp_batch_read_ranges's;
  * the index tables are tamp_batch_seek_index's, with the stream's ROWS in ckpt_first (R rows of stream i: checkpoints 1 .. R) and
  * ckpt_first[n_streams] rows in each table.  A range is cut at the checkpoints it crosses and every piece is a UNIT of its own,

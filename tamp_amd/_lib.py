@@ -52,6 +52,7 @@ SYMBOLS = (
     "tamp_batch_read_ranges",
     "tamp_batch_read_ranges_grid",
     "tamp_batch_seek_index",
+    "tamp_batch_seek_index_extend",
     "tamp_batch_read_ranges_seek",
     "tamp_batch_segment_ends",
     "tamp_batch_write_ranges",
@@ -246,6 +247,8 @@ def load() -> C.CDLL:
     lib.tamp_batch_read_ranges_grid.restype = i32
     lib.tamp_batch_seek_index.argtypes = [vp, sz, u8, vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, sz, i32, i32, vp]
     lib.tamp_batch_seek_index.restype = i32
+    lib.tamp_batch_seek_index_extend.argtypes = [vp, sz, u8, vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, sz, i32, i32, vp]
+    lib.tamp_batch_seek_index_extend.restype = i32
     lib.tamp_batch_read_ranges_seek.argtypes = [vp, sz, u8, vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, vp]
     lib.tamp_batch_read_ranges_seek.restype = i32
     lib.tamp_batch_segment_ends.argtypes = [vp, vp, vp, vp, sz, i32, i32, vp]

@@ -943,6 +943,10 @@ class SeekIndex:
                          dev(self.state, np.uint8, torch.uint8).contiguous(), self.interval, self.window_bits,
                          dev(self.size, np.int64, torch.int64), dev(self.status, np.int8, torch.int8))
 
+    def extend(self, data, in_off=None, in_len=None, **kwargs) -> "SeekIndex":
+        """``extend_seek_index(data, in_off, in_len, seek_index=self, ...)``: a new index for the grown batch; this one stays."""
+        return extend_seek_index(data, in_off, in_len, seek_index=self, **kwargs)
+
     def save(self, path) -> None:
         """One ``.npz`` file at exactly ``path``, with host arrays."""
         h = self.to("cpu")
@@ -1051,6 +1055,142 @@ def build_seek_index(data, in_off=None, in_len=None, *, interval=None, dictionar
         if not (S >= 0xFFFFFFFF).any():
             break
         S = size
+    return SeekIndex(first, in_pos[:total], state[:total], N, w, size, status)
+
+
+def extend_seek_index(data, in_off=None, in_len=None, *, seek_index, dictionary=None, device: int = 0, stream=None) -> SeekIndex:
+    """``seek_index`` brought up to date with streams that have GROWN since it was made, without decoding what it already covers
+    (``tamp_batch_seek_index_extend``; not in the reference).  ``data`` is the grown batch, in the forms
+    ``build_seek_index`` takes: every stream's old bytes are a prefix of its bytes now, and streams behind the index's last one
+    are new and indexed from their headers.  The result equals ``build_seek_index`` of the grown batch at the index's own
+    ``interval`` and ``window_bits``; the old index is not modified (its rows are copied to their new places).  Decoding resumes
+    at each stream's restart row -- the last row whose ``in_pos`` lies below the last row's -- and not at its last row: the rows
+    made at the old end of the input are decoded again.  Two calls: one with the rows the index has, for the sizes, and one that
+    writes the new rows."""
+    if not isinstance(seek_index, SeekIndex):  # (all decided before the library is looked for)
+        raise ValueError("seek_index: a SeekIndex expected")
+    on_device = _is_torch(data)
+    if on_device and (in_off is None or in_len is None or not (_is_torch(in_off) and _is_torch(in_len))):
+        raise ValueError("in_off, in_len: CUDA tensors expected with CUDA data")
+    n = len(data) if in_off is None and not on_device else len(in_len)
+    n_old = len(seek_index.first) - 1
+    if n_old < 0 or n < n_old:
+        raise ValueError("seek_index: it holds more streams than the data")
+    if seek_index.interval is None:
+        raise ValueError("seek_index.interval: the index's own interval expected")
+    N = _seek_interval(seek_index.interval, 8)
+    w = seek_index.window_bits
+    if not _is_int(w) or not 8 <= int(w) <= 15:
+        raise ValueError("seek_index.window_bits: 8 .. 15 expected")
+    w = int(w)
+    for t in (seek_index.first, seek_index.in_pos, seek_index.state):
+        if _is_torch(t) != on_device or (on_device and not t.is_cuda):
+            raise ValueError("seek_index: on another memory kind than the data (SeekIndex.to)")
+    stride = 16 + (1 << w)
+    if len(seek_index.state.shape) != 2 or int(seek_index.state.shape[1]) != stride or len(seek_index.state) != len(seek_index.in_pos):
+        raise ValueError("seek_index.state: one row of 16 + (1 << window_bits) bytes per entry of in_pos expected")
+    if on_device:
+        import torch
+
+        if stream is not None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=data.device)):
+                return extend_seek_index(data, in_off, in_len, seek_index=seek_index, dictionary=dictionary, device=device)
+        lib = _lib.load()
+        dev = data.device
+        in_off_t, in_len_t = in_off.to(torch.int64), in_len.to(torch.int32)
+        dict_t = None if dictionary is None else (dictionary if _is_torch(dictionary) else torch.from_numpy(_np_u8(dictionary).copy())).to(dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        old_first = seek_index.first.to(device=dev, dtype=torch.int64)
+        old_rows = int(seek_index.in_pos.numel())
+        h_first = old_first.cpu().numpy()  # (one small read-back: a first that is no running sum cannot place the rows)
+        if int(h_first[0]) != 0 or (np.diff(h_first) < 0).any() or int(h_first[-1]) != old_rows:
+            raise ValueError("seek_index.first: a running sum from 0 to the number of rows expected")
+        have = torch.zeros(n, dtype=torch.int64, device=dev)
+        have[:n_old] = old_first[1:] - old_first[:-1]
+        have_t = have.to(torch.int32)
+        size_t = torch.zeros(n, dtype=torch.int64, device=dev)
+        status_t = torch.zeros(n, dtype=torch.int8, device=dev)
+
+        def call(first_t, in_pos_t, state_t):
+            _lib.check_launch(lib.tamp_batch_seek_index_extend(
+                _ptr(dict_t), 0 if dict_t is None else int(dict_t.numel()), w, _ptr(data), _ptr(in_off_t), _ptr(in_len_t), N, _ptr(first_t),
+                _ptr(have_t), _ptr(in_pos_t), _ptr(state_t), stride, _ptr(size_t), _ptr(status_t), n, _lib.MEM_DEVICE, dev.index or 0,
+                C.c_void_p(st)))
+
+        # 1. the sizes: room = have, on a copy of the rows (the call writes the rows behind each restart row again)
+        first1 = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        first1[1:] = torch.cumsum(have, 0)
+        in_pos1 = torch.zeros(old_rows + 1, dtype=torch.int32, device=dev)
+        state1 = torch.zeros((old_rows + 1, stride), dtype=torch.uint8, device=dev)
+        in_pos1[:old_rows] = seek_index.in_pos.to(torch.int32)
+        state1[:old_rows] = seek_index.state
+        call(first1, in_pos1, state1)
+        # 2. the new layout; 3. the old rows to their places (a row its stream has no room for any more goes to the spare row)
+        rows = torch.clamp(size_t - 1, min=0) // N
+        first_t = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        first_t[1:] = torch.cumsum(rows, 0)
+        total = int(first_t[-1].item())
+        in_pos_t = torch.zeros(total + 1, dtype=torch.int32, device=dev)
+        state_t = torch.zeros((total + 1, stride), dtype=torch.uint8, device=dev)
+        if old_rows:
+            owner = torch.repeat_interleave(torch.arange(n, device=dev), have, output_size=old_rows)
+            r = torch.arange(old_rows, device=dev) - first1[owner]
+            dst = torch.where(r < rows[owner], first_t[owner] + r, torch.full_like(r, total))
+            in_pos_t.index_copy_(0, dst, in_pos1[:old_rows])
+            state_t.index_copy_(0, dst, state1[:old_rows])
+        # 4. the new rows
+        call(first_t, in_pos_t, state_t)
+        return SeekIndex(first_t, in_pos_t[:total], state_t[:total], N, w, size_t, status_t,
+                         (data, in_off_t, in_len_t, dict_t, have_t, in_pos_t, state_t))
+    if in_off is None:
+        flat, in_off, in_len = pack_streams(data)
+    else:
+        flat = _np_u8(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint32)
+    live = in_len > 0
+    if live.any() and int((in_off[live].astype(np.uint64) + in_len[live]).max()) > flat.size:
+        raise ValueError("in_off, in_len: a stream lies outside the data")
+    old_first = np.ascontiguousarray(seek_index.first, dtype=np.uint64)
+    if int(old_first[0]) != 0 or (np.diff(old_first.astype(np.int64)) < 0).any() or int(old_first[-1]) != len(seek_index.in_pos):
+        raise ValueError("seek_index.first: a running sum from 0 to the number of rows expected")
+    lib = _lib.load()
+    dict_a = None if dictionary is None else _np_u8(dictionary)
+    if not flat.size:
+        flat = np.zeros(1, np.uint8)
+    old_rows = len(seek_index.in_pos)
+    have = np.zeros(n, dtype=np.uint32)
+    have[:n_old] = np.diff(old_first.astype(np.int64)).astype(np.uint32)
+    size = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.int8)
+
+    def call(first, in_pos, state):
+        _lib.check_launch(lib.tamp_batch_seek_index_extend(
+            _ptr(dict_a), 0 if dict_a is None else len(dict_a), w, _ptr(flat), _ptr(in_off), _ptr(in_len), N, _ptr(first), _ptr(have),
+            _ptr(in_pos), _ptr(state), stride, _ptr(size), _ptr(status), n, _lib.MEM_HOST, device, None))
+
+    # 1. the sizes: room = have, on a copy of the rows (the call writes the rows behind each restart row again)
+    first1 = np.zeros(n + 1, dtype=np.uint64)
+    first1[1:] = np.cumsum(have.astype(np.uint64))
+    in_pos1 = np.zeros(max(old_rows, 1), dtype=np.uint32)
+    in_pos1[:old_rows] = seek_index.in_pos
+    state1 = _aligned_rows(max(old_rows, 1), stride)
+    state1[:old_rows] = seek_index.state
+    call(first1, in_pos1, state1)
+    # 2. the new layout; 3. the old rows to their places
+    rows = np.where(size > 0, (np.maximum(size, np.uint64(1)) - np.uint64(1)) // np.uint64(N), np.uint64(0)).astype(np.uint64)
+    first = np.zeros(n + 1, dtype=np.uint64)
+    first[1:] = np.cumsum(rows)
+    total = int(first[-1])
+    in_pos = np.zeros(max(total, 1), dtype=np.uint32)
+    state = _aligned_rows(max(total, 1), stride)
+    for i in np.flatnonzero(have[:n_old]):
+        k = min(int(have[i]), int(rows[i]))
+        a, b = int(first1[i]), int(first[i])
+        in_pos[b : b + k] = in_pos1[a : a + k]
+        state[b : b + k] = state1[a : a + k]
+    # 4. the new rows
+    call(first, in_pos, state)
     return SeekIndex(first, in_pos[:total], state[:total], N, w, size, status)
 
 

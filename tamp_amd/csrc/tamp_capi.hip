@@ -3732,6 +3732,26 @@ int tamp_batch_seek_index(const uint8_t* dictionary, size_t dictionary_len, uint
     return seek_index_host(ctx, c);
 }
 
+int tamp_batch_seek_index_extend(const uint8_t* dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in,
+                                 const uint64_t* in_off, const uint32_t* in_len, uint32_t interval, const uint64_t* ckpt_first,
+                                 const uint32_t* ckpt_have, uint32_t* ckpt_in, void* ckpt_state, size_t state_stride, uint64_t* decoded_size,
+                                 int8_t* status, size_t n_streams, int mem, int device, void* stream) {
+    // (refused before a device is looked for)
+    if (!in_off || !in_len || !ckpt_first || !ckpt_have || !decoded_size || !status || (!in && n_streams) || !interval) return TAMP_AMD_BAD_ARGUMENT;
+    if ((mem != TAMP_AMD_MEM_HOST && mem != TAMP_AMD_MEM_DEVICE) || device == TAMP_AMD_ALL_DEVICES) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams > 0xFFFFFFFFull || max_window_bits < 8 || max_window_bits > 15) return TAMP_AMD_BAD_ARGUMENT;
+    if ((state_stride & 15) || state_stride < tamp_amd_decoder_state_size(max_window_bits) || (reinterpret_cast<uintptr_t>(ckpt_state) & 15))
+        return TAMP_AMD_BAD_ARGUMENT;
+    if (mem == TAMP_AMD_MEM_HOST && n_streams && ckpt_first[n_streams] > ckpt_first[0] && (!ckpt_in || !ckpt_state)) return TAMP_AMD_BAD_ARGUMENT;
+    if (n_streams == 0) return TAMP_OK;
+    const SeekIndexCall c = {dictionary, dictionary_len, max_window_bits, in, in_off, in_len, interval, ckpt_first, ckpt_in,
+                             static_cast<uint8_t*>(ckpt_state), state_stride, decoded_size, status, n_streams};
+    DeviceCtx* ctx = nullptr;
+    if (const int rc = get_ctx(device, &ctx)) return rc;
+    if (mem == TAMP_AMD_MEM_DEVICE) return launch_seek_extend(ctx, c, ckpt_have, nullptr, static_cast<hipStream_t>(stream));
+    return seek_extend_host(ctx, c, ckpt_have);
+}
+
 int tamp_batch_read_ranges_seek(const uint8_t* dictionary, size_t dictionary_len, uint8_t max_window_bits, const uint8_t* in,
                                 const uint64_t* in_off, const uint32_t* in_len, uint32_t interval, const uint64_t* ckpt_first,
                                 const uint32_t* ckpt_in, const void* ckpt_state, size_t state_stride, const uint32_t* range_stream,

@@ -7,6 +7,8 @@
 // the room ran out -- so begin / interval is an address.
 //   tamp_seek_index_kernel   a wavefront per stream: decodes with the window in LDS and no output at all, and stores a row each time
 //                            the decoded count reaches a multiple of the interval with a byte still to come
+//   tamp_seek_extend_kernel  the same loop for streams that have GROWN (tamp_batch_seek_index_extend): entered at the stream's
+//                            restart row, the last row whose in_pos is smaller than the last row's, and writing the rows behind it
 //   tamp_seek_count_kernel   a lane per range, the shared tile scan: the range's verdict and units, their exclusive scan
 //   tamp_seek_units_kernel   a lane per unit (range x checkpoint interval): owner by binary search, the checks of the row it
 //                            starts at, its 40-byte record
@@ -84,6 +86,45 @@ __device__ __forceinline__ void seek_load_window(uint8_t* win, const uint8_t* sr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The checks of a row that decoding starts at -- a unit of a read, the restart row of an extension: row `row` of the tables is row r
+// of a stream of n compressed bytes whose header has hs bytes, the first of them h0.
+__host__ __device__ inline bool seek_row_holds(const uint32_t* ckpt_in, const uint8_t* states, uint64_t stride, uint64_t row, uint64_t r,
+                                               uint32_t n, uint32_t hs, uint32_t h0) {
+    const uint32_t start = ckpt_in[row];
+    if (start < hs || start > n) return false;
+    // (the row in front of it, where that one's entry can be one at all: an entry beyond the stream spoils its own row only)
+    if (r >= 1 && ckpt_in[row - 1] > start && ckpt_in[row - 1] <= n) return false;
+    const uint8_t* const sp = states + row * stride;
+    uint32_t w[4];
+    for (int b = 0; b < 4; b++) w[b] = (uint32_t)sp[4 * b] | (uint32_t)sp[4 * b + 1] << 8 | (uint32_t)sp[4 * b + 2] << 16 | (uint32_t)sp[4 * b + 3] << 24;
+    const uint32_t wp = w[1] & 0xFFFFu, nb = (w[1] >> 16) & 0xFFu, ts = w[1] >> 24;
+    const uint32_t pend_off = w[2] & 0xFFFFu, pend_size = w[2] >> 16;
+    const uint32_t conf = w[3] & 0xFFu, skip = (w[3] >> 8) & 0xFFu, flags = (w[3] >> 16) & 0xFFu;
+    const uint32_t W = 1u << decode_header(h0).wbits;
+    if (conf != h0) return false;
+    if ((flags & (kDsConfigured | kDsHeaderStashed)) != kDsConfigured) return false;
+    if (ts != kTokNone && ts != kTokRle && ts != kTokExtHaveSize) return false;
+    if (wp >= W || nb > 32) return false;
+    // a token in delivery: what it still holds must lie inside the window and inside itself
+    if (ts == kTokRle && skip > pend_off) return false;
+    if (ts == kTokExtHaveSize && skip && (pend_off >= W || pend_off + pend_size > W || skip > pend_size)) return false;
+    return true;
+}
+
+// The RESTART ROW of a stream that holds `have` rows (tamp_batch_seek_index_extend): the last of them whose in_pos is smaller than
+// the last row's.  -> how many rows are final (the restart row and those in front of it; 0: restart from the header), or
+// kSeekBadRestart when a row between the two lies beyond the stream's n bytes: no index of a prefix of the stream looks so.
+constexpr uint32_t kSeekBadRestart = 0xFFFFFFFFu;
+__host__ __device__ inline uint32_t seek_restart_rows(const uint32_t* in_pos, uint32_t have, uint32_t n) {
+    if (have < 2) return 0;
+    const uint32_t last = in_pos[have - 1];
+    for (uint32_t r = have - 1; r-- > 0;) {
+        if (in_pos[r] < last) return r + 1;
+        if (in_pos[r] > n) return kSeekBadRestart;
+    }
+    return 0;
+}
+
 struct SeekIndexArgs {
     const uint8_t* in;
     const uint64_t* in_off;
@@ -99,8 +140,22 @@ struct SeekIndexArgs {
     int8_t* status;
     uint32_t interval, max_wbits, n_streams;
 };
+// What an extension adds.  A device-memory call gives `have` alone: the rows each stream holds, and the wavefront finds and checks
+// its restart row itself.  A host-memory call has done both on the host (restart_state is not null then): have[s] is the number of
+// FINAL rows (kSeekBadRestart: the restart row did not hold up), the tables hold the stream's rows BEHIND those, `in` its compressed
+// bytes from byte in_base[s] on -- the restart row's in_pos, or 0 -- and row slot[s] of restart_state is the restart row.
+struct SeekExtendArgs {
+    SeekIndexArgs x;
+    const uint32_t* have;
+    const uint32_t* in_base;
+    const uint32_t* slot;
+    const uint8_t* restart_state;
+};
 
-__global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
+// The index loop, a wavefront per stream.  kExtend: entered at the restart row, the way tamp_read_seek_kernel enters its own loop at
+// a unit's row; without it `e` is not looked at and every stream starts at its header.
+template <bool kExtend>
+__device__ __forceinline__ void seek_index_streams(const SeekIndexArgs& a, const SeekExtendArgs* e) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
     const uint32_t wave = uni32(threadIdx.x >> 6);
@@ -109,10 +164,13 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
     const uint64_t N = a.interval;
 
     for (uint32_t s = gw; s < a.n_streams; s += tw) {
+        const bool staged = kExtend && e->restart_state != nullptr;
+        const uint32_t in_base = staged ? uni32(e->in_base[s]) : 0u;  // the stream's bytes in front of `in`
         const uint8_t* const in = a.in + a.in_off[s];
         const uint32_t n = uni32(a.in_len[s]);
         const uint64_t f0 = a.ckpt_first[s], f1 = a.ckpt_first[s + 1];
-        const uint64_t room = f1 > f0 ? f1 - f0 : 0;  // rows this stream may write
+        uint64_t row_base = 0;                        // the stream's rows in front of its rows of the tables (staged: the final ones)
+        uint64_t room = f1 > f0 ? f1 - f0 : 0;        // rows [row_base, room) of the stream may be written
         uint64_t pos = 0, next = N, krow = 0;         // decoded bytes; the next multiple of the interval; rows so far (stored or not)
         int res = kInputExhausted;
 
@@ -120,10 +178,19 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
             if (n >= kSeekMaxIn) { res = kBadArgument; break; }
             if (a.max_wbits < 8 || a.max_wbits > 15) { res = kInvalidConf; break; }
             if (n == 0) break;
-            const uint32_t h0 = uni32(in[0]);
-            const uint32_t hs = 1 + (h0 & 1);
-            if (n < hs) break;
-            if (hs == 2 && uni32(in[1])) { res = kInvalidConf; break; }
+            uint32_t final_rows = kExtend ? uni32(e->have[s]) : 0u;  // rows [0, final_rows) stand as they are; the last is the restart row
+            const uint8_t* restart_row = nullptr;
+            uint32_t h0, hs;
+            if (in_base == 0) {
+                h0 = uni32(in[0]);
+                hs = 1 + (h0 & 1);
+                if (n < hs) break;
+                if (hs == 2 && uni32(in[1])) { res = kInvalidConf; break; }
+            } else {  // (the host saw the header; the restart row carries its first byte)
+                if (final_rows == 0 || final_rows == kSeekBadRestart || n < in_base) { res = kSeekBadIndex; break; }
+                h0 = uni32(e->restart_state[uni32(e->slot[s]) * a.state_stride + 12]);
+                hs = 1 + (h0 & 1);
+            }
             const StreamHeader hd = decode_header(h0);
             if (hd.wbits > a.max_wbits) { res = kInvalidConf; break; }
             const uint32_t W = 1u << hd.wbits, mask = W - 1;
@@ -133,25 +200,72 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
                 if (!a.dict || a.dict_len < W) { res = kInvalidConf; break; }
                 seed = a.dict;
             }
-            seek_load_window(win, seed, W, lane);
+            uint32_t start = 0;  // the restart row's in_pos
+            if (kExtend && staged) {
+                if (final_rows && final_rows != kSeekBadRestart) {
+                    restart_row = e->restart_state + uni32(e->slot[s]) * a.state_stride;
+                    start = in_base, row_base = final_rows, room += row_base;
+                }
+            } else if (kExtend && final_rows) {  // the rule, 64 rows a step from the last one down, and the restart row's checks
+                uint32_t found = kSeekBadRestart;
+                if (final_rows <= room) {
+                    const uint32_t* const rows_in = a.ckpt_in + f0;
+                    const uint32_t last = uni32(rows_in[final_rows - 1]);
+                    uint32_t top = final_rows - 1;  // rows [0, top) are still to be looked at
+                    found = 0;
+                    while (top && !found) {
+                        const bool live = lane < top;
+                        const uint32_t v = live ? rows_in[top - 1 - lane] : last;
+                        const uint64_t lower = __ballot(live && v < last), other = __ballot(live && v > n);
+                        if (other & ((lower & (0 - lower)) - 1)) found = kSeekBadRestart;  // (behind the restart row: none beyond the stream)
+                        else if (lower) found = top - (uint32_t)(__ffsll((unsigned long long)lower) - 1);
+                        else top = top > 64 ? top - 64 : 0;
+                    }
+                    found = uni32(found);
+                    if (found && found != kSeekBadRestart && !seek_row_holds(a.ckpt_in, a.ckpt_state, a.state_stride, f0 + found - 1, found - 1, n, hs, h0))
+                        found = kSeekBadRestart;
+                }
+                final_rows = found;
+                if (final_rows && final_rows != kSeekBadRestart) {
+                    restart_row = a.ckpt_state + (f0 + final_rows - 1) * a.state_stride;
+                    start = uni32(a.ckpt_in[f0 + final_rows - 1]);
+                }
+            }
+            if (kExtend && final_rows == kSeekBadRestart) { res = kSeekBadIndex; break; }
 
-            RefReader r{in, n};
+            RefReader r{in, n - in_base};
             r.ip = hs;
             uint32_t wp = 0, pend_off = 0, pend_size = 0;
+            uint32_t row_ts = kTokNone, row_skip = 0;  // the token the restart row lies in
+            if (kExtend && restart_row) {
+                const uint32_t* const sw = reinterpret_cast<const uint32_t*>(restart_row);
+                const uint32_t s0 = uni32(sw[0]), s1 = uni32(sw[1]), s2 = uni32(sw[2]), s3 = uni32(sw[3]);
+                const uint32_t carried = min((s1 >> 16) & 0xFFu, 32u);
+                wp = s1 & 0xFFFFu & mask, row_ts = s1 >> 24;
+                pend_off = s2 & 0xFFFFu, pend_size = s2 >> 16;
+                row_skip = (s3 >> 8) & 0xFFu;
+                if (carried) r.bb = s0 & (0xFFFFFFFFu << (32 - carried)), r.nb = carried;
+                r.ip = start - in_base;
+                seek_load_window(win, restart_row + 16, W, lane);
+                krow = final_rows, pos = krow * N, next = pos + N;
+            } else {
+                seek_load_window(win, seed, W, lane);
+            }
+
             bool last_flush = false;
             // a checkpoint at a token boundary waits until a byte behind it is certain: its words, and the window as it stands
             bool waiting = false;
             SeekWords held = {0, 0, 0, 0};
             uint32_t held_in = 0;
             auto store_row = [&](const SeekWords& w, uint32_t in_pos) {
-                if (krow < room) {
-                    uint8_t* const row = a.ckpt_state + (f0 + krow) * a.state_stride;
+                if (krow < room && (!kExtend || krow >= row_base)) {
+                    uint8_t* const row = a.ckpt_state + (f0 + krow - row_base) * a.state_stride;
                     __builtin_amdgcn_wave_barrier();
                     for (uint32_t k = lane * 16; k < W; k += 1024)
                         *reinterpret_cast<uint4*>(row + 16 + k) = *reinterpret_cast<const uint4*>(win + k);
                     if (lane == 0) {
                         *reinterpret_cast<uint4*>(row) = make_uint4(w.w0, w.w1, w.w2, w.w3);
-                        a.ckpt_in[f0 + krow] = in_pos;
+                        a.ckpt_in[f0 + krow - row_base] = in_pos + in_base;
                     }
                     __builtin_amdgcn_wave_barrier();
                 }
@@ -160,13 +274,12 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
             auto release = [&]() {
                 if (waiting) store_row(held, held_in), waiting = false;
             };
-            // `len` bytes of the token at hand are delivered from `pos` on; each multiple of the interval INSIDE it is a row
+            // bytes [done, len) of the token at hand are delivered from `pos` on; each multiple of the interval INSIDE it is a row
             // What the reference's buffer holds meanwhile: a plain match stays in it until it is delivered (pre_bb / pre_nb: the buffer
             // in front of the token); an RLE run or extended match has left it, and the call that picks the token up refills first
             // (decompressor.c:437), so every row behind the first one inside such a token sees that refill.
-            auto inside = [&](uint32_t len, uint32_t ts, uint32_t pre_bb, uint32_t pre_nb) {
+            auto inside = [&](uint32_t len, uint32_t done, uint32_t ts, uint32_t pre_bb, uint32_t pre_nb) {
                 const bool plain = ts == kTokNone;
-                uint32_t done = 0;
                 while ((uint64_t)(len - done) > next - pos) {
                     done += (uint32_t)(next - pos);
                     pos = next, next += N;
@@ -175,9 +288,60 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
                 }
                 pos += len - done;
             };
+            // a token that delivers bytes, `done` of them in front of the restart row already (their side of the window with them)
+            auto deliver = [&](const ExactTok& t, uint32_t done, uint32_t pre_bb, uint32_t pre_nb) {
+                if (t.kind == kExLit) {
+                    if (lane == 0) win[wp] = (uint8_t)t.arg;
+                    wp = (wp + 1) & mask;
+                    pos++;
+                } else if (t.kind == kExRle) {
+                    if (!done) {
+                        const uint32_t c = uni32(win[(wp - 1) & mask]);
+                        seek_window_rle(win, wp, c, t.len, W, lane);
+                        if ((uint64_t)t.len > next - pos) pend_off = t.len;  // (what a partial run parks, decompressor.c:143-148)
+                    }
+                    inside(t.len, done, kTokRle, r.bb, r.nb);
+                } else if (t.kind == kExExt) {
+                    if (!done && (uint64_t)t.len > next - pos) pend_off = t.arg, pend_size = t.len;  // (decompressor.c:243-249)
+                    inside(t.len, done, kTokExtHaveSize, r.bb, r.nb);
+                    seek_window_ext(win, wp, t.arg, t.len, W, lane);
+                } else {
+                    inside(t.len, done, kTokNone, pre_bb, pre_nb);  // (the token stays in the buffer until it is delivered, :555-562)
+                    seek_window_match(win, wp, t.arg, t.len, mask, lane);
+                }
+                if (pos == next) {  // a boundary: the object as the call that filled its room left it
+                    held = seek_pack(r.bb, r.nb, wp, kTokNone, pend_off, pend_size, h0, 0, kDsConfigured, a.max_wbits);
+                    held_in = r.ip, waiting = true;
+                    next += N;
+                }
+            };
+
+            if (kExtend && (row_ts != kTokNone || row_skip)) {  // the token the restart row lies in (decompressor.c:441-460)
+                ExactTok t;
+                const uint32_t pre_bb = r.bb, pre_nb = r.nb;  // (a plain match: the row's buffer is the one in front of it)
+                if (row_ts != kTokNone) {
+                    const bool rle = row_ts == kTokRle;
+                    r.refill();  // (the call that picks such a token up refills first)
+                    if (row_skip) {
+                        t = {rle ? (uint32_t)kExRle : (uint32_t)kExExt, rle ? pend_off : pend_size, pend_off};
+                        if (!rle && (pend_off >= W || pend_off + pend_size > W)) t.kind = kExOob;
+                    } else {
+                        uint32_t parked = 0;
+                        t = exact_payload(r, hd, rle, row_ts == kTokExtHaveSize ? 1 : 0, pend_size, &parked);
+                        if (parked) pend_size = parked;
+                    }
+                } else {
+                    t = exact_token_state(r, hd, nullptr);
+                    if (t.kind != kExMatch) t.kind = kExOob;
+                }
+                // (a row that the checks let through and that no index of this stream holds: the token is not the one it names)
+                if (t.kind == kExOob || row_skip > t.len) { res = kSeekBadIndex, pos = 0; break; }
+                if (t.kind == kExShort) break;
+                deliver(t, row_skip, pre_bb, pre_nb);
+            }
 
             for (;;) {  // decompressor.c:431-575
-                if (!(r.ip < n || r.nb)) break;
+                if (!(r.ip < r.n || r.nb)) break;
                 r.refill();
                 if (r.nb == 0) break;
                 const uint32_t pre_bb = r.bb, pre_nb = r.nb;
@@ -197,28 +361,7 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
                 }
                 last_flush = false;
                 release();
-                if (t.kind == kExLit) {
-                    if (lane == 0) win[wp] = (uint8_t)t.arg;
-                    wp = (wp + 1) & mask;
-                    pos++;
-                } else if (t.kind == kExRle) {
-                    const uint32_t c = uni32(win[(wp - 1) & mask]);
-                    seek_window_rle(win, wp, c, t.len, W, lane);
-                    if ((uint64_t)t.len > next - pos) pend_off = t.len;  // (what a partial run parks, decompressor.c:143-148)
-                    inside(t.len, kTokRle, r.bb, r.nb);
-                } else if (t.kind == kExExt) {
-                    if ((uint64_t)t.len > next - pos) pend_off = t.arg, pend_size = t.len;  // (decompressor.c:243-249)
-                    inside(t.len, kTokExtHaveSize, r.bb, r.nb);
-                    seek_window_ext(win, wp, t.arg, t.len, W, lane);
-                } else {
-                    inside(t.len, kTokNone, pre_bb, pre_nb);  // (the token stays in the buffer until it is delivered, :555-562)
-                    seek_window_match(win, wp, t.arg, t.len, mask, lane);
-                }
-                if (pos == next) {  // a boundary: the object as the call that filled its room left it
-                    held = seek_pack(r.bb, r.nb, wp, kTokNone, pend_off, pend_size, h0, 0, kDsConfigured, a.max_wbits);
-                    held_in = r.ip, waiting = true;
-                    next += N;
-                }
+                deliver(t, 0, pre_bb, pre_nb);
             }
         } while (false);
 
@@ -226,6 +369,11 @@ __global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) {
         __builtin_amdgcn_wave_barrier();
     }
 }
+
+__global__ void __launch_bounds__(256) tamp_seek_index_kernel(SeekIndexArgs a) { seek_index_streams<false>(a, nullptr); }
+
+// tamp_batch_seek_index_extend: the same loop from each stream's restart row on.
+__global__ void __launch_bounds__(256) tamp_seek_extend_kernel(SeekExtendArgs e) { seek_index_streams<true>(e.x, &e); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Planning a read: host and device run the same two functions.
@@ -302,23 +450,7 @@ __host__ __device__ inline bool seek_range_unit(const SeekCaller& c, uint64_t q,
     if (k) {
         const uint64_t row = f0 + k - 1;
         start = c.ckpt_in[row];
-        if (start < p.hs || start > n) return false;
-        // (the row in front of it, where that one's entry can be one at all: an entry beyond the stream spoils its own row only)
-        if (k >= 2 && c.ckpt_in[row - 1] > start && c.ckpt_in[row - 1] <= n) return false;
-        const uint8_t* const sp = c.states + row * c.stride;
-        uint32_t w[4];
-        for (int b = 0; b < 4; b++) w[b] = (uint32_t)sp[4 * b] | (uint32_t)sp[4 * b + 1] << 8 | (uint32_t)sp[4 * b + 2] << 16 | (uint32_t)sp[4 * b + 3] << 24;
-        const uint32_t wp = w[1] & 0xFFFFu, nb = (w[1] >> 16) & 0xFFu, ts = w[1] >> 24;
-        const uint32_t pend_off = w[2] & 0xFFFFu, pend_size = w[2] >> 16;
-        const uint32_t conf = w[3] & 0xFFu, skip = (w[3] >> 8) & 0xFFu, flags = (w[3] >> 16) & 0xFFu;
-        const uint32_t W = 1u << decode_header((c.in + c.in_off[i])[0]).wbits;
-        if (conf != (c.in + c.in_off[i])[0]) return false;
-        if ((flags & (kDsConfigured | kDsHeaderStashed)) != kDsConfigured) return false;
-        if (ts != kTokNone && ts != kTokRle && ts != kTokExtHaveSize) return false;
-        if (wp >= W || nb > 32) return false;
-        // a token in delivery: what it still holds must lie inside the window and inside itself
-        if (ts == kTokRle && skip > pend_off) return false;
-        if (ts == kTokExtHaveSize && skip && (pend_off >= W || pend_off + pend_size > W || skip > pend_size)) return false;
+        if (!seek_row_holds(c.ckpt_in, c.states, c.stride, row, k - 1, n, p.hs, (c.in + c.in_off[i])[0])) return false;
         u.row = (uint32_t)row;
         if (row > 0xFFFFFFFEull) return false;
     }
